@@ -30,6 +30,9 @@ A "step" = one pass of the hot path over one batch whose inputs -- emissions AND
 C-ABI step (`abi_kernels_only`, ctc) and the
 cold-cache operator (`fresh_targets`) are reported next to it.
 
+Warm-up: the --warmup W steps go on, repeating their own inputs, until WARMUP_MIN_S seconds have passed (W = 0: none),
+so that the --steps K timed steps start in a steady state; the line reports what ran as `warmup_run`.
+
 Per-kernel times come from HIP events recorded on the stream each launch goes to, inside the timed region
 (engine.PHASE_EVENTS); `roofline.frac` is STEP level -- the batch's algorithmic bytes over the sum of all kernel
 groups of a step (for CTC that is one launch + the repair launch) -- with the dominant kernel's own figure under
@@ -41,6 +44,7 @@ collected with scripts/collect_round.sh on the same commands).
   python bench.py --workload transducer             # cfg4 (the reference's 1000 word pieces)
   python bench.py --config cfg5                     # one GPU's shard of cfg5 (T=2000, C=512, 128 utterances per GPU)
   python bench.py --gpus 8 --config cfg5            # cfg5 itself: spawns its own 8 ranks (train.py:344-347 does too)
+  python bench.py --dump-outputs bench_outputs      # + the last timed step's loss and gradients as bench_outputs/*.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W   # ... or under a launcher (RANK / WORLD_SIZE set)
 
@@ -96,7 +100,8 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5,
+                    help="untimed steps before the timed ones; with W > 0 they go on until WARMUP_MIN_S have passed")
     ap.add_argument("--workload", default="ctc", choices=["ctc", "asg", "transducer"])
     ap.add_argument("--config", default=None, choices=["cfg2", "cfg3", "cfg4", "cfg5"],
                     help="a BASELINE.json configuration by name (sets workload and shape; cfg5 adds the all-reduce)")
@@ -116,7 +121,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the labelled extra measurements (profiling runs)")
     ap.add_argument("--cpu-sample-utts", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned in its last step (loss, gradients) "
+                         "as DIR/<name>.npy, float32, at most DUMP_BYTES in all (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config:
         shape = {"cfg2": ("ctc", 128, 1000, 100), "cfg3": ("asg", 128, 1000, 100), "cfg4": ("transducer", 64, 800, None),
                  "cfg5": ("ctc", 128, 2000, 512)}[args.config]
@@ -189,18 +199,25 @@ def make_ctc(args, rank, n_batches, dist=None):
     # cfg5 (BASELINE configs[4]): "RCCL all-reduce of transition grads".  Pure CTC has none, so the harness averages the
     # buffer an ASG criterion of this size would exchange -- [(C+1), C] fp32, 1.05 MB at C = 512 -- once per step
     exchange = torch.zeros(C + 1, C, device=x.device) if args.config == "cfg5" else None
+    keep, kept = args.dump_outputs is not None, {}  # (--dump-outputs: the loss of the last step)
 
     # the headline protocol: the emissions are a producer's OUTPUT (ctc_benchmark.py:22, train.py:262-266), so
     # loss.backward() has the graph below them to run on the autograd engine
     def step(i):
         xr.grad = None
-        ctc.CTCLoss(xr.view_as(xr), batches[i % n_batches], blank).backward()
+        loss = ctc.CTCLoss(xr.view_as(xr), batches[i % n_batches], blank)
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
         if exchange is not None:
             parallel.all_reduce_mean_([exchange], force=FORCE_DIST)
 
     def leaf_step(i):  # (the emissions ARE the leaf: the gradient of the forward launch becomes x.grad, no engine)
         xr.grad = None
-        ctc.CTCLoss(xr, batches[i % n_batches], blank).backward()
+        loss = ctc.CTCLoss(xr, batches[i % n_batches], blank)
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
         if exchange is not None:
             parallel.all_reduce_mean_([exchange], force=FORCE_DIST)
 
@@ -260,6 +277,8 @@ def make_ctc(args, rank, n_batches, dist=None):
             E.reduce_loss(nll, scale, 1.0)
             E.ctc_grad(x, tg, blank, ws, nll, coef, gout, dx)
             E._done(tok)
+            if keep:
+                kept["nll"] = nll
 
     def launch_clock(reps=24):
         """Duration of the meet-in-the-middle launch ALONE, measured on the device: the constant 100 MHz clock at the entry
@@ -287,9 +306,17 @@ def make_ctc(args, rank, n_batches, dist=None):
                 exchange_bytes=0 if exchange is None else exchange.numel() * 4,
                 metric=f"utterances/sec fwd+bwd (ctc_benchmark T={T},C={C},B={B}); HBM GB/s vs peak",
                 call="CTCLoss(x, targets, blank).backward()", algorithmic_bytes_per_utt=8 * T * C)
+
+    def outputs():  # what the timed call handed back in its last step
+        if args.mode == "abi":
+            if args.ctc_step == "pipelined":
+                return {"loss": last[0][2], "nll": last[0][1], "grad_emissions": dx}
+            return {"nll": kept["nll"], "grad_emissions": dx}
+        return {"loss": kept["loss"], "grad_emissions": xr.grad}
+
     return dict(step=step, leaf_step=leaf_step, abi_step=abi_step, module_step=module_step, engine_step=engine_step,
                 engine_proper_step=engine_proper_step, meta=meta, launch_clock=launch_clock, training_step=training_step, viterbi_step=viterbi_step,
-                payload=("ctc", x, batches[0], blank))
+                payload=("ctc", x, batches[0], blank), outputs=outputs)
 
 
 def make_asg(args, rank, n_batches, dist):
@@ -303,18 +330,25 @@ def make_asg(args, rank, n_batches, dist):
     # asg_benchmark.py:20-22: a free (C+1) x C transitions tensor with requires_grad (here a leaf ON the device)
     transitions = torch.randn(C + 1, C, generator=torch.Generator().manual_seed(7)).cuda().requires_grad_(True)
     batches = [torch.randint(C - 2, (B, L), generator=g).tolist() for _ in range(n_batches)]
+    keep, kept = args.dump_outputs is not None, {}  # (--dump-outputs: the loss of the last step)
 
     def step(i):  # (emissions that are a producer's output: asg_benchmark.py:20 hands over `.cuda()` of a host leaf)
         x.grad = None
         transitions.grad = None
-        asg.ASGLoss(x.view_as(x), transitions, batches[i % n_batches]).backward()
+        loss = asg.ASGLoss(x.view_as(x), transitions, batches[i % n_batches])
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
         if dist is not None:  # the one exchange step of the path (train.py:205-208: DDP averages criterion grads)
             parallel.all_reduce_mean_([transitions.grad], force=FORCE_DIST)
 
     def leaf_step(i):
         x.grad = None
         transitions.grad = None
-        asg.ASGLoss(x, transitions, batches[i % n_batches]).backward()
+        loss = asg.ASGLoss(x, transitions, batches[i % n_batches])
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
         if dist is not None:
             parallel.all_reduce_mean_([transitions.grad], force=FORCE_DIST)
 
@@ -346,7 +380,8 @@ def make_asg(args, rank, n_batches, dist):
                 call="ASGLoss(x, transitions, targets).backward()",
                 algorithmic_bytes_per_utt=8 * T * C, algorithmic_bytes_per_batch=8 * (C + 1) * C)
     wl = dict(step=step, leaf_step=leaf_step, engine_step=engine_step, training_step=training_step, meta=meta,
-              payload=("asg", x.detach(), transitions.detach(), batches[0]))
+              payload=("asg", x.detach(), transitions.detach(), batches[0]),
+              outputs=lambda: {"loss": kept["loss"], "grad_emissions": x.grad, "grad_transitions": transitions.grad})
     if vit_module is not None:
         wl["viterbi_step"] = viterbi_step
     return wl
@@ -373,14 +408,21 @@ def make_transducer(args, rank, n_batches):
     batches = [[torch.tensor([g2i[ch] for _ in range(Lp) for ch in rnd.choice(tokens)]) for _ in range(B)]
                for _ in range(n_batches)]
     crit = transducer.Transducer(tokens, g2i, blank="optional", allow_repeats=False, reduction="mean")
+    keep, kept = args.dump_outputs is not None, {}  # (--dump-outputs: the loss of the last step)
 
     def step(i):  # (emissions that are a producer's output: transducer_benchmark.py:33 hands over `.cuda()` of a host leaf)
         x.grad = None
-        crit(x.view_as(x), batches[i % n_batches]).backward()
+        loss = crit(x.view_as(x), batches[i % n_batches])
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
 
     def leaf_step(i):
         x.grad = None
-        crit(x, batches[i % n_batches]).backward()
+        loss = crit(x, batches[i % n_batches])
+        loss.backward()
+        if keep:
+            kept["loss"] = loss
 
     def engine_step(i):  # (a producer with kernels of its own, as under train.py:262-266)
         x.grad = None
@@ -422,7 +464,8 @@ def make_transducer(args, rank, n_batches):
 
     return dict(step=step, leaf_step=leaf_step, engine_step=engine_step, training_step=training_step,
                 training_step_prepared=training_step_prepared, fresh_prepared_step=fresh_prepared_step, viterbi_step=viterbi_step,
-                meta=meta, payload=("transducer", x.detach(), crit, batches[0]))
+                meta=meta, payload=("transducer", x.detach(), crit, batches[0]),
+                outputs=lambda: {"loss": kept["loss"], "grad_emissions": x.grad})
 
 
 # --------------------------------------------------------------------------------------------------
@@ -518,16 +561,47 @@ def pmc_traffic(key, phases):
 
 PMC_SOURCE = [None]  # which committed file `traffic` came from (printed in the line)
 
+WARMUP_MIN_S = 2.0  # the headline's warm-up lasts at least this long (timed_loop: min_warmup_s)
+WARMUP_RUN = [None]  # warm-up steps and seconds of the last timed_loop (printed in the line)
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: bytes of array data in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as path/<name>.npy in float32.  An array larger than its share of
+    DUMP_BYTES keeps a fixed sample of its rows (last axis whole; row indices drawn with seed 0, sorted), the same
+    for every build at the same arguments.  -> {name: what was written} for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    left, written = DUMP_BYTES, {}
+    for n, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - n)
+        rec = {"shape": list(a.shape)}
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, share // rows[0].nbytes)
+            idx = np.sort(np.random.RandomState(0).choice(rows.shape[0], keep, replace=False))
+            a = rows[idx]
+            rec["rows_sampled"] = f"{keep} of {rows.shape[0]} (seed 0)"
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = rec
+    return written
+
 
 # --------------------------------------------------------------------------------------------------
-def timed_loop(step, steps, warmup, fence, collect_events):
+def timed_loop(step, steps, warmup, fence, collect_events, min_warmup_s=0.0, dist=None):
     """-> (seconds of the timed region, ms per step of the dominant kernel group measured INSIDE it, ms per step of every
     group measured during warm-up).  HIP events around every launch perturb the step (each record is a packet on the
     stream, ~5 us on the critical path), so the timed region brackets only the dominant group -- found during the
     warm-up steps, which bracket them all -- and only three of its launches, a third of the run apart (measured at the
     CTC benchmark, 20 steps: every 4th launch bracketed 0.0472-0.0486 ms a step, every 10th 0.0455-0.0458).  (The
     cyclic garbage collector is left alone: a collection right before the timed region made the 20 steps after it 15 us
-    slower each, switching it off for the region leaves every step's cycles and their device buffers alive.)"""
+    slower each, switching it off for the region leaves every step's cycles and their device buffers alive.)
+    min_warmup_s: with warmup > 0, the warm-up goes on (repeating its own steps' inputs) until it has run that long: the
+    host takes about twice as long to issue a step for up to ~0.7 s of back-to-back steps, and a short timed region
+    that starts there measures the host instead of the step (cfg2, 2000 steps: 0.040 or 0.047 ms from run to run).
+    Under a process group every rank runs the same number of warm-up steps."""
     from gtn_applications_amd import engine as E
 
     def collect(events, n):
@@ -538,12 +612,26 @@ def timed_loop(step, steps, warmup, fence, collect_events):
         return {k: float(np.sum(v)) / n for k, v in phases.items()}
 
     cal = min(warmup, 3) if collect_events else 0
+    if collect_events:  # (before the warm-up: nothing but steps between its end and the timed region)
+        E.prealloc_events(16 * (steps + cal))
+    t_warm = time.perf_counter()
     for i in range(warmup - cal):
         step(i)
+    n_more = 0
+    while warmup and min_warmup_s > 0:
+        done = time.perf_counter() - t_warm >= min_warmup_s
+        if dist is not None:
+            flag = torch.tensor([float(done)], device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            done = bool(flag.item())
+        if done:
+            break
+        for _ in range(20):
+            step(n_more % warmup)
+            n_more += 1
     fence()
     warm = {}
     if cal:
-        E.prealloc_events(16 * (steps + cal))
         E.PHASE_EVENTS, E.PHASE_ONLY = [], None
         for i in range(warmup - cal, warmup):
             step(i)
@@ -555,8 +643,6 @@ def timed_loop(step, steps, warmup, fence, collect_events):
     # bracket three launches of the dominant group in the timed region (every launch of a run of fewer than four steps)
     E.PHASE_STRIDE = max(1, steps // 3) if warm else 1
     E._PHASE_COUNT.clear()
-    if collect_events and not warm:
-        E.prealloc_events(16 * steps)
     t0 = time.perf_counter()
     for i in range(steps):
         step(warmup + i)
@@ -565,6 +651,7 @@ def timed_loop(step, steps, warmup, fence, collect_events):
     events, E.PHASE_EVENTS, E.PHASE_ONLY = E.PHASE_EVENTS, None, None
     stride, E.PHASE_STRIDE = E.PHASE_STRIDE, 1
     timed = collect(events, max(1, steps // stride))
+    WARMUP_RUN[0] = dict(steps=warmup + n_more, s=t0 - t_warm)
     return elapsed, {**warm, **timed}
 
 
@@ -637,11 +724,14 @@ def main():
 
     api_step = wl["leaf_step"] if args.emissions == "leaf" else wl["step"]
     step = wl["abi_step"] if args.mode == "abi" else api_step if args.targets == "fresh" else (lambda i: api_step(0))
-    elapsed, phase_ms = timed_loop(step, args.steps, args.warmup, fence, True)
+    elapsed, phase_ms = timed_loop(step, args.steps, args.warmup, fence, True, WARMUP_MIN_S, dist)
+    warmup_run = WARMUP_RUN[0]
     if dist is not None:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    dumped = dump_outputs(args.dump_outputs, wl["outputs"]()) if args.dump_outputs and rank == 0 else None
 
     B = meta["B"]
     ms = elapsed * 1e3 / args.steps
@@ -657,7 +747,7 @@ def main():
         par = f"dp{world} (utterance shards, no data-path collective)"
     out = {
         "metric": meta["metric"], "value": value, "unit": "utt/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "warmup": args.warmup, "warmup_run": warmup_run, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": meta["workload"], "mode": args.mode, "targets": ("pre-staged" if args.mode != "api" else "fresh (new targets every step)" if args.targets == "fresh" else
                                "same list every step (the reference benchmark's protocol: resident on the device after the first call)"),
@@ -672,6 +762,8 @@ def main():
     }
     if repaired is not None:
         out["config"]["utterances_repaired_in_log_domain"] = repaired
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1, "arrays": dumped}
     alg_bytes = meta["algorithmic_bytes_per_utt"] * B + meta.get("algorithmic_bytes_per_batch", 0)
     if phase_ms:
         dom = max(phase_ms, key=phase_ms.get)
