@@ -144,6 +144,7 @@ _SIGS = {
     "wfl_dense_max_classes": (c_int, []),
     "wfl_dense_on_chip_classes": (c_int, []),
     "wfl_dense_workspace_field": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "wfl_dense_workspace_field_c": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_dense_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_dense_grad": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "wfl_dense_grad_parts": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),

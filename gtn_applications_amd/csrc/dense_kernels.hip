@@ -1564,6 +1564,29 @@ extern "C" int wfl_dense_workspace_field(int B, int T, int field, int64_t* offse
   }
 }
 
+// The same for any class count: beyond the on-chip limit the wide workspace (dense_wide.h) holds the flags -- the batch's
+// range verdict on W, the same for every utterance.
+extern "C" int wfl_dense_workspace_field_c(int B, int T, int C, int field, int64_t* offset_bytes, int64_t* length_bytes) {
+  if (C <= 0) {
+    set_error("dense_workspace_field: bad arguments");
+    return WFL_ERR_INVALID;
+  }
+  if (dense_log_on_chip(C)) return wfl_dense_workspace_field(B, T, field, offset_bytes, length_bytes);
+  if (B <= 0 || T <= 0 || !offset_bytes || !length_bytes) {
+    set_error("dense_workspace_field: bad arguments");
+    return WFL_ERR_INVALID;
+  }
+  const WideWs w = wide_carve(nullptr, B, T, C);
+  switch (field) {
+    case WFL_DENSE_WS_FLAGS:
+      *offset_bytes = (int64_t)((char*)w.flag - (char*)nullptr), *length_bytes = (int64_t)8 * B;
+      return WFL_OK;
+    default:
+      set_error("dense_workspace_field: unknown field %d", field);
+      return WFL_ERR_INVALID;
+  }
+}
+
 int wfl_dense_forward(const float* x, const float* W, int B, int T, int C, int semiring, float* alpha, float* beta,
                       int32_t* bptr, float* logz, void* ws, void* stream) {
   return wfl_dense_forward_parts(x, W, B, T, C, semiring, alpha, beta, bptr, logz, ws, WFL_DENSE_ALL, stream);
@@ -1688,7 +1711,7 @@ int wfl_dense_grad_parts(const float* x, const float* W, int B, int T, int C, co
   hipStream_t st = (hipStream_t)stream;
   if (!dense_log_on_chip(C)) {
     if (!main_part) return WFL_OK;  // (one piece: it goes with the main part)
-    const int rc = wide_grad(x, B, T, C, alpha, beta, logz, coef, coef_w, gout, accumulate, addend, dW_addend, dx, dW,
+    const int rc = wide_grad(x, W, B, T, C, alpha, beta, logz, coef, coef_w, gout, accumulate, addend, dW_addend, dx, dW,
                              dW_partial, ws, st);
     WFL_LAUNCH_CHECK();
     return rc;

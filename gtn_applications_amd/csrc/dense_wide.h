@@ -16,8 +16,16 @@
 //   braw_t    = P^T (e_{t+1} (.) braw_{t+1} / maxb_{t+1}),  beta_t = braw_t / maxb_t * exp(cb_t),
 //               cb_t = cb_{t+1} + mxp_{t+1} + log maxb_t,  braw_{T-1} = 1, cb_{T-1} = 0
 // The normalisation lags the product by one frame (a frame's maximum is only complete when its launch ends), so a
-// stored value is at most N times / at least 2^-126 of the frame's largest: fp32 holds it.  The cumulative offsets
-// are doubles (they reach 10^4 at T = 1000).  `alpha` / `beta` hold araw / braw; the workspace the rest.
+// stored value is at most N times the frame's largest; what falls below 2^-126 of it is lost.  That is negligible only
+// when every transition is within a bounded gap of its row maximum, so the batch gets a range verdict on W[1:] with the
+// rule of the on-chip sweeps: an entry that is -inf, NaN or +inf, or finite and more than 2^-60 (kHardGap) below its
+// row maximum, flags the batch (wide_prep_kernel, per row).  Without a flag every state i receives at least 2^-60 of
+// the frame's largest state through P[i][argmax], so a lost state contributes at most N 2^-126 / 2^-60 of a surviving
+// term to the next frame (beta: the same through P^T), and the posteriors obey the same bound.  A flagged batch is
+// recomputed in the log domain behind the product (wide_log_sweep_kernel, wide_log_grad_x_kernel,
+// wide_log_grad_w_kernel; each returns at once on a clean verdict).  The cumulative offsets are doubles (they reach
+// 10^4 at T = 1000).  `alpha` / `beta` hold araw / braw (a flagged batch: log scores relative to cuma / cb); the
+// workspace the rest.
 //
 // Gradient: emission posteriors elementwise; the transition gradient is the second matrix product of the path,
 //     dW[1+i][j] = P[i][j] * sum_{b, t >= 1} U[(b,t)][i] V[(b,t)][j],   V = araw_{t-1} / maxa_{t-1},
@@ -46,8 +54,12 @@ struct WideWs {
   float* mxp;    // [B][T]
   float* maxa;   // [B][T]
   float* maxb;   // [B][T]
-  double* cuma;  // [B][T]
+  double* cuma;  // [B][T]    (a flagged batch: the log-domain frames' references)
   double* cb;    // [B][T]
+  double* zlog;      // [B]    ln Z of the log-domain sweep (a flagged batch)
+  int32_t* rowhard;  // [C]    range verdict of row 1 + i of W
+  int32_t* flag;     // [B][2] the batch's verdict, per utterance (engine.dense_flagged)
+  int32_t* hard;     // [1]    the batch's verdict (written by wide_log_sweep_kernel, read by the gradient launches)
 };
 __host__ __device__ inline size_t wide_align(size_t n) { return (n + 15) & ~(size_t)15; }
 __host__ __device__ inline WideWs wide_carve(void* ws, int B, int T, int C) {
@@ -62,16 +74,21 @@ __host__ __device__ inline WideWs wide_carve(void* ws, int B, int T, int C) {
   w.maxb = (float*)p, p += wide_align((size_t)4 * B * T);
   w.cuma = (double*)p, p += wide_align((size_t)8 * B * T);
   w.cb = (double*)p, p += wide_align((size_t)8 * B * T);
+  w.zlog = (double*)p, p += wide_align((size_t)8 * B);
+  w.rowhard = (int32_t*)p, p += wide_align((size_t)4 * C);
+  w.flag = (int32_t*)p, p += wide_align((size_t)8 * B);
+  w.hard = (int32_t*)p;
   return w;
 }
 static size_t wide_ws_bytes(int B, int T, int C) {
   return 2 * wide_align((size_t)4 * C * C) + wide_align((size_t)4 * C) + wide_align((size_t)4 * B) +
-         3 * wide_align((size_t)4 * B * T) + 2 * wide_align((size_t)8 * B * T) + 64;
+         3 * wide_align((size_t)4 * B * T) + 2 * wide_align((size_t)8 * B * T) + wide_align((size_t)8 * B) +
+         wide_align((size_t)4 * C) + wide_align((size_t)8 * B) + 16 + 64;
 }
 
 __device__ __forceinline__ float wide_clean(float v) { return (v == v) ? v : WFL_NEG_INF; }  // NaN policy: impossible
 
-// one workgroup per row i of W[1:, :]: rm_i, P[i][:], PT[:][i]
+// one workgroup per row i of W[1:, :]: rm_i, P[i][:], PT[:][i], and the row's range verdict (the header)
 __global__ void __launch_bounds__(256) wide_prep_kernel(const float* __restrict__ W, int C, WideWs w) {
   __shared__ float red[64];
   const int i = blockIdx.x;
@@ -81,11 +98,16 @@ __global__ void __launch_bounds__(256) wide_prep_kernel(const float* __restrict_
   m = blk_max(m, red);
   const float ref = (m > -3.0e38f && m < 3.0e38f) ? m : 0.f;  // (a row of -inf: P = 0, any finite reference does)
   if (threadIdx.x == 0) w.rm[i] = ref;
+  int hard = 0;
   for (int j = threadIdx.x; j < C; j += 256) {
-    const float p = __expf(wide_clean(row[j]) - ref);
+    const float raw = row[j];
+    hard |= !((raw - m) * kLog2e >= -kHardGap);  // -inf, NaN, +inf (m = +inf: NaN), a row of -inf, a gap beyond 2^-60
+    const float p = __expf(wide_clean(raw) - ref);
     w.P[(int64_t)i * C + j] = p;
     w.PT[(int64_t)j * C + i] = p;
   }
+  hard = __syncthreads_or(hard);
+  if (threadIdx.x == 0) w.rowhard[i] = hard ? 1 : 0;
 }
 
 // one wave per (b, t): mxp; t == 0: m0 and alpha's first frame; t == T-1: beta's last frame.  The maxima of the
@@ -486,6 +508,10 @@ static bool wide_resident_frames(const float* x, int B, int T, int C, const Wide
   }();
   if (NR == 0 || off || T < 2 || T > kWideResidentMaxT) return false;
   const size_t lds = wide_resident_lds(NR, T);
+  if (lds > (size_t)kLdsBytes) return false;
+  const void* k = NR == 4 ? (const void*)wide_resident_sweep_kernel<4> : (const void*)wide_resident_sweep_kernel<5>;
+  // (beyond 48 KB -- T > ~5900 -- the launch asks for the larger allocation first, as every large-LDS launch here does)
+  if (lds > 48 * 1024 && set_max_dynamic_lds(k, (int)lds) != hipSuccess) return false;
   const dim3 grid((unsigned)B, beta ? 2u : 1u);
   if (NR == 4)
     hipLaunchKernelGGL(wide_resident_sweep_kernel<4>, grid, dim3(1024), lds, st, x, B, T, C, w, alpha, beta);
@@ -572,7 +598,7 @@ __global__ void __launch_bounds__(256) wide_grad_x_kernel(int B, int T, int C, W
                                                           float* __restrict__ dx) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= (int64_t)B * T) return;
+  if (r >= (int64_t)B * T || *w.hard) return;  // (a flagged batch: wide_log_grad_x_kernel)
   const int b = (int)(r / T);
   const float g = gout ? gout[0] : 1.f;
   const float ma = w.maxa[r], mb = w.maxb[r], lz = logz[b];
@@ -596,6 +622,7 @@ __global__ void __launch_bounds__(256) wide_grad_w_kernel(const float* __restric
   __shared__ float Vs[kWideTK][kWideTN + 4];
   __shared__ float ku[2][kWideTK], kv[2][kWideTK];  // the rows' scalars, double-buffered: chunk n + 1's are formed while chunk
   __shared__ int64_t krow[2][kWideTK];              // n's operands are on their way
+  if (*w.hard) return;  // (a flagged batch: wide_log_grad_w_kernel)
   const int i0 = blockIdx.x * kWideTM, j0 = blockIdx.y * kWideTN;
   const int64_t K = (int64_t)B * (T - 1);
   const int nsplit = (int)gridDim.z;
@@ -676,7 +703,7 @@ __global__ void __launch_bounds__(256) wide_reduce_w_kernel(int B, int T, int C,
                                                             int accumulate, const float* __restrict__ dW_addend,
                                                             const float* __restrict__ partial, float* __restrict__ dW) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (int64_t)(C + 1) * C) return;
+  if (e >= (int64_t)(C + 1) * C || *w.hard) return;  // (a flagged batch: wide_log_grad_w_kernel)
   const float g = gout ? gout[0] : 1.f;
   float v = 0.f;
   if (e < C) {  // start row
@@ -985,6 +1012,228 @@ __global__ void __launch_bounds__(256) wide_viterbi_first_kernel(const float* __
   bptr[at] = -1;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Log-domain repair of a flagged batch (the header: the range verdict).  The same recurrences as dense_chain_kernel, W
+// read from global memory (4 C^2 bytes does not fit a workgroup; L2 serves it), the frame vector in LDS as floats
+// relative to a double reference per frame:
+//     y_t[s] = LSE_k (Wd(s, k) + z_{t-1}[k]) - m_{t-1},   m_{t-1} = max_k z_{t-1}[k],   ref_t = ref_{t-1} + m_{t-1}
+//     alpha: Wd(s, k) = W[1+s][k], stored y + x_t, z_t = y + x_t;   beta: Wd(s, k) = W[1+k][s], stored y, z_t = y + x_t
+// Stored value + ref_t (cuma / cb) is the log score; ln Z to zlog (double) and logz.  One workgroup per (utterance,
+// direction), one launch behind the probability-domain product; every workgroup reads the rows' verdicts first and
+// returns at once on a clean batch.  alpha: a wave per state, its lanes along the row of W (coalesced); beta: a thread
+// per state, walking its column (the wave's lanes read consecutive columns of a row).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kWideLogThreads = 1024;
+static size_t wide_log_lds(int C) { return (size_t)2 * 4 * C + 2 * 4 * (kWideLogThreads / 64) + 64; }
+
+__device__ __forceinline__ void lse_push(float& m, float& s, float v) {  // running (max, sum of exp(. - max))
+  if (v > m) {
+    s = s * __expf(m - v) + 1.f;
+    m = v;
+  } else if (m > WFL_NEG_INF) {
+    s += __expf(v - m);
+  }
+}
+
+__global__ void __launch_bounds__(kWideLogThreads) wide_log_sweep_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                                         int B, int T, int C, WideWs w, float* __restrict__ alpha,
+                                                                         float* __restrict__ beta, float* __restrict__ logz) {
+  extern __shared__ __attribute__((aligned(16))) char wide_log_smem[];
+  constexpr int NW = kWideLogThreads / 64;
+  float* zb = reinterpret_cast<float*>(wide_log_smem);  // [2][C] z of the frame before / of this frame
+  float* red = zb + 2 * C;                              // [2][NW] the waves' maxima of z, by frame parity
+  const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int h = 0;
+  for (int i = tid; i < C; i += kWideLogThreads) h |= w.rowhard[i];
+  h = __syncthreads_or(h);
+  if (dir == 0 && tid == 0) {
+    w.flag[2 * b] = w.flag[2 * b + 1] = h ? 1 : 0;
+    if (b == 0) *w.hard = h ? 1 : 0;
+  }
+  if (!h) return;
+  const float* xb = x + (int64_t)b * T * C;
+  float* ob = (dir == 0 ? alpha : beta) + (int64_t)b * T * C;
+  double* ref = (dir == 0 ? w.cuma : w.cb) + (int64_t)b * T;
+  auto tf = [&](int n) { return dir == 0 ? n : T - 1 - n; };
+  double R = 0.0;  // reference of the vector z of the frame before
+  // frame tf(0): alpha_0 = x_0 + W[0], beta_{T-1} = 0
+  {
+    const int t = tf(0);
+    float top = WFL_NEG_INF;
+    for (int s = tid; s < C; s += kWideLogThreads) {
+      const float xv = wide_clean(xb[(int64_t)t * C + s]);
+      const float val = dir == 0 ? xv + wide_clean(W[s]) : 0.f;
+      ob[(int64_t)t * C + s] = val;
+      const float z = dir == 0 ? val : xv;
+      zb[s] = z;
+      top = fmaxf(top, z);
+    }
+    top = wave_max(top);
+    if (lane == 0) red[wave] = top;
+    if (tid == 0) ref[t] = 0.0;
+    __syncthreads();
+  }
+  for (int n = 1; n < T; ++n) {
+    const int t = tf(n);
+    const float* zp = zb + ((n - 1) & 1) * C;
+    float* zn = zb + (n & 1) * C;
+    float m = red[((n - 1) & 1) * NW];
+    for (int q = 1; q < NW; ++q) m = fmaxf(m, red[((n - 1) & 1) * NW + q]);
+    const float mf = (m > -3.0e38f && m < 3.0e38f) ? m : 0.f;  // (a dead utterance stays dead)
+    R += (double)mf;
+    float top = WFL_NEG_INF;
+    if (dir == 0) {
+      for (int s = wave; s < C; s += NW) {
+        const float* wrow = W + (int64_t)(1 + s) * C;
+        float lm = WFL_NEG_INF, ls = 0.f;
+        for (int k = lane; k < C; k += 64) lse_push(lm, ls, wide_clean(wrow[k]) + zp[k]);
+        const float M = wave_max(lm);
+        const float S = wave_sum(lm > WFL_NEG_INF ? ls * __expf(lm - M) : 0.f);
+        if (lane == 0) {
+          const float y = M > WFL_NEG_INF ? M + __logf(S) - mf : WFL_NEG_INF;
+          const float z = y + wide_clean(xb[(int64_t)t * C + s]);
+          ob[(int64_t)t * C + s] = z;
+          zn[s] = z;
+          top = fmaxf(top, z);
+        }
+      }
+    } else {
+      for (int s = tid; s < C; s += kWideLogThreads) {
+        float lm = WFL_NEG_INF, ls = 0.f;
+        for (int k = 0; k < C; ++k) lse_push(lm, ls, wide_clean(W[(int64_t)(1 + k) * C + s]) + zp[k]);
+        const float y = lm > WFL_NEG_INF ? lm + __logf(ls) - mf : WFL_NEG_INF;
+        ob[(int64_t)t * C + s] = y;
+        const float z = y + wide_clean(xb[(int64_t)t * C + s]);
+        zn[s] = z;
+        top = fmaxf(top, z);
+      }
+    }
+    top = wave_max(top);
+    if (lane == 0) red[(n & 1) * NW + wave] = top;
+    if (tid == 0) ref[t] = R;
+    __syncthreads();
+  }
+  if (dir == 0) {  // ln Z = R + m + log sum exp(z - m) over the last frame
+    const float* zl = zb + ((T - 1) & 1) * C;
+    float m = red[((T - 1) & 1) * NW];
+    for (int q = 1; q < NW; ++q) m = fmaxf(m, red[((T - 1) & 1) * NW + q]);
+    float s = 0.f;
+    if (m > WFL_NEG_INF)
+      for (int i = tid; i < C; i += kWideLogThreads) s += __expf(zl[i] - m);
+    s = wave_sum(s);
+    __syncthreads();  // (red is reused)
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+      float tot = 0.f;
+      for (int q = 0; q < NW; ++q) tot += red[q];
+      const bool live = m > WFL_NEG_INF && m < 3.0e38f;
+      const double z = live ? R + (double)m + log((double)tot) : (double)m;
+      w.zlog[b] = z;
+      logz[b] = (float)z;
+    }
+  }
+}
+
+// dx of a flagged batch: (accumulate ? dx : 0) + gout * addend + coef[b] * gout * exp(alpha + beta - ln Z); one wave per row
+__global__ void __launch_bounds__(256) wide_log_grad_x_kernel(int B, int T, int C, WideWs w, const float* __restrict__ alpha,
+                                                              const float* __restrict__ beta, const float* __restrict__ logz,
+                                                              const float* __restrict__ coef, const float* __restrict__ gout,
+                                                              int accumulate, const float* __restrict__ addend,
+                                                              float* __restrict__ dx) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (int64_t)B * T || !*w.hard) return;
+  const int b = (int)(r / T);
+  const float g = gout ? gout[0] : 1.f;
+  const float cf = (coef ? coef[b] : 1.f) * g;
+  const float zf = logz[b];
+  const bool dead = !(zf > WFL_NEG_INF) || !(zf < __builtin_inff());
+  const float k = dead ? 0.f : (float)(w.cuma[r] + w.cb[r] - w.zlog[b]);
+  for (int i = lane; i < C; i += 64) {
+    const float post = dead ? 0.f : __expf(alpha[r * C + i] + beta[r * C + i] + k);
+    float v = cf * (post == post ? post : 0.f);
+    if (addend) v += g * addend[r * C + i];
+    if (accumulate) v += dx[r * C + i];
+    dx[r * C + i] = v;
+  }
+}
+
+// dW of a flagged batch: every thread owns kWideLogNP entries of dW (start row, then the transition pairs) and walks all
+// (b, t) of the batch -- the frame's alpha_{t-1} and x_t + beta_t staged in LDS -- so that no partial sums are needed:
+//     dW[0][i] += coef_w[b] gout exp(alpha_0[i] + beta_0[i] - ln Z)
+//     dW[1+i][j] += coef_w[b] gout exp(alpha_{t-1}[j] + W[1+i][j] + x_t[i] + beta_t[i] - ln Z)
+constexpr int kWideLogNP = 16;
+__global__ void __launch_bounds__(256) wide_log_grad_w_kernel(const float* __restrict__ x, const float* __restrict__ W, int B, int T,
+                                                              int C, WideWs w, const float* __restrict__ alpha,
+                                                              const float* __restrict__ beta, const float* __restrict__ logz,
+                                                              const float* __restrict__ coef_w, const float* __restrict__ gout,
+                                                              int accumulate, const float* __restrict__ dW_addend,
+                                                              float* __restrict__ dW) {
+  extern __shared__ __attribute__((aligned(16))) char wide_logw_smem[];
+  if (!*w.hard) return;
+  float* ap = reinterpret_cast<float*>(wide_logw_smem);  // [C] alpha_{t-1} (t = 0: the start posteriors' exponents)
+  float* xp = ap + C;                                     // [C] x_t + beta_t + the references - ln Z
+  const int tid = threadIdx.x;
+  const int64_t n = (int64_t)(C + 1) * C;
+  const float g = gout ? gout[0] : 1.f;
+  float acc[kWideLogNP], wv[kWideLogNP];
+  int ii[kWideLogNP], jj[kWideLogNP];  // jj < 0: a start entry (ii = its state); ii < 0: no entry
+#pragma unroll
+  for (int k = 0; k < kWideLogNP; ++k) {
+    const int64_t e = (int64_t)blockIdx.x * kWideLogNP * 256 + tid + k * 256;
+    acc[k] = 0.f, wv[k] = WFL_NEG_INF, ii[k] = -1, jj[k] = -1;
+    if (e < C) {
+      ii[k] = (int)e;
+    } else if (e < n) {
+      const int64_t p = e - C;
+      ii[k] = (int)(p / C), jj[k] = (int)(p % C), wv[k] = wide_clean(W[e]);
+    }
+  }
+  for (int b = 0; b < B; ++b) {
+    const float zf = logz[b];
+    if (!(zf > WFL_NEG_INF) || !(zf < __builtin_inff())) continue;  // (block-uniform)
+    const double lz = w.zlog[b];
+    const int64_t bt = (int64_t)b * T;
+    float ab[kWideLogNP];
+#pragma unroll
+    for (int k = 0; k < kWideLogNP; ++k) ab[k] = 0.f;
+    for (int t = 0; t < T; ++t) {
+      __syncthreads();
+      const int64_t r = bt + t;
+      if (t == 0) {
+        const float k0 = (float)(w.cuma[r] + w.cb[r] - lz);
+        for (int i = tid; i < C; i += 256) ap[i] = alpha[r * C + i] + beta[r * C + i] + k0;
+      } else {
+        const float k1 = (float)(w.cuma[r - 1] + w.cb[r] - lz);
+        for (int i = tid; i < C; i += 256) {
+          ap[i] = alpha[(r - 1) * C + i];
+          xp[i] = wide_clean(x[r * C + i]) + beta[r * C + i] + k1;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kWideLogNP; ++k) {
+        if (ii[k] < 0 || (t == 0) != (jj[k] < 0)) continue;
+        const float v = t == 0 ? ap[ii[k]] : ap[jj[k]] + wv[k] + xp[ii[k]];
+        if (v > WFL_NEG_INF) ab[k] += __expf(v);
+      }
+    }
+    const float cw = (coef_w ? coef_w[b] : 1.f) * g;
+#pragma unroll
+    for (int k = 0; k < kWideLogNP; ++k) acc[k] += cw * ab[k];
+  }
+#pragma unroll
+  for (int k = 0; k < kWideLogNP; ++k) {
+    const int64_t e = (int64_t)blockIdx.x * kWideLogNP * 256 + tid + k * 256;
+    if (e >= n) continue;
+    float v = acc[k];
+    if (dW_addend) v += g * dW_addend[e];
+    if (accumulate) v += dW[e];
+    dW[e] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static int wide_forward(const float* x, const float* W, int B, int T, int C, int semiring, float* alpha, float* beta,
                         int32_t* bptr, float* logz, void* ws, hipStream_t st) {
@@ -996,6 +1245,12 @@ static int wide_forward(const float* x, const float* W, int B, int T, int C, int
       hipLaunchKernelGGL(wide_viterbi_frame_kernel, tiles, dim3(256), 0, st, x, W, B, T, C, t, alpha, bptr);
     return WFL_OK;
   }
+  const size_t llds = wide_log_lds(C);  // (the log-domain repair behind the product: the frame vectors in LDS)
+  if (llds > (size_t)kLdsBytes) {
+    set_error("dense_forward: C=%d classes: the log-domain repair of a flagged batch needs %zu bytes of LDS", C, llds);
+    return WFL_ERR_UNSUPPORTED;
+  }
+  if (llds > 48 * 1024) WFL_HIP_CHECK(set_max_dynamic_lds((const void*)wide_log_sweep_kernel, (int)llds));
   const WideWs w = wide_carve(ws, B, T, C);
   hipLaunchKernelGGL(wide_prep_kernel, dim3((unsigned)C), dim3(256), 0, st, W, C, w);
   hipLaunchKernelGGL(wide_rows_kernel, dim3((unsigned)(((int64_t)B * T + 3) / 4)), dim3(256), 0, st, x, W, B, T, C, w, alpha,
@@ -1006,16 +1261,21 @@ static int wide_forward(const float* x, const float* W, int B, int T, int C, int
       hipLaunchKernelGGL(wide_frame_mfma_kernel, grid, dim3(64 * kWideMfmaWaves), 0, st, x, B, T, C, s, w, alpha, beta);
   }
   hipLaunchKernelGGL(wide_scan_kernel, dim3((unsigned)B), dim3(256), 0, st, B, T, C, w, alpha, beta != nullptr, logz);
+  hipLaunchKernelGGL(wide_log_sweep_kernel, dim3((unsigned)B, beta ? 2u : 1u), dim3(kWideLogThreads), llds, st, x, W, B, T, C, w,
+                     alpha, beta, logz);
   return WFL_OK;
 }
 
-static int wide_grad(const float* x, int B, int T, int C, const float* alpha, const float* beta, const float* logz,
+static int wide_grad(const float* x, const float* W, int B, int T, int C, const float* alpha, const float* beta, const float* logz,
                      const float* coef, const float* coef_w, const float* gout, int accumulate, const float* addend,
                      const float* dW_addend, float* dx, float* dW, float* dW_partial, const void* ws, hipStream_t st) {
   const WideWs w = wide_carve(const_cast<void*>(ws), B, T, C);
-  if (dx)
+  if (dx) {
     hipLaunchKernelGGL(wide_grad_x_kernel, dim3((unsigned)(((int64_t)B * T + 3) / 4)), dim3(256), 0, st, B, T, C, w, alpha, beta,
                        logz, coef, gout, accumulate, addend, dx);
+    hipLaunchKernelGGL(wide_log_grad_x_kernel, dim3((unsigned)(((int64_t)B * T + 3) / 4)), dim3(256), 0, st, B, T, C, w, alpha,
+                       beta, logz, coef, gout, accumulate, addend, dx);
+  }
   if (dW) {
     if (T > 1) {
       const dim3 grid((unsigned)((C + kWideTM - 1) / kWideTM), (unsigned)((C + kWideTN - 1) / kWideTN), (unsigned)wide_split(C));
@@ -1025,6 +1285,10 @@ static int wide_grad(const float* x, int B, int T, int C, const float* alpha, co
     }
     hipLaunchKernelGGL(wide_reduce_w_kernel, dim3((unsigned)(((int64_t)(C + 1) * C + 255) / 256)), dim3(256), 0, st, B, T, C, w,
                        alpha, beta, logz, coef_w, gout, accumulate, dW_addend, dW_partial, dW);
+    const size_t lds = (size_t)8 * C;  // (<= wide_log_lds(C): checked by wide_forward)
+    if (lds > 48 * 1024) WFL_HIP_CHECK(set_max_dynamic_lds((const void*)wide_log_grad_w_kernel, (int)lds));
+    hipLaunchKernelGGL(wide_log_grad_w_kernel, dim3((unsigned)(((int64_t)(C + 1) * C + kWideLogNP * 256 - 1) / (kWideLogNP * 256))),
+                       dim3(256), lds, st, x, W, B, T, C, w, alpha, beta, logz, coef_w, gout, accumulate, dW_addend, dW);
   }
   return WFL_OK;
 }

@@ -713,14 +713,12 @@ def dense_forward(x, W, need_beta=True):
 
 
 def dense_flagged(st):
-    """[B] bool: utterances the probability-domain sweep handed to the log-domain kernels (none beyond the on-chip class
-    count: there the frames of the whole batch are one product per frame, csrc/dense_wide.h, with no second arithmetic).
-    (the workspace's layout is the library's: wfl_dense_workspace_field)"""
+    """[B] bool: utterances the probability-domain sweeps handed to the log-domain kernels.  Beyond the on-chip class
+    count (csrc/dense_wide.h: the frames of the whole batch are one product per frame) the verdict is the batch's, on W:
+    every utterance or none.  (the workspace's layout is the library's: wfl_dense_workspace_field_c)"""
     B, T = st.B, st.T
-    if st.C > N.lib.wfl_dense_on_chip_classes():
-        return torch.zeros(B, dtype=torch.bool, device=st.ws.device)
     off, n = ctypes.c_int64(), ctypes.c_int64()
-    N.check(N.lib.wfl_dense_workspace_field(B, T, N.DENSE_WS_FLAGS, ctypes.byref(off), ctypes.byref(n)))
+    N.check(N.lib.wfl_dense_workspace_field_c(B, T, st.C, N.DENSE_WS_FLAGS, ctypes.byref(off), ctypes.byref(n)))
     return st.ws[off.value:off.value + n.value].view(torch.int32).view(B, 2).ne(0).any(dim=1)
 
 

@@ -313,6 +313,10 @@ int wfl_dense_on_chip_classes(void);
  * utterance to the log-domain kernels. */
 #define WFL_DENSE_WS_FLAGS 0
 int wfl_dense_workspace_field(int B, int T, int field, int64_t* offset_bytes, int64_t* length_bytes);
+/* The same for any class count C.  Beyond wfl_dense_on_chip_classes() the flags are the batch's range verdict on W
+ * (an entry of W[1:] that is -inf, NaN, +inf or more than 2^-60 below its row maximum), the same for every utterance:
+ * such a batch is recomputed by the log-domain launches behind the probability-domain product. */
+int wfl_dense_workspace_field_c(int B, int T, int C, int field, int64_t* offset_bytes, int64_t* length_bytes);
 /* forward_score(intersect(emissions, transitions)) (asg.py:114): logz [B]; alpha, beta [B,T,C] are
  * opaque inputs of wfl_dense_grad in the log semiring (scaled probabilities for utterances served
  * by the probability-domain sweep, log scores for utterances it had to hand to the log-domain

@@ -381,6 +381,17 @@ def test_dense_workspace_flags_lie_inside_the_workspace():
         N.check(N.lib.wfl_dense_workspace_field(B, T, N.DENSE_WS_FLAGS, ctypes.byref(off), ctypes.byref(n)))
         assert n.value == 8 * B and off.value % 4 == 0 and 0 < off.value and off.value + n.value <= total.value
     assert N.lib.wfl_dense_workspace_field(4, 100, 99, ctypes.byref(off), ctypes.byref(n)) != 0
+    # any class count (wfl_dense_workspace_field_c): on chip the same field, beyond it the wide workspace's flags
+    for (B, T, C) in [(1, 1, 193), (3, 7, 200), (130, 9, 257), (32, 250, 1000), (16, 250, 192)]:
+        part, total = ctypes.c_int64(), ctypes.c_int64()
+        N.check(N.lib.wfl_dense_workspace(B, T, C, ctypes.byref(part), ctypes.byref(total)))
+        N.check(N.lib.wfl_dense_workspace_field_c(B, T, C, N.DENSE_WS_FLAGS, ctypes.byref(off), ctypes.byref(n)))
+        assert n.value == 8 * B and off.value % 4 == 0 and 0 < off.value and off.value + n.value <= total.value
+        if C <= N.lib.wfl_dense_on_chip_classes():
+            off2, n2 = ctypes.c_int64(), ctypes.c_int64()
+            N.check(N.lib.wfl_dense_workspace_field(B, T, N.DENSE_WS_FLAGS, ctypes.byref(off2), ctypes.byref(n2)))
+            assert (off2.value, n2.value) == (off.value, n.value)
+    assert N.lib.wfl_dense_workspace_field_c(4, 100, 300, 99, ctypes.byref(off), ctypes.byref(n)) != 0
 
 
 def test_targets_on_device_accepts_tensors_and_lists_alike():
