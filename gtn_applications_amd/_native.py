@@ -1,7 +1,8 @@
-"""ctypes binding of libwfl.so (C ABI declared in include/wfl.h).
+"""ctypes binding of libwfl.so (C ABI declared in include/wfl.h) and the torch extension of the operator paths
+(`ops`: _wfl_torch.so, csrc/torch_ops.cpp).
 
-The library is built in-tree by `__graft_entry__.build()` / `make -C gtn_applications_amd/csrc`.
-There is NO fallback: if the shared object is missing or a symbol cannot be resolved the import
+Both are built in-tree by `__graft_entry__.build()` / `make -C gtn_applications_amd/csrc`.
+There is NO fallback: if a shared object is missing or a symbol cannot be resolved the import
 fails loudly -- the product path never routes around the HIP extension.
 """
 import ctypes
@@ -10,6 +11,8 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8,
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WFL_LIB_PATH") or os.path.join(_HERE, "libwfl.so")  # (override: A/B builds of the kernels)
+OPS_PATH = os.path.join(_HERE, "_wfl_torch.so")
+_BUILD_HINT = "build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C gtn_applications_amd/csrc`"
 
 WFL_OK = 0
 ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME = 1, 2, 3
@@ -63,14 +66,21 @@ def _load():
     import torch  # noqa: F401
 
     if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "or `make -C gtn_applications_amd/csrc`. There is no CPU fallback."
-        )
+        raise ImportError(f"{LIB_PATH} is missing: {_BUILD_HINT}. There is no CPU fallback.")
     return ctypes.CDLL(LIB_PATH)
 
 
+def _load_ops():
+    # autograd nodes, target staging, the CTC step's per-stream state and stream ordering (csrc/torch_ops.cpp)
+    if not os.path.exists(OPS_PATH):
+        raise ImportError(f"{OPS_PATH} is missing: {_BUILD_HINT}.")
+    from . import _wfl_torch
+
+    return _wfl_torch
+
+
 lib = _load()
+ops = _load_ops()
 
 _P = c_void_p  # device pointers and opaque handles travel as void*
 _SIGS = {

@@ -12,6 +12,7 @@ import os
 
 import torch
 
+from .. import _native as N
 from .. import engine as E
 from .. import graph as G
 
@@ -134,22 +135,14 @@ def collapse_and_unpack(paths, garbage_idx, num_replabels):
     return E.split_rows(out, out_lens, torch.int32)
 
 
-_NODE = False
+# csrc/torch_ops.cpp (the step's launches in one native call), or None under WFL_ASG_NATIVE=0 (A/B, tests: the Python
+# spelling of the same sequence below)
+_NODE = N.ops if os.environ.get("WFL_ASG_NATIVE", "1") != "0" else None
 _PHASES = ("lattice_gather", "lattice_chain", "lattice_grad", "dense_chain", "dense_grad")
 
 
 def _native_node():
-    """csrc/torch_ops.cpp (the step's launches in one native call), or None if the extension was not built /
-    WFL_ASG_NATIVE=0 (A/B, tests: the Python spelling of the same sequence below)."""
-    global _NODE
-    if _NODE is False:
-        _NODE = None
-        if os.environ.get("WFL_ASG_NATIVE", "1") != "0":
-            try:
-                from .. import _wfl_torch as mod
-                _NODE = mod if hasattr(mod, "asg_forward") else None
-            except ImportError:
-                pass
+    """The native step (_NODE): csrc/torch_ops.cpp, imported once by _native; None under WFL_ASG_NATIVE=0."""
     return _NODE
 
 
@@ -157,8 +150,6 @@ def max_classes():
     """Largest class count the ASG kernels accept (wfl_dense_max_classes: an index-width bound, 16384 -- up to
     wfl_dense_on_chip_classes() the transition matrix is private to a workgroup, beyond it is streamed from L2 by the
     batched per-frame product of csrc/dense_wide.h).  The reference has no limit (asg.py:198-199)."""
-    from .. import _native as N
-
     return int(N.lib.wfl_dense_max_classes())
 
 
@@ -262,7 +253,7 @@ class ASGLossFunction(torch.autograd.Function):
                 pack = tg.cache[("asg_fal", C)] = E.PackedLattice.asg_force_align(tg.flat, tg.offsets, C, dev)
         need_dx, need_dw = inputs.requires_grad, transitions.requires_grad
         need_grad = need_dx or need_dw
-        node = _native_node()
+        node = _NODE
         timed = node is not None and E.phase_due(_PHASES)  # (a step whose launch groups bench.py brackets with events)
         if node is not None and not timed and not torch.cuda.is_current_stream_capturing():
             # every launch below in one native call (csrc/torch_ops.cpp::asg_forward): the same sequence, ~60 us of host

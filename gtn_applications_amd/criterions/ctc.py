@@ -10,6 +10,7 @@ import os
 
 import torch
 
+from .. import _native as N
 from .. import engine as E
 from .. import graph as G
 
@@ -137,7 +138,7 @@ class _EagerLoss(torch.Tensor):
 
     def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
         if (gradient is None and not retain_graph and not create_graph and inputs is None and fast_backward_enabled()
-                and not torch.is_anomaly_enabled() and _native_node().ctc_fast_backward(self)):
+                and not torch.is_anomaly_enabled() and _NODE.ctc_fast_backward(self)):
             return None
         return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs=inputs)
 
@@ -152,9 +153,7 @@ def fast_backward_enabled():
     torch.Tensor.backward, which is always correct (tests/test_host_library.py pins the fall-back)."""
     global _FAST_BACKWARD_OK
     if _FAST_BACKWARD_OK is None:
-        node = _native_node()
-        built = getattr(node, "built_for_torch", None)
-        _FAST_BACKWARD_OK = bool(built) and built() == torch_release(torch.__version__)
+        _FAST_BACKWARD_OK = _NODE.built_for_torch() == torch_release(torch.__version__)
     return _FAST_BACKWARD and _FAST_BACKWARD_OK
 
 
@@ -163,18 +162,12 @@ def torch_release(version):
     return str(version).split("+")[0]
 
 
+_NODE = N.ops  # the C++ autograd node of the pipelined step (csrc/torch_ops.cpp)
+
+
 def _native_node():
-    """The C++ autograd node of the pipelined step (csrc/torch_ops.cpp), or None if the extension was not built."""
-    global _NODE
-    if _NODE is False:
-        try:
-            from .. import _wfl_torch as _NODE
-        except ImportError:
-            _NODE = None
+    """The C++ autograd node of the pipelined step (_NODE: csrc/torch_ops.cpp, imported once by _native)."""
     return _NODE
-
-
-_NODE = False
 
 
 @E.on_input_device
@@ -183,43 +176,26 @@ def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax):
     kernels take -- routed through the C++ autograd node: same checks, same staging, same launch, but neither the
     forward nor the backward passes through Python's autograd.Function machinery (which costs more host time than
     the step's kernels take on the GPU at the benchmark shape)."""
-    node = _native_node()
-    if (node is not None and type(log_probs) is torch.Tensor and log_probs.is_cuda and log_probs.requires_grad
+    if (type(log_probs) is torch.Tensor and log_probs.is_cuda and log_probs.requires_grad
             and log_probs.dtype == torch.float32 and log_probs.dim() == 3 and log_probs.is_contiguous()
             and torch.is_grad_enabled() and log_probs.shape[1] > 0 and reduction in ("none", "mean")):
-        B, T, C = log_probs.shape
-        dev = log_probs.device
-        if type(targets) in (list, tuple):
-            # staging, upload, checks and launch in one native call (csrc/torch_ops.cpp); None: not its case after all
-            lim = (int(blank_idx), reduction == "mean", fused_log_softmax, E.CTC_FAST_MAX_LEN, E.CTC_FAST_MAX_CLASSES,
-                   E.CTC_FAST_MAX_CLASSES_LONG)
-            tok = None if E.PHASE_EVENTS is None else E._mark("ctc_step")
-            if tok is None:
-                loss = node.ctc_loss_lists(log_probs, targets, *lim)
-            else:  # (profiling: the event pair brackets the launch, not the staging)
+        lim = (int(blank_idx), reduction == "mean", fused_log_softmax, E.CTC_FAST_MAX_LEN, E.CTC_FAST_MAX_CLASSES,
+               E.CTC_FAST_MAX_CLASSES_LONG)
+        tok = None if E.PHASE_EVENTS is None else E._mark("ctc_step")
+        lists = type(targets) in (list, tuple)
+        # staging, upload, checks and launch in one native call (csrc/torch_ops.cpp)
+        loss = _NODE.ctc_loss_lists(log_probs, targets, *lim) if tok is None and lists else None
+        if loss is None:  # profiling, targets that call does not read, or not the hot case after all
+            st = _NODE.stage_targets(targets, log_probs.device) if lists else None
+            if st is None:
+                st = E.targets_on_device(targets, log_probs.device)._st
+            if tok is not None:  # (profiling: the event pair brackets the launch, not the staging)
                 E._event_pool().append(tok[1])  # (recorded too early: take the start event again after the staging)
-                st = node.stage_lists(targets, log_probs)
                 tok = (tok[0], E._event())
-                loss = node.ctc_loss_staged(log_probs, st, *lim)
-                E._done(tok)
-            if loss is not None:
-                loss.__class__ = _EagerLoss
-                return loss
-        tg = E.targets_on_device(targets, dev)
-        if E.ctc_fast_path_ok(tg.max_len, C):
-            if tg.B != B:
-                raise ValueError(f"got {tg.B} targets for a batch of {B}")
-            E.check_labels(tg, C, "CTCLoss")
-            if not 0 <= int(blank_idx) < C:
-                raise ValueError(f"CTCLoss: blank index {blank_idx} is outside [0, {C})")
-            ws, nll = E.ctc_workspace(log_probs, tg.max_len)
-            lse = E.row_lse(log_probs.detach()) if fused_log_softmax else None
-            fac = tg._off_fac + 4 * B * (0 if reduction == "none" else 1)  # byte offset of scale_<reduction>
-            tok = E._mark("ctc_step")
-            words, _ = E.ctc_host_state(log_probs, tg.max_len)
-            loss = node.ctc_step(log_probs, tg.dev_buf, 0, tg._off_flat, fac, fac + 16 * B, tg.max_len, int(blank_idx),
-                                 ws, nll, lse, tg.n, 0 if words is None else words.data_ptr())
+            loss = _NODE.ctc_loss_staged(log_probs, st, *lim)
             E._done(tok)
+        if loss is not None:
+            loss.__class__ = _EagerLoss
             return loss
     fn = _FusedLogSoftmaxCTCLoss if fused_log_softmax else CTCLossFunction
     return fn.apply(log_probs, targets, blank_idx, reduction)

@@ -566,22 +566,14 @@ def _transitions_pack(transitions, B, C, device):
     return _PACK_CACHE.get(key, build)[0]
 
 
-_NODE = False
+# csrc/torch_ops.cpp (the step's launches in one native call), or None under WFL_TRANSDUCER_NATIVE=0 (A/B, tests: the Python
+# spelling of the same sequence below)
+_NODE = N.ops if os.environ.get("WFL_TRANSDUCER_NATIVE", "1") != "0" else None
 _PHASES = ("lattice_gather", "lattice_chain", "lattice_grad")
 
 
 def _native_node():
-    """csrc/torch_ops.cpp (the step's launches in one native call), or None if the extension was not built /
-    WFL_TRANSDUCER_NATIVE=0 (A/B, tests: the Python spelling of the same sequence)."""
-    global _NODE
-    if _NODE is False:
-        _NODE = None
-        if os.environ.get("WFL_TRANSDUCER_NATIVE", "1") != "0":
-            try:
-                from .. import _wfl_torch as mod
-                _NODE = mod if hasattr(mod, "lattice_loss_forward") else None
-            except ImportError:
-                pass
+    """The native step (_NODE): csrc/torch_ops.cpp, imported once by _native; None under WFL_TRANSDUCER_NATIVE=0."""
     return _NODE
 
 
@@ -606,7 +598,7 @@ class TransducerLossFunction(torch.autograd.Function):
         pack, scale, cpos, cneg, _ = _numerator_entry(targets, tokens, lexicon, transitions, C, dev, reduction, B)
         need_grad = inputs.requires_grad or (transition_params is not None and transition_params.requires_grad)
         den = dense = None
-        node = _native_node() if transitions is None else None
+        node = _NODE if transitions is None else None
         timed = node is not None and E.phase_due(_PHASES)  # (a step whose launch groups bench.py brackets with events)
         if node is not None and not timed and not torch.cuda.is_current_stream_capturing():
             # gather, sweeps (with the gradient beside them), loss reduction and join in one native call

@@ -13,6 +13,7 @@
 #include <torch/csrc/autograd/functions/accumulate_grad.h>
 #include <torch/csrc/autograd/python_variable.h>
 #include <torch/extension.h>
+#include <pybind11/numpy.h>
 
 #include <cstdlib>
 #include <cstring>
@@ -46,8 +47,8 @@ void check(int rc, const char* what) { TORCH_CHECK(rc == WFL_OK, what, ": ", wfl
 
 // Loss and gradient of a CTC batch in ONE pipelined launch (wfl_ctc_forward_backward); backward only applies the
 // upstream scalar to the gradient computed here (like torch's own CTC the gradient is produced eagerly).
-//   staged: the uint8 device buffer of engine.CtcTargets (offsets | flat labels | per-utterance factors), addressed
-//   by the byte offsets that follow; ws / nll: the per-stream scratch of engine.ctc_workspace; lse: optional row
+//   staged: the uint8 device buffer of StagedTargets (offsets | flat labels | per-utterance factors), addressed
+//   by the byte offsets that follow; ws / nll: the per-stream scratch of ctc_workspace (below); lse: optional row
 //   log-sum-exps of x (fused log_softmax, ctc.py:107).
 struct CtcStep : public torch::autograd::Function<CtcStep> {
   static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x, const at::Tensor& staged, int64_t off_offsets,
@@ -123,31 +124,40 @@ struct CtcStep : public torch::autograd::Function<CtcStep> {
 };
 
 // ------------------------------------------------------------------------------------------------------------
-// Targets of a batch, staged and uploaded without passing through Python objects: what engine.CtcTargets does
-// (flatten list-of-int-lists -> [int64 offsets | int32 labels | six per-utterance factor arrays] in a pinned ring ->
-// one wfl_upload -> small content-keyed cache), for the one operator whose kernels are shorter than that Python code.
+// Targets of a batch, staged and uploaded without passing through Python objects: list-of-int-lists (or 1-D int
+// tensors) -> [int64 offsets | int32 labels | six per-utterance factor arrays] in a pinned ring -> one wfl_upload ->
+// small content-keyed cache.  The one stager of the package: engine.CtcTargets is a thin wrapper around its handle.
 // ------------------------------------------------------------------------------------------------------------
+// the per-utterance factor arrays behind the labels, in this order: scale_b (1/len_b for "mean", 1 for "none"), then
+// both times +1/B and -1/B (ctc.py:53-58,87, asg.py:116-121,171-179)
+enum Factor { kScaleNone, kScaleMean, kCposNone, kCposMean, kCnegNone, kCnegMean, kFactors };
+const char* const kFactorNames[kFactors] = {"scale_none", "scale_mean", "cpos_none", "cpos_mean", "cneg_none", "cneg_mean"};
+
 struct StagedTargets {
-  at::Tensor dev_buf;  // uint8, device
-  std::string key_bytes;  // [offsets | labels] as staged (confirms a cache hit byte for byte)
+  at::Tensor dev_buf;  // uint8 on the batch's device (CPU: the unpinned host buffer it was staged in)
+  std::string key_bytes;  // [offsets | labels] as staged (confirms a cache hit byte for byte; the host copies)
   int64_t B = 0, n = 0, max_len = 0, off_flat = 0, off_fac = 0;
   long label_min = 0, label_max = -1;
+  py::object owner = py::none();  // the Python wrapper (engine.CtcTargets) handed out for this batch while it is in the cache
   hipStream_t up_stream = nullptr;  // the stream the upload was queued on ...
   hipEvent_t up_event = nullptr;    // ... and this batch's OWN event behind it (the staging slot's event is re-recorded
                                     // by later uploads, possibly on another stream)
-  int slot = 0;
+  int dev_index = 0;  // (an event belongs to the device it was created on)
   StagedTargets() = default;
   StagedTargets(const StagedTargets&) = delete;
   StagedTargets& operator=(const StagedTargets&) = delete;
   ~StagedTargets() {
     if (up_event) free_events(dev_index).push_back(up_event);  // (creating an event costs more than recording one: kept for the next batch)
   }
-  int dev_index = 0;  // (an event belongs to the device it was created on)
   static std::vector<hipEvent_t>& free_events(int dev) {
-    // (never destroyed: the target caches are torn down by static destructors at exit, in no particular order, and
-    // their entries come through here)
-    static auto* pools = new std::unordered_map<int, std::vector<hipEvent_t>>();
+    static auto* pools = new std::unordered_map<int, std::vector<hipEvent_t>>();  // (never destroyed: see g_targets)
     return (*pools)[dev];
+  }
+  // every hand-out: a use on another stream than the one that uploaded the batch is ordered behind the upload
+  void wait_upload() const {
+    if (!up_event) return;
+    const hipStream_t now = c10::hip::getCurrentHIPStream(dev_index).stream();
+    if (now != up_stream) (void)hipStreamWaitEvent(now, up_event, 0);
   }
 };
 
@@ -172,6 +182,7 @@ struct PinnedRing {  // reusable pinned staging buffers; a slot is reused after 
     }
     return buf[slot].data_ptr<uint8_t>();
   }
+  void unused() { i = (i + kSlots - 1) % kSlots; }  // (the slot next() gave out was not uploaded from)
   void uploaded(int slot, hipStream_t stream) {
     if (!ev[slot]) (void)hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming);
     (void)hipEventRecord(ev[slot], stream);
@@ -259,13 +270,27 @@ struct TargetCache {  // per device: ring + LRU of the last 64 distinct batches
   PinnedRing ring;
   LastBatch last;
   using Key = std::tuple<uint64_t, uint64_t, int64_t>;
-  std::list<std::pair<Key, std::shared_ptr<StagedTargets>>> lru;
-  std::map<Key, decltype(lru)::iterator> index;
+  using Lru = std::list<std::pair<Key, std::shared_ptr<StagedTargets>>>;
+  Lru lru;
+  std::map<Key, Lru::iterator> index;
+  void evict(Lru::iterator it) {
+    // the entry lets go of its wrapper (which holds the entry: the cycle ends here) and is no longer recognised
+    it->second->owner = py::none();
+    if (last.st == it->second) last.clear();
+    index.erase(it->first);
+    lru.erase(it);
+  }
 };
-std::unordered_map<int, TargetCache> g_targets;
+// (never destroyed: its entries hold Python objects, which static destructors would release after the interpreter)
+std::unordered_map<int, TargetCache>& g_targets = *new std::unordered_map<int, TargetCache>();
 
-// -> staged targets, or nullptr if `targets` is not a list / tuple of lists / tuples of ints (the caller falls back)
-std::shared_ptr<StagedTargets> stage_targets(const py::handle& targets, const at::Device& dev) {
+// -> staged targets of `dev` (CPU: an unpinned host buffer, nothing uploaded), or nullptr if `targets` is not a list /
+// tuple of lists / tuples of ints or 1-D CPU int64 / int32 tensors (the caller normalises the rows and calls again)
+std::shared_ptr<StagedTargets> stage_targets(const py::handle& targets, const at::Device& device) {
+  TORCH_CHECK(device.is_cuda() || device.is_cpu(), "stage_targets: a CUDA or CPU device, not ", device);
+  const at::Device dev = device.is_cuda() && !device.has_index()
+                             ? at::Device(at::kCUDA, c10::hip::getCurrentHIPStream().device_index())
+                             : device;
   PyObject* t = targets.ptr();
   if (!PyList_Check(t) && !PyTuple_Check(t)) return nullptr;
   const Py_ssize_t B = PySequence_Fast_GET_SIZE(t);
@@ -288,18 +313,19 @@ std::shared_ptr<StagedTargets> stage_targets(const py::handle& targets, const at
       return nullptr;
     total += n, max_len = std::max<int64_t>(max_len, n);
   }
-  TargetCache& tc = g_targets[dev.index()];
-  auto on_this_stream = [&](const std::shared_ptr<StagedTargets>& e) {
-    const hipStream_t now = c10::hip::getCurrentHIPStream(dev.index()).stream();
-    // reused on another stream than the one that uploaded it: order this stream behind the upload
-    if (now != e->up_stream && e->up_event) (void)hipStreamWaitEvent(now, e->up_event, 0);
+  TargetCache& tc = g_targets[dev.is_cuda() ? dev.index() : -1];
+  auto hand_out = [](const std::shared_ptr<StagedTargets>& e) {
+    e->wait_upload();
     return e;
   };
-  if (tc.last.matches(rows, B)) return on_this_stream(tc.last.st);  // the same label objects as last time: nothing to stage
+  if (tc.last.matches(rows, B)) return hand_out(tc.last.st);  // the same label objects as last time: nothing to stage
+  const bool cuda = dev.is_cuda();
   const int64_t off_flat = 8 * (B + 1), off_fac = (off_flat + 4 * std::max<int64_t>(total, 1) + 7) & ~(int64_t)7;
-  const int64_t nbytes = off_fac + 4 * B * 6;
-  int slot;
-  uint8_t* base = tc.ring.next(nbytes + 16, slot);
+  const int64_t nbytes = off_fac + 4 * B * kFactors;
+  int slot = 0;
+  at::Tensor host;  // (CPU: staged where it stays)
+  if (!cuda) host = at::empty({nbytes}, at::TensorOptions().dtype(at::kByte));
+  uint8_t* base = cuda ? tc.ring.next(nbytes + 16, slot) : host.data_ptr<uint8_t>();
   int64_t* off = reinterpret_cast<int64_t*>(base);
   int32_t* flat = reinterpret_cast<int32_t*>(base + off_flat);
   long lo = 0, hi = -1;
@@ -341,9 +367,11 @@ std::shared_ptr<StagedTargets> stage_targets(const py::handle& targets, const at
 #endif
       v = PyLong_AsLong(o);
       if (v == -1 && PyErr_Occurred()) {
+        const bool overflow = PyErr_ExceptionMatches(PyExc_OverflowError);
         PyErr_Clear();
-        tc.ring.i = (tc.ring.i + PinnedRing::kSlots - 1) % PinnedRing::kSlots;  // slot not used
-        return nullptr;  // not ints: the Python path normalises (numpy ints, ranges, ...)
+        if (overflow) throw py::value_error("target label does not fit int32");
+        if (cuda) tc.ring.unused();
+        return nullptr;  // not ints: the Python side normalises (numpy ints, ranges, ...)
       }
       put(v);
     }
@@ -356,66 +384,87 @@ std::shared_ptr<StagedTargets> stage_targets(const py::handle& targets, const at
   if (hit != tc.index.end() && (int64_t)hit->second->second->key_bytes.size() == nkey &&
       memcmp(hit->second->second->key_bytes.data(), base, (size_t)nkey) == 0) {
     tc.lru.splice(tc.lru.begin(), tc.lru, hit->second);
-    tc.ring.i = (tc.ring.i + PinnedRing::kSlots - 1) % PinnedRing::kSlots;  // nothing was uploaded from the slot
+    if (cuda) tc.ring.unused();  // nothing was uploaded from the slot
     auto& e = hit->second->second;
     tc.last.remember(rows, B, e);  // (seen before, by content: next time its objects are recognised without the staging)
-    return on_this_stream(e);
+    return hand_out(e);
   }
-  // per-utterance factors (engine._FACTORS order): scale_none, scale_mean, then both times +1/B and -1/B
+  memset(base + nkey, 0, (size_t)(off_fac - nkey));  // (the alignment gap: the same batch is the same bytes)
   float* fac = reinterpret_cast<float*>(base + off_fac);
   const float inv_b = 1.0f / (float)(B > 0 ? B : 1);
   for (Py_ssize_t b = 0; b < B; ++b) {
     const float ln = (float)(off[b + 1] - off[b]);
     const float mean = ln > 0.f ? 1.0f / ln : 1.0f;
-    fac[b] = 1.0f, fac[B + b] = mean, fac[2 * B + b] = inv_b, fac[3 * B + b] = mean * inv_b;
-    fac[4 * B + b] = -inv_b, fac[5 * B + b] = mean * -inv_b;
+    fac[kScaleNone * B + b] = 1.0f, fac[kScaleMean * B + b] = mean;
+    fac[kCposNone * B + b] = inv_b, fac[kCposMean * B + b] = mean * inv_b;
+    fac[kCnegNone * B + b] = -inv_b, fac[kCnegMean * B + b] = mean * -inv_b;
   }
   auto st = std::make_shared<StagedTargets>();
   st->B = B, st->n = total, st->max_len = max_len, st->off_flat = off_flat, st->off_fac = off_fac;
   st->label_min = lo, st->label_max = hi;
   st->key_bytes.assign(reinterpret_cast<const char*>(base), (size_t)nkey);
-  st->dev_buf = at::empty({nbytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-  const hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
-  check(wfl_upload(st->dev_buf.data_ptr(), base, nbytes, (void*)stream), "stage_targets");
-  tc.ring.uploaded(slot, stream);
-  st->up_stream = stream, st->slot = slot;
-  {
-    st->dev_index = dev.index();
+  st->dev_index = dev.index();
+  if (cuda) {
+    st->dev_buf = at::empty({nbytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    const hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    check(wfl_upload(st->dev_buf.data_ptr(), base, nbytes, (void*)stream), "stage_targets");
+    tc.ring.uploaded(slot, stream);
+    st->up_stream = stream;
     auto& pool = StagedTargets::free_events(st->dev_index);
     if (!pool.empty())
       st->up_event = pool.back(), pool.pop_back();
     else if (hipEventCreateWithFlags(&st->up_event, hipEventDisableTiming) != hipSuccess)
       st->up_event = nullptr;
     if (st->up_event) (void)hipEventRecord(st->up_event, stream);
+  } else {
+    st->dev_buf = host;
   }
-  if (hit != tc.index.end()) {  // (same hash, different bytes: replace)
-    tc.lru.erase(hit->second);
-    tc.index.erase(hit);
-  }
+  if (hit != tc.index.end()) tc.evict(hit->second);  // (same hash, different bytes: replace)
   tc.lru.emplace_front(key, st);
   tc.index[key] = tc.lru.begin();
-  if (tc.lru.size() > 64) {
-    tc.index.erase(tc.lru.back().first);
-    tc.lru.pop_back();
-  }
+  if (tc.lru.size() > 64) tc.evict(std::prev(tc.lru.end()));
   return st;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// What the CTC step keeps between calls, per (device, stream, shape): its workspace and its host-state words.
+// ------------------------------------------------------------------------------------------------------------
 struct WsKey {
   int dev;
   void* stream;
   int64_t B, T, C, L;
   bool operator<(const WsKey& o) const { return std::tie(dev, stream, B, T, C, L) < std::tie(o.dev, o.stream, o.B, o.T, o.C, o.L); }
 };
-std::map<WsKey, std::pair<at::Tensor, at::Tensor>> g_ws;  // (engine.ctc_workspace: scratch + nll per stream and shape)
+WsKey ws_key(const at::Tensor& x, int64_t max_len) {
+  return {x.device().index(), current_stream(x), x.size(0), x.size(1), x.size(2), max_len};
+}
+
+// scratch + per-utterance nll of the pipelined step: consecutive steps on a stream are ordered, so they can share it
+// (the nll is overwritten by the next step of the same shape on the same stream)
+std::map<WsKey, std::pair<at::Tensor, at::Tensor>> g_ws;
+const std::pair<at::Tensor, at::Tensor>& ctc_workspace(const at::Tensor& x, int64_t max_len) {
+  const WsKey wk = ws_key(x, max_len);
+  auto w = g_ws.find(wk);
+  if (w == g_ws.end()) {
+    int64_t n = 0;
+    check(wfl_ctc_workspace((int)wk.B, (int)wk.T, (int)wk.C, (int)max_len, &n), "ctc_workspace");
+    if (g_ws.size() >= 16) g_ws.clear();
+    const auto f32 = x.options().dtype(at::kFloat);
+    w = g_ws.emplace(wk, std::make_pair(at::empty({n}, f32), at::empty({wk.B}, f32))).first;
+  }
+  return w->second;
+}
 
 // The step's memory between calls (wfl_ctc_call::host_state: two pinned int32 per stream and shape, written by the
-// repair launch without anybody waiting).  Handed out from pinned pages that are never freed: a launch still in flight
-// may write its word whatever happens to the workspace cache above.
+// repair launch without anybody waiting).  At most kShapes shapes at once (variable-length training sees thousands),
+// least recently used first out: its pair goes to the next new shape -- a late write of the evicted shape's launch can
+// then only mislead that shape's FIRST choice of launch, never a result.  The pairs are cut from pinned pages that are
+// never freed: a launch still in flight may write its words whatever happens to the workspace above.
 struct HostStatePool {
-  static constexpr size_t kWords = 1024;
+  static constexpr size_t kWords = 1024, kShapes = 256;
   std::mutex mu;
-  std::map<WsKey, int32_t*> table;
+  std::list<std::pair<WsKey, int32_t*>> lru;  // most recently used first
+  std::map<WsKey, decltype(lru)::iterator> index;
   std::vector<int32_t*> pages;
   size_t used = kWords;
 };
@@ -426,21 +475,32 @@ HostStatePool& host_state_pool() {
 int32_t* ctc_host_state(const WsKey& k) {
   HostStatePool& P = host_state_pool();
   std::lock_guard<std::mutex> lock(P.mu);
-  auto it = P.table.find(k);
-  if (it != P.table.end()) return it->second;
+  auto it = P.index.find(k);
+  if (it != P.index.end()) {
+    P.lru.splice(P.lru.begin(), P.lru, it->second);
+    return it->second->second;
+  }
   // (a stream that is being captured into a graph: no allocation, no memory -- the captured step replays one choice)
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing((hipStream_t)k.stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
-  if (P.used + 2 > HostStatePool::kWords) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, HostStatePool::kWords * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return nullptr;
-    memset(p, 0, HostStatePool::kWords * sizeof(int32_t));
-    P.pages.push_back(static_cast<int32_t*>(p));
-    P.used = 0;
+  int32_t* w;
+  if (P.lru.size() >= HostStatePool::kShapes) {
+    w = P.lru.back().second;
+    P.index.erase(P.lru.back().first);
+    P.lru.pop_back();
+  } else {
+    if (P.used + 2 > HostStatePool::kWords) {
+      void* p = nullptr;
+      if (hipHostMalloc(&p, HostStatePool::kWords * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return nullptr;
+      P.pages.push_back(static_cast<int32_t*>(p));
+      P.used = 0;
+    }
+    w = P.pages.back() + P.used;
+    P.used += 2;
   }
-  int32_t* w = P.pages.back() + P.used;
-  P.used += 2;
-  P.table[k] = w;
+  w[0] = w[1] = 0;
+  P.lru.emplace_front(k, w);
+  P.index[k] = P.lru.begin();
   return w;
 }
 // forget what the steps remembered: the next call of every shape starts with the lane-exponent step (tests that run
@@ -451,13 +511,14 @@ void ctc_reset_host_state() {
   for (int32_t* page : P.pages) memset(page, 0, HostStatePool::kWords * sizeof(int32_t));
 }
 
-// CTCLoss(log_probs, targets, blank, reduction) for the hot case, everything between the Python call and the launch
-// in this one function.  Returns None when the case is not the hot one (the caller takes the Python path).
+// CTCLoss(log_probs, targets, blank, reduction) for the hot case, from staged targets to the launch in this one
+// function.  Returns None when the case is not the hot one (the caller takes the Python path).
 py::object ctc_loss_staged(const at::Tensor& x, const std::shared_ptr<StagedTargets>& st, int64_t blank, bool mean,
                            bool fused_lse, int64_t lim_len, int64_t lim_c, int64_t lim_c_long) {
   const auto B = x.size(0), T = x.size(1), C = x.size(2);
   if (!st) return py::none();
   if (!(st->max_len <= lim_len && C <= (st->max_len <= 63 ? lim_c : lim_c_long))) return py::none();
+  TORCH_CHECK(st->dev_buf.device() == x.device(), "ctc_loss_staged: targets staged for another device");
   if (st->B != B) throw py::value_error("got " + std::to_string(st->B) + " targets for a batch of " + std::to_string(B));
   if (st->label_min < 0 || st->label_max >= C) {
     const long bad = st->label_min < 0 ? st->label_min : st->label_max;
@@ -466,23 +527,16 @@ py::object ctc_loss_staged(const at::Tensor& x, const std::shared_ptr<StagedTarg
   }
   if (blank < 0 || blank >= C)
     throw py::value_error("CTCLoss: blank index " + std::to_string(blank) + " is outside [0, " + std::to_string(C) + ")");
-  void* stream = current_stream(x);
-  const WsKey wk{x.device().index(), stream, B, T, C, st->max_len};
-  auto w = g_ws.find(wk);
-  if (w == g_ws.end()) {
-    int64_t n = 0;
-    check(wfl_ctc_workspace((int)B, (int)T, (int)C, (int)st->max_len, &n), "ctc_workspace");
-    if (g_ws.size() >= 16) g_ws.clear();
-    w = g_ws.emplace(wk, std::make_pair(at::empty({n}, x.options()), at::empty({B}, x.options()))).first;
-  }
+  const auto& w = ctc_workspace(x, st->max_len);
   c10::optional<at::Tensor> lse;
   if (fused_lse) {
     lse = at::empty({B, T}, x.options());
-    check(wfl_row_lse(x.data_ptr<float>(), B * T, (int)C, lse->data_ptr<float>(), stream), "row_lse");
+    check(wfl_row_lse(x.data_ptr<float>(), B * T, (int)C, lse->data_ptr<float>(), current_stream(x)), "row_lse");
   }
-  const int64_t fac = st->off_fac + 4 * B * (mean ? 1 : 0);  // scale_<reduction>; cneg_<reduction> is 4 arrays on
-  return py::cast(CtcStep::apply(x, st->dev_buf, 0, st->off_flat, fac, fac + 16 * B, st->max_len, blank, w->second.first,
-                                 w->second.second, lse, st->n, reinterpret_cast<int64_t>(ctc_host_state(wk))));
+  const int64_t scale = st->off_fac + 4 * B * (mean ? kScaleMean : kScaleNone);
+  const int64_t coef = st->off_fac + 4 * B * (mean ? kCnegMean : kCnegNone);
+  return py::cast(CtcStep::apply(x, st->dev_buf, 0, st->off_flat, scale, coef, st->max_len, blank, w.first, w.second, lse,
+                                 st->n, reinterpret_cast<int64_t>(ctc_host_state(ws_key(x, st->max_len)))));
 }
 
 // CTCLoss(log_probs, targets, blank, reduction) for the hot case, everything between the Python call and the launch
@@ -490,17 +544,6 @@ py::object ctc_loss_staged(const at::Tensor& x, const std::shared_ptr<StagedTarg
 py::object ctc_loss_lists(const at::Tensor& x, const py::handle& targets, int64_t blank, bool mean, bool fused_lse,
                           int64_t lim_len, int64_t lim_c, int64_t lim_c_long) {
   return ctc_loss_staged(x, stage_targets(targets, x.device()), blank, mean, fused_lse, lim_len, lim_c, lim_c_long);
-}
-
-std::shared_ptr<StagedTargets> stage_lists(const py::handle& targets, const at::Tensor& like) {
-  return stage_targets(targets, like.device());
-}
-
-at::Tensor ctc_step(const at::Tensor& x, const at::Tensor& staged, int64_t off_offsets, int64_t off_flat,
-                    int64_t off_scale, int64_t off_coef, int64_t max_len, int64_t blank, const at::Tensor& ws,
-                    const at::Tensor& nll, const c10::optional<at::Tensor>& lse, int64_t n_labels, int64_t host_state) {
-  return CtcStep::apply(x, staged, off_offsets, off_flat, off_scale, off_coef, max_len, blank, ws, nll, lse, n_labels,
-                        host_state);
 }
 
 // `loss.backward()` for the loss a CtcStep node returned, without running THIS node on the autograd engine: the gradient
@@ -569,7 +612,7 @@ std::string built_for_torch() { return TORCH_VERSION; }
 // Every launch of an ASG step's forward in ONE native call: counterpart of ASGLossFunction.forward,
 // /root/reference/criterions/asg.py:84-139 (the per-sample graph loop under gtn.parallel_for and the reduction), after
 // the targets have been packed (engine.PackedLattice.asg_force_align, cached per batch).  The Python spelling of the same
-// sequence (criterions/asg.py, kept as the fall-back when this module is missing and for phase timing) is ~15 tensor
+// sequence (criterions/asg.py, kept for phase timing and WFL_ASG_NATIVE=0) is ~15 tensor
 // allocations, 8 ctypes calls, a stream context and three events: 180-205 us of interpreter time per step, against
 // 450 us of kernels at the benchmark shape and ~100 us at a training batch of 8.  Host-side plumbing only.
 //   numerator (force-aligned lattice, lattice engine) on `side_stream`, forked from the current stream; its gradient
@@ -711,7 +754,7 @@ std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, in
 // acceptors has been packed (wfl_transducer_pack_batch, cached per batch): gather (+ row log-sum-exps when the
 // log_softmax of transducer.py:186-187 is fused), the sweeps -- with the emission gradient beside them when asked for and
 // possible --, the loss reduction, the join.  Same sequence as criterions/transducer.py spells in Python (kept for
-// phase timing, transition models and builds without this module).
+// phase timing, transition models and WFL_TRANSDUCER_NATIVE=0).
 // Returns ({loss, xg, alpha, beta, logz, row_lse, dx}, in_launch); dx undefined unless in_launch.
 // ------------------------------------------------------------------------------------------------------------
 std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& x, int64_t desc_ptr, const at::Tensor& ints,
@@ -780,17 +823,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       },
       "waiter's later work after the event of order_mark");
   m.def("built_for_torch", &built_for_torch, "torch version whose headers this module was compiled against");
-  m.def("ctc_step", &ctc_step, "CTC loss + eager gradient in one pipelined launch (C++ autograd node)");
   m.def("asg_forward", &asg_forward, "every launch of an ASG step's forward in one native call (criterions/asg.py)");
   m.def("lattice_loss_forward", &lattice_loss_forward,
         "gather, sweeps (+ the gradient beside them), loss reduction and join of a Transducer step without transitions");
-  m.def("ctc_reset_host_state", &ctc_reset_host_state, "zero the steps' memory of which launch to start with");
+  py::tuple factors((size_t)kFactors);
+  for (int f = 0; f < kFactors; ++f) factors[f] = kFactorNames[f];
+  m.attr("FACTORS") = factors;
   py::class_<StagedTargets, std::shared_ptr<StagedTargets>>(m, "StagedTargets")
       .def_readonly("B", &StagedTargets::B)
       .def_readonly("n", &StagedTargets::n)
-      .def_readonly("max_len", &StagedTargets::max_len);
-  m.def("stage_lists", &stage_lists, "stage + upload list-of-int-list targets (None if they are something else)");
-  m.def("ctc_loss_staged", &ctc_loss_staged, "the second half of ctc_loss_lists (profiling: bracket the launch alone)");
+      .def_readonly("max_len", &StagedTargets::max_len)
+      .def_readonly("label_min", &StagedTargets::label_min)
+      .def_readonly("label_max", &StagedTargets::label_max)
+      .def_readonly("off_flat", &StagedTargets::off_flat)
+      .def_readonly("off_fac", &StagedTargets::off_fac)
+      .def_readonly("dev_buf", &StagedTargets::dev_buf)
+      .def_property_readonly("offsets",
+                             [](const StagedTargets& s) {
+                               return py::array_t<int64_t>(s.B + 1, reinterpret_cast<const int64_t*>(s.key_bytes.data()));
+                             })
+      .def_property_readonly("flat",
+                             [](const StagedTargets& s) {
+                               return py::array_t<int32_t>(s.n, reinterpret_cast<const int32_t*>(s.key_bytes.data() + s.off_flat));
+                             })
+      .def_readwrite("owner", &StagedTargets::owner, "the Python wrapper handed out for this batch (engine.CtcTargets)")
+      .def("wait_upload", &StagedTargets::wait_upload, "order the current stream behind this batch's upload");
+  m.def("stage_targets", &stage_targets,
+        "stage + upload a batch's targets through the content-keyed cache (None if the rows are not lists / tuples of "
+        "ints or 1-D CPU int64 / int32 tensors)");
+  m.def("ctc_loss_staged", &ctc_loss_staged, "the CTC step for staged targets (None: not the hot case)");
   m.def("ctc_loss_lists", &ctc_loss_lists,
         "CTCLoss for list-of-int-list targets: staging, upload, checks and the pipelined launch in one native call");
+  m.def("ctc_workspace", &ctc_workspace, "(scratch, nll) of the CTC step per (device, current stream, shape)");
+  m.def(
+      "ctc_host_state", [](const at::Tensor& x, int64_t max_len) { return reinterpret_cast<int64_t>(ctc_host_state(ws_key(x, max_len))); },
+      "address of the CTC step's two pinned host-state words per (device, current stream, shape); 0 while capturing");
+  m.def("ctc_reset_host_state", &ctc_reset_host_state, "zero the steps' memory of which launch to start with");
 }

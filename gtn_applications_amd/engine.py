@@ -2,10 +2,9 @@
 lattices and the calls into libwfl.so.  torch is plumbing here (device memory + current stream);
 all arithmetic happens in the HIP kernels behind the C ABI (include/wfl.h).
 """
-import collections
 import ctypes
-import os
 import itertools
+import sys
 import threading
 from collections import OrderedDict
 
@@ -151,21 +150,6 @@ def _mark(name):
 def _done(tok):
     if tok is not None:
         PHASE_EVENTS.append((tok[0], tok[1], _event()))
-
-
-_WFLPY = None
-
-
-def _staging_helper():
-    """the CPython helper of the target staging (csrc/wflpy.c), or its numpy stand-in when the extension is missing"""
-    global _WFLPY
-    if _WFLPY is None:
-        try:
-            from . import _wflpy as mod
-        except ImportError:
-            from . import _wflpy_np as mod
-        _WFLPY = mod
-    return _WFLPY
 
 
 def flatten_any(targets):
@@ -479,19 +463,6 @@ def lattice_viterbi(x, pack, weights=None):
 
 
 _SIDE_STREAMS = {}
-_ORDER = False
-
-
-def _order_module():
-    """csrc/torch_ops.cpp's stream-ordering entry points (a ring of device-scope events), or None if it is not built."""
-    global _ORDER
-    if _ORDER is False:
-        try:
-            from . import _wfl_torch as mod
-            _ORDER = mod if hasattr(mod, "order_mark") else None
-        except ImportError:
-            _ORDER = None
-    return _ORDER
 
 
 def _order_after(waiter, signaller):
@@ -499,11 +470,7 @@ def _order_after(waiter, signaller):
     per call; between the criteria's forked streams that record held the host for ~0.4 ms a call whenever the GPU had
     work queued (a Transducer step with a back-off model: 1.17 ms, 1.1 of them host, against 0.41 with the ring of
     device-scope events csrc/torch_ops.cpp keeps: order_event_flags) -- the host could not run ahead of the GPU."""
-    mod = _order_module()
-    if mod is None:
-        waiter.wait_stream(signaller)
-    else:
-        mod.order_after(waiter.cuda_stream, signaller.cuda_stream, waiter.device.index)
+    N.ops.order_after(waiter.cuda_stream, signaller.cuda_stream, waiter.device.index)
 
 
 class side_stream:
@@ -540,19 +507,11 @@ class side_stream:
 
     def mark(self):
         """Event after what has been launched on the side stream so far (call inside the block)."""
-        mod = _order_module()
-        if mod is not None:
-            return mod.order_mark(self.side.cuda_stream, self.side.device.index)
-        ev = torch.cuda.Event()
-        ev.record(self.side)
-        return ev
+        return N.ops.order_mark(self.side.cuda_stream, self.side.device.index)
 
     def join_at(self, ev, *tensors):
         """The current stream waits for the side stream only up to `ev` (work launched after it keeps overlapping)."""
-        if isinstance(ev, int):
-            _order_module().order_wait(self.cur.cuda_stream, ev)
-        else:
-            self.cur.wait_event(ev)
+        N.ops.order_wait(self.cur.cuda_stream, ev)
         for t in tensors:
             if t is not None:
                 t.record_stream(self.cur)
@@ -758,10 +717,10 @@ def upload(dst, pinned, nbytes):
 
 
 class _StagingRing:
-    """Pinned host buffers through which a batch's targets reach the device in ONE asynchronous copy.  A slot is
+    """Pinned host buffers through which a batch's packed lattices reach the device in ONE asynchronous copy.  A slot is
     reused only after the copy that last read it has completed (event per slot)."""
 
-    def __init__(self, slots=8, nbytes=1 << 18):
+    def __init__(self, slots=4, nbytes=1 << 22):
         self.bufs, self.views, self.events = [None] * slots, [None] * slots, [None] * slots
         self.i, self.nbytes = 0, nbytes
 
@@ -783,67 +742,69 @@ class _StagingRing:
             buf = self.bufs[i]
         return i, buf, self.views[i]
 
+    def __del__(self):
+        # (freed with its thread: the buffers go back to torch's pinned pool, which must not hand them out while an
+        # upload still reads them -- at interpreter exit nothing will)
+        if not sys.is_finalizing():
+            for ev in self.events:
+                if ev is not None:
+                    ev.synchronize()
 
-_STAGING = {}
-_LATTICE_STAGING = {}
+
+_LATTICE_RINGS = threading.local()
 
 
 def _lattice_ring(device):
-    """The pinned staging ring of the lattice packers on `device` -- one PER HOST THREAD: Transducer.prepare packs the
-    next batch on a side thread while the caller's thread packs (ASG force alignment, Viterbi, CTC lattices) right
-    after the loss; a ring's cursor, its `ring.i -= 1` retake and its per-slot events are not atomic, and two threads
-    handed the same pinned slot would upload each other's bytes.  (The C++ operator's ring, csrc/torch_ops.cpp
+    """The pinned staging ring of the lattice packers on `device` -- one PER HOST THREAD, freed with it: Transducer.prepare
+    packs the next batch on a side thread while the caller's thread packs (ASG force alignment, Viterbi, CTC lattices)
+    right after the loss; a ring's cursor, its `ring.i -= 1` retake and its per-slot events are not atomic, and two
+    threads handed the same pinned slot would upload each other's bytes.  (The target stager's ring, csrc/torch_ops.cpp
     PinnedRing, is per device and only touched under the GIL without releasing it.)"""
-    key = (device.index, threading.get_ident())
-    ring = _LATTICE_STAGING.get(key)
+    rings = getattr(_LATTICE_RINGS, "by_device", None)
+    if rings is None:
+        rings = _LATTICE_RINGS.by_device = {}
+    ring = rings.get(device.index)
     if ring is None:
-        ring = _LATTICE_STAGING[key] = _StagingRing(slots=4, nbytes=1 << 22)
+        ring = rings[device.index] = _StagingRing()
     return ring
-_FACTORS = ("scale_none", "scale_mean", "cpos_none", "cpos_mean", "cneg_none", "cneg_mean")
+
+
+_FACTORS = N.ops.FACTORS  # (the order of the per-utterance factor arrays behind the labels)
 
 
 class CtcTargets:
     """Targets of a batch as the kernels want them, resident on the device: int64 offsets [B+1], int32 flat labels
     and the per-utterance loss / gradient factors of both reductions (scale_b = 1/len_b for "mean", 1 for "none";
     +-scale_b/B: ctc.py:53-58,87, asg.py:116-121,171-179) in ONE buffer filled on the host and uploaded with one
-    asynchronous copy from pinned memory.  Lists of int lists are flattened by the CPython helper (_wflpy), lists
-    of 1-D tensors by one torch.cat."""
+    asynchronous copy from pinned memory -- by the C++ operator's stager (csrc/torch_ops.cpp stage_targets; on the CPU:
+    a host buffer, nothing uploaded).  A wrapper around its handle: a batch with the same content on the same device
+    is the SAME object while the stager's 64-entry cache holds it, so `cache` (what callers derive from the batch:
+    factor views, packed lattices) survives with it."""
 
-    __slots__ = ("max_len", "B", "dev_buf", "cache", "label_min", "label_max", "n", "_off_flat", "_off_fac", "_key",
-                 "_lens", "_uploaded")
+    __slots__ = ("_st", "cache", "dev_buf", "B", "n", "max_len", "label_min", "label_max", "_lens")
 
-    def __init__(self, targets, device, flat=None, lens=None, _staged=None):
-        self.cache = {}  # derived device objects (factor views, packed lattices), keyed by the caller
-        st = _staged if _staged is not None else _stage_targets(targets, device, flat, lens)
-        slot, host, nbytes, B, n, self.max_len, self.label_min, self.label_max, self._off_flat, self._off_fac, ck = st
-        self._key = (host[1][:ck[2]].tobytes(), ck)  # host copy of [offsets | labels]
-        self.B, self.n, self._lens = B, n, None
-        view = host[1]
-        if device.type == "cuda":
-            ring = _STAGING[(device.index, threading.get_ident())]  # (the ring _stage_targets filled: same thread)
-            self.dev_buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            upload(self.dev_buf, host[0], nbytes)
-            ev = ring.events[slot]
-            if ev is None:
-                ev = ring.events[slot] = torch.cuda.Event()
-            ev.record()  # (the staging slot: reusable once this upload has read it)
-            # the targets' OWN event: a later user on ANOTHER stream orders itself behind the upload (targets_on_device);
-            # the slot's event may have been re-recorded by then, possibly on a different stream
-            own = torch.cuda.Event()
-            own.record()
-            self._uploaded = (stream_ptr(), own)
-        else:  # host-only uses (tests of the packers): same layout, no device
-            self.dev_buf = torch.from_numpy(view[:nbytes].copy())
-            self._uploaded = None
+    def __new__(cls, targets, device):
+        st = N.ops.stage_targets(targets, device)
+        if st is None:  # rows of numpy ints / ranges / tensors the stager does not read: normalise once, stage again
+            st = N.ops.stage_targets([t.tolist() if hasattr(t, "tolist") else [int(v) for v in t] for t in targets],
+                                     device)
+            if st is None:
+                raise TypeError("targets must be a sequence of int sequences or 1-D int tensors")
+        tg = st.owner
+        if tg is None:
+            tg = st.owner = object.__new__(cls)
+            tg._st, tg.cache, tg.dev_buf, tg._lens = st, {}, st.dev_buf, None
+            tg.B, tg.n, tg.max_len, tg.label_min, tg.label_max = st.B, st.n, st.max_len, st.label_min, st.label_max
+        return tg
 
-    # host copies of the staged content (the key bytes hold offsets and labels back to back)
+    # host copies of the staged content
     @property
     def offsets(self):
-        return np.frombuffer(self._key[0], dtype=np.int64, count=self.B + 1)
+        return self._st.offsets
 
     @property
     def flat(self):
-        return np.frombuffer(self._key[0], dtype=np.int32, count=self.n, offset=self._off_flat)
+        return self._st.flat
 
     @property
     def lens(self):
@@ -857,12 +818,11 @@ class CtcTargets:
         if what == "offsets":
             return base
         if what == "flat":
-            return base + self._off_flat
-        return base + self._off_fac + 4 * self.B * _FACTORS.index(what)
+            return base + self._st.off_flat
+        return base + self._st.off_fac + 4 * self.B * _FACTORS.index(what)
 
     def factor(self, what):
-        k = _FACTORS.index(what)
-        lo = self._off_fac + 4 * self.B * k
+        lo = self._st.off_fac + 4 * self.B * _FACTORS.index(what)
         return self.dev_buf[lo:lo + 4 * self.B].view(_F32)
 
     @property
@@ -871,59 +831,8 @@ class CtcTargets:
 
     @property
     def dev_flat(self):
-        return self.dev_buf[self._off_flat:self._off_flat + 4 * max(self.n, 1)].view(torch.int32)
-
-
-def _stage_targets(targets, device, flat=None, lens=None):
-    """Fill a staging slot with [offsets | flat | factors]; returns what CtcTargets needs plus a content key."""
-    _wflpy = _staging_helper()
-
-    key = device.index if device.type == "cuda" else -1
-    ring = _STAGING.get((key, threading.get_ident()))  # (per host thread, as _lattice_ring)
-    if ring is None:
-        ring = _STAGING[(key, threading.get_ident())] = _StagingRing()
-    pinned = device.type == "cuda"
-    B = len(lens) if flat is not None else len(targets)
-    off_flat = 8 * (B + 1)
-    tail = 4 * B * len(_FACTORS) + 16
-    slot, buf, view = ring.next(off_flat + tail + 4096, pinned)
-    if flat is None and len(targets) and all(type(t) is torch.Tensor and t.dim() == 1 and not t.is_cuda for t in targets):
-        lens = [t.numel() for t in targets]
-        flat = torch.cat(targets).to(torch.int32).numpy() if sum(lens) else np.zeros(0, np.int32)
-    if flat is not None:
-        n = int(flat.size)
-        if off_flat + 4 * n + tail > buf.numel():
-            ring.i -= 1
-            slot, buf, view = ring.next(off_flat + 4 * n + tail, pinned)
-        offs = view[:off_flat].view(np.int64)
-        offs[0] = 0
-        np.cumsum(lens, out=offs[1:])
-        view[off_flat:off_flat + 4 * n].view(np.int32)[:] = flat
-        max_len = max(lens) if lens else 0
-        lo, hi = (int(flat.min()), int(flat.max())) if n else (0, -1)
-    else:
-        rows = targets
-        while True:
-            cap = (buf.numel() - off_flat - tail) // 4
-            try:
-                res = _wflpy.flatten_into(rows, buf.data_ptr() + off_flat, cap, buf.data_ptr())
-            except TypeError:  # rows of tensors / ranges / numpy ints: normalise once and retry
-                rows = [t.tolist() if hasattr(t, "tolist") else [int(v) for v in t] for t in rows]
-                continue
-            if res is not None:
-                break
-            need = off_flat + 4 * int(view[:off_flat].view(np.int64)[B]) + tail
-            ring.i -= 1
-            slot, buf, view = ring.next(need, pinned)
-        n, max_len, lo, hi = res
-    off_fac = (off_flat + 4 * max(n, 1) + 7) & ~7
-    nbytes = off_fac + 4 * B * len(_FACTORS)
-    _wflpy.factors_into(buf.data_ptr(), B, buf.data_ptr() + off_fac)  # (the six _FACTORS arrays, in that order)
-    # content key of the batch: a 128-bit hash of [offsets | labels] (hashing the bytes object itself costs Python more
-    # than the staging); a cache hit is confirmed byte for byte before it is used (targets_on_device)
-    nkey = off_flat + 4 * n
-    content = _wflpy.content_key(buf.data_ptr(), nkey) + (nkey, key)
-    return slot, (buf, view), nbytes, B, n, max_len, lo, hi, off_flat, off_fac, content
+        off = self._st.off_flat
+        return self.dev_buf[off:off + 4 * max(self.n, 1)].view(torch.int32)
 
 
 _CTC_WS_SIZES = {}
@@ -1004,82 +913,26 @@ def row_argmax(x):
     return out
 
 
-_CTC_WS_CACHE = {}
-
-
 def ctc_workspace(x, max_len):
     """Scratch of the pipelined step (checkpoints, flags, certificate words) and the per-utterance nll, one per
-    (device, stream, shape): consecutive steps on a stream are ordered, so they can share it -- no allocation per
-    call.  (The returned nll is overwritten by the next step of the same shape on the same stream.)"""
-    B, T, C = x.shape
-    idx = x.device.index
-    key = (idx, torch._C._cuda_getCurrentRawStream(idx), B, T, C, max_len)
-    hit = _CTC_WS_CACHE.get(key)
-    if hit is None:
-        n_ws = _CTC_WS_SIZES.get(key[2:])
-        if n_ws is None:
-            n = ctypes.c_int64()
-            N.check(N.lib.wfl_ctc_workspace(B, T, C, max_len, ctypes.byref(n)))
-            n_ws = _CTC_WS_SIZES[key[2:]] = n.value
-        if len(_CTC_WS_CACHE) >= 16:
-            _CTC_WS_CACHE.clear()
-        hit = _CTC_WS_CACHE[key] = (torch.empty(n_ws, dtype=_F32, device=x.device),
-                                    torch.empty(B, dtype=_F32, device=x.device))
-    return hit
-
-
-_CTC_STATE = collections.OrderedDict()  # (device, stream, shape) -> (pinned word pair, CtcCall), least recently used first
-_CTC_STATE_MAX = 256                    # shapes remembered at once (variable-length training sees thousands)
-_CTC_PAGES = []                         # pinned int32 pages the pairs are cut from (never freed: a launch may still write)
-_CTC_FREE = []                          # word pairs free for reuse: (page tensor, offset)
-
-
-def _ctc_state_slot():
-    if not _CTC_FREE:
-        page = torch.zeros(1024, dtype=torch.int32).pin_memory()  # ONE pinned allocation per 512 shapes
-        _CTC_PAGES.append(page)
-        _CTC_FREE.extend((page, o) for o in range(1022, -1, -2))
-    page, o = _CTC_FREE.pop()
-    words = page[o:o + 2]
-    words.zero_()
-    return words
+    (device, stream, shape), kept by the C++ operator: consecutive steps on a stream are ordered, so they can share it
+    -- no allocation per call.  (The returned nll is overwritten by the next step of the same shape on the same stream.)"""
+    return N.ops.ctc_workspace(x, max_len)
 
 
 def ctc_host_state(x, max_len):
-    """The CTC step's memory between calls (`wfl_ctc_call.host_state`, include/wfl.h): two int32 of pinned host memory
-    per (device, stream, shape) -- the repair launch leaves there how many utterances it recomputed, the next call of
-    the shape reads it (no synchronisation) and picks its launch.  Owned here, by the caller of the C ABI: the pairs
-    are cut from a few pinned pages that are never freed (a launch may still write them), at most _CTC_STATE_MAX shapes
-    are remembered (least recently used first out: its pair goes to the next new shape -- a late write of the evicted
-    shape's launch can then only mislead that shape's FIRST choice of launch, never a result), zeroed by
-    ctc_reset_state().  Returns (pinned words, CtcCall struct)."""
-    B, T, C = x.shape
-    idx = x.device.index
-    key = (idx, torch._C._cuda_getCurrentRawStream(idx), B, T, C, max_len)
-    hit = _CTC_STATE.get(key)
-    if hit is None:
-        if torch.cuda.is_current_stream_capturing():
-            # (a step captured into a graph replays ONE choice and must not allocate: no memory, lane-exponent step first)
-            return None, N.CtcCall(0, None)
-        if len(_CTC_STATE) >= _CTC_STATE_MAX:
-            _, (old_words, _call) = _CTC_STATE.popitem(last=False)
-            _CTC_FREE.append((old_words._base if old_words._base is not None else old_words, old_words.storage_offset()))
-        words = _ctc_state_slot()
-        hit = _CTC_STATE[key] = (words, N.CtcCall(0, words.data_ptr()))
-    else:
-        _CTC_STATE.move_to_end(key)
-    return hit
+    """The CTC step's memory between calls (`wfl_ctc_call.host_state`, include/wfl.h): the address of two int32 of pinned
+    host memory per (device, stream, shape) -- the repair launch leaves there how many utterances it recomputed, the
+    next call of the shape reads it (no synchronisation) and picks its launch.  One pool, the C++ operator's, for every
+    caller: at most 256 shapes (least recently used out, its pair reused), pages never freed (a launch may still write
+    them), zeroed by ctc_reset_state(); 0 while the current stream is being captured (no allocation: the captured step
+    replays one choice)."""
+    return N.ops.ctc_host_state(x, max_len)
 
 
 def ctc_reset_state():
     """Forget which launch the CTC steps preferred (tests that run unrelated data through one shape)."""
-    for words, _ in _CTC_STATE.values():
-        words.zero_()
-    try:
-        from . import _wfl_torch
-    except ImportError:
-        return
-    _wfl_torch.ctc_reset_host_state()
+    N.ops.ctc_reset_host_state()
 
 
 def ctc_forward_backward(x, tg, blank, coef, gout, dx, loss_scale=None, want_loss=False, lse=None, shared_ws=False):
@@ -1100,8 +953,7 @@ def ctc_forward_backward(x, tg, blank, coef, gout, dx, loss_scale=None, want_los
         nll = torch.empty(B, dtype=_F32, device=x.device)
     loss = torch.empty((), dtype=_F32, device=x.device) if want_loss else None
     tok = _mark("ctc_step")
-    words, call = ctc_host_state(x, tg.max_len)
-    call.n_labels = tg.n
+    call = N.CtcCall(tg.n, ctc_host_state(x, tg.max_len) or None)
     N.check(
         N.lib.wfl_ctc_forward_backward_call(ptr(x), B, T, C, ptr(tg.addr("flat")), ptr(tg.addr("offsets")), tg.max_len,
                                             blank, ptr(ws), ptr(nll), ptr(coef), ptr(gout), ptr(dx), ptr(loss_scale),
@@ -1165,27 +1017,10 @@ def loss_factors(tg, reduction, norm_lens=None):
     return hit
 
 
-_TARGET_CACHE = LRU(64)
-
-
 def targets_on_device(targets, device):
-    """Stage and upload the targets of a batch (once per distinct content: a hash of the staged bytes is the key of a
-    small LRU and a hit is confirmed byte for byte, so a repeated batch -- the reference benchmarks reuse one target list -- skips the upload and keeps its
-    derived objects).  A CtcTargets built earlier is passed through."""
+    """Stage and upload the targets of a batch (once per distinct content: the stager's cache, CtcTargets).  A CtcTargets
+    built earlier is passed through -- ordered, like every hand-out of the cache, behind its upload."""
     if isinstance(targets, CtcTargets):
+        targets._st.wait_upload()
         return targets
-    _wflpy = _staging_helper()
-
-    st = _stage_targets(targets, device)
-    data = _TARGET_CACHE.data
-    hit = data.get(st[-1])
-    if hit is not None and _wflpy.same_bytes(st[1][0].data_ptr(), hit._key[0]):
-        data.move_to_end(st[-1])
-        if hit._uploaded is not None and hit._uploaded[0] != stream_ptr():
-            torch.cuda.current_stream().wait_event(hit._uploaded[1])
-        return hit
-    val = data[st[-1]] = CtcTargets(None, device, _staged=st)
-    data.move_to_end(st[-1])
-    if len(data) > _TARGET_CACHE.capacity:
-        data.popitem(last=False)
-    return val
+    return CtcTargets(targets, device)

@@ -4,7 +4,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gtn_applications_amd import engine as E
 from gtn_applications_amd.criterions import ctc
-from gtn_applications_amd import _wfl_torch as node
+from gtn_applications_amd._native import ops as node
 
 B, T, C, L, N = 128, 1000, 100, 44, 1000
 g = torch.Generator().manual_seed(0)
@@ -25,8 +25,8 @@ def timed(fn, n=N, skip=50):
     return host
 
 
-st = node.stage_lists(tg, x)
-print("stage_lists (same targets)   %.1f us" % timed(lambda: node.stage_lists(tg, x)))
+st = node.stage_targets(tg, x.device)
+print("stage_targets (same targets) %.1f us" % timed(lambda: node.stage_targets(tg, x.device)))
 print("ctc_loss_staged (forward)    %.1f us" % timed(lambda: node.ctc_loss_staged(x, st, *lim)))
 print("ctc_loss_lists (forward)     %.1f us" % timed(lambda: node.ctc_loss_lists(x, tg, *lim)))
 print("CTCLoss() (forward)          %.1f us" % timed(lambda: ctc.CTCLoss(x, tg, C - 1)))

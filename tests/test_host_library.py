@@ -707,69 +707,98 @@ def test_asg_has_no_on_chip_class_limit():
         asg.ASG(asg.max_classes(), 1, True)
 
 
-def test_cpp_autograd_extension_is_built_and_exports_the_ctc_node():
+def test_cpp_autograd_extension_is_built_and_exports_the_ctc_loss_entry_points():
     """csrc/torch_ops.cpp -> _wfl_torch.so (no compute call: there is no GPU here)."""
     import torch  # noqa: F401
-    from gtn_applications_amd import _wfl_torch
+    from gtn_applications_amd import _native as N
 
-    assert callable(_wfl_torch.ctc_step)
+    assert callable(N.ops.ctc_loss_staged) and callable(N.ops.ctc_loss_lists)
 
 
-def test_cpython_helper_factors_and_content_key():
-    """_wflpy: per-utterance loss / gradient factors (ctc.py:53-58,87) and the 128-bit content key of the target cache."""
-    from gtn_applications_amd import _wflpy
+def test_staged_targets_factors_and_content_cache():
+    """The stager (csrc/torch_ops.cpp stage_targets) on the CPU: per-utterance loss / gradient factors
+    (ctc.py:53-58,87), and its content-keyed cache -- equal content is the same CtcTargets object, however it is
+    spelled; other content is another."""
+    import torch
 
+    from gtn_applications_amd import engine as E
+
+    cpu = torch.device("cpu")
     lens = [4, 0, 1, 7, 3]
-    off = np.zeros(len(lens) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    B = len(lens)
-    fac = np.full((6, B), np.nan, dtype=np.float32)
-    _wflpy.factors_into(off.ctypes.data, B, fac.ctypes.data)
-    mean = np.array([1.0 / n if n else 1.0 for n in lens], dtype=np.float32)
-    np.testing.assert_array_equal(fac[0], np.ones(B, np.float32))
-    np.testing.assert_array_equal(fac[1], mean)
-    np.testing.assert_allclose(fac[2], np.float32(1.0 / B), rtol=1e-7)
-    np.testing.assert_allclose(fac[3], mean / B, rtol=1e-6)
-    np.testing.assert_allclose(fac[4], -fac[2], rtol=0)
-    np.testing.assert_allclose(fac[5], -fac[3], rtol=0)
     rs = np.random.RandomState(0)
-    buf = rs.randint(0, 256, size=1000).astype(np.uint8)
-    keys = set()
-    for n in (0, 1, 8, 15, 16, 17, 31, 32, 999, 1000):
-        k = _wflpy.content_key(buf.ctypes.data, n)
-        assert k == _wflpy.content_key(buf.copy().ctypes.data, n)  # content, not address
-        keys.add(k)
-    assert len(keys) == 10  # (prefixes of different length hash differently)
-    other = buf.copy()
-    other[500] ^= 1
-    assert _wflpy.content_key(other.ctypes.data, 1000) != _wflpy.content_key(buf.ctypes.data, 1000)
-    assert _wflpy.same_bytes(buf.ctypes.data, buf.tobytes()) and not _wflpy.same_bytes(other.ctypes.data, buf.tobytes())
+    rows = [rs.randint(0, 50, size=n).tolist() for n in lens]
+    tg = E.CtcTargets(rows, cpu)
+    B = len(lens)
+    mean = np.array([1.0 / n if n else 1.0 for n in lens], dtype=np.float32)
+    fac = {f: tg.factor(f).numpy() for f in ("scale_none", "scale_mean", "cpos_none", "cpos_mean", "cneg_none", "cneg_mean")}
+    np.testing.assert_array_equal(fac["scale_none"], np.ones(B, np.float32))
+    np.testing.assert_array_equal(fac["scale_mean"], mean)
+    np.testing.assert_allclose(fac["cpos_none"], np.float32(1.0 / B), rtol=1e-7)
+    np.testing.assert_allclose(fac["cpos_mean"], mean / B, rtol=1e-6)
+    np.testing.assert_allclose(fac["cneg_none"], -fac["cpos_none"], rtol=0)
+    np.testing.assert_allclose(fac["cneg_mean"], -fac["cpos_mean"], rtol=0)
+    for f in fac:
+        assert tg.addr(f) == tg.factor(f).data_ptr()
+    assert E.CtcTargets([list(r) for r in rows], cpu) is tg  # content, not the objects
+    assert E.targets_on_device([torch.tensor(r, dtype=torch.long) for r in rows], cpu) is tg
+    flipped = [list(r) for r in rows]
+    flipped[3][2] ^= 1
+    other = E.CtcTargets(flipped, cpu)
+    assert other is not tg and other.flat.tolist() != tg.flat.tolist()
+    assert E.CtcTargets(rows, cpu) is tg
+    short, longer = E.CtcTargets([[1, 2]], cpu), E.CtcTargets([[1, 2, 0]], cpu)
+    assert short is not longer and short.flat.tolist() == [1, 2] and longer.flat.tolist() == [1, 2, 0]
 
 
-def test_numpy_stand_in_of_the_staging_helper_equals_it():
-    """engine._staging_helper falls back to _wflpy_np when csrc/wflpy.c was not built: same flattening, same factors,
-    same byte comparison (the content key may differ: it only keys a per-process cache)."""
-    from gtn_applications_amd import _wflpy, _wflpy_np
+def test_stager_flattens_rows_of_every_kind():
+    """The one stager: ragged rows (an empty one, a tuple) -> offsets, flat labels, extent; numpy-array rows and range
+    rows (normalised once in Python) stage the same values; a label outside int32 is rejected."""
+    import torch
 
+    from gtn_applications_amd import engine as E
+
+    cpu = torch.device("cpu")
     rows = [[3, 1, 4], [], [1, 5, 9, 2, 6], (5, 3)]
-    B = len(rows)
-    out = {}
-    for name, mod in (("c", _wflpy), ("np", _wflpy_np)):
-        off = np.zeros(B + 1, np.int64)
-        flat = np.full(16, -7, np.int32)
-        fac = np.zeros(6 * B, np.float32)
-        res = mod.flatten_into(rows, flat.ctypes.data, flat.size, off.ctypes.data)
-        mod.factors_into(off.ctypes.data, B, fac.ctypes.data)
-        assert mod.flatten_into(rows, flat.ctypes.data, 3, off.ctypes.data) is None and off[B] == 10  # too small: size reported
-        key = mod.content_key(flat.ctypes.data, 40)
-        assert key == mod.content_key(flat.ctypes.data, 40) and len(key) == 2
-        assert mod.same_bytes(flat.ctypes.data, flat[:10].tobytes()) and not mod.same_bytes(flat.ctypes.data, b"\\x01" * 8)
-        with pytest.raises(TypeError):
-            mod.flatten_into([np.arange(3)], flat.ctypes.data, flat.size, off.ctypes.data)
-        out[name] = (res, off.copy(), flat.copy(), fac.copy())
-    assert out["c"][0] == out["np"][0] == (10, 5, 1, 9)
-    for a, b in zip(out["c"][1:], out["np"][1:]):
-        np.testing.assert_array_equal(a, b)
+    tg = E.CtcTargets(rows, cpu)
+    assert (tg.B, tg.n, tg.max_len, tg.label_min, tg.label_max) == (4, 10, 5, 1, 9)
+    assert tg.offsets.tolist() == [0, 3, 3, 8, 10] and tg.lens == [3, 0, 5, 2]
+    assert tg.flat.tolist() == [3, 1, 4, 1, 5, 9, 2, 6, 5, 3]
+    assert tg.dev_offsets.tolist() == tg.offsets.tolist() and tg.dev_flat.tolist() == tg.flat.tolist()
+    as_numpy = E.CtcTargets([np.asarray(r, dtype=np.int64) for r in rows], cpu)
+    assert as_numpy.offsets.tolist() == tg.offsets.tolist() and as_numpy.flat.tolist() == tg.flat.tolist()
+    ranges = [range(2, 6), range(0), range(7, 4, -1)]
+    as_ranges = E.CtcTargets(ranges, cpu)
+    assert as_ranges.offsets.tolist() == [0, 4, 4, 7] and as_ranges.flat.tolist() == [2, 3, 4, 5, 7, 6, 5]
+    assert (as_ranges.max_len, as_ranges.label_min, as_ranges.label_max) == (4, 2, 7)
+    for bad in (2**31, -(2**31) - 1, 2**70):
+        with pytest.raises(ValueError):
+            E.CtcTargets([[1, 2], [bad]], cpu)
+
+
+def test_stager_stages_lists_tuples_and_int_tensors_byte_identically():
+    """The same batch as lists, as tuples and as 1-D int64 / int32 tensors (a strided one too), each staged afresh:
+    byte-identical buffers [offsets | labels | factors]."""
+    import torch
+
+    from gtn_applications_amd import _native as N
+
+    cpu = torch.device("cpu")
+    rows = [[3, 1, 4], [], [1, 5, 9, 2, 6], [5, 3], [0]]
+    forms = {
+        "lists": rows,
+        "tuples": [tuple(r) for r in rows],
+        "int64": [torch.tensor(r, dtype=torch.int64) for r in rows],
+        "int32": [torch.tensor(r, dtype=torch.int32) for r in rows],
+        "strided": [torch.tensor([v for v in r for _ in (0, 1)], dtype=torch.int64)[::2] for r in rows],
+    }
+    staged = {}
+    for name, batch in forms.items():
+        for k in range(65):  # (other batches first: out of the 64-entry cache, so this one is staged, not found)
+            N.ops.stage_targets([[k, 7, 7, 7]], cpu)
+        staged[name] = N.ops.stage_targets(batch, cpu)
+    bufs = {name: bytes(st.dev_buf.numpy()) for name, st in staged.items()}
+    assert len({id(st) for st in staged.values()}) == len(forms)
+    assert len(set(bufs.values())) == 1, {k: len(v) for k, v in bufs.items()}
 
 
 @pytest.mark.parametrize("blank,repeats", [("none", True), ("optional", True), ("forced", True), ("optional", False)])
