@@ -7,7 +7,7 @@ fails loudly -- the product path never routes around the HIP extension.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint, c_uint8, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WFL_LIB_PATH") or os.path.join(_HERE, "libwfl.so")  # (override: A/B builds of the kernels)
@@ -86,6 +86,7 @@ _P = c_void_p  # device pointers and opaque handles travel as void*
 _SIGS = {
     "wfl_last_error": (c_char_p, []),
     "wfl_version": (c_int, []),
+    "wfl_order_event_flags": (c_uint, []),
     "wfl_free": (None, [_P]),
     # host graph library
     "wfl_graph_new": (_P, []),

@@ -135,15 +135,8 @@ def collapse_and_unpack(paths, garbage_idx, num_replabels):
     return E.split_rows(out, out_lens, torch.int32)
 
 
-# csrc/torch_ops.cpp (the step's launches in one native call), or None under WFL_ASG_NATIVE=0 (A/B, tests: the Python
-# spelling of the same sequence below)
-_NODE = N.ops if os.environ.get("WFL_ASG_NATIVE", "1") != "0" else None
+# the step's launch groups, in the order csrc/torch_ops.cpp::asg_forward takes their timing events
 _PHASES = ("lattice_gather", "lattice_chain", "lattice_grad", "dense_chain", "dense_grad")
-
-
-def _native_node():
-    """The native step (_NODE): csrc/torch_ops.cpp, imported once by _native; None under WFL_ASG_NATIVE=0."""
-    return _NODE
 
 
 def max_classes():
@@ -242,7 +235,7 @@ class ASGLossFunction(torch.autograd.Function):
         if isinstance(targets, PackedNumerator):
             if targets.B != B:
                 raise ValueError(f"got {targets.B} targets for a batch of {B}")
-            tg, pack, scale, cpos, cneg = None, targets.pack, targets.scale, targets.cpos, targets.cneg
+            pack, scale, cpos, cneg = targets.pack, targets.scale, targets.cpos, targets.cneg
         else:
             tg = E.targets_on_device(targets, dev)
             if tg.B != B:
@@ -253,78 +246,34 @@ class ASGLossFunction(torch.autograd.Function):
                 pack = tg.cache[("asg_fal", C)] = E.PackedLattice.asg_force_align(tg.flat, tg.offsets, C, dev)
         need_dx, need_dw = inputs.requires_grad, transitions.requires_grad
         need_grad = need_dx or need_dw
-        node = _NODE
-        timed = node is not None and E.phase_due(_PHASES)  # (a step whose launch groups bench.py brackets with events)
-        if node is not None and not timed and not torch.cuda.is_current_stream_capturing():
-            # every launch below in one native call (csrc/torch_ops.cpp::asg_forward): the same sequence, ~60 us of host
-            # time instead of ~200 (what a step costs at a training batch of 8, where the kernels take less than that)
-            early = need_grad and _EARLY_GRAD and all(E.may_hand_over(t) and t.device == x.device
-                                                      for t in (inputs, transitions) if t.requires_grad)
-            fork = E.side_stream(dev)
-            up = getattr(pack, "_uploaded", None)
-            if up is not None and up[0] not in (E.stream_ptr(), fork.side.cuda_stream):
-                fork.side.wait_event(up[1])  # (a cached pack uploaded on a third stream)
-            loss, da, db, dz, ws, dx_num, dw_num, dx, dW = node.asg_forward(
-                x, W, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cpos, cneg, need_dx, need_dw, early,
-                fork.side.cuda_stream)
-            fcc = E.DenseState()
-            fcc.B, fcc.T, fcc.C, fcc.alpha, fcc.beta, fcc.logz, fcc.ws = B, T, C, da, db, dz, ws
-            ctx.aux = (x, W, fcc, cpos, dx_num, dw_num, fork if need_grad else None)
-            ctx.devices = (inputs.device, transitions.device)
-            ctx.early = None
-            if early:
-                ctx.early = _EarlyGrads(dx, dW, inputs, transitions)
-                ctx.eager_take = ctx.early.take
-                E.watch_node_hooks(ctx)
-            return loss if inputs.is_cuda else loss.cpu()
-        # numerator (force-aligned lattice) and denominator (fully connected) sweeps are independent and
-        # both latency-bound: fork the numerator onto a second stream so that they overlap.  The numerator is
-        # the shorter of the two, so its gradient (for grad_output = 1) is computed right behind its sweeps, still
-        # under the denominator's; backward adds it, scaled by grad_output, inside the denominator's gradient kernel.
-        # (its buffers first, on this stream: the numerator's stream is the longer one, a fill there is a fill on the
-        # step's critical path)
-        E._PHASE_FORCE = timed
-        try:
-            return ASGLossFunction._forward_launches(ctx, inputs, transitions, x, W, tg, pack, scale, cpos, cneg, need_dx,
-                                                     need_dw, dev)
-        finally:
-            E._PHASE_FORCE = False
-
-    @staticmethod
-    def _forward_launches(ctx, inputs, transitions, x, W, tg, pack, scale, cpos, cneg, need_dx, need_dw, dev):
-        """The step's launches, one engine call after the other (asg_forward of csrc/torch_ops.cpp is the same sequence)."""
-        need_grad = need_dx or need_dw
-        dx_num = torch.empty_like(x) if need_dx else None
-        dw_num = torch.zeros_like(W) if need_dw else None
-        with E.side_stream(dev) as fork:
-            for t in (dx_num, dw_num):
-                if t is not None:
-                    t.record_stream(fork.side)
-            fal = E.lattice_forward(x, pack, weights=W, need_beta=need_grad)
-            swept = fork.mark()
-            if need_grad:
-                E.lattice_grad(fal, cneg, coef_w=cneg, gout=None, dx=dx_num, accumulate=False, dW=dw_num)
-        fcc = E.dense_forward(x, W, need_beta=need_grad)
-        # the loss only needs the numerator's sweeps; its gradient keeps running and is joined in backward
-        fork.join_at(swept, fal.xg, fal.alpha, fal.beta, fal.logz)
-        loss = E.reduce_loss(fcc.logz, scale, 1.0, minus=fal.logz)
+        # Every launch of the step in one native call (csrc/torch_ops.cpp::asg_forward): ~60 us of host time instead of
+        # the ~200 the same sequence costs spelled in Python (what a step costs at a training batch of 8, where the
+        # kernels take less than that).  The numerator (force-aligned lattice) and the denominator (fully connected)
+        # sweeps are independent and both latency-bound: the numerator runs on a second stream, its gradient (for
+        # grad_output = 1) right behind its sweeps, still under the denominator's.
+        # `early`: the denominator's gradient right behind its sweeps as well, for grad_output = 1 (with the numerator's
+        # as its addend): between the forward and the backward kernels of a step the GPU otherwise waits ~30 us for the
+        # host to come back through the autograd engine.  `loss.backward()` takes the two buffers as they are
+        # (E.EagerLoss); should the engine run this node after all, backward scales them by grad_output.  Plain leaf
+        # tensors (the reference's asg_benchmark.py:19-31 protocol on device tensors) get them as .grad; a model's
+        # output, an nn.Parameter (the ASG module, anything under DistributedDataParallel) get them as the root
+        # gradients of an engine pass that starts at those tensors (E.EagerLoss.backward).
+        early = need_grad and _EARLY_GRAD and all(E.may_hand_over(t) and t.device == x.device
+                                                  for t in (inputs, transitions) if t.requires_grad)
+        fork = E.side_stream(dev)
+        up = getattr(pack, "_uploaded", None)
+        if up is not None and up[0] not in (E.stream_ptr(), fork.side.cuda_stream):
+            fork.side.wait_event(up[1])  # (a cached pack uploaded on a third stream)
+        phases = E.phase_events("asg", _PHASES)  # (None: no launch group of this step is timed)
+        loss, da, db, dz, ws, dx_num, dw_num, dx, dW = N.ops.asg_forward(
+            x, W, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cpos, cneg, need_dx, need_dw, early,
+            fork.side.cuda_stream, phases or [])
+        fcc = E.DenseState()
+        fcc.B, fcc.T, fcc.C, fcc.alpha, fcc.beta, fcc.logz, fcc.ws = B, T, C, da, db, dz, ws
         ctx.aux = (x, W, fcc, cpos, dx_num, dw_num, fork if need_grad else None)
         ctx.devices = (inputs.device, transitions.device)
         ctx.early = None
-        if need_grad and _EARLY_GRAD and all(E.may_hand_over(t) and t.device == x.device
-                                             for t in (inputs, transitions) if t.requires_grad):
-            # The denominator's gradient right behind its sweeps, for grad_output = 1 (as the numerator's): between the
-            # forward and the backward kernels of a step the GPU otherwise waits ~30 us for the host to come back
-            # through the autograd engine.  `loss.backward()` takes the two buffers as they are (E.EagerLoss); should
-            # the engine run this node after all, backward scales them by grad_output.  Plain leaf tensors (the reference's
-            # asg_benchmark.py:19-31 protocol on device tensors) get them as .grad; a model's output, an nn.Parameter
-            # (the ASG module, anything under DistributedDataParallel) get them as the root gradients of an engine
-            # pass that starts at those tensors (E.EagerLoss.backward).
-            dx = torch.empty_like(x) if need_dx else None
-            dW = torch.empty_like(W) if need_dw else None
-            fork.join(dx_num, dw_num)
-            E.dense_grad(x, W, fcc, cpos, coef_w=cpos, gout=None, dx=dx, accumulate=False, dW=dW, addend=dx_num,
-                         dW_addend=dw_num)
+        if early:
             ctx.early = _EarlyGrads(dx, dW, inputs, transitions)
             ctx.eager_take = ctx.early.take
             E.watch_node_hooks(ctx)

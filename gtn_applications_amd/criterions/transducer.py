@@ -566,15 +566,9 @@ def _transitions_pack(transitions, B, C, device):
     return _PACK_CACHE.get(key, build)[0]
 
 
-# csrc/torch_ops.cpp (the step's launches in one native call), or None under WFL_TRANSDUCER_NATIVE=0 (A/B, tests: the Python
-# spelling of the same sequence below)
-_NODE = N.ops if os.environ.get("WFL_TRANSDUCER_NATIVE", "1") != "0" else None
-_PHASES = ("lattice_gather", "lattice_chain", "lattice_grad")
-
-
-def _native_node():
-    """The native step (_NODE): csrc/torch_ops.cpp, imported once by _native; None under WFL_TRANSDUCER_NATIVE=0."""
-    return _NODE
+# the launch groups of a step without a transition model, in the order csrc/torch_ops.cpp::lattice_loss_forward takes
+# their timing events
+_PHASES = ("lattice_gather", "lattice_chain")
 
 
 class TransducerLossFunction(torch.autograd.Function):
@@ -597,22 +591,22 @@ class TransducerLossFunction(torch.autograd.Function):
         params = E.as_device_f32(transition_params.detach(), dev) if transitions is not None else None
         pack, scale, cpos, cneg, _ = _numerator_entry(targets, tokens, lexicon, transitions, C, dev, reduction, B)
         need_grad = inputs.requires_grad or (transition_params is not None and transition_params.requires_grad)
-        den = dense = None
-        node = _NODE if transitions is None else None
-        timed = node is not None and E.phase_due(_PHASES)  # (a step whose launch groups bench.py brackets with events)
-        if node is not None and not timed and not torch.cuda.is_current_stream_capturing():
-            # gather, sweeps (with the gradient beside them), loss reduction and join in one native call
-            # (csrc/torch_ops.cpp::lattice_loss_forward): the sequence below, without the interpreter between the launches
+        if transitions is None:
+            # gather, sweeps, loss reduction and join in one native call (csrc/torch_ops.cpp::lattice_loss_forward).
+            # The emission gradient is the whole backward pass here: the sweeps' launch computes it for grad_output = 1
+            # as it goes when it can (in_launch), backward scales it and patches what is left.
             up = getattr(pack, "_uploaded", None)
             if up is not None and up[0] != E.stream_ptr():  # a cached pack uploaded on another stream
                 torch.cuda.current_stream().wait_event(up[1])
             want_dx = inputs.requires_grad and _IN_LAUNCH_GRAD
-            (loss, xg, al, be, lz, lse, dx_early), in_launch = node.lattice_loss_forward(
-                x, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cneg, bool(log_softmax), want_dx, need_grad)
+            phases = E.phase_events("transducer", _PHASES)  # (None: no launch group of this step is timed)
+            (loss, xg, al, be, lz, lse, dx_early), in_launch = N.ops.lattice_loss_forward(
+                x, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cneg, bool(log_softmax), want_dx, need_grad,
+                phases or [])
             num = E.LatticeState()
             num.pack, num.T, num.C, num.weights, num.bptr = pack, T, C, None, None
             num.xg, num.alpha, num.beta, num.logz = xg, al, be, lz
-            num.x, num.row_lse, num.in_launch = (x if log_softmax else None), lse, in_launch
+            num.x, num.row_lse = (x if log_softmax else None), lse
             ctx.aux = (x, params, num, None, cpos, cneg, None)
             ctx.early = None
             ctx.devices = (inputs.device, None)
@@ -622,54 +616,33 @@ class TransducerLossFunction(torch.autograd.Function):
                 if ctx.eager_take is not None:
                     E.watch_node_hooks(ctx)
             return loss if inputs.is_cuda else loss.cpu()
-        if transitions is not None:  # normaliser: forward_score(emissions o transitions), transducer.py:286-288
-            # independent of the numerator sweep: forked onto a second stream so that the two overlap
-            with E.side_stream(dev) as fork:
-                if _DENSE_NGRAM and params.numel() == C and _dense_unigram(transitions, C):
-                    # one state, one self-loop per token: the frames are independent and the normaliser is a sum of
-                    # row log-sum-exps of x + p -- no sweep at all
-                    den = _UnigramNormaliser(x, params)
-                    dense = "unigram"
-                elif _DENSE_NGRAM and _dense_bigram(transitions, C):
-                    xd, Wd = _bigram_dense_operands(x, params, C)
-                    den = E.dense_forward(xd, Wd, need_beta=need_grad)
-                    dense = (xd, Wd)
-                else:
-                    den = E.lattice_forward(x, _transitions_pack(transitions, B, C, dev), weights=params,
-                                            need_beta=need_grad)
-        # without a transition model the emission gradient is the whole backward pass: the sweeps' launch computes it
-        # for grad_output = 1 as it goes (E.lattice_forward grad_into), backward scales it and patches what is left
-        dx_early = None
-        if transitions is None and inputs.requires_grad and _IN_LAUNCH_GRAD:
-            dx_early = torch.empty_like(x)
-        E._PHASE_FORCE = timed
-        try:
-            num = E.lattice_forward(x, pack, weights=params, need_beta=need_grad, log_softmax=log_softmax,
-                                    grad_into=(cneg, dx_early) if dx_early is not None else None, defer_join=True)
-        finally:
-            E._PHASE_FORCE = False
-        if not num.in_launch:
-            dx_early = None
-        if den is not None:
-            if dense == "unigram":
-                fork.join(den.xp, den.lse, den.logz)
-            elif dense is not None:
-                fork.join(dense[0], dense[1], den.alpha, den.beta, den.logz, den.ws)
+        # normaliser: forward_score(emissions o transitions), transducer.py:286-288, independent of the numerator sweep:
+        # forked onto a second stream so that the two overlap
+        dense = None
+        with E.side_stream(dev) as fork:
+            if _DENSE_NGRAM and params.numel() == C and _dense_unigram(transitions, C):
+                # one state, one self-loop per token: the frames are independent and the normaliser is a sum of
+                # row log-sum-exps of x + p -- no sweep at all
+                den = _UnigramNormaliser(x, params)
+                dense = "unigram"
+            elif _DENSE_NGRAM and _dense_bigram(transitions, C):
+                xd, Wd = _bigram_dense_operands(x, params, C)
+                den = E.dense_forward(xd, Wd, need_beta=need_grad)
+                dense = (xd, Wd)
             else:
-                fork.join(den.xg, den.alpha, den.beta, den.logz)
-            loss = E.reduce_loss(den.logz, scale, 1.0, minus=num.logz)
+                den = E.lattice_forward(x, _transitions_pack(transitions, B, C, dev), weights=params,
+                                        need_beta=need_grad)
+        num = E.lattice_forward(x, pack, weights=params, need_beta=need_grad, log_softmax=log_softmax)
+        if dense == "unigram":
+            fork.join(den.xp, den.lse, den.logz)
+        elif dense is not None:
+            fork.join(dense[0], dense[1], den.alpha, den.beta, den.logz, den.ws)
         else:
-            loss = E.reduce_loss(num.logz, scale, -1.0)
-        if num.in_launch:
-            E.lattice_side_join()  # (behind the loss reduction: it ran under the tail of the gradient beside the sweeps)
+            fork.join(den.xg, den.alpha, den.beta, den.logz)
+        loss = E.reduce_loss(den.logz, scale, 1.0, minus=num.logz)
         ctx.aux = (x, params, num, den, cpos, cneg, dense)
         ctx.early = None
-        ctx.devices = (inputs.device, None if transition_params is None else transition_params.device)
-        if dx_early is not None:
-            ctx.early = _EarlyGrad(dx_early, num, cneg, inputs)  # (holds no reference to ctx: no cycle to collect)
-            ctx.eager_take = ctx.early.take if E.may_hand_over(inputs) else None
-            if ctx.eager_take is not None:
-                E.watch_node_hooks(ctx)
+        ctx.devices = (inputs.device, transition_params.device)
         return loss if inputs.is_cuda else loss.cpu()
 
     @staticmethod

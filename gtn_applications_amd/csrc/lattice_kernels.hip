@@ -3931,7 +3931,7 @@ struct InLaunchGrad {
   const float* row_lse;
   float* dx;
   int done;        // out: 1 if the launch computed the occupancy gradient
-  int defer_join;  // in: the caller joins the side stream itself (wfl_lattice_side_join), behind more of its own launches
+  int caller_joins;  // in: the caller joins the side stream itself (wfl_lattice_side_join), behind more of its own launches
 };
 static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, const float* floats, const float* xg, int T,
                                 const float* weights, int semiring, float* alpha, float* beta, int32_t* bptr, float* logz,
@@ -3955,6 +3955,8 @@ int wfl_lattice_forward_grad(const wfl_lattice_desc* d, const int32_t* ints, con
   *in_launch = g.done;
   return rc;
 }
+
+unsigned wfl_order_event_flags(void) { return wfl::order_event_flags(); }
 
 int wfl_lattice_side_join(void* stream) {
   SideStream* side = side_stream_of_device();
@@ -4112,7 +4114,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
     // (the gradient beside the sweeps: joined only here -- the certificate and the log-domain launch, which normally
     // finds nothing to do, ran under its tail.  An utterance the log-domain launch re-sweeps while gradient workgroups
     // still read its alpha / beta gets rows of garbage from them; wfl_lattice_grad_rest overwrites exactly those.)
-    if (join_side && !(g && g->defer_join)) WFL_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, join_side->join, 0));
+    if (join_side && !(g && g->caller_joins)) WFL_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, join_side->join, 0));
   } else if (semiring == WFL_SEMIRING_TROPICAL) {
     if (!bptr) {
       set_error("lattice_forward: tropical semiring needs a back-pointer buffer");

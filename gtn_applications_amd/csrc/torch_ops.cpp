@@ -26,18 +26,6 @@
 #include "../../include/wfl.h"
 
 namespace {
-// ordering-only events of this device: no timestamp, a device-scope release when recorded (csrc/device_common.h has the
-// reasoning and the WFL_ORDER_EVENTS switch; kept in step by hand: this file does not include the kernels' headers)
-unsigned order_event_flags() {
-  static const unsigned flags = [] {
-    const char* v = getenv("WFL_ORDER_EVENTS");
-    if (v && !strcmp(v, "nofence")) return (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
-    if (v && !strcmp(v, "default")) return (unsigned)hipEventDisableTiming;
-    return (unsigned)(hipEventDisableTiming | hipEventReleaseToDevice);
-  }();
-  return flags;
-}
-
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
@@ -611,14 +599,15 @@ std::string built_for_torch() { return TORCH_VERSION; }
 // ------------------------------------------------------------------------------------------------------------
 // Every launch of an ASG step's forward in ONE native call: counterpart of ASGLossFunction.forward,
 // /root/reference/criterions/asg.py:84-139 (the per-sample graph loop under gtn.parallel_for and the reduction), after
-// the targets have been packed (engine.PackedLattice.asg_force_align, cached per batch).  The Python spelling of the same
-// sequence (criterions/asg.py, kept for phase timing and WFL_ASG_NATIVE=0) is ~15 tensor
-// allocations, 8 ctypes calls, a stream context and three events: 180-205 us of interpreter time per step, against
-// 450 us of kernels at the benchmark shape and ~100 us at a training batch of 8.  Host-side plumbing only.
+// the targets have been packed (engine.PackedLattice.asg_force_align, cached per batch).  Spelled in Python, one engine
+// call after the other, the same sequence took 180-205 us of interpreter time per step, against 450 us of kernels at the
+// benchmark shape and ~100 us at a training batch of 8.  Host-side plumbing only.
 //   numerator (force-aligned lattice, lattice engine) on `side_stream`, forked from the current stream; its gradient
 //   for grad_output = 1 right behind its sweeps; denominator (dense engine) on the current stream; the loss reduction
 //   after the numerator's sweeps; `early`: the denominator's gradient (+ the numerator's, as its addend) for
 //   grad_output = 1 as well.
+//   `phases`: timing events for bench.py (engine.phase_events), a start / end handle per launch group -- lattice_gather,
+//   lattice_chain, lattice_grad (the numerator's stream), dense_chain, dense_grad (this one) --, 0: not timed.
 // Returns {loss, den_alpha, den_beta, den_logz, den_ws, dx_num, dw_num, dx, dW} (undefined where not asked for).
 // ------------------------------------------------------------------------------------------------------------
 struct EventRing {  // fork / join events of the native steps, per device (created on first use, never destroyed)
@@ -629,7 +618,7 @@ struct EventRing {  // fork / join events of the native steps, per device (creat
   hipEvent_t take() {
     std::lock_guard<std::mutex> lock(mu);
     hipEvent_t& e = ev[next++ % kN];
-    if (!e) TORCH_CHECK(hipEventCreateWithFlags(&e, order_event_flags()) == hipSuccess, "hipEventCreate");
+    if (!e) TORCH_CHECK(hipEventCreateWithFlags(&e, wfl_order_event_flags()) == hipSuccess, "hipEventCreate");
     return e;
   }
 };
@@ -648,6 +637,19 @@ void used_on(const at::Tensor& t, const c10::hip::HIPStream& s) {
 }
 float* fptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
+// The timing events of launch group i of a native step (engine.phase_events): handles ev[2 i] and ev[2 i + 1], recorded
+// on the stream the group runs on right before and right after its launches; 0 (or no pair at all): not timed.
+struct Phase {
+  const std::vector<int64_t>& ev;
+  size_t i;
+  void mark(size_t k, hipStream_t s) const {
+    if (2 * i + k < ev.size() && ev[2 * i + k])
+      TORCH_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(ev[2 * i + k]), s) == hipSuccess, "hipEventRecord");
+  }
+  void start(hipStream_t s) const { mark(0, s); }
+  void end(hipStream_t s) const { mark(1, s); }
+};
+
 c10::hip::HIPStream& fill_stream(int dev) {  // a third stream per device: the step's one fill, off both critical paths
   static std::mutex mu;
   static auto* streams = new std::map<int, c10::hip::HIPStream>();
@@ -659,7 +661,8 @@ c10::hip::HIPStream& fill_stream(int dev) {  // a third stream per device: the s
 
 std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, int64_t desc_ptr, const at::Tensor& ints,
                                     const at::Tensor& floats, const at::Tensor& scale, const at::Tensor& cpos,
-                                    const at::Tensor& cneg, bool need_dx, bool need_dw, bool early, int64_t side_stream) {
+                                    const at::Tensor& cneg, bool need_dx, bool need_dw, bool early, int64_t side_stream,
+                                    const std::vector<int64_t>& phases) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "asg_forward: x must be a contiguous float32 [B,T,C] device tensor");
   TORCH_CHECK(W.is_cuda() && W.scalar_type() == at::kFloat && W.is_contiguous(), "asg_forward: W must be contiguous float32");
@@ -680,7 +683,12 @@ std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, in
   used_on(dx_num, side_s);
   at::Tensor dw_num;
   hipEvent_t filled = nullptr;
-  if (need_dw) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(ms, &cap) == hipSuccess, "hipStreamIsCapturing");
+  if (need_dw && cap != hipStreamCaptureStatusNone) {
+    dw_num = at::zeros_like(W);  // (under capture: on this stream, before the fork -- the fill stream is not in the graph)
+    used_on(dw_num, side_s);
+  } else if (need_dw) {
     const c10::hip::HIPStream& fs = fill_stream(dev);
     c10::hip::HIPStreamGuard guard(fs);  // (the buffer belongs to that stream: nothing of an earlier step can still be using it)
     dw_num = at::zeros_like(W);
@@ -699,16 +707,23 @@ std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, in
     al = at::empty({std::max<int64_t>(n_ab, 1)}, f32);
     if (need_grad) be = at::empty({std::max<int64_t>(n_ab, 1)}, f32);
     lz = at::empty({B}, f32);
+    const Phase gather{phases, 0}, chain{phases, 1}, grad{phases, 2};
+    gather.start(ss);
     check(wfl_lattice_gather(d, ip, x.data_ptr<float>(), T, C, xg.data_ptr<float>(), nullptr, ss), "asg_forward");
+    gather.end(ss), chain.start(ss);
     check(wfl_lattice_forward(d, ip, floats.data_ptr<float>(), xg.data_ptr<float>(), T, W.data_ptr<float>(), WFL_SEMIRING_LOG,
                               al.data_ptr<float>(), fptr(be), nullptr, lz.data_ptr<float>(), ss),
           "asg_forward");
+    chain.end(ss);
     if (filled) TORCH_CHECK(hipStreamWaitEvent(ss, filled, 0) == hipSuccess, "hipStreamWaitEvent");
-    if (need_grad)
+    if (need_grad) {
+      grad.start(ss);
       check(wfl_lattice_grad(d, ip, floats.data_ptr<float>(), xg.data_ptr<float>(), T, C, W.data_ptr<float>(),
                              al.data_ptr<float>(), be.data_ptr<float>(), lz.data_ptr<float>(), cneg.data_ptr<float>(),
                              cneg.data_ptr<float>(), nullptr, 0, nullptr, nullptr, fptr(dx_num), fptr(dw_num), ss),
             "asg_forward");
+      grad.end(ss);
+    }
   }
   hipEvent_t num_done = ring.take();
   TORCH_CHECK(hipEventRecord(num_done, ss) == hipSuccess, "hipEventRecord");
@@ -739,10 +754,17 @@ std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, in
   // launches, rather than on the numerator's stream with an event each way.  (The log-domain launches stay here too:
   // beside the gradient kernel, which fills every SIMD's registers, an "empty" launch of 2 B workgroups only gets
   // through as that kernel's workgroups retire: measured 86 us.)
+  const Phase chain{phases, 3}, grad{phases, 4};
+  chain.start(ms);
   dense_forward(WFL_DENSE_ALL, ms);
+  chain.end(ms);
   TORCH_CHECK(hipStreamWaitEvent(ms, num_done, 0) == hipSuccess, "hipStreamWaitEvent");
   used_on(lz, main_s);
-  if (early) dense_grad(WFL_DENSE_ALL, ms);
+  if (early) {
+    grad.start(ms);
+    dense_grad(WFL_DENSE_ALL, ms);
+    grad.end(ms);
+  }
   check(wfl_reduce_loss(dz.data_ptr<float>(), lz.data_ptr<float>(), scale.data_ptr<float>(), B, 1.0f, 0, loss.data_ptr<float>(), ms),
         "asg_forward");
   return {loss, da, db, dz, ws, dx_num, dw_num, dx, dW};
@@ -753,14 +775,14 @@ std::vector<at::Tensor> asg_forward(const at::Tensor& x, const at::Tensor& W, in
 // TransducerLossFunction.forward, /root/reference/criterions/transducer.py:239-315, after the batch of alignment
 // acceptors has been packed (wfl_transducer_pack_batch, cached per batch): gather (+ row log-sum-exps when the
 // log_softmax of transducer.py:186-187 is fused), the sweeps -- with the emission gradient beside them when asked for and
-// possible --, the loss reduction, the join.  Same sequence as criterions/transducer.py spells in Python (kept for
-// phase timing, transition models and WFL_TRANSDUCER_NATIVE=0).
+// possible --, the loss reduction, the join.  (A Transducer WITH a transition model issues its launches from
+// criterions/transducer.py.)  `phases`: as asg_forward's, for lattice_gather and lattice_chain.
 // Returns ({loss, xg, alpha, beta, logz, row_lse, dx}, in_launch); dx undefined unless in_launch.
 // ------------------------------------------------------------------------------------------------------------
 std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& x, int64_t desc_ptr, const at::Tensor& ints,
                                                               const at::Tensor& floats, const at::Tensor& scale,
                                                               const at::Tensor& cneg, bool log_softmax, bool want_dx,
-                                                              bool need_beta) {
+                                                              bool need_beta, const std::vector<int64_t>& phases) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "lattice_loss_forward: x must be a contiguous float32 [B,T,C] device tensor");
   const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
@@ -775,7 +797,11 @@ std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& 
   at::Tensor lse = log_softmax ? at::empty({B, T}, f32) : at::Tensor();
   at::Tensor dx = (want_dx && need_beta) ? at::empty_like(x) : at::Tensor();
   const int32_t* ip = ints.data_ptr<int32_t>();
+  const Phase gather{phases, 0}, chain{phases, 1};
+  const hipStream_t hs = reinterpret_cast<hipStream_t>(st);
+  gather.start(hs);
   check(wfl_lattice_gather(d, ip, x.data_ptr<float>(), T, C, xg.data_ptr<float>(), fptr(lse), st), "lattice_loss_forward");
+  gather.end(hs), chain.start(hs);
   int flag = 0;
   if (dx.defined()) {
     flag = 2;  // (the join comes behind the loss reduction, which then runs under the gradient's tail)
@@ -788,6 +814,7 @@ std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& 
                               al.data_ptr<float>(), fptr(be), nullptr, lz.data_ptr<float>(), st),
           "lattice_loss_forward");
   }
+  chain.end(hs);
   check(wfl_reduce_loss(lz.data_ptr<float>(), nullptr, scale.data_ptr<float>(), B, -1.0f, 0, loss.data_ptr<float>(), st),
         "lattice_loss_forward");
   const bool in_launch = flag != 0 && dx.defined();
@@ -807,21 +834,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         order_after(reinterpret_cast<hipStream_t>(waiter), reinterpret_cast<hipStream_t>(signaller), dev);
       },
       "waiter's later work after signaller's earlier work (raw stream handles): a pooled device-scope event");
-  m.def(
-      "order_mark",
-      [](int64_t signaller, int dev) {
-        hipEvent_t e = event_ring(dev).take();
-        TORCH_CHECK(hipEventRecord(e, reinterpret_cast<hipStream_t>(signaller)) == hipSuccess, "hipEventRecord");
-        return reinterpret_cast<int64_t>(e);
-      },
-      "a pooled device-scope event recorded behind signaller's work so far (its handle: valid for the next 31 takes)");
-  m.def(
-      "order_wait",
-      [](int64_t waiter, int64_t event) {
-        TORCH_CHECK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(waiter), reinterpret_cast<hipEvent_t>(event), 0) == hipSuccess,
-                    "hipStreamWaitEvent");
-      },
-      "waiter's later work after the event of order_mark");
   m.def("built_for_torch", &built_for_torch, "torch version whose headers this module was compiled against");
   m.def("asg_forward", &asg_forward, "every launch of an ASG step's forward in one native call (criterions/asg.py)");
   m.def("lattice_loss_forward", &lattice_loss_forward,

@@ -120,27 +120,33 @@ def on_input_device(fn):
     return wrapped
 
 
-_PHASE_FORCE = False
-
-
-def phase_due(names):
-    """Will a launch group of `names` be bracketed in THIS step?  For operator paths that issue all their launches in
-    one native call (criterions/asg.py): they take the Python spelling of the same sequence in the steps whose groups
-    are being timed -- under PHASE_STRIDE every PHASE_STRIDE-th step -- with `_PHASE_FORCE` set around it."""
+def phase_events(step, names):
+    """The timing events of a step that issues every launch group of `names` in one native call (csrc/torch_ops.cpp:
+    criterions/asg.py, transducer.py): a start and an end handle per group, 0 for a group not timed, which the call
+    records around the group's launches -- or None when no group of THIS step is timed.  Under PHASE_STRIDE every
+    PHASE_STRIDE-th step of `step` is, with all its groups that are due; each pair goes to PHASE_EVENTS, as _done does."""
     if PHASE_EVENTS is None or (PHASE_ONLY is not None and not any(n in PHASE_ONLY for n in names)):
-        return False
+        return None
     if PHASE_STRIDE > 1:
-        key = "step:" + names[0]
+        key = "step:" + step
         k = _PHASE_COUNT[key] = _PHASE_COUNT.get(key, 0) + 1
         if k % PHASE_STRIDE:
-            return False
-    return True
+            return None
+    handles = []
+    for name in names:
+        if PHASE_ONLY is None or name in PHASE_ONLY:
+            a, b = _event(), _event()  # (recorded once by _event: their HIP events exist; the call records them again)
+            PHASE_EVENTS.append((name, a, b))
+            handles += [a.cuda_event, b.cuda_event]
+        else:
+            handles += [0, 0]
+    return handles
 
 
 def _mark(name):
     if PHASE_EVENTS is None or (PHASE_ONLY is not None and name not in PHASE_ONLY):
         return None
-    if PHASE_STRIDE > 1 and not _PHASE_FORCE:
+    if PHASE_STRIDE > 1:
         k = _PHASE_COUNT[name] = _PHASE_COUNT.get(name, 0) + 1
         if k % PHASE_STRIDE:
             return None
@@ -326,7 +332,7 @@ class PackedLattice:
 class LatticeState:
     """Everything the backward pass needs from a forward pass of the lattice engine."""
 
-    __slots__ = ("pack", "T", "C", "xg", "alpha", "beta", "logz", "weights", "bptr", "x", "row_lse", "in_launch")
+    __slots__ = ("pack", "T", "C", "xg", "alpha", "beta", "logz", "weights", "bptr", "x", "row_lse")
 
 
 def lattice_diagnostics():
@@ -338,22 +344,10 @@ def lattice_diagnostics():
     return dict(zip(names, (int(v) for v in out)))
 
 
-def lattice_side_join():
-    """The current stream waits for the gradient workgroups that ran beside the sweeps (lattice_forward with
-    defer_join=True)."""
-    N.check(N.lib.wfl_lattice_side_join(stream_ptr()))
-
-
-def lattice_forward(x, pack, weights=None, need_beta=True, semiring=N.SEMIRING_LOG, log_softmax=False, grad_into=None,
-                    defer_join=False):
+def lattice_forward(x, pack, weights=None, need_beta=True, semiring=N.SEMIRING_LOG, log_softmax=False):
     """forward_score(intersect(emissions, A_b)) for every b: returns a LatticeState whose `logz`
     holds the per-utterance score (gtn call sites: ctc.py:50, asg.py:111, stc.py:86,
-    transducer.py:283,287).
-
-    grad_into = (coef, dx): ask the sweeps' launch to compute the emission gradient for grad_output = 1 as well
-    (wfl_lattice_forward_grad); `st.in_launch` says whether it did -- lattice_grad_rest finishes the job.
-    defer_join=True: if it did, the caller MUST call lattice_side_join() before anything else touches dx, alpha or
-    beta (it queues the loss reduction first, which then runs under the gradient's tail)."""
+    transducer.py:283,287)."""
     B, T, C = x.shape
     d = pack.desc
     up = getattr(pack, "_uploaded", None)
@@ -382,24 +376,12 @@ def lattice_forward(x, pack, weights=None, need_beta=True, semiring=N.SEMIRING_L
     N.check(N.lib.wfl_lattice_gather(pack._desc_ref, ptr(pack.ints), ptr(x), T, C, ptr(st.xg), ptr(st.row_lse), s))
     _done(tok)
     tok = _mark("lattice_chain" + tag)
-    st.in_launch = False
-    if grad_into is not None and st.beta is not None:
-        coef, dx = grad_into
-        flag = ctypes.c_int(2 if defer_join else 0)
-        N.check(
-            N.lib.wfl_lattice_forward_grad(
-                pack._desc_ref, ptr(pack.ints), ptr(pack.floats), ptr(st.xg), T, C, ptr(weights), ptr(st.alpha),
-                ptr(st.beta), ptr(st.logz), ptr(coef), ptr(st.x), ptr(st.row_lse), ptr(dx), ctypes.byref(flag), s,
-            )
+    N.check(
+        N.lib.wfl_lattice_forward(
+            pack._desc_ref, ptr(pack.ints), ptr(pack.floats), ptr(st.xg), T, ptr(weights), semiring,
+            ptr(st.alpha), ptr(st.beta), ptr(st.bptr), ptr(st.logz), s,
         )
-        st.in_launch = bool(flag.value)
-    else:
-        N.check(
-            N.lib.wfl_lattice_forward(
-                pack._desc_ref, ptr(pack.ints), ptr(pack.floats), ptr(st.xg), T, ptr(weights), semiring,
-                ptr(st.alpha), ptr(st.beta), ptr(st.bptr), ptr(st.logz), s,
-            )
-        )
+    )
     _done(tok)
     return st
 
@@ -431,8 +413,8 @@ def lattice_grad(st, coef, coef_w=None, gout=None, dx=None, accumulate=False, dW
 
 
 def lattice_grad_rest(st, coef, gout, dx):
-    """After a forward pass with st.in_launch: dx (already scaled by grad_output) gets the rows of the utterances the
-    launch did not serve (wfl_lattice_grad_rest)."""
+    """After a forward pass whose launch computed the emission gradient beside the sweeps (wfl_lattice_forward_grad):
+    dx (already scaled by grad_output) gets the rows of the utterances the launch did not serve (wfl_lattice_grad_rest)."""
     p = st.pack
     tok = _mark("lattice_grad" + ("/shared" if p.desc.shared else ""))
     N.check(
@@ -469,7 +451,7 @@ def _order_after(waiter, signaller):
     """`waiter`'s later work after `signaller`'s earlier work.  torch's Stream.wait_stream creates and records an event
     per call; between the criteria's forked streams that record held the host for ~0.4 ms a call whenever the GPU had
     work queued (a Transducer step with a back-off model: 1.17 ms, 1.1 of them host, against 0.41 with the ring of
-    device-scope events csrc/torch_ops.cpp keeps: order_event_flags) -- the host could not run ahead of the GPU."""
+    device-scope events csrc/torch_ops.cpp keeps: wfl_order_event_flags) -- the host could not run ahead of the GPU."""
     N.ops.order_after(waiter.cuda_stream, signaller.cuda_stream, waiter.device.index)
 
 
@@ -504,17 +486,6 @@ class side_stream:
         for t in tensors:
             if t is not None:
                 t.record_stream(cur)
-
-    def mark(self):
-        """Event after what has been launched on the side stream so far (call inside the block)."""
-        return N.ops.order_mark(self.side.cuda_stream, self.side.device.index)
-
-    def join_at(self, ev, *tensors):
-        """The current stream waits for the side stream only up to `ev` (work launched after it keeps overlapping)."""
-        N.ops.order_wait(self.cur.cuda_stream, ev)
-        for t in tensors:
-            if t is not None:
-                t.record_stream(self.cur)
 
 
 class EagerLoss(torch.Tensor):

@@ -43,6 +43,9 @@ extern "C" {
 
 const char* wfl_last_error(void);
 int wfl_version(void);
+/* hipEventCreateWithFlags flags of the library's stream-ordering events (fork / join of its side streams), as chosen
+ * by WFL_ORDER_EVENTS (csrc/device_common.h): for callers that order their own streams the same way. */
+unsigned wfl_order_event_flags(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Host WFST library (replaces gtn.Graph and the graph functions the criteria call)
