@@ -3734,6 +3734,8 @@ __global__ void __launch_bounds__(256) scale_kernel(float* __restrict__ v, int64
   for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] *= f;
 }
 
+#include "lattice_streamed.h"
+
 }  // namespace wfl
 
 using namespace wfl;
@@ -3757,6 +3759,50 @@ static void ab_tail(const wfl_lattice_desc& d, int T, int64_t& tail, int& nch1) 
   tail = ab_main_elems(d, T);
 }
 
+static int64_t ab_tuned_elems(const wfl_lattice_desc& d, int T) {
+  int64_t tail;
+  int nch1;
+  ab_tail(d, T, tail, nch1);
+  // (+ kDumpDoubles doubles behind the tail: where the lanes without a state of the unrolled sweeps "store")
+  // (+ behind that: a progress word per utterance, and -- alpha only -- `bad` and the OccHeader lists)
+  // (... + the in-flight gradient's header: OccHeader, its per-tile words last)
+  return tail + 2 * ((int64_t)d.B * nch1 + d.B) + 2 * (int64_t)d.B + 2 + 2 * kDumpDoubles + 12 * (int64_t)d.B + 32 + 2048 + 4 +
+         16 + (int64_t)d.B * (T / kLiveTile + 2);
+}
+
+// ---- streamed sweeps (lattice_streamed.h): acceptors whose arcs do not fit LDS ----------------------------------
+// WFL_LATTICE_STREAMED (tests; read once per process): unset = automatic, 1 = every log / tropical sweep and gradient
+// streamed with the states in LDS where they fit, 2 = the same with the state vectors in global memory
+static int streamed_env() {
+  static const int v = [] {
+    const char* e = getenv("WFL_LATTICE_STREAMED");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
+}
+// emission rows per chunk of the streamed sweeps (their renormalisation interval: the gradient needs the same number)
+static int stream_rpc(const wfl_lattice_desc& d) {
+  return std::max(2, std::min(16, kStreamThreads * kPre / std::max(1, d.max_labels)) & ~1);  // even: 8-byte aligned LDS behind the rows
+}
+static size_t stream_lds_bytes(const wfl_lattice_desc& d, bool states_in_lds) {
+  return (size_t)2 * stream_rpc(d) * d.max_labels * 4 + 64 * 4 + (states_in_lds ? (size_t)2 * d.max_states * 8 : 0);
+}
+// The path of a descriptor, decided from its maxima for the whole batch -- the same answer for the sweeps, the
+// gradient and the workspace query: 0 = the tuned launches (run_chain: the acceptor fits LDS), 1 = streamed with the
+// state vectors in LDS, 2 = streamed with the state vectors in the alpha / beta arrays
+static int stream_mode(const wfl_lattice_desc& d) {
+  const int env = streamed_env();
+  if (env != 1 && env != 2) {
+    int nt, rpc;
+    chain_config(d, nt, rpc);
+    if (chain_lds_bytes(d, rpc) <= (size_t)kLdsBytes) return 0;
+  }
+  return env != 2 && stream_lds_bytes(d, true) <= (size_t)kLdsBytes ? 1 : 2;
+}
+// where the streamed area starts in the alpha buffer (float units, behind the tuned layout; 16-byte aligned)
+static int64_t stream_area_off(const wfl_lattice_desc& d, int T) { return (ab_tuned_elems(d, T) + 3) & ~(int64_t)3; }
+static std::atomic<uint64_t> g_streamed_launches{0};  // wfl_lattice_diagnostics out[8]
+
 int wfl_lattice_workspace(const wfl_lattice_desc* d, int T, int64_t* xg_elems, int64_t* ab_elems) {
   if (!d || T < 0) {
     set_error("lattice_workspace: bad arguments");
@@ -3764,16 +3810,85 @@ int wfl_lattice_workspace(const wfl_lattice_desc* d, int T, int64_t* xg_elems, i
   }
   // xg: log-domain rows | probability-domain factors of the same rows | one reference per row
   if (xg_elems) *xg_elems = 2 * xg_main(*d, T) + (int64_t)d->B * T;
-  if (ab_elems) {
-    int64_t tail;
-    int nch1;
-    ab_tail(*d, T, tail, nch1);
-    // (+ kDumpDoubles doubles behind the tail: where the lanes without a state of the unrolled sweeps "store")
-    // (+ behind that: a progress word per utterance, and -- alpha only -- `bad` and the OccHeader lists)
-    // (... + the in-flight gradient's header: OccHeader, its per-tile words last)
-    *ab_elems = tail + 2 * ((int64_t)d->B * nch1 + d->B) + 2 * (int64_t)d->B + 2 + 2 * kDumpDoubles + 12 * (int64_t)d->B + 32 + 2048 + 4 +
-                16 + (int64_t)d->B * (T / kLiveTile + 2);
+  if (ab_elems) *ab_elems = stream_mode(*d) ? stream_area_off(*d, T) + stream_area_words(*d) : ab_tuned_elems(*d, T);
+  return WFL_OK;
+}
+
+// the streamed sweeps: the arc pre-pass, then one workgroup per (utterance, direction)
+static int lattice_forward_streamed(const wfl_lattice_desc* d, const int32_t* ints, const float* floats, const float* xg,
+                                    int T, const float* weights, int semiring, float* alpha, float* beta, int32_t* bptr,
+                                    float* logz, void* stream, int mode) {
+  if (semiring != WFL_SEMIRING_LOG && semiring != WFL_SEMIRING_TROPICAL) {
+    set_error("lattice_forward: unknown semiring %d", semiring);
+    return WFL_ERR_INVALID;
   }
+  if (semiring == WFL_SEMIRING_TROPICAL && !bptr) {
+    set_error("lattice_forward: tropical semiring needs a back-pointer buffer");
+    return WFL_ERR_INVALID;
+  }
+  int64_t tail;
+  int nch1;
+  ab_tail(*d, T, tail, nch1);
+  const hipStream_t s = (hipStream_t)stream;
+  const int work = 3 * d->max_arcs + 2 * d->max_eps;
+  const unsigned bx = (unsigned)std::max(1, std::min(256, (work + 255) / 256));
+  hipLaunchKernelGGL(stream_stage_kernel, dim3(bx, d->shared ? 1u : (unsigned)d->B), dim3(256), 0, s, *d, ints, floats,
+                     weights, reinterpret_cast<int32_t*>(alpha + stream_area_off(*d, T)));
+  WFL_LAUNCH_CHECK();
+  const int R = stream_rpc(*d);
+  const size_t lds = stream_lds_bytes(*d, mode == 1);
+  const bool log = semiring == WFL_SEMIRING_LOG;
+  const dim3 grid((unsigned)d->B, log && beta ? 2u : 1u);
+  auto launch = [&](auto kern) -> int {
+    if (lds > 48 * 1024) WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)kern, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(kStreamThreads), lds, s, *d, ints, floats, xg, T, R, alpha, log ? beta : nullptr,
+                       log ? nullptr : bptr, logz, tail, nch1, stream_area_off(*d, T));
+    return WFL_OK;
+  };
+  int rc;
+  if (log)
+    rc = mode == 1 ? launch(stream_chain_kernel<WFL_SEMIRING_LOG, true>) : launch(stream_chain_kernel<WFL_SEMIRING_LOG, false>);
+  else
+    rc = mode == 1 ? launch(stream_chain_kernel<WFL_SEMIRING_TROPICAL, true>)
+                   : launch(stream_chain_kernel<WFL_SEMIRING_TROPICAL, false>);
+  if (rc) return rc;
+  WFL_LAUNCH_CHECK();
+  g_streamed_launches.fetch_add(1);
+  return WFL_OK;
+}
+
+// the gradient of streamed sweeps: emission rows per (utterance, tile of frames), learnable weights arc-major
+static int lattice_grad_streamed(const wfl_lattice_desc* d, const int32_t* ints, const float* floats, const float* xg, int T,
+                                 int C, const float* weights, const float* alpha, const float* beta, const float* logz,
+                                 const float* coef, const float* coef_w, const float* gout, int accumulate, const float* x,
+                                 const float* row_lse, float* dx, float* dW, void* stream) {
+  int64_t tail;
+  int nch1;
+  ab_tail(*d, T, tail, nch1);
+  const hipStream_t s = (hipStream_t)stream;
+  const int R = stream_rpc(*d);
+  if (dx) {
+    const int Kmax = std::max(1, d->max_labels);
+    // frames per workgroup: a few workgroups per CU over the batch, the [TS][labels] tile within 64 KiB
+    const int TS = std::max(1, std::min({16, (int)std::min<int64_t>(16, (int64_t)T * d->B / 512), 16384 / Kmax}));
+    const size_t lds = (((size_t)TS * Kmax + 1) & ~(size_t)1) * 4 + 8 * (size_t)TS + 4 * ((size_t)Kmax + 2) + 2 * (size_t)C + 16;
+    if (lds > (size_t)kLdsBytes) {
+      set_error("lattice_grad: needs %zu B of LDS (limit %d)", lds, kLdsBytes);
+      return WFL_ERR_UNSUPPORTED;
+    }
+    if (lds > 48 * 1024) WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)stream_grad_kernel, (int)lds));
+    hipLaunchKernelGGL(stream_grad_kernel, dim3((unsigned)((T + TS - 1) / TS), (unsigned)d->B), dim3(256), lds, s, *d, ints,
+                       floats, xg, T, C, R, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, TS, tail, nch1,
+                       stream_area_off(*d, T));
+    WFL_LAUNCH_CHECK();
+  }
+  const int nba = (d->max_arcs + 255) / 256, nbe = (d->max_eps + 255) / 256;
+  if (dW && nba + nbe > 0) {
+    hipLaunchKernelGGL(stream_dw_kernel, dim3((unsigned)(nba + nbe), (unsigned)d->B), dim3(256), 0, s, *d, ints, floats, xg,
+                       T, R, weights, alpha, beta, logz, coef_w, gout, dW, nba, tail, nch1);
+    WFL_LAUNCH_CHECK();
+  }
+  g_streamed_launches.fetch_add(1);
   return WFL_OK;
 }
 
@@ -3979,6 +4094,8 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
     set_error("lattice_forward: %d distinct labels per utterance (limit 1024)", d->max_labels);
     return WFL_ERR_UNSUPPORTED;
   }
+  if (const int mode = stream_mode(*d))
+    return lattice_forward_streamed(d, ints, floats, xg, T, weights, semiring, alpha, beta, bptr, logz, stream, mode);
   int nt, rpc, nch1;
   int64_t tail;
   chain_config(*d, nt, rpc);
@@ -4172,6 +4289,9 @@ static int lattice_grad_impl(const wfl_lattice_desc* d, const int32_t* ints, con
     return WFL_ERR_INVALID;
   }
   if (T <= 0) return WFL_OK;
+  if (stream_mode(*d))  // (the sweeps took the same decision: the streamed layout)
+    return lattice_grad_streamed(d, ints, floats, xg, T, C, weights, alpha, beta, logz, coef, coef_w, gout, accumulate, x,
+                                 row_lse, dx, dW, stream);
   // frames per LDS sub-tile: alpha, beta, gathered emissions and the per-label accumulators of TS
   // frames; ~40 KiB at most so that several workgroups are co-resident (each one is a load ->
   // barrier -> compute -> barrier -> stream-out sequence, overlap comes from co-residency).  Measured on MI355X
@@ -4344,15 +4464,16 @@ int wfl_lattice_diagnostics(uint64_t* out, int n) {
   }
   LiveState& ls = live_state();
   std::lock_guard<std::mutex> lock(ls.mu);
-  const uint64_t v[8] = {ls.attempts,
+  const uint64_t v[9] = {ls.attempts,
                          ls.host ? (uint64_t) * (volatile uint32_t*)&ls.host[0] : 0,
                          ls.host ? (uint64_t) * (volatile uint32_t*)&ls.host[1] : 0,
                          ls.skipped,
                          ls.backoff_left,
                          ls.env_serial ? 1u : 0u,
                          (uint64_t)ls.max_spins,
-                         ls.fork ? 1u : 0u};
-  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+                         ls.fork ? 1u : 0u,
+                         g_streamed_launches.load()};
+  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
   return WFL_OK;
 }
 

@@ -33,7 +33,7 @@ extern "C" {
 
 #define WFL_OK 0
 #define WFL_ERR_INVALID 1     /* bad argument (shape, null pointer, label out of range ...) */
-#define WFL_ERR_UNSUPPORTED 2 /* valid request this build cannot serve (e.g. lattice too large for LDS) */
+#define WFL_ERR_UNSUPPORTED 2 /* valid request this build cannot serve (e.g. more than 65535 states) */
 #define WFL_ERR_RUNTIME 3     /* HIP runtime error (message has the hipError string) */
 
 #define WFL_EPSILON (-1) /* gtn.epsilon; pinned by tests/trans_backoff_test.txt:3 */
@@ -278,7 +278,12 @@ int wfl_lattice_forward_grad(const wfl_lattice_desc* d, const int32_t* ints, con
  *   out[4] calls left in the current back-off   out[5] 1 = the environment announces serialised launches
  *   out[6] the gate's bound (polls of ~2 us)           (AMD_SERIALIZE_KERNEL / HIP_LAUNCH_BLOCKING): never tried
  *   out[7] 1 = the side stream forks from the caller's stream (default)
- * The device counters behind out[1..2] are read without synchronisation: they lag the stream. n <= 8 words. */
+ *   out[8] launches of the streamed sweeps and their gradient (process-wide host counter: one per wfl_lattice_forward /
+ *          wfl_lattice_grad call that took them).  Acceptors whose sweeps do not fit one CU's LDS (more than 160 KiB
+ *          of arcs, states and emission rows) are swept with their arcs streamed from L2 -- decided from the
+ *          descriptor's maxima, the same way by every call (and by wfl_lattice_workspace, which then asks for room
+ *          for the streamed arc copies behind the alpha layout); WFL_LATTICE_STREAMED=1 / 2 forces that path (tests).
+ * The device counters behind out[1..2] are read without synchronisation: they lag the stream. n <= 9 words. */
 int wfl_lattice_diagnostics(uint64_t* out, int n);
 int wfl_lattice_grad_rest(const wfl_lattice_desc* d, const int32_t* ints, const float* floats,
                           const float* xg, int T, int C, const float* weights, const float* alpha,
