@@ -261,9 +261,7 @@ class ASGLossFunction(torch.autograd.Function):
         early = need_grad and _EARLY_GRAD and all(E.may_hand_over(t) and t.device == x.device
                                                   for t in (inputs, transitions) if t.requires_grad)
         fork = E.side_stream(dev)
-        up = getattr(pack, "_uploaded", None)
-        if up is not None and up[0] not in (E.stream_ptr(), fork.side.cuda_stream):
-            fork.side.wait_event(up[1])  # (a cached pack uploaded on a third stream)
+        pack.order_behind_upload(fork.side)  # (a cached pack uploaded on a third stream)
         phases = E.phase_events("asg", _PHASES)  # (None: no launch group of this step is timed)
         loss, da, db, dz, ws, dx_num, dw_num, dx, dW = N.ops.asg_forward(
             x, W, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cpos, cneg, need_dx, need_dw, early,
@@ -290,11 +288,7 @@ class ASGLossFunction(torch.autograd.Function):
             gout = E.as_device_f32(grad_output.detach().reshape(1), (dx if dx is not None else dW).device)
             dx = E.scale_inplace(dx, gout) if dx is not None and ctx.needs_input_grad[0] else None
             dW = E.scale_inplace(dW, gout) if dW is not None and ctx.needs_input_grad[1] else None
-            if dx is not None and ctx.devices[0].type != "cuda":
-                dx = dx.to(ctx.devices[0])
-            if dW is not None and ctx.devices[1].type != "cuda":
-                dW = dW.to(ctx.devices[1])
-            return dx, dW, None, None
+            return E.on_device_of(dx, ctx.devices[0]), E.on_device_of(dW, ctx.devices[1]), None, None
         x, W, fcc, cpos, dx_num, dw_num, fork = ctx.aux
         gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] and dx_num is not None else None
@@ -304,11 +298,7 @@ class ASGLossFunction(torch.autograd.Function):
             # + posteriors of the fully connected graph, - posteriors of the force-aligned one (asg.py:158-168)
             E.dense_grad(x, W, fcc, cpos, coef_w=cpos, gout=gout, dx=dx, accumulate=False, dW=dW,
                          addend=dx_num if dx is not None else None, dW_addend=dw_num if dW is not None else None)
-        if dx is not None and ctx.devices[0].type != "cuda":
-            dx = dx.to(ctx.devices[0])
-        if dW is not None and ctx.devices[1].type != "cuda":
-            dW = dW.to(ctx.devices[1])
-        return dx, dW, None, None
+        return E.on_device_of(dx, ctx.devices[0]), E.on_device_of(dW, ctx.devices[1]), None, None
 
 
 def ASGLoss(*args):

@@ -82,7 +82,7 @@ class CTCLossFunction(torch.autograd.Function):
     @staticmethod
     @E.on_input_device
     def backward(ctx, grad_output):
-        kind, x = ctx.aux[0], ctx.aux[1]
+        kind, x, *_ = ctx.aux
         gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
         if kind == "pipelined":
             _, _, tg, blank, dx, coef, lse = ctx.aux

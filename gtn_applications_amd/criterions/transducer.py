@@ -7,6 +7,7 @@ transducer.py:265-281) runs in the C++ host library; everything that touches the
 -- `intersect(emissions, .)`, `forward_score`, `viterbi_path`, `backward`
 (transducer.py:283-288,321-336,216-221) -- runs on the lattice engine kernels.
 """
+import collections
 import ctypes
 import itertools
 import os
@@ -281,9 +282,12 @@ class Transducer(torch.nn.Module):
         live (default: the current device)."""
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.tokens.arc_sort(True)
-        return PreparedTargets(targets, _prepare(targets, self.tokens, self.lexicon,
-                                                 _numerator_transitions(self.transitions, self._num_emission_classes),
-                                                 self._num_emission_classes, dev, self.reduction), len(targets))
+        C = self._num_emission_classes
+        graph = None
+        if self.transitions is not None:
+            graph = _dispatch(self.transitions, C, self.transition_params.numel()).numerator
+        return PreparedTargets(targets, _prepare(targets, self.tokens, self.lexicon, graph, C, dev, self.reduction),
+                               len(targets))
 
     @E.on_input_device
     def forward(self, inputs, targets):
@@ -302,22 +306,11 @@ class Transducer(torch.nn.Module):
         B, T, C = outputs.shape
         dev = E.require_gpu()
         x = E.as_device_f32(outputs.detach(), dev)
-        labels = None
+        kind = "none"
         if self.transitions is not None:
             params = E.as_device_f32(self.transition_params.detach(), dev)
-            if _DENSE_NGRAM and params.numel() == C and _dense_unigram(self.transitions, C):
-                # one node, one self-loop per token: the best path takes, frame by frame, the first maximum of x + p
-                labels = E.row_argmax(x + params[:C]).cpu().numpy().reshape(-1)
-                offsets = np.arange(B + 1, dtype=np.int64) * T
-            elif _DENSE_NGRAM and _dense_bigram(self.transitions, C):
-                # the fully connected recursion of the dense engine in the max-plus semiring (as the normaliser of the
-                # loss takes its log-semiring one): its best state per frame IS the label path, no epsilon to remove
-                xd, Wd = _bigram_dense_operands(x, params, C)
-                labels = E.dense_viterbi(xd, Wd).cpu().numpy().reshape(-1)
-                offsets = np.arange(B + 1, dtype=np.int64) * T
-        if labels is not None:
-            pass
-        elif self.transitions is not None:
+            kind = _dispatch(self.transitions, C, params.numel()).kind
+        if kind == "general":
             pack = _transitions_pack(self.transitions, B, C, dev)
             arc_paths, _ = E.lattice_viterbi(x, pack, weights=params)
             olab = self.transitions.arrays()["olabel"]
@@ -330,8 +323,15 @@ class Transducer(torch.nn.Module):
             np.cumsum(np.bincount(np.repeat(np.arange(B), lens)[keep], minlength=B), out=offsets[1:])
             labels = np.ascontiguousarray(labs[keep], dtype=np.int32)
         else:
-            # viterbi_path of the bare emissions graph: per frame, the first maximal label
-            labels = E.row_argmax(x).cpu().numpy().reshape(-1)
+            if kind == "bigram":
+                # the fully connected recursion of the dense engine in the max-plus semiring (as the normaliser of the
+                # loss takes its log-semiring one): its best state per frame IS the label path, no epsilon to remove
+                frames = E.dense_viterbi(*_bigram_dense_operands(x, params, C))
+            else:
+                # viterbi_path of the bare emissions graph: per frame, the first maximal label -- of x + p under the
+                # unigram model (one node, one self-loop per token)
+                frames = E.row_argmax(x + params if kind == "unigram" else x)
+            labels = frames.cpu().numpy().reshape(-1)
             offsets = np.arange(B + 1, dtype=np.int64) * T
         self.tokens.arc_sort()
         # one native call for the batch (the reference's gtn.parallel_for over process(b), transducer.py:232);
@@ -341,7 +341,15 @@ class Transducer(torch.nn.Module):
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
 
 
-_BIGRAM_SEEN = {}
+def _dense_unigram(transitions, C):
+    """True iff `transitions` is make_transitions_graph(1, C) (transducer.py:32-58 with ngram = 1): one start + accept
+    node with a self-loop per token, arc i labelled i."""
+    if transitions.num_nodes() != 1 or transitions.num_arcs() != C:
+        return False
+    a = transitions.arrays()
+    idx = np.arange(C)
+    return bool(a["start"][0] and a["accept"][0] and (a["src"] == 0).all() and (a["dst"] == 0).all()
+                and (a["ilabel"] == idx).all() and (a["olabel"] == idx).all())
 
 
 def _dense_bigram(transitions, C):
@@ -351,33 +359,23 @@ def _dense_bigram(transitions, C):
     forward_score(intersect(emissions, transitions)) (transducer.py:286-288) is then the fully connected recursion of
     the dense engine (csrc/dense_kernels.hip) with W[0] = start scores, W[1+b][a] = bigram score and the end
     arcs' scores added to the last frame -- instead of the general lattice sweep with (C+1) C^2 arcs."""
-    hit = _BIGRAM_SEEN.get(id(transitions))
-    if hit is not None and hit[0] is transitions and hit[1] == C:
-        return hit[2]
-    ok = False
-    if transitions.num_nodes() == C + 2 and transitions.num_arcs() == C + C * C + C + 1:
-        a = transitions.arrays()
-        idx = np.arange(C, dtype=np.int64)
-        ab = np.arange(C * C, dtype=np.int64)
-        eps = np.arange(C + 1, dtype=np.int64)
-        s, d, il, ol = (np.asarray(a[k]) for k in ("src", "dst", "ilabel", "olabel"))
-        n0, n1 = C, C + C * C
-        st, ac = np.flatnonzero(np.asarray(a["start"])), np.flatnonzero(np.asarray(a["accept"]))  # (per-node flags)
-        ok = (st.tolist() == [0] and ac.tolist() == [C + 1]
-              and (s[:n0] == 0).all() and (d[:n0] == 1 + idx).all() and (il[:n0] == idx).all() and (ol[:n0] == idx).all()
-              and (s[n0:n1] == 1 + ab // C).all() and (d[n0:n1] == 1 + ab % C).all() and (il[n0:n1] == ab % C).all()
-              and (ol[n0:n1] == ab % C).all()
-              and (s[n1:] == eps).all() and (d[n1:] == C + 1).all() and (il[n1:] == G.epsilon).all() and (ol[n1:] == G.epsilon).all())
-    if len(_BIGRAM_SEEN) > 64:
-        _BIGRAM_SEEN.clear()
-    _BIGRAM_SEEN[id(transitions)] = (transitions, C, bool(ok))  # (holds the graph: its id stays unique)
-    return bool(ok)
+    if transitions.num_nodes() != C + 2 or transitions.num_arcs() != C + C * C + C + 1:
+        return False
+    a = transitions.arrays()
+    idx = np.arange(C, dtype=np.int64)
+    ab = np.arange(C * C, dtype=np.int64)
+    eps = np.arange(C + 1, dtype=np.int64)
+    s, d, il, ol = (np.asarray(a[k]) for k in ("src", "dst", "ilabel", "olabel"))
+    n0, n1 = C, C + C * C
+    st, ac = np.flatnonzero(np.asarray(a["start"])), np.flatnonzero(np.asarray(a["accept"]))  # (per-node flags)
+    return bool(st.tolist() == [0] and ac.tolist() == [C + 1]
+                and (s[:n0] == 0).all() and (d[:n0] == 1 + idx).all() and (il[:n0] == idx).all() and (ol[:n0] == idx).all()
+                and (s[n0:n1] == 1 + ab // C).all() and (d[n0:n1] == 1 + ab % C).all() and (il[n0:n1] == ab % C).all()
+                and (ol[n0:n1] == ab % C).all()
+                and (s[n1:] == eps).all() and (d[n1:] == C + 1).all() and (il[n1:] == G.epsilon).all() and (ol[n1:] == G.epsilon).all())
 
 
-_NUM_TRANSITIONS = {}
-
-
-def _numerator_transitions(transitions, C):
+def _bigram_numerator_graph(transitions, C):
     """The transition graph the NUMERATOR's alignments are intersected with when the Transducer carries the dense
     bigram model (_bigram_route).  make_transitions_graph(2, C) reaches its accepting node through one epsilon arc per
     history (transducer.py:32-58), so every alignment acceptor ends in an epsilon arc -- and an acceptor with an epsilon
@@ -386,15 +384,7 @@ def _numerator_transitions(transitions, C):
     after label c), so it is the dense normaliser's trick again: the end arcs' scores ride on the last frame's emissions
     and the graph loses its epsilon arcs -- every node accepts instead.  The remaining arcs are laid out like the dense
     engine's matrix W [(C+1), C] row-major (include/wfl.h): arc c = start -> c, arc (1 + b) C + a = bigram a -> b, so that
-    numerator and normaliser read their weights from ONE tensor, as ASG's do.  Anything but the dense bigram: the graph
-    itself."""
-    if transitions is not None and _DENSE_NGRAM and transitions.num_nodes() == 1 and _dense_unigram(transitions, C):
-        return None  # (the unigram model's scores are added to the emissions: _unigram_route)
-    if transitions is None or not (_DENSE_NGRAM and _dense_bigram(transitions, C)):
-        return transitions
-    hit = _NUM_TRANSITIONS.get(id(transitions))
-    if hit is not None and hit[0] is transitions:
-        return hit[1]
+    numerator and normaliser read their weights from ONE tensor, as ASG's do."""
     a = transitions.arrays()
     idx = np.arange(C, dtype=np.int32)
     prev = np.tile(idx, C)    # a: fastest
@@ -405,10 +395,39 @@ def _numerator_transitions(transitions, C):
     g = G.Graph(False)
     g.add_nodes(np.asarray(a["start"]), np.ones(C + 2, dtype=np.asarray(a["accept"]).dtype))
     g.add_arcs(src, dst, lab, lab)
-    if len(_NUM_TRANSITIONS) > 64:
-        _NUM_TRANSITIONS.clear()
-    _NUM_TRANSITIONS[id(transitions)] = (transitions, g)
     return g
+
+
+# What a transition graph is, structurally, for C emission classes.  kind: "unigram" (make_transitions_graph(1, C)),
+# "bigram" (make_transitions_graph(2, C)) or "general"; numerator: the graph the numerator's alignments are intersected
+# with -- None for the unigram model (its scores are added to the emissions: _unigram_route), _bigram_numerator_graph for
+# the bigram model, the graph itself otherwise.
+_TransitionModel = collections.namedtuple("_TransitionModel", "kind numerator")
+_MODELS = E.LRU(64)
+
+
+def _transition_model(transitions, C):
+    """The _TransitionModel of (transitions, C): classified arc by arc once, then looked up."""
+    def build():
+        if _dense_unigram(transitions, C):
+            model = _TransitionModel("unigram", None)
+        elif _dense_bigram(transitions, C):
+            model = _TransitionModel("bigram", _bigram_numerator_graph(transitions, C))
+        else:
+            model = _TransitionModel("general", transitions)
+        return model, transitions  # (holds the graph: its id stays unique)
+
+    return _MODELS.get((id(transitions), C), build)[0]
+
+
+def _dispatch(transitions, C, num_params):
+    """The _TransitionModel the loss, prepare() and viterbi() of a criterion with `transitions` act on: the graph's own
+    where a dense route may take it -- the WFL_DENSE_NGRAM switch is on and there is one parameter per arc -- and the
+    general one otherwise."""
+    model = _transition_model(transitions, C)
+    if model.kind != "general" and not (_DENSE_NGRAM and num_params == transitions.num_arcs()):
+        return _TransitionModel("general", transitions)
+    return model
 
 
 def _numerator_entry(targets, tokens, lexicon, graph, C, dev, reduction, B):
@@ -425,30 +444,33 @@ def _numerator_entry(targets, tokens, lexicon, graph, C, dev, reduction, B):
     if nb != B:
         raise ValueError(f"got {nb} targets for a batch of {B}")
     pack = entry[0]
-    up = getattr(pack, "_uploaded", None)
-    if up is not None and up[0] != E.stream_ptr() and not getattr(pack, "_seen_here", None) == E.stream_ptr():
+    if pack.order_behind_upload():
         # uploaded on another stream (the prefetch thread's, or an earlier step's): its memory stays this stream's too
         pack._blob.record_stream(torch.cuda.current_stream())
-        pack._seen_here = E.stream_ptr()
     return entry
 
 
-def _bigram_route(inputs, targets, tokens, lexicon, transition_params=None, transitions=None, reduction="none"):
-    """TransducerLoss with the dense bigram model as the ASG step it is (None: not that case).  Emissions with the end
-    arcs' scores on the last frame and the matrix W of the dense engine are formed from `transition_params` =
-    [start C | bigram a -> b at C + a C + b | end arcs of nodes 0 .. C] by differentiable torch ops -- autograd maps the
-    two gradients back -- and ASGLoss (one native call: csrc/torch_ops.cpp::asg_forward) does the rest."""
-    if transitions is None or transition_params is None or inputs.dim() != 3:
-        return None
-    B, T, C = inputs.shape
-    if T == 0 or not (_DENSE_NGRAM and _dense_bigram(transitions, C)) or transition_params.numel() != C + C * C + C + 1:
-        return None
+def _bigram_dense_operands(x, params, C):
+    """(emissions with the end arcs' scores on the last frame, W [(C+1), C] of the dense engine) for the bigram
+    transition model: params = [start C | bigram a -> b at C + a C + b | end arcs of nodes 0 .. C]"""
+    n1 = C + C * C
+    Wd = torch.cat([params[:C].view(1, C), params[C:n1].view(C, C).t()], dim=0)
+    xd = x.clone()
+    xd[:, -1, :] += params[n1 + 1:]
+    return xd, Wd
+
+
+def _bigram_route(inputs, targets, tokens, lexicon, transition_params, numerator, reduction):
+    """TransducerLoss with the dense bigram model as the ASG step it is; `numerator`: the model's numerator graph
+    (_bigram_numerator_graph).  Emissions with the end arcs' scores on the last frame and the matrix W of the dense
+    engine are formed from `transition_params` (_bigram_dense_operands), and ASGLoss (one native call:
+    csrc/torch_ops.cpp::asg_forward) does the rest."""
     from . import asg as _asg
 
+    B, T, C = inputs.shape
     dev = E.require_gpu()
     with torch.cuda.device(dev):
-        pack, scale, cpos, cneg, _ = _numerator_entry(targets, tokens, lexicon, _numerator_transitions(transitions, C), C, dev,
-                                                       reduction, B)
+        pack, scale, cpos, cneg, _ = _numerator_entry(targets, tokens, lexicon, numerator, C, dev, reduction, B)
     return _BigramAsAsg.apply(inputs, transition_params, _asg.PackedNumerator(pack, scale, cpos, cneg, B))
 
 
@@ -478,12 +500,8 @@ class _BigramAsAsg(torch.autograd.Function):
 
         B, T, C = inputs.shape
         dev = E.require_gpu()
-        x = E.as_device_f32(inputs.detach(), dev)
-        p = E.as_device_f32(transition_params.detach(), dev).reshape(-1)
-        n1 = C + C * C
-        Wd = torch.cat([p[:C].view(1, C), p[C:n1].view(C, C).t()], dim=0)
-        xd = x.clone()
-        xd[:, -1, :] += p[n1 + 1:]
+        xd, Wd = _bigram_dense_operands(E.as_device_f32(inputs.detach(), dev),
+                                        E.as_device_f32(transition_params.detach(), dev).reshape(-1), C)
         # (what ASGLossFunction.forward asks its operands: which gradients the step will be asked for -- the end arcs'
         # gradient is the last frame's rows of the emission gradient, so the parameters alone ask for that one too)
         xd.requires_grad_(inputs.requires_grad or transition_params.requires_grad)
@@ -508,52 +526,7 @@ class _BigramAsAsg(torch.autograd.Function):
             # (the emission gradient is computed for it even when the caller's emissions ask for none)
             end = dxd[:, -1, :].sum(dim=0)
             dp = torch.cat([dWd[0], dWd[1:].t().reshape(-1), end.new_zeros(1), end]).reshape(par_shape)
-            if par_dev.type != "cuda":
-                dp = dp.to(par_dev)
-        dx = None
-        if need_x:
-            dx = dxd if in_dev.type == "cuda" else dxd.to(in_dev)
-        return dx, dp, None
-
-
-class _UnigramNormaliser:
-    """forward_score(intersect(emissions, transitions)) (transducer.py:286-288) for make_transitions_graph(1, C): one
-    start + accept node with a self-loop per token, so  log Z_b = sum_t logsumexp_c (x[b,t,c] + p_c)."""
-
-    __slots__ = ("xp", "lse", "logz")
-
-    def __init__(self, x, params):
-        # NaN policy of the lattice path this replaces: a NaN score is an impossible arc (-inf)
-        self.xp = torch.nan_to_num(x + params[:x.shape[2]], nan=float("-inf"), posinf=float("inf"), neginf=float("-inf"))
-        self.lse = E.row_lse(self.xp)
-        self.logz = self.lse.sum(dim=1)
-
-    def posteriors(self):
-        # (a frame whose scores are all -inf has no path through it: zero posteriors, as the lattice path gives)
-        lse = self.lse.unsqueeze(2)
-        return torch.where(torch.isfinite(lse), torch.exp(self.xp - lse), torch.zeros_like(self.xp))
-
-
-def _dense_unigram(transitions, C):
-    """True iff `transitions` is make_transitions_graph(1, C) (transducer.py:32-58 with ngram = 1): one start + accept
-    node with a self-loop per token, arc i labelled i."""
-    if transitions.num_nodes() != 1 or transitions.num_arcs() != C:
-        return False
-    a = transitions.arrays()
-    idx = np.arange(C)
-    return bool(a["start"][0] and a["accept"][0] and (a["src"] == 0).all() and (a["dst"] == 0).all()
-                and (a["ilabel"] == idx).all() and (a["olabel"] == idx).all())
-
-
-def _bigram_dense_operands(x, params, C):
-    """(emissions with the end arcs' scores on the last frame, W [(C+1), C] of the dense engine) for the bigram
-    transition model: params = [start C | bigram a -> b at a C + b | end arcs of nodes 0 .. C]"""
-    Wd = torch.empty((C + 1, C), dtype=torch.float32, device=x.device)
-    Wd[0] = params[:C]
-    Wd[1:] = params[C:C + C * C].view(C, C).t()
-    xd = x.clone()
-    xd[:, -1, :] += params[C + C * C + 1:]
-    return xd, Wd
+        return E.on_device_of(dxd if need_x else None, in_dev), E.on_device_of(dp, par_dev), None
 
 
 def _transitions_pack(transitions, B, C, device):
@@ -566,12 +539,20 @@ def _transitions_pack(transitions, B, C, device):
     return _PACK_CACHE.get(key, build)[0]
 
 
+# what TransducerLossFunction.forward leaves on its node for backward: the emissions, the transition parameters (None
+# without transitions), the LatticeStates of numerator and normaliser (None without transitions), the gradient factors
+_Saved = collections.namedtuple("_Saved", "x params num den cpos cneg")
+
 # the launch groups of a step without a transition model, in the order csrc/torch_ops.cpp::lattice_loss_forward takes
 # their timing events
 _PHASES = ("lattice_gather", "lattice_chain")
 
 
 class TransducerLossFunction(torch.autograd.Function):
+    """transducer.py:237-343, the general path: the numerator's alignments intersected with `transitions` as they are
+    and both forward scores on the lattice engine, whatever the transition model (TransducerLoss is what routes the dense
+    n-gram models elsewhere).  Backward finds the forward's state on the node as `ctx.aux`, a _Saved."""
+
     @staticmethod
     @E.on_input_device
     def forward(ctx, inputs, targets, tokens, lexicon, transition_params=None, transitions=None,
@@ -595,9 +576,6 @@ class TransducerLossFunction(torch.autograd.Function):
             # gather, sweeps, loss reduction and join in one native call (csrc/torch_ops.cpp::lattice_loss_forward).
             # The emission gradient is the whole backward pass here: the sweeps' launch computes it for grad_output = 1
             # as it goes when it can (in_launch), backward scales it and patches what is left.
-            up = getattr(pack, "_uploaded", None)
-            if up is not None and up[0] != E.stream_ptr():  # a cached pack uploaded on another stream
-                torch.cuda.current_stream().wait_event(up[1])
             want_dx = inputs.requires_grad and _IN_LAUNCH_GRAD
             phases = E.phase_events("transducer", _PHASES)  # (None: no launch group of this step is timed)
             (loss, xg, al, be, lz, lse, dx_early), in_launch = N.ops.lattice_loss_forward(
@@ -607,7 +585,7 @@ class TransducerLossFunction(torch.autograd.Function):
             num.pack, num.T, num.C, num.weights, num.bptr = pack, T, C, None, None
             num.xg, num.alpha, num.beta, num.logz = xg, al, be, lz
             num.x, num.row_lse = (x if log_softmax else None), lse
-            ctx.aux = (x, params, num, None, cpos, cneg, None)
+            ctx.aux = _Saved(x, None, num, None, cpos, cneg)
             ctx.early = None
             ctx.devices = (inputs.device, None)
             if in_launch:
@@ -618,29 +596,12 @@ class TransducerLossFunction(torch.autograd.Function):
             return loss if inputs.is_cuda else loss.cpu()
         # normaliser: forward_score(emissions o transitions), transducer.py:286-288, independent of the numerator sweep:
         # forked onto a second stream so that the two overlap
-        dense = None
         with E.side_stream(dev) as fork:
-            if _DENSE_NGRAM and params.numel() == C and _dense_unigram(transitions, C):
-                # one state, one self-loop per token: the frames are independent and the normaliser is a sum of
-                # row log-sum-exps of x + p -- no sweep at all
-                den = _UnigramNormaliser(x, params)
-                dense = "unigram"
-            elif _DENSE_NGRAM and _dense_bigram(transitions, C):
-                xd, Wd = _bigram_dense_operands(x, params, C)
-                den = E.dense_forward(xd, Wd, need_beta=need_grad)
-                dense = (xd, Wd)
-            else:
-                den = E.lattice_forward(x, _transitions_pack(transitions, B, C, dev), weights=params,
-                                        need_beta=need_grad)
+            den = E.lattice_forward(x, _transitions_pack(transitions, B, C, dev), weights=params, need_beta=need_grad)
         num = E.lattice_forward(x, pack, weights=params, need_beta=need_grad, log_softmax=log_softmax)
-        if dense == "unigram":
-            fork.join(den.xp, den.lse, den.logz)
-        elif dense is not None:
-            fork.join(dense[0], dense[1], den.alpha, den.beta, den.logz, den.ws)
-        else:
-            fork.join(den.xg, den.alpha, den.beta, den.logz)
+        fork.join(den.xg, den.alpha, den.beta, den.logz)
         loss = E.reduce_loss(den.logz, scale, 1.0, minus=num.logz)
-        ctx.aux = (x, params, num, den, cpos, cneg, dense)
+        ctx.aux = _Saved(x, params, num, den, cpos, cneg)
         ctx.early = None
         ctx.devices = (inputs.device, transition_params.device)
         return loss if inputs.is_cuda else loss.cpu()
@@ -657,42 +618,16 @@ class TransducerLossFunction(torch.autograd.Function):
             gout = E.as_device_f32(grad_output.detach().reshape(1), dx.device)
             E.scale_inplace(dx, gout)
             E.lattice_grad_rest(ctx.early.num, ctx.early.cneg, gout, dx)
-            return (dx if ctx.devices[0].type == "cuda" else dx.to(ctx.devices[0])), None, None, None, None, None, None
-        x, params, num, den, cpos, cneg, dense = ctx.aux
+            return E.on_device_of(dx, ctx.devices[0]), None, None, None, None, None, None
+        x, params, num, den, cpos, cneg = ctx.aux
         gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.zeros_like(params) if (params is not None and ctx.needs_input_grad[4]) else None
-        if (dx is not None or dW is not None) and dense == "unigram":
-            # posterior of label c in frame t under the unigram model: softmax(x + p), whatever the other frames do
-            post = den.posteriors() * (cpos * gout).view(-1, 1, 1)
-            if dW is not None:
-                dW += post.sum(dim=(0, 1))
-            if dx is not None:
-                dx.copy_(post)
-            E.lattice_grad(num, cneg, coef_w=cneg, gout=gout, dx=dx, accumulate=True, dW=dW)
-        elif (dx is not None or dW is not None) and dense is not None:
-            # the dense normaliser first (its emission gradient alone, for a moment, in dx: the last frame's rows are
-            # also the gradient of the end arcs' scores), then the numerator's lattice on top
-            xd, Wd = dense
-            C = x.shape[2]
-            ddx = dx if dx is not None else torch.empty_like(x)
-            dWd = torch.empty_like(Wd) if dW is not None else None
-            E.dense_grad(xd, Wd, den, cpos, coef_w=cpos, gout=gout, dx=ddx, accumulate=False, dW=dWd)
-            if dW is not None:
-                dW[:C] = dWd[0]
-                dW[C:C + C * C] = dWd[1:].t().reshape(-1)
-            if dW is not None:
-                dW[C + C * C + 1:] = ddx[:, -1, :].sum(dim=0)
-            E.lattice_grad(num, cneg, coef_w=cneg, gout=gout, dx=dx, accumulate=True, dW=dW)
-        elif dx is not None or dW is not None:
+        if dx is not None or dW is not None:
             E.lattice_grad(num, cneg, coef_w=cneg, gout=gout, dx=dx, accumulate=False, dW=dW)
             if den is not None:
                 E.lattice_grad(den, cpos, coef_w=cpos, gout=gout, dx=dx, accumulate=True, dW=dW)
-        if dx is not None and ctx.devices[0].type != "cuda":
-            dx = dx.to(ctx.devices[0])
-        if dW is not None and ctx.devices[1].type != "cuda":
-            dW = dW.to(ctx.devices[1])
-        return dx, None, None, None, dW, None, None
+        return E.on_device_of(dx, ctx.devices[0]), None, None, None, E.on_device_of(dW, ctx.devices[1]), None, None
 
 
 class _FusedLogSoftmaxTransducerLoss(TransducerLossFunction):
@@ -728,29 +663,28 @@ class _EarlyGrad:
 _IN_LAUNCH_GRAD = os.environ.get("WFL_TRANSDUCER_IN_LAUNCH_GRAD", "1") != "0"  # (0: gradient in backward -- A/B, tests)
 
 
-def _unigram_route(inputs, targets, tokens, lexicon, transition_params=None, transitions=None, reduction="none"):
+def _unigram_route(inputs, targets, tokens, lexicon, transition_params, reduction):
     """TransducerLoss with the unigram model (make_transitions_graph(1, C): one node, a self-loop per label) as the
-    transition-free step on other emissions (None: not that case).  Every arc with label c carries p_c in numerator and
+    transition-free step on other emissions.  Every arc with label c carries p_c in numerator and
     normaliser alike, so with x' = x + p the normaliser is  sum_t logsumexp_c x'[t]  and the loss is the negated
     numerator score of log_softmax(x') -- the fused log_softmax criterion (one native call, the gradient beside the
     sweeps); autograd sums the emission gradient over (b, t) into `transition_params`."""
-    if transitions is None or transition_params is None or inputs.dim() != 3 or not _DENSE_NGRAM:
-        return None
-    C = inputs.shape[2]
-    if inputs.shape[1] == 0 or transition_params.numel() != C or not _dense_unigram(transitions, C):
-        return None
     x = inputs if inputs.dtype == torch.float32 else inputs.float()
     p = transition_params.to(device=x.device, dtype=torch.float32)
     return E.make_eager(_FusedLogSoftmaxTransducerLoss.apply(x + p, targets, tokens, lexicon, None, None, reduction))
 
 
-def TransducerLoss(*args):
-    """transducer.py:346 (`TransducerLoss = TransducerLossFunction.apply`): same call, same result."""
-    for route in (_bigram_route, _unigram_route):
-        routed = route(*args)
-        if routed is not None:
-            return routed
-    return E.make_eager(TransducerLossFunction.apply(*args))
+def TransducerLoss(inputs, targets, tokens, lexicon, transition_params=None, transitions=None, reduction="none"):
+    """transducer.py:346 (`TransducerLoss = TransducerLossFunction.apply`): same call, same result -- the dense n-gram
+    models by their own routes (_dispatch)."""
+    if transitions is not None and transition_params is not None and inputs.dim() == 3 and inputs.shape[1] > 0:
+        model = _dispatch(transitions, inputs.shape[2], transition_params.numel())
+        if model.kind == "unigram":
+            return _unigram_route(inputs, targets, tokens, lexicon, transition_params, reduction)
+        if model.kind == "bigram":
+            return _bigram_route(inputs, targets, tokens, lexicon, transition_params, model.numerator, reduction)
+    return E.make_eager(TransducerLossFunction.apply(inputs, targets, tokens, lexicon, transition_params, transitions,
+                                                     reduction))
 
 
 # -------------------------------------------------------------------------------------------------
@@ -832,11 +766,7 @@ class ConvTransduce1DFunction(torch.autograd.Function):
         N.check(N.lib.wfl_conv_grad(E.ptr(x), B, T, C, E.ptr(tab), tab.shape[0], kernel_size, stride,
                                     kernels.blank_idx, kernels.flags, E.ptr(params), sr, E.ptr(delta), E.ptr(dx),
                                     E.ptr(dparams), E.stream_ptr()))
-        if ctx.devices[0].type != "cuda":
-            dx = dx.to(ctx.devices[0])
-        if dparams is not None and ctx.devices[1].type != "cuda":
-            dparams = dparams.to(ctx.devices[1])
-        return dx, None, None, None, dparams, None
+        return E.on_device_of(dx, ctx.devices[0]), None, None, None, E.on_device_of(dparams, ctx.devices[1]), None
 
 
 class ConvTransduce1D(torch.nn.Module):

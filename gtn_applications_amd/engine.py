@@ -230,6 +230,7 @@ class PackedLattice:
         self.device = device
         self._host = None
         self._uploaded = None
+        self._ordered = set()  # (streams order_behind_upload has ordered behind the upload)
         if cuda:
             blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
             upload(blob, buf, nbytes)
@@ -238,7 +239,7 @@ class PackedLattice:
                 ev = ring.events[slot] = torch.cuda.Event()
             ev.record()  # (the staging slot: reusable once this upload has read it)
             # the lattice's OWN event: packs are cached and may be used from another stream later, by which time the
-            # slot's event may have been re-recorded on some other stream (lattice_forward orders itself behind this one)
+            # slot's event may have been re-recorded on some other stream (order_behind_upload waits for this one)
             own = torch.cuda.Event()
             own.record()
             self._uploaded = (stream_ptr(), own)
@@ -253,6 +254,21 @@ class PackedLattice:
         self.extra = self.floats[nf:nf + ne] if (ne and blob is not None) else None
         self._n = (ni, nf)
         self._desc_ref = ctypes.byref(self.desc)
+
+    def order_behind_upload(self, stream=None):
+        """Before the pack is read on the current stream, or on `stream`, a side stream forked from it: that stream
+        waits for the pack's upload if it was issued on neither -- a cached pack met again on another stream, one
+        Transducer.prepare uploaded on its own.  Once per stream (the event is recorded once): True if it waited."""
+        up = self._uploaded
+        if up is None:
+            return False
+        cur = stream_ptr()
+        key = cur if stream is None else (stream.cuda_stream or None)
+        if up[0] in (cur, key) or key in self._ordered:
+            return False
+        (torch.cuda.current_stream() if stream is None else stream).wait_event(up[1])
+        self._ordered.add(key)
+        return True
 
     # host copies of the blobs (tests, diagnostics): kept when there is no device, fetched back otherwise
     @property
@@ -350,9 +366,7 @@ def lattice_forward(x, pack, weights=None, need_beta=True, semiring=N.SEMIRING_L
     transducer.py:283,287)."""
     B, T, C = x.shape
     d = pack.desc
-    up = getattr(pack, "_uploaded", None)
-    if up is not None and up[0] != stream_ptr():  # a cached pack uploaded on another stream
-        torch.cuda.current_stream().wait_event(up[1])
+    pack.order_behind_upload()
     if d.B != B:
         raise ValueError(f"lattice batch has {d.B} utterances, emissions have {B}")
     n_xg, n_ab = ctypes.c_int64(), ctypes.c_int64()
@@ -593,6 +607,12 @@ def make_eager(loss):
     if type(loss) is torch.Tensor and getattr(loss.grad_fn, "eager_take", None) is not None:
         loss.__class__ = EagerLoss
     return loss
+
+
+def on_device_of(grad, device):
+    """What a backward returns for a tensor that lives on `device`: the criteria compute on the GPU and accept CPU
+    tensors, whose gradients go back to the host (None stays None)."""
+    return grad if grad is None or device.type == "cuda" else grad.to(device)
 
 
 def scale_inplace(v, s):

@@ -13,7 +13,7 @@ crit = TR.Transducer([(n,) for n in range(Nn)], {n: n for n in range(Nn)}, blank
 x = torch.from_numpy(rs.randn(B, T, Nn + 1).astype(np.float32)).cuda().requires_grad_(True)
 targets = [torch.tensor(rs.randint(0, Nn, size=rs.randint(20, 45)).tolist()) for _ in range(B)]
 loss = crit(x, targets)
-num = loss.grad_fn.aux[2]
+num = loss.grad_fn.aux.num
 off = ctypes.c_int64()
 N.check(N.lib.wfl_lattice_formats_offset(ctypes.byref(num.pack.desc), T, ctypes.byref(off)))
 torch.cuda.synchronize()

@@ -17,7 +17,7 @@ targets = [t.squeeze() for t in torch.randint(N, size=(B, L)).split(1)]
 dev = x.device
 params = crit.transition_params.detach()
 crit.tokens.arc_sort(True)
-nb, entry = TR._pack_entry(targets, crit.tokens, crit.lexicon, TR._numerator_transitions(crit.transitions, C), C, dev, "mean")
+nb, entry = TR._pack_entry(targets, crit.tokens, crit.lexicon, TR._transition_model(crit.transitions, C).numerator, C, dev, "mean")
 pack, scale, cpos, cneg, _ = entry
 num = E.lattice_forward(x, pack, weights=params, need_beta=True)
 torch.cuda.synchronize()

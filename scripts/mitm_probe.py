@@ -14,7 +14,7 @@ crit = transducer.Transducer(tokens, g2i, blank="optional", allow_repeats=False,
 loss = crit(x, tg)
 torch.cuda.synchronize()
 node = loss.grad_fn
-num = node.aux[2]
+num = node.aux.num
 d = num.pack.desc
 al, be = num.alpha, num.beta
 off = ctypes.c_int64()

@@ -253,7 +253,7 @@ def test_transducer_dense_bigram_route_beyond_the_on_chip_limit(blank, T, hard):
     x = rs.randn(B, T, C).astype(np.float32)
     targets = [rs.randint(0, ntok, size=5).tolist(), rs.randint(0, ntok, size=3).tolist()]
     m = tr.Transducer(tokens, g2i, **kw)
-    assert tr._dense_bigram(m.transitions, C)
+    assert tr._transition_model(m.transitions, C).kind == "bigram"
     params = (0.3 * rs.randn(m.transition_params.numel())).astype(np.float32)
     if hard:
         a = 11  # bigram a -> b at C + a C + b (transducer._bigram_route)

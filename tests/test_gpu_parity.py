@@ -1507,7 +1507,7 @@ def _sweep_formats(loss, B, T):
 
     from gtn_applications_amd import _native as N
 
-    num = loss.grad_fn.aux[2]
+    num = loss.grad_fn.aux.num
     off = ctypes.c_int64()
     N.check(N.lib.wfl_lattice_formats_offset(ctypes.byref(num.pack.desc), T, ctypes.byref(off)))
     torch.cuda.synchronize()
@@ -1659,7 +1659,7 @@ def test_transducer_dense_ngram_transitions(crit, ngram, blank, route, monkeypat
     x = rs.randn(B, T, C).astype(np.float32)
     targets = [rs.randint(0, ntok, size=5).tolist(), rs.randint(0, ntok, size=3).tolist()]
     m = tr.Transducer(tokens, g2i, **kw)
-    assert tr._dense_bigram(m.transitions, C) == (ngram == 2)
+    assert (tr._transition_model(m.transitions, C).kind == "bigram") == (ngram == 2)
     params = (0.3 * rs.randn(m.transition_params.numel())).astype(np.float32)
     with torch.no_grad():
         m.transition_params.copy_(torch.from_numpy(params))

@@ -196,6 +196,54 @@ def test_backoff_text_fixture_loads(golden_dir, tmp_path):
     assert a["ilabel"][0] == G.epsilon and a["start"].tolist() == [0] * 7 + [1]
 
 
+def test_transition_graphs_are_classified_once_and_dispatched_by_the_switch(golden_dir, monkeypatch):
+    """criterions/transducer.py::_transition_model on the smallest graphs that tell the kinds apart, its cache, and
+    _dispatch, which reads the WFL_DENSE_NGRAM switch at every call."""
+    uni = TR._transition_model(TR.make_transitions_graph(1, 3), 3)
+    assert uni == ("unigram", None)
+
+    bigram = TR.make_transitions_graph(2, 3)
+    model = TR._transition_model(bigram, 3)
+    assert model.kind == "bigram"
+    a, n = bigram.arrays(), model.numerator.arrays()
+    assert model.numerator.num_nodes() == 5 and n["accept"].tolist() == [1] * 5
+    assert n["start"].tolist() == a["start"].tolist() == [1, 0, 0, 0, 0]
+    assert model.numerator.num_arcs() == 3 + 9
+    assert not (n["ilabel"] == G.epsilon).any() and not (n["olabel"] == G.epsilon).any()
+    arcs = list(zip(n["src"].tolist(), n["dst"].tolist(), n["ilabel"].tolist(), n["olabel"].tolist()))
+    assert arcs[:3] == [(0, 1 + c, c, c) for c in range(3)]
+    for prev in range(3):
+        for cur in range(3):
+            assert arcs[(1 + cur) * 3 + prev] == (1 + prev, 1 + cur, cur, cur)
+    assert TR._transition_model(bigram, 3) is model  # (the same graph object: looked up)
+
+    trigram = TR.make_transitions_graph(3, 2)
+    assert TR._transition_model(trigram, 2) == ("general", trigram)
+    with open(os.path.join(golden_dir, "reference_literals.json")) as f:
+        lit = json.load(f)["backoff_transitions"]
+    backoff = G.Graph(False)
+    for node in range(8):
+        backoff.add_node(node in lit["start"], node in lit["accept"])
+    for arc in lit["arcs"]:
+        backoff.add_arc(*arc)
+    assert TR._transition_model(backoff, lit["N"] + 1) == ("general", backoff)
+    lab = a["ilabel"].copy()
+    lab[3 + 4] = 0  # bigram 1 -> 1 relabelled
+    relabelled = G.Graph(False)
+    relabelled.add_nodes(a["start"], a["accept"])
+    relabelled.add_arcs(a["src"], a["dst"], lab, lab)
+    assert TR._transition_model(relabelled, 3) == ("general", relabelled)
+
+    # the record is structural; the switch and the parameter count decide at the dispatch, call by call
+    monkeypatch.setattr(TR, "_DENSE_NGRAM", True)
+    assert TR._dispatch(bigram, 3, bigram.num_arcs()) is model
+    assert TR._dispatch(bigram, 3, 7) == ("general", bigram)
+    monkeypatch.setattr(TR, "_DENSE_NGRAM", False)
+    assert TR._dispatch(bigram, 3, bigram.num_arcs()) == ("general", bigram)
+    assert TR._dispatch(TR.make_transitions_graph(1, 3), 3, 3).kind == "general"
+    assert TR._transition_model(bigram, 3) is model
+
+
 def test_pack_epsilon_levels_and_sorting():
     trans = TR.make_transitions_graph(2, 3)  # 5 nodes: start, 3 histories, </s>; epsilon arcs into </s>
     wid = np.arange(trans.num_arcs(), dtype=np.int32)
