@@ -22,6 +22,8 @@ DENSE_MAIN, DENSE_REPAIR, DENSE_REDUCE, DENSE_ALL = 1, 2, 4, 7  # parts of wfl_d
 CTC_WS_REJECTED, CTC_WS_STATUS, CTC_WS_LOG2Z, CTC_WS_ZRANGE, CTC_WS_DEBUG, CTC_WS_CLOCK = 0, 1, 2, 3, 4, 5
 DENSE_WS_FLAGS = 0  # wfl_dense_workspace_field (include/wfl.h: WFL_DENSE_WS_FLAGS)
 CONV_SPIKE, CONV_BLANK_OPTIONAL = 1, 2
+DECODE_NAN_IS_MAX, DECODE_BLANK_SEPARATED = 1, 2  # flags of wfl_decode_emissions / wfl_decode_paths
+TOKENS_NONE, TOKENS_OPTIONAL, TOKENS_FORCED, TOKENS_OPTIONAL_NO_REPEATS = 0, 1, 2, 3  # wfl_graph_token_kind
 
 
 class WflError(RuntimeError):
@@ -119,6 +121,7 @@ _SIGS = {
     "wfl_transducer_pack_batch_into": (_P, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, c_int64]),
     "wfl_lattice_host_external": (c_int64, [_P]),
     "wfl_transducer_decode_batch": (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, c_int]),
+    "wfl_graph_token_kind": (c_int, [_P, POINTER(c_int)]),
     "wfl_lattice_pack_ctc": (_P, [_P, _P, c_int, c_int, c_int]),
     "wfl_lattice_pack_asg_fal": (_P, [_P, _P, c_int, c_int]),
     "wfl_lattice_pack_stc": (_P, [_P, _P, c_int, c_int, c_float, c_int]),
@@ -171,6 +174,11 @@ _SIGS = {
                                               _P, _P, _P]),
     "wfl_row_lse": (c_int, [_P, c_int64, c_int, _P, _P]),
     "wfl_row_argmax": (c_int, [_P, c_int64, c_int, _P, _P]),
+    # device: the decode behind a best path
+    "wfl_decode_chunk_frames": (c_int, []),
+    "wfl_decode_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "wfl_decode_emissions": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
+    "wfl_decode_paths": (c_int, [_P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
     "wfl_upload": (c_int, [_P, _P, c_int64, _P]),
     "wfl_reduce_loss": (c_int, [_P, _P, _P, c_int, c_float, c_int, _P, _P]),
     "wfl_scale": (c_int, [_P, c_int64, _P, _P]),

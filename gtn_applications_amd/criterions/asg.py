@@ -343,4 +343,8 @@ class ASG(torch.nn.Module):
         dev = E.require_gpu()
         x = E.as_device_f32(outputs.detach(), dev)
         W = E.as_device_f32(self.transitions.detach(), dev)
-        return collapse_and_unpack(E.dense_viterbi(x, W), self.garbage_idx, self.num_replabels)
+        paths = E.dense_viterbi(x, W)
+        if outputs.is_cuda and B > 0:
+            # collapse, garbage and replabels on the device: only the labels that survive travel (csrc/decode_kernels.hip)
+            return E.decode_paths(paths, self.garbage_idx, self.num_replabels)
+        return collapse_and_unpack(paths, self.garbage_idx, self.num_replabels)

@@ -227,6 +227,11 @@ class CTC(torch.nn.Module):
 
     def viterbi(self, outputs):
         """Greedy decode (ctc.py:126-135): argmax, collapse repeats, drop blank."""
+        if (outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 3 and outputs.numel() > 0
+                and 0 <= self.blank < outputs.shape[2]):
+            # argmax (torch.argmax's rule for NaNs), collapse and drop on the device: only the labels that survive travel
+            return E.decode_emissions(outputs.detach().contiguous(), self.blank, flags=N.DECODE_NAN_IS_MAX,
+                                      dtype=torch.int64)
         best = torch.argmax(outputs, dim=2).to("cpu").numpy()
         flat, lens = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
         return E.split_rows(flat, lens, torch.int64)

@@ -300,6 +300,10 @@ class Transducer(torch.nn.Module):
         return TransducerLoss(inputs, targets, self.tokens, self.lexicon, self.transition_params,
                               self.transitions, self.reduction)
 
+    def _device_decode(self, C):
+        self.tokens.arc_sort()  # (the order the host decode looks at the graph in, below)
+        return _token_decode_plan(self.tokens, C)
+
     def viterbi(self, outputs):
         """transducer.py:199-234: best frame-level path (under the transition model if any), then
         the shortest token sequence that path can transduce to."""
@@ -323,11 +327,19 @@ class Transducer(torch.nn.Module):
             np.cumsum(np.bincount(np.repeat(np.arange(B), lens)[keep], minlength=B), out=offsets[1:])
             labels = np.ascontiguousarray(labs[keep], dtype=np.int32)
         else:
+            # (drop, flags) of the device decode, or None: the host decodes (a token graph that is not make_token_graph's,
+            # labels outside its alphabet, emissions that came from the host)
+            plan = self._device_decode(C) if outputs.is_cuda and B > 0 and T > 0 else None
             if kind == "bigram":
                 # the fully connected recursion of the dense engine in the max-plus semiring (as the normaliser of the
                 # loss takes its log-semiring one): its best state per frame IS the label path, no epsilon to remove
                 frames = E.dense_viterbi(*_bigram_dense_operands(x, params, C))
+                if plan is not None:
+                    return E.decode_paths(frames, plan[0], flags=plan[1])
             else:
+                if plan is not None:
+                    # argmax (of x + p under the unigram model), collapse and drop in one pass over x on the device
+                    return E.decode_emissions(x, plan[0], bias=params if kind == "unigram" else None, flags=plan[1])
                 # viterbi_path of the bare emissions graph: per frame, the first maximal label -- of x + p under the
                 # unigram model (one node, one self-loop per token)
                 frames = E.row_argmax(x + params if kind == "unigram" else x)
@@ -339,6 +351,25 @@ class Transducer(torch.nn.Module):
         out, out_off = G.transducer_decode_batch(self.tokens, labels, offsets)
         flat = torch.from_numpy(out)  # (int32: torch.IntTensor, as transducer.py:233)
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
+
+
+def _token_decode_plan(tokens, C):
+    """(drop, flags) with which the device decode (wfl_decode_emissions / wfl_decode_paths) transduces frame labels below
+    C through `tokens` exactly as wfl_transducer_decode_batch does -- collapse repeats, drop the blank, within what the
+    graph accepts (csrc/graph.cpp::token_decode) --, or None: `tokens` is none of make_token_graph's four graphs, or
+    labels below C lie outside its alphabet (the host composes those)."""
+    n = ctypes.c_int()
+    mode = N.lib.wfl_graph_token_kind(tokens._h, ctypes.byref(n))
+    if mode < 0:
+        return None
+    blank = None if mode == N.TOKENS_NONE else n.value
+    if C > n.value + (blank is not None):
+        return None
+    if blank is not None and blank >= C:  # (emissions without a column for the blank)
+        if mode == N.TOKENS_FORCED:
+            return None
+        blank = None
+    return blank, N.DECODE_BLANK_SEPARATED if mode == N.TOKENS_FORCED else 0
 
 
 def _dense_unigram(transitions, C):

@@ -1053,6 +1053,13 @@ int wfl_transducer_decode_batch(const wfl_graph* tokens, const int32_t* labels, 
   return WFL_OK;
 }
 
+int wfl_graph_token_kind(const wfl_graph* tokens, int* n_tokens) {
+  int n = 0;
+  const int mode = tokens ? wfl::token_graph_kind(tokens, &n) : -1;
+  if (n_tokens) *n_tokens = mode < 0 ? 0 : n;
+  return mode;
+}
+
 void wfl_host_pool_wake(void) { host_pool().wake(); }
 
 void wfl_lattice_host_free(wfl_lattice_host* h) { delete h; }

@@ -823,9 +823,120 @@ std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& 
   return {{loss, xg, al, be, lz, lse, dx}, in_launch};
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The decode behind viterbi() (wfl_decode_emissions / wfl_decode_paths, csrc/decode_kernels.hip): counterpart of
+// the reference's criterions/ctc.py:126-135, asg.py:225-234, transducer.py:216-232.  The kernels store the collapsed
+// result straight into pinned host memory -- ONE buffer per device, grown on demand, held under its lock from the
+// launch until the result has been copied out of it --, the host waits on one event and copies the labels that
+// survived into a fresh CPU tensor: no hipMemcpyAsync, nothing of size B T crosses the link, and what is returned
+// never aliases the buffer.
+// ------------------------------------------------------------------------------------------------------------
+struct DecodeBuffer {
+  std::mutex mu;
+  at::Tensor pinned;  // [offsets: (B + 1) int64, padded to 16 bytes | labels: capacity int32]
+  hipEvent_t done = nullptr;
+};
+struct DeviceScope {  // the input's device current for the launches (viterbi() may be called with another one current)
+  int prev = -1;
+  explicit DeviceScope(int dev) {
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
+  }
+  ~DeviceScope() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+DecodeBuffer& decode_buffer(int dev) {
+  static std::mutex mu;
+  static auto* buffers = new std::map<int, DecodeBuffer>();  // (never destroyed: see g_targets)
+  std::lock_guard<std::mutex> lock(mu);
+  return (*buffers)[dev];
+}
+
+// launch(ws, out, capacity, out_offsets, stream) issues the decode; returns the B label sequences as views of one
+// CPU tensor of int32 or (as_int64) int64
+template <class Launch>
+std::vector<at::Tensor> decode_collect(const at::Tensor& on, int B, int T, int R, bool as_int64, const Launch& launch) {
+  const auto cpu = at::TensorOptions().dtype(as_int64 ? at::kLong : at::kInt);
+  if (B == 0) return {};
+  const int dev = on.device().index();
+  int64_t capacity = 0, ws_bytes = 0;
+  check(wfl_decode_workspace(B, T, R, &capacity, &ws_bytes), "decode");
+  const int64_t off_bytes = ((int64_t)(B + 1) * 8 + 15) & ~(int64_t)15, need = off_bytes + capacity * 4;
+  at::Tensor ws = at::empty({ws_bytes}, on.options().dtype(at::kByte));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+  DecodeBuffer& buf = decode_buffer(dev);
+  at::Tensor flat;
+  std::vector<int64_t> lens((size_t)B);
+  {
+    py::gil_scoped_release nogil;
+    std::lock_guard<std::mutex> lock(buf.mu);
+    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
+      int64_t cap = 1 << 16;
+      while (cap < need) cap <<= 1;
+      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+    }
+    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
+    uint8_t* base = buf.pinned.data_ptr<uint8_t>();
+    const int64_t* offsets = reinterpret_cast<const int64_t*>(base);
+    const int32_t* labels = reinterpret_cast<const int32_t*>(base + off_bytes);
+    launch(ws.data_ptr(), reinterpret_cast<int32_t*>(base + off_bytes), capacity, reinterpret_cast<int64_t*>(base), (void*)stream);
+    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess, "decode: ",
+                hipGetErrorString(hipGetLastError()));
+    const int64_t total = offsets[B];
+    TORCH_CHECK(offsets[0] == 0 && total >= 0 && total <= capacity, "decode: the kernels left inconsistent offsets");
+    flat = at::empty({total}, cpu);
+    if (as_int64) {
+      int64_t* dst = flat.data_ptr<int64_t>();
+      for (int64_t i = 0; i < total; ++i) dst[i] = labels[i];
+    } else if (total) {
+      memcpy(flat.data_ptr<int32_t>(), labels, (size_t)total * sizeof(int32_t));
+    }
+    for (int b = 0; b < B; ++b) lens[(size_t)b] = offsets[b + 1] - offsets[b];
+  }
+  return flat.split_with_sizes(lens);
+}
+
+std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
+                                         int64_t num_replabels, int64_t flags, bool as_int64) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
+              "decode_emissions: x must be a contiguous float32 [B,T,C] device tensor");
+  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->device() == x.device() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == C,
+                "decode_emissions: bias must be a contiguous float32 [C] tensor on x's device");
+    bp = bias->data_ptr<float>();
+  }
+  DeviceScope scope(x.device().index());
+  const float* xp = x.data_ptr<float>();
+  return decode_collect(x, B, T, (int)num_replabels, as_int64, [&](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
+    check(wfl_decode_emissions(xp, bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out, cap, offs, s), "decode_emissions");
+  });
+}
+
+std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
+                                     bool as_int64) {
+  TORCH_CHECK(paths.is_cuda() && paths.scalar_type() == at::kInt && paths.dim() == 2 && (paths.size(1) == 0 || paths.stride(1) == 1) &&
+                  paths.size(1) >= T,
+              "decode_paths: paths must be an int32 [B, >= T] device tensor with unit stride along the frames");
+  const int B = (int)paths.size(0);
+  const int64_t stride = B > 1 ? paths.stride(0) : paths.size(1);
+  DeviceScope scope(paths.device().index());
+  const int32_t* pp = paths.data_ptr<int32_t>();
+  return decode_collect(paths, B, (int)T, (int)num_replabels, as_int64, [&](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
+    check(wfl_decode_paths(pp, stride, B, (int)T, (int)drop, (int)num_replabels, (int)flags, ws, out, cap, offs, s), "decode_paths");
+  });
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
+        py::arg("flags"), py::arg("as_int64"),
+        "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors");
+  m.def("decode_paths", &decode_paths, py::arg("paths"), py::arg("T"), py::arg("drop"), py::arg("num_replabels"),
+        py::arg("flags"), py::arg("as_int64"), "viterbi()'s decode from [B, >= T] int32 device label paths: B CPU tensors");
   m.def("ctc_fast_backward", &ctc_fast_backward,
         "loss.backward() of a CtcStep loss without the autograd engine (false: not the plain case, use the engine)");
   m.def(

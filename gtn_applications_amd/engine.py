@@ -904,6 +904,25 @@ def row_argmax(x):
     return out
 
 
+def decode_chunk_frames():
+    """Frames per chunk of the device decode (wfl_decode_chunk_frames): what crosses a chunk boundary is carried."""
+    return int(N.lib.wfl_decode_chunk_frames())
+
+
+def decode_emissions(x, drop, bias=None, num_replabels=0, flags=0, dtype=torch.int32):
+    """viterbi()'s decode from emissions, on the device (wfl_decode_emissions through csrc/torch_ops.cpp): per frame the
+    first maximal class of x [B,T,C] (+ bias [C]), runs collapsed, `drop` (None: nothing) dropped, replabels unpacked.
+    Returns B CPU tensors of `dtype` (int32 or int64), views of one tensor; only what survives the collapse leaves the
+    device."""
+    return N.ops.decode_emissions(x, bias, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64)
+
+
+def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int32):
+    """The same decode from [B, >= T] int32 device label paths (wfl_dense_viterbi's): wfl_decode_paths."""
+    T = paths.shape[1] if T is None else T
+    return N.ops.decode_paths(paths, T, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64)
+
+
 def ctc_workspace(x, max_len):
     """Scratch of the pipelined step (checkpoints, flags, certificate words) and the per-utterance nll, one per
     (device, stream, shape), kept by the C++ operator: consecutive steps on a stream are ordered, so they can share it

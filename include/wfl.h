@@ -196,6 +196,13 @@ int64_t wfl_lattice_host_external(const wfl_lattice_host* h);
  * `tokens` goes through the graph algebra per utterance on the host pool (nthreads: 1 = serial in the caller). */
 int wfl_transducer_decode_batch(const wfl_graph* tokens, const int32_t* labels, const int64_t* offsets, int B,
                                 int32_t* out, int64_t out_capacity, int64_t* out_offsets, int nthreads);
+/* Which make_token_graph(N tokens, blank, allow_repeats) (transducer.py:78-123) `tokens` is, arc for arc (all weights
+ * zero): 0 blank "none", 1 blank "optional", 2 blank "forced" (each with repeats allowed), 3 blank "optional" without
+ * repeats; *n_tokens = N (the blank, where there is one, is label N).  -1: none of them.  All four transduce a
+ * frame-label sequence the same way wherever they accept it -- collapse repeats, drop the blank -- and only the
+ * "forced" graph rejects sequences over its alphabet (WFL_DECODE_BLANK_SEPARATED below): what picks `drop` and the
+ * flags of the device decode. */
+int wfl_graph_token_kind(const wfl_graph* tokens, int* n_tokens);
 /* Bulk builders for the three fixed-topology label graphs (no per-arc host calls):
  *   CTC  create_ctc_graph          ctc.py:15-29     targets flat + offsets[B+1], blank
  *   ASG  create_force_align_graph  asg.py:72-81 composed with the transitions graph asg.py:54-69:
@@ -479,6 +486,41 @@ int wfl_row_argmax(const float* x, int64_t rows, int C, int32_t* out, void* stre
 int wfl_ctc_grad(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets,
                  int max_len, int blank, const float* ws, const float* nll, const float* coef,
                  const float* gout, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device kernels: the decode behind a best path (csrc/decode_kernels.hip)
+ *   what every criterion's viterbi() ends with -- ctc.py:126-135, asg.py:225-234, transducer.py:216-232 -- per
+ *   utterance and in frame order:
+ *     frame t is kept iff lab[t] != lab[t-1] (t = 0: always a candidate) and lab[t] != drop   (drop = -1: nothing);
+ *     num_replabels = R > 0: unpack_replabels (asg.py:35-49) on the kept values -- v >= R emits v - R; v < R emits
+ *       u - R another v + 1 times if the kept value right before it in the row is a label u >= R, else nothing;
+ *     WFL_DECODE_BLANK_SEPARATED (needs drop >= 0): the row decodes to nothing unless it starts and ends with `drop`
+ *       and no two different non-drop labels are adjacent (make_token_graph(blank="forced"), transducer.py:78-123).
+ *   Labels are >= 0.  out: the utterances back to back in batch order (capacity B T max(1, R) int32),
+ *   out_offsets [B+1] int64.  Both are written by plain stores of a kernel, in a fixed order (no atomics: the result
+ *   is deterministic), so they may be any device-accessible memory -- pinned host memory delivers the few labels that
+ *   survive the collapse to the host without a copy call (wfl_upload's trick in the other direction).  ws: device
+ *   scratch of wfl_decode_workspace's size, 16-byte aligned, contents irrelevant before and after.  Three launches on
+ *   `stream`, no allocation, no synchronisation.  WFL_ERR_INVALID: B < 1, T < 1, C < 1, R < 0, drop outside [-1, C)
+ *   (paths: < -1), path_stride < T, out_capacity too small, an unknown flag.
+ * ------------------------------------------------------------------------------------------------ */
+#define WFL_DECODE_NAN_IS_MAX 1       /* emissions: a NaN is the maximum, the first NaN wins (torch.argmax, ctc.py:128) */
+#define WFL_DECODE_BLANK_SEPARATED 2  /* reject rows the blank="forced" token graph does not accept */
+/* frames per chunk: the frames are split into chunks over the grid, and the previous label, the last kept value and
+ * the output count are carried across the chunk boundaries (tests straddle them) */
+int wfl_decode_chunk_frames(void);
+/* out_capacity = B T max(1, num_replabels) (int32 elements of `out`), ws_bytes = the device scratch of a call */
+int wfl_decode_workspace(int B, int T, int num_replabels, int64_t* out_capacity, int64_t* ws_bytes);
+/* lab[b][t] = the first maximal class of x[b,t,:] + bias (x [B,T,C] float32; bias [C] or NULL: the unigram transition
+ * model's x + params, transducer.py:205-216, added in float32), never written to memory.  Ties: the lowest class.
+ * Default: NaN counts as -inf, a row without a finite score gives class 0 (wfl_row_argmax's rule);
+ * WFL_DECODE_NAN_IS_MAX: torch.argmax's (ctc.py:128).  Replaces ctc.py:126-135 and transducer.py:216-232. */
+int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C, int drop, int num_replabels, int flags,
+                         void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream);
+/* lab[b][t] = paths[b * path_stride + t]: the label paths of wfl_dense_viterbi.  Replaces asg.py:225-234 and
+ * transducer.py:216-232 under the bigram transition model. */
+int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, int drop, int num_replabels, int flags,
+                     void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* small device utilities used by the Python layer (kept here so the product never needs a
  * torch op inside the timed path) */

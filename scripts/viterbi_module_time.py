@@ -1,6 +1,7 @@
 """What train.py:279 pays per step for `criterion.viterbi(outputs)` at the benchmark shapes: the MODULE call (device
 decode + copy to the host + collapse / unpack), and beside it the row-by-row spelling of the host part alone (the
-reference's asg.py:228-234 / ctc.py:130-134), for comparison."""
+reference's asg.py:228-234 / ctc.py:130-134), for comparison.  --module-only: the module calls alone (under a profiler:
+every copy in the trace is then one of theirs)."""
 import itertools, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
@@ -26,7 +27,8 @@ with torch.no_grad():
     crit.transitions.normal_()
 print(f"ASG.viterbi  B={B} T={T} C={C}: {timed(lambda: crit.viterbi(x)):.2f} ms per call")
 from gtn_applications_amd import engine as E
-paths = E.dense_viterbi(x, crit.transitions.detach()).cpu()
+ROWWISE = "--module-only" not in sys.argv
+paths = E.dense_viterbi(x, crit.transitions.detach()).cpu() if ROWWISE else None
 
 
 def rowwise():
@@ -38,10 +40,11 @@ def rowwise():
     return out
 
 
-print(f"   its host part row by row (asg.py:228-234): {timed(rowwise, 5):.2f} ms")
+if ROWWISE:
+    print(f"   its host part row by row (asg.py:228-234): {timed(rowwise, 5):.2f} ms")
 c = ctc.CTC(C - 1, True)
 print(f"CTC.viterbi  B={B} T={T} C={C}: {timed(lambda: c.viterbi(x)):.2f} ms per call")
-best = torch.argmax(x, dim=2).cpu()
+best = torch.argmax(x, dim=2).cpu() if ROWWISE else None
 
 
 def ctc_rowwise():
@@ -54,4 +57,11 @@ def ctc_rowwise():
     return res
 
 
-print(f"   its host part row by row (ctc.py:130-134): {timed(ctc_rowwise, 5):.2f} ms")
+if ROWWISE:
+    print(f"   its host part row by row (ctc.py:130-134): {timed(ctc_rowwise, 5):.2f} ms")
+from gtn_applications_amd.criterions import transducer
+
+toks = [chr(ord("a") + i) for i in range(C - 1)]  # 99 tokens + optional blank = 100 classes
+for ngram in (0, 1, 2):
+    t = transducer.Transducer(toks, {k: i for i, k in enumerate(toks)}, ngram=ngram, blank="optional", allow_repeats=False).cuda()
+    print(f"Transducer.viterbi ngram={ngram}  B={B} T={T} C={C}: {timed(lambda: t.viterbi(x)):.2f} ms per call")
