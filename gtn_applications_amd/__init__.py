@@ -3,8 +3,9 @@ facebookresearch/gtn_applications (criterions/{ctc,asg,stc,transducer}.py), back
 gfx950 HIP kernels behind the C ABI of include/wfl.h (libwfl.so).  See DESIGN.md."""
 from . import _native  # noqa: F401  (fails loudly if libwfl.so or _wfl_torch.so is missing)
 from . import graph  # noqa: F401
+from .metrics import ErrorCounter  # noqa: F401
 
-__all__ = ["graph", "criterions", "engine", "load_criterion", "load_from_checkpoint"]
+__all__ = ["graph", "criterions", "engine", "metrics", "ErrorCounter", "load_criterion", "load_from_checkpoint"]
 
 
 def load_criterion(criterion_type, preprocessor, config):

@@ -15,6 +15,7 @@ import torch
 from .. import _native as N
 from .. import engine as E
 from .. import graph as G
+from .. import metrics as M
 
 
 def pack_replabels(tokens, num_replabels):
@@ -335,16 +336,32 @@ class ASG(torch.nn.Module):
                 targets[idx] = interleaved
         return ASGLoss(inputs, self.transitions, targets, "mean")
 
-    def viterbi(self, outputs):
-        """asg.py:211-237: best label sequence under emissions + transitions, repeats collapsed,
-        garbage dropped, replabels unpacked."""
+    def _best_paths(self, outputs):
+        """(label paths [B,T] int32 on the device, whether viterbi() and errors() decode them there)"""
         B, T, C = outputs.shape
         assert C == self.N, "Wrong number of classes in output."
         dev = E.require_gpu()
         x = E.as_device_f32(outputs.detach(), dev)
         W = E.as_device_f32(self.transitions.detach(), dev)
-        paths = E.dense_viterbi(x, W)
-        if outputs.is_cuda and B > 0:
+        return E.dense_viterbi(x, W), outputs.is_cuda and B > 0
+
+    def viterbi(self, outputs):
+        """asg.py:211-237: best label sequence under emissions + transitions, repeats collapsed,
+        garbage dropped, replabels unpacked."""
+        paths, on_device = self._best_paths(outputs)
+        if on_device:
             # collapse, garbage and replabels on the device: only the labels that survive travel (csrc/decode_kernels.hip)
             return E.decode_paths(paths, self.garbage_idx, self.num_replabels)
         return collapse_and_unpack(paths, self.garbage_idx, self.num_replabels)
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter):
+        """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
+        (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
+        the device the count runs behind the same decode and the predictions never reach the host."""
+        counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
+        with torch.no_grad():
+            if not (outputs.is_cuda and outputs.shape[0] > 0):
+                return counter(self.viterbi(outputs), targets)
+            paths, _ = self._best_paths(outputs)
+            return counter.totals(M.decode_paths_errors(counter, targets, paths, self.garbage_idx, self.num_replabels))

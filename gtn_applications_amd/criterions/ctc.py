@@ -13,6 +13,7 @@ import torch
 from .. import _native as N
 from .. import engine as E
 from .. import graph as G
+from .. import metrics as M
 
 
 class CTCLossFunction(torch.autograd.Function):
@@ -225,13 +226,32 @@ class CTC(torch.nn.Module):
             )
         return CTCLoss(log_probs, [t.tolist() for t in targets], self.blank, "mean")
 
-    def viterbi(self, outputs):
-        """Greedy decode (ctc.py:126-135): argmax, collapse repeats, drop blank."""
+    def _device_decode(self, outputs):
+        """(x, drop, flags) of the device decode viterbi() and errors() take, or None: the host decodes"""
         if (outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 3 and outputs.numel() > 0
                 and 0 <= self.blank < outputs.shape[2]):
+            return outputs.detach().contiguous(), self.blank, N.DECODE_NAN_IS_MAX
+        return None
+
+    def viterbi(self, outputs):
+        """Greedy decode (ctc.py:126-135): argmax, collapse repeats, drop blank."""
+        plan = self._device_decode(outputs)
+        if plan is not None:
             # argmax (torch.argmax's rule for NaNs), collapse and drop on the device: only the labels that survive travel
-            return E.decode_emissions(outputs.detach().contiguous(), self.blank, flags=N.DECODE_NAN_IS_MAX,
-                                      dtype=torch.int64)
+            return E.decode_emissions(plan[0], plan[1], flags=plan[2], dtype=torch.int64)
         best = torch.argmax(outputs, dim=2).to("cpu").numpy()
         flat, lens = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
         return E.split_rows(flat, lens, torch.int64)
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter):
+        """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
+        (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
+        the device the count runs behind the same decode and the predictions never reach the host."""
+        C = outputs.shape[2]
+        counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")  # (the blank is never emitted)
+        with torch.no_grad():
+            plan = self._device_decode(outputs)
+            if plan is None:
+                return counter(self.viterbi(outputs), targets)
+            return counter.totals(M.decode_emissions_errors(counter, targets, plan[0], plan[1], flags=plan[2]))

@@ -21,6 +21,7 @@ import torch
 from .. import _native as N
 from .. import engine as E
 from .. import graph as G
+from .. import metrics as M
 
 
 def make_scalar_graph(weight):
@@ -304,9 +305,10 @@ class Transducer(torch.nn.Module):
         self.tokens.arc_sort()  # (the order the host decode looks at the graph in, below)
         return _token_decode_plan(self.tokens, C)
 
-    def viterbi(self, outputs):
-        """transducer.py:199-234: best frame-level path (under the transition model if any), then
-        the shortest token sequence that path can transduce to."""
+    def _decode_plan(self, outputs):
+        """What viterbi() and errors() decode, after the best frame-level path (under the transition model if any):
+        ("emissions", x, drop, bias, flags) / ("paths", frames, drop, flags): the device decode's operands;
+        ("host", labels, offsets): frame labels on the host, for wfl_transducer_decode_batch."""
         B, T, C = outputs.shape
         dev = E.require_gpu()
         x = E.as_device_f32(outputs.detach(), dev)
@@ -325,32 +327,59 @@ class Transducer(torch.nn.Module):
             keep = labs != G.epsilon
             offsets = np.zeros(B + 1, np.int64)
             np.cumsum(np.bincount(np.repeat(np.arange(B), lens)[keep], minlength=B), out=offsets[1:])
-            labels = np.ascontiguousarray(labs[keep], dtype=np.int32)
+            return "host", np.ascontiguousarray(labs[keep], dtype=np.int32), offsets
+        # (drop, flags) of the device decode, or None: the host decodes (a token graph that is not make_token_graph's,
+        # labels outside its alphabet, emissions that came from the host)
+        plan = self._device_decode(C) if outputs.is_cuda and B > 0 and T > 0 else None
+        if kind == "bigram":
+            # the fully connected recursion of the dense engine in the max-plus semiring (as the normaliser of the
+            # loss takes its log-semiring one): its best state per frame IS the label path, no epsilon to remove
+            frames = E.dense_viterbi(*_bigram_dense_operands(x, params, C))
+            if plan is not None:
+                return "paths", frames, plan[0], plan[1]
         else:
-            # (drop, flags) of the device decode, or None: the host decodes (a token graph that is not make_token_graph's,
-            # labels outside its alphabet, emissions that came from the host)
-            plan = self._device_decode(C) if outputs.is_cuda and B > 0 and T > 0 else None
-            if kind == "bigram":
-                # the fully connected recursion of the dense engine in the max-plus semiring (as the normaliser of the
-                # loss takes its log-semiring one): its best state per frame IS the label path, no epsilon to remove
-                frames = E.dense_viterbi(*_bigram_dense_operands(x, params, C))
-                if plan is not None:
-                    return E.decode_paths(frames, plan[0], flags=plan[1])
-            else:
-                if plan is not None:
-                    # argmax (of x + p under the unigram model), collapse and drop in one pass over x on the device
-                    return E.decode_emissions(x, plan[0], bias=params if kind == "unigram" else None, flags=plan[1])
-                # viterbi_path of the bare emissions graph: per frame, the first maximal label -- of x + p under the
-                # unigram model (one node, one self-loop per token)
-                frames = E.row_argmax(x + params if kind == "unigram" else x)
-            labels = frames.cpu().numpy().reshape(-1)
-            offsets = np.arange(B + 1, dtype=np.int64) * T
+            if plan is not None:
+                # argmax (of x + p under the unigram model), collapse and drop in one pass over x on the device
+                return "emissions", x, plan[0], params if kind == "unigram" else None, plan[1]
+            # viterbi_path of the bare emissions graph: per frame, the first maximal label -- of x + p under the
+            # unigram model (one node, one self-loop per token)
+            frames = E.row_argmax(x + params if kind == "unigram" else x)
+        return "host", frames.cpu().numpy().reshape(-1), np.arange(B + 1, dtype=np.int64) * T
+
+    def viterbi(self, outputs):
+        """transducer.py:199-234: best frame-level path (under the transition model if any), then
+        the shortest token sequence that path can transduce to."""
+        plan = self._decode_plan(outputs)
+        if plan[0] == "paths":
+            return E.decode_paths(plan[1], plan[2], flags=plan[3])
+        if plan[0] == "emissions":
+            return E.decode_emissions(plan[1], plan[2], bias=plan[3], flags=plan[4])
+        return self._host_decode(plan[1], plan[2])
+
+    def _host_decode(self, labels, offsets):
         self.tokens.arc_sort()
         # one native call for the batch (the reference's gtn.parallel_for over process(b), transducer.py:232);
         # ambiguous decodings: the shortest wins (transducer.py:226-228)
         out, out_off = G.transducer_decode_batch(self.tokens, labels, offsets)
         flat = torch.from_numpy(out)  # (int32: torch.IntTensor, as transducer.py:233)
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter):
+        """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
+        (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
+        the device the count runs behind the same decode and the predictions never reach the host."""
+        C = outputs.shape[2]
+        dplan = self._device_decode(C)
+        # (a blank in the last column is never emitted)
+        counter.check_hypothesis_labels(C - 1 if dplan is not None and dplan[0] == C - 1 else C, "Transducer.errors")
+        with torch.no_grad():
+            plan = self._decode_plan(outputs)
+            if plan[0] == "paths":
+                return counter.totals(M.decode_paths_errors(counter, targets, plan[1], plan[2], flags=plan[3]))
+            if plan[0] == "emissions":
+                return counter.totals(M.decode_emissions_errors(counter, targets, plan[1], plan[2], bias=plan[3], flags=plan[4]))
+            return counter(self._host_decode(plan[1], plan[2]), targets)
 
 
 def _token_decode_plan(tokens, C):

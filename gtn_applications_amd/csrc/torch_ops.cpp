@@ -17,6 +17,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <list>
 #include <map>
 #include <mutex>
@@ -897,36 +898,186 @@ std::vector<at::Tensor> decode_collect(const at::Tensor& on, int B, int T, int R
   return flat.split_with_sizes(lens);
 }
 
-std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
-                                         int64_t num_replabels, int64_t flags, bool as_int64) {
+// What a decode op checks once and then issues -- launch(ws, out, capacity, out_offsets, stream) --, shared by the op
+// that collects the labels on the host and the one that counts errors behind the same launch.
+struct DecodeCall {
+  at::Tensor on;  // the input: its device is the launches'
+  int B = 0, T = 0, R = 0;
+  std::function<void(void*, int32_t*, int64_t, int64_t*, void*)> launch;
+};
+
+DecodeCall emissions_call(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
+                          int64_t flags) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "decode_emissions: x must be a contiguous float32 [B,T,C] device tensor");
   const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
-  const float* bp = nullptr;
+  at::Tensor bt;
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->device() == x.device() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == C,
                 "decode_emissions: bias must be a contiguous float32 [C] tensor on x's device");
-    bp = bias->data_ptr<float>();
+    bt = *bias;
   }
-  DeviceScope scope(x.device().index());
-  const float* xp = x.data_ptr<float>();
-  return decode_collect(x, B, T, (int)num_replabels, as_int64, [&](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
-    check(wfl_decode_emissions(xp, bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out, cap, offs, s), "decode_emissions");
-  });
+  return {x, B, T, (int)num_replabels, [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
+            const float* bp = bt.defined() ? bt.data_ptr<float>() : nullptr;
+            check(wfl_decode_emissions(x.data_ptr<float>(), bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out, cap,
+                                       offs, s),
+                  "decode_emissions");
+          }};
 }
 
-std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
-                                     bool as_int64) {
+DecodeCall paths_call(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags) {
   TORCH_CHECK(paths.is_cuda() && paths.scalar_type() == at::kInt && paths.dim() == 2 && (paths.size(1) == 0 || paths.stride(1) == 1) &&
                   paths.size(1) >= T,
               "decode_paths: paths must be an int32 [B, >= T] device tensor with unit stride along the frames");
   const int B = (int)paths.size(0);
   const int64_t stride = B > 1 ? paths.stride(0) : paths.size(1);
+  return {paths, B, (int)T, (int)num_replabels, [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
+            check(wfl_decode_paths(paths.data_ptr<int32_t>(), stride, B, (int)T, (int)drop, (int)num_replabels, (int)flags, ws, out,
+                                   cap, offs, s),
+                  "decode_paths");
+          }};
+}
+
+std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
+                                         int64_t num_replabels, int64_t flags, bool as_int64) {
+  const DecodeCall c = emissions_call(x, bias, drop, num_replabels, flags);
+  DeviceScope scope(x.device().index());
+  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+}
+
+std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
+                                     bool as_int64) {
+  const DecodeCall c = paths_call(paths, T, drop, num_replabels, flags);
   DeviceScope scope(paths.device().index());
-  const int32_t* pp = paths.data_ptr<int32_t>();
-  return decode_collect(paths, B, (int)T, (int)num_replabels, as_int64, [&](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
-    check(wfl_decode_paths(pp, stride, B, (int)T, (int)drop, (int)num_replabels, (int)flags, ws, out, cap, offs, s), "decode_paths");
-  });
+  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Token and word error counts behind the decode (wfl_errors_count, csrc/error_kernels.hip): counterpart of the
+// reference's compute_edit_distance (train.py:74-87).  Hypotheses and references stay on the device; the B x 4
+// counts land in a small pinned buffer per device behind one event, the way decode_collect lands its labels.
+// ------------------------------------------------------------------------------------------------------------
+struct ErrorTable {  // a side's expansion table on the device: int32 [exp_ptr: V + 1 | exp_sym], or none (identity)
+  const int32_t* ptr = nullptr;
+  const int32_t* sym = nullptr;
+  int V = 0, longest = 1;
+};
+ErrorTable error_table(const c10::optional<at::Tensor>& t, int64_t V, int64_t longest, int dev, const char* what) {
+  ErrorTable e;
+  if (!t.has_value() || !t->defined()) return e;
+  TORCH_CHECK(t->is_cuda() && t->device().index() == dev && t->scalar_type() == at::kInt && t->is_contiguous() && V >= 1 &&
+                  t->numel() > V && longest >= 0 && longest <= INT32_MAX,
+              "errors: the ", what, " table must be a contiguous int32 [V + 1 + symbols] tensor on the batch's device");
+  e.ptr = t->data_ptr<int32_t>(), e.sym = e.ptr + V + 1, e.V = (int)V, e.longest = (int)longest;
+  return e;
+}
+
+struct ErrorBuffer {
+  std::mutex mu;
+  at::Tensor pinned;  // [B][4] int32
+  hipEvent_t done = nullptr;
+};
+ErrorBuffer& error_buffer(int dev) {
+  static std::mutex mu;
+  static auto* buffers = new std::map<int, ErrorBuffer>();  // (never destroyed: see g_targets)
+  std::lock_guard<std::mutex> lock(mu);
+  return (*buffers)[dev];
+}
+
+// the count behind hypotheses that are on device `dev` already; -> int64 CPU tensor [B, 4]
+at::Tensor errors_collect(int dev, int B, const int32_t* hyp, const int64_t* hyp_off, int64_t hyp_capacity,
+                          const std::shared_ptr<StagedTargets>& ref, const ErrorTable& ht, const ErrorTable& rt, int64_t sep) {
+  TORCH_CHECK(ref && ref->dev_buf.is_cuda() && ref->dev_buf.device().index() == dev,
+              "errors: the targets must be staged on the device of the hypotheses");
+  if (ref->B != B) throw py::value_error("errors: " + std::to_string(B) + " predictions for " + std::to_string(ref->B) + " targets");
+  if (rt.ptr && ref->n > 0 && (ref->label_min < 0 || ref->label_max >= rt.V))
+    throw py::value_error("errors: target label " + std::to_string(ref->label_min < 0 ? ref->label_min : ref->label_max) +
+                          " is outside the reference table [0, " + std::to_string(rt.V) + ")");
+  int64_t ws_bytes = 0;
+  check(wfl_errors_workspace(B, hyp_capacity, ref->n, ht.longest, rt.longest, &ws_bytes), "errors");
+  at::Tensor ws = at::empty({ws_bytes}, at::TensorOptions().dtype(at::kByte).device(at::Device(at::kCUDA, (c10::DeviceIndex)dev)));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+  ref->wait_upload();
+  const char* rbase = static_cast<const char*>(ref->dev_buf.data_ptr());
+  at::Tensor counts = at::empty({B, 4}, at::TensorOptions().dtype(at::kLong));
+  ErrorBuffer& buf = error_buffer(dev);
+  {
+    py::gil_scoped_release nogil;
+    std::lock_guard<std::mutex> lock(buf.mu);
+    const int64_t need = (int64_t)B * 4;
+    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
+      int64_t cap = 1 << 12;
+      while (cap < need) cap <<= 1;
+      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kInt).pinned_memory(true));
+    }
+    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
+    int32_t* landed = buf.pinned.data_ptr<int32_t>();
+    check(wfl_errors_count(hyp, hyp_off, reinterpret_cast<const int32_t*>(rbase + ref->off_flat),
+                           reinterpret_cast<const int64_t*>(rbase), B, ht.ptr, ht.sym, ht.V, rt.ptr, rt.sym, rt.V,
+                           sep < 0 ? -1 : (int)sep, hyp_capacity, ref->n, ws.data_ptr(), landed, (void*)stream),
+          "errors_count");
+    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess, "errors: ",
+                hipGetErrorString(hipGetLastError()));
+    int64_t* dst = counts.data_ptr<int64_t>();
+    for (int64_t i = 0; i < need; ++i) dst[i] = landed[i];
+  }
+  return counts;
+}
+
+// hypotheses that are on the host: staged like targets (the one stager), then counted on the device
+at::Tensor errors_count(const std::shared_ptr<StagedTargets>& hyp, const std::shared_ptr<StagedTargets>& ref,
+                        const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                        const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  TORCH_CHECK(hyp && hyp->dev_buf.is_cuda(), "errors_count: the predictions must be staged on a GPU");
+  const int dev = hyp->dev_buf.device().index();
+  if (hyp->B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
+  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
+  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
+  if (ht.ptr && hyp->n > 0 && (hyp->label_min < 0 || hyp->label_max >= ht.V))
+    throw py::value_error("errors: predicted label " + std::to_string(hyp->label_min < 0 ? hyp->label_min : hyp->label_max) +
+                          " is outside the hypothesis table [0, " + std::to_string(ht.V) + ")");
+  DeviceScope scope(dev);
+  hyp->wait_upload();
+  const char* hbase = static_cast<const char*>(hyp->dev_buf.data_ptr());
+  return errors_collect(dev, (int)hyp->B, reinterpret_cast<const int32_t*>(hbase + hyp->off_flat),
+                        reinterpret_cast<const int64_t*>(hbase), hyp->n, ref, ht, rt, sep);
+}
+
+// the decode's launch into device buffers, the count behind it: the predictions never reach the host
+at::Tensor decode_errors(const DecodeCall& c, const std::shared_ptr<StagedTargets>& ref,
+                         const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                         const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  const int dev = c.on.device().index();
+  if (c.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
+  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
+  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
+  TORCH_CHECK(c.B > 0, "errors: an empty batch of emissions for ", ref ? ref->B : 0, " targets");
+  DeviceScope scope(dev);
+  int64_t capacity = 0, ws_bytes = 0;
+  check(wfl_decode_workspace(c.B, c.T, c.R, &capacity, &ws_bytes), "decode");
+  const auto bytes = c.on.options().dtype(at::kByte);
+  at::Tensor ws = at::empty({ws_bytes}, bytes);
+  at::Tensor out = at::empty({capacity}, bytes.dtype(at::kInt));
+  at::Tensor offs = at::empty({c.B + 1}, bytes.dtype(at::kLong));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+  c.launch(ws.data_ptr(), out.data_ptr<int32_t>(), capacity, offs.data_ptr<int64_t>(), (void*)stream);
+  return errors_collect(dev, c.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, ref, ht, rt, sep);
+}
+
+at::Tensor decode_emissions_errors(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
+                                   int64_t flags, const std::shared_ptr<StagedTargets>& ref,
+                                   const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                                   const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  return decode_errors(emissions_call(x, bias, drop, num_replabels, flags), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
+                       ref_longest, sep);
+}
+
+at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
+                               const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
+                               int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table, int64_t ref_V,
+                               int64_t ref_longest, int64_t sep) {
+  return decode_errors(paths_call(paths, T, drop, num_replabels, flags), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
+                       ref_longest, sep);
 }
 
 }  // namespace
@@ -937,6 +1088,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors");
   m.def("decode_paths", &decode_paths, py::arg("paths"), py::arg("T"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), "viterbi()'s decode from [B, >= T] int32 device label paths: B CPU tensors");
+  m.def("errors_count", &errors_count,
+        "token and word error counts (train.py:74-87) of staged predictions against staged targets: int64 CPU [B, 4]");
+  m.def("decode_emissions_errors", &decode_emissions_errors,
+        "decode_emissions' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
+  m.def("decode_paths_errors", &decode_paths_errors,
+        "decode_paths' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
   m.def("ctc_fast_backward", &ctc_fast_backward,
         "loss.backward() of a CtcStep loss without the autograd engine (false: not the plain case, use the engine)");
   m.def(

@@ -522,6 +522,42 @@ int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C,
 int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, int drop, int num_replabels, int flags,
                      void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
+ *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
+ *   train.py:278-284 and test.py:94-109 -- per utterance b:
+ *     1. s_hyp = the labels hyp[hyp_off[b] .. hyp_off[b+1]) with each label replaced by its expansion, s_ref the same
+ *        over ref.  Each side has its own optional table (exp_ptr int32 [V+1], exp_sym int32 [exp_ptr[V]]): label v
+ *        stands for the symbols exp_sym[exp_ptr[v] .. exp_ptr[v+1]), possibly none (tokens_to_text for word pieces,
+ *        to_text for graphemes, train.py:80).  NULL tables: a label is its own symbol.  A label outside [0, V)
+ *        expands to nothing.
+ *     2. sep >= 0: leading and trailing `sep` symbols are removed from both strings (str.strip(wordsep)).
+ *     3. counts[b][0] = the Levenshtein distance of the two strings (unit costs), counts[b][1] = |s_ref|.
+ *     4. sep >= 0: the words of a string are its maximal runs of symbols other than `sep` (no empty words:
+ *        filter(None, split(wordsep)), train.py:81-82); counts[b][2] = the Levenshtein distance of the two word
+ *        sequences -- two words are equal iff they are the same symbols in the same order, compared exactly --,
+ *        counts[b][3] = the number of reference words.  sep < 0: both 0.
+ *   hyp / hyp_off are what wfl_decode_emissions / wfl_decode_paths left (hyp_capacity: their out_capacity; the lengths
+ *   are known only on the device, the kernels read the offsets themselves), ref / ref_off the targets of the batch
+ *   (int64 offsets [B+1], int32 labels, ref_labels of them).  Every index read from device memory is clamped to its
+ *   buffer.  counts [B][4] int32 is written by plain stores of a kernel: any device-accessible memory, pinned host
+ *   memory included.  ws: device scratch of wfl_errors_workspace's size, 16-byte aligned, contents irrelevant before
+ *   and after.  Three launches on `stream`, no allocation, no synchronisation, no atomics.
+ *   WFL_ERR_INVALID: B < 1, a NULL required pointer, a negative capacity, a table pointer without its partner, V < 1
+ *   with a table, a negative max_expansion.  Any string length is served, 0 on either or both sides included.
+ * ------------------------------------------------------------------------------------------------ */
+/* ws_bytes = the device scratch of a wfl_errors_count call (compute_edit_distance, train.py:74-87, test.py:94-109) whose tables' longest expansions are
+ * hyp_max_expansion / ref_max_expansion symbols (1 without a table): derived from the capacities and these maxima, never
+ * from data on the device.  WFL_ERR_UNSUPPORTED: a side's capacity x max_expansion beyond 2^30 - 1 symbols. */
+int wfl_errors_workspace(int B, int64_t hyp_capacity, int64_t ref_labels, int hyp_max_expansion, int ref_max_expansion,
+                         int64_t* ws_bytes);
+/* counts[b] = {token distance, reference tokens, word distance, reference words} of utterance b: compute_edit_distance
+ * (train.py:74-87; test.py:94-109) for the whole batch */
+int wfl_errors_count(const int32_t* hyp, const int64_t* hyp_off, const int32_t* ref, const int64_t* ref_off, int B,
+                     const int32_t* hyp_exp_ptr, const int32_t* hyp_exp_sym, int hyp_V, const int32_t* ref_exp_ptr,
+                     const int32_t* ref_exp_sym, int ref_V, int sep, int64_t hyp_capacity, int64_t ref_labels, void* ws,
+                     int32_t* counts /* [B][4] */, void* stream);
+
 /* small device utilities used by the Python layer (kept here so the product never needs a
  * torch op inside the timed path) */
 /* dst[0..nbytes) (device) = src_pinned[0..nbytes) (PINNED host memory, e.g. hipHostMalloc / a pin_memory tensor), by
