@@ -149,6 +149,7 @@ _SIGS = {
     # device: ConvTransduce1D
     "wfl_stc_augment": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
     "wfl_stc_augment_grad": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P]),
+    "wfl_conv_lds_limit": (c_int, []),
     "wfl_conv_forward": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     "wfl_conv_grad": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P,
                               _P]),

@@ -775,6 +775,8 @@ class _KernelTable:
                     tab[k, 1] |= 1 << i
                 n += 3 + ns + int(skip)
         self.table, self.num_arcs = tab, n
+        toks = [c for tok in self.lexicon for c in tok]
+        self.min_tok, self.max_tok = (min(toks), max(toks)) if toks else (0, 0)  # checked against C in the forward
         self.flags = (N.CONV_SPIKE if spike else 0) | (N.CONV_BLANK_OPTIONAL if blank_optional else 0)
         self._dev = {}
 
@@ -784,11 +786,35 @@ class _KernelTable:
             t = self._dev[device] = torch.from_numpy(self.table).to(device)
         return t
 
+    def check_classes(self, C):
+        """Every sub-token and the blank index must name one of a row's C classes: the kernels index a window's LDS
+        copy with them, unchecked (the reference scores an entry with a label no emission carries -inf: DESIGN.md 3.4)."""
+        blank = self.blank_idx
+        if not 0 <= blank < C:
+            raise ValueError(f"ConvTransduce1D: blank_idx {blank} is outside the input's {C} classes")
+        if self.min_tok < 0 or self.max_tok >= C:
+            k, c = next((k, c) for k, tok in enumerate(self.lexicon) for c in tok if not 0 <= c < C)
+            raise ValueError(f"ConvTransduce1D: lexicon entry {k} {self.lexicon[k]} has sub-token {c}, outside the "
+                             f"input's {C} classes")
+
 
 class ConvTransduce1DFunction(torch.autograd.Function):
     """transducer.py:461-552.  `kernels` is the lexicon table built by ConvTransduce1D (a list of
     kernel graphs made by make_kernel_graph is accepted too and converted).  Unlike the reference
     there is no process-global CTX_GRAPHS: everything backward needs lives on `ctx` (re-entrant)."""
+
+    @classmethod
+    def apply(cls, inputs, kernels, kernel_size, stride, kernel_params=None, viterbi=False):
+        # The backward keeps the window and its gradient rows in LDS, twice the forward's bytes: a shape only the
+        # forward has room for is refused before the forward runs, not in the middle of autograd.  (Asked here: inside
+        # forward() grad mode is off and ctx.needs_input_grad ignores torch.no_grad().)
+        if (torch.is_grad_enabled() and inputs.dim() == 3
+                and any(t is not None and t.requires_grad for t in (inputs, kernel_params))):
+            C = inputs.shape[2]
+            if 1 <= kernel_size <= 16 and 2 * kernel_size * C * 4 > N.lib.wfl_conv_lds_limit():  # (conv_check's test)
+                raise N.WflUnsupported(N.ERR_UNSUPPORTED, f"conv_grad: window of {kernel_size} frames x {C} classes "
+                                                          "does not fit LDS")
+        return super().apply(inputs, kernels, kernel_size, stride, kernel_params, viterbi)
 
     @staticmethod
     @E.on_input_device
@@ -798,6 +824,7 @@ class ConvTransduce1DFunction(torch.autograd.Function):
             raise ValueError(f"Input ({T}) too short for kernel ({kernel_size})")
         if not isinstance(kernels, _KernelTable):
             raise TypeError("ConvTransduce1DFunction: pass the ConvTransduce1D module's kernel table")
+        kernels.check_classes(C)
         dev = E.require_gpu()
         x = E.as_device_f32(inputs.detach(), dev)
         params = E.as_device_f32(kernel_params.detach(), dev) if kernel_params is not None else None

@@ -347,6 +347,8 @@ static int conv_check(const float* x, int B, int T, int C, const int32_t* ktab, 
   return WFL_OK;
 }
 
+int wfl_conv_lds_limit(void) { return kLdsBytes; }
+
 int wfl_conv_forward(const float* x, int B, int T, int C, const int32_t* ktab, int K, int ks, int stride, int blank,
                      int flags, const float* params, int semiring, float* out, void* stream) {
   int Tout = 0;

@@ -385,6 +385,9 @@ int wfl_dense_viterbi(const float* x, const float* W, int B, int T, int C, float
  * ------------------------------------------------------------------------------------------------ */
 #define WFL_CONV_SPIKE 1          /* flags: no self loops on sub-token states */
 #define WFL_CONV_BLANK_OPTIONAL 2 /* flags: state 2L-1 accepts, skip arcs between different sub-tokens */
+/* Bytes of LDS a launch may use: the forward stages ks*C*4 of them, the backward twice that, and either returns
+ * WFL_ERR_UNSUPPORTED beyond it (a caller that will need the gradient can ask before it runs the forward). */
+int wfl_conv_lds_limit(void);
 int wfl_conv_forward(const float* x, int B, int T, int C, const int32_t* ktab, int K, int ks,
                      int stride, int blank, int flags, const float* params, int semiring, float* out,
                      void* stream);

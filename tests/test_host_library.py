@@ -371,6 +371,33 @@ def test_conv_kernel_table_matches_kernel_graphs():
             assert tab.num_arcs == n
 
 
+def test_conv_transduce_checks_classes_and_backward_lds_before_it_needs_a_gpu():
+    """A sub-token or blank outside the input's classes never reaches the kernels (they index LDS with it), and a shape only
+    the forward has LDS for is refused when a gradient will be asked for: both before the first device call."""
+    import torch
+
+    from gtn_applications_amd.criterions import transducer as TR
+
+    x = torch.zeros(1, 5, 4)
+    for lexicon, entry in (([(0, 1), (), (2, 4)], 2), ([(0, -1), (2,)], 0)):
+        tab = TR._KernelTable(lexicon, True, False)
+        tab.blank_idx = 3
+        with pytest.raises(ValueError, match=f"entry {entry} "):
+            TR.ConvTransduce1DFunction.apply(x, tab, 5, 1)
+    assert (tab.min_tok, tab.max_tok) == (-1, 2)
+    tab = TR._KernelTable([(0, 1), ()], True, False)
+    for blank in (4, -1):
+        tab.blank_idx = blank
+        with pytest.raises(ValueError, match="blank_idx"):
+            TR.ConvTransduce1DFunction.apply(x, tab, 5, 1)
+    limit = N.lib.wfl_conv_lds_limit()
+    assert limit >= 64 * 1024
+    tab.blank_idx = 2
+    C = limit // (2 * 15 * 4) + 1  # the smallest row whose backward does not fit at ks = 15
+    with pytest.raises(N.WflUnsupported, match=f"conv_grad: window of 15 frames x {C} classes does not fit LDS"):
+        TR.ConvTransduce1DFunction.apply(torch.zeros(1, 15, C, requires_grad=True), tab, 15, 1)
+
+
 def test_load_criterion_factory(golden_dir):
     """utils.load_criterion (utils.py:245-273): criterion types, output sizes, unknown type"""
     import types
