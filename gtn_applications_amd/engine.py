@@ -228,6 +228,7 @@ class PackedLattice:
         finally:
             N.lib.wfl_lattice_host_free(host_handle)
         self.device = device
+        self.max_wid = -1  # largest learnable-weight id of the arcs where the constructor knows it (from_graphs)
         self._host = None
         self._uploaded = None
         self._ordered = set()  # (streams order_behind_upload has ordered behind the upload)
@@ -300,7 +301,9 @@ class PackedLattice:
                 arr.append(w.ctypes.data)
             wid_ptrs = (ctypes.c_void_p * n)(*arr)
         h = N.lib.wfl_lattice_pack(handles, wid_ptrs, n, B, int(bool(shared)), int(C))
-        return cls(h, device)
+        pack = cls(h, device)
+        pack.max_wid = max((int(w.max()) for w in keep if w.size), default=-1)
+        return pack
 
     @classmethod
     def transducer_batch(cls, tokens, lexicon, transitions, flat, offsets, C, device, nthreads=0, extra=None):
@@ -345,6 +348,13 @@ class PackedLattice:
         return src[off:off + count]
 
 
+def check_weight_ids(pack, weights, what):
+    """The kernels index `weights` (and the gradient w.r.t. it) with the arcs' weight ids: an id beyond the tensor is a
+    caller error, rejected before any kernel reads or adds there.  (raw addresses cannot be checked)"""
+    if pack.max_wid >= 0 and isinstance(weights, torch.Tensor) and weights.numel() <= pack.max_wid:
+        raise ValueError(f"{what}: weight id {pack.max_wid} is outside the {weights.numel()} learnable weights")
+
+
 class LatticeState:
     """Everything the backward pass needs from a forward pass of the lattice engine."""
 
@@ -369,6 +379,7 @@ def lattice_forward(x, pack, weights=None, need_beta=True, semiring=N.SEMIRING_L
     pack.order_behind_upload()
     if d.B != B:
         raise ValueError(f"lattice batch has {d.B} utterances, emissions have {B}")
+    check_weight_ids(pack, weights, "lattice_forward")
     n_xg, n_ab = ctypes.c_int64(), ctypes.c_int64()
     N.check(N.lib.wfl_lattice_workspace(pack._desc_ref, T, ctypes.byref(n_xg), ctypes.byref(n_ab)))
     dev = x.device
@@ -415,6 +426,7 @@ def lattice_formats(st):
 def lattice_grad(st, coef, coef_w=None, gout=None, dx=None, accumulate=False, dW=None):
     """Posteriors of the lattice -> dense emission gradient rows (and learnable-weight grads)."""
     p = st.pack
+    check_weight_ids(p, dW, "lattice_grad")
     tok = _mark("lattice_grad" + ("/shared" if p.desc.shared else ""))
     N.check(
         N.lib.wfl_lattice_grad(
