@@ -39,7 +39,7 @@ class WflUnsupported(WflError):
 class CtcCall(ctypes.Structure):
     """Mirror of `wfl_ctc_call` (include/wfl.h)."""
 
-    _fields_ = [("n_labels", c_int64), ("host_state", c_void_p)]
+    _fields_ = [("n_labels", c_int64), ("host_state", c_void_p), ("input_lengths", c_void_p)]
 
 
 class LatticeDesc(ctypes.Structure):
@@ -168,6 +168,8 @@ _SIGS = {
     "wfl_ctc_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     "wfl_ctc_workspace_field": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_ctc_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "wfl_ctc_forward_lengths": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "wfl_ctc_grad_lengths": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "wfl_ctc_grad": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "wfl_ctc_forward_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P]),
@@ -179,10 +181,14 @@ _SIGS = {
     "wfl_decode_chunk_frames": (c_int, []),
     "wfl_decode_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_decode_emissions": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
+    "wfl_decode_emissions_lengths": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
     "wfl_decode_paths": (c_int, [_P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
     # device: token and word error counts behind a best path
     "wfl_errors_workspace": (c_int, [c_int, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wfl_errors_count": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int64, c_int64, _P, _P, _P]),
+    # device: per-utterance input lengths of a padded CTC batch
+    "wfl_ctc_pad_frames": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "wfl_zero_pad_rows": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "wfl_upload": (c_int, [_P, _P, c_int64, _P]),
     "wfl_reduce_loss": (c_int, [_P, _P, _P, c_int, c_float, c_int, _P, _P]),
     "wfl_scale": (c_int, [_P, c_int64, _P, _P]),

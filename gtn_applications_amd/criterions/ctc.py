@@ -6,6 +6,7 @@ on host threads (ctc.py:38-65), this sends the whole batch through the CTC fast-
 (csrc/ctc_kernels.hip; up to four target positions per lane) -- or, for targets longer than 255
 labels, through the generic lattice engine (csrc/lattice_kernels.hip).  Both are HIP paths; there is no CPU path.
 """
+import operator
 import os
 
 import torch
@@ -16,7 +17,54 @@ from .. import graph as G
 from .. import metrics as M
 
 
+def check_input_lengths(input_lengths, B, T, what, keep_full=False):
+    """The per-utterance input lengths of a padded batch as a tuple of B ints, or None when every utterance has all T
+    frames (`input_lengths` None, or all equal to T: exactly the call without lengths).  `input_lengths`: B integers
+    1 <= T_b <= T as a list, a tuple or a 1-D integer tensor -- a device tensor is read back, which costs one
+    synchronisation.  ValueError naming the utterance otherwise; nothing here needs a device.  keep_full: lengths that
+    all equal T are returned as they are -- for emissions that are not float32, which are taken WITH lengths only (the
+    padded copy is what converts them), whatever the lengths of the batch at hand are."""
+    if input_lengths is None:
+        return None
+    if isinstance(input_lengths, torch.Tensor):
+        if input_lengths.dim() != 1:
+            raise ValueError(f"{what}: input_lengths must be 1-D, got a tensor of {input_lengths.dim()} dimensions")
+        if input_lengths.dtype.is_floating_point or input_lengths.dtype.is_complex or input_lengths.dtype == torch.bool:
+            raise ValueError(f"{what}: input_lengths must be integers, got a {input_lengths.dtype} tensor")
+        values = input_lengths.tolist()
+    elif isinstance(input_lengths, (list, tuple)):
+        values = list(input_lengths)
+    else:
+        raise ValueError(f"{what}: input_lengths must be a list, a tuple or a 1-D integer tensor, "
+                         f"got {type(input_lengths).__name__}")
+    if len(values) != B:
+        raise ValueError(f"{what}: got {len(values)} input lengths for a batch of {B}")
+    lens = []
+    for b, v in enumerate(values):
+        if isinstance(v, torch.Tensor) and v.dim() == 0 and not (v.dtype.is_floating_point or v.dtype == torch.bool):
+            v = v.item()
+        try:
+            n = None if isinstance(v, bool) else operator.index(v)
+        except TypeError:
+            n = None
+        if n is None:
+            raise ValueError(f"{what}: the input length of utterance {b} is not an integer: {v!r}")
+        if not 1 <= n <= T:
+            raise ValueError(f"{what}: input length {n} of utterance {b} is outside [1, {T}]")
+        lens.append(n)
+    return None if not keep_full and all(n == T for n in lens) else tuple(lens)
+
+
 class CTCLossFunction(torch.autograd.Function):
+    """`input_lengths` (padded batches; an addition to the reference's call): utterance b has the frames [0, T_b), the
+    frames behind them are read as certain-blank frames -- 0 for the blank, -inf for every other class -- which are the
+    identity of the CTC label graph ("Input lengths as certain-blank frames").  The training step of float32
+    device emissions with targets of up to 63 labels substitutes them inside its launches (wfl_ctc_call.input_lengths);
+    every other route runs unchanged on a copy of the emissions padded that way (wfl_ctc_pad_frames).  The pad rows of
+    every gradient are set to exactly 0 (wfl_zero_pad_rows) before it is handed out.  Whenever `input_lengths` is passed, emissions of
+    another floating dtype are taken too (the padded copy is float32, the gradient comes back in their dtype) -- also
+    when all the lengths equal T; float32 emissions with such lengths take exactly the path without lengths."""
+
     @staticmethod
     def create_ctc_graph(target, blank_idx):
         """ctc.py:15-29 as a host graph (API parity; the kernels never need it)."""
@@ -36,14 +84,20 @@ class CTCLossFunction(torch.autograd.Function):
 
     @staticmethod
     @E.on_input_device
-    def forward(ctx, log_probs, targets, blank_idx=0, reduction="none"):
+    def forward(ctx, log_probs, targets, blank_idx=0, reduction="none", input_lengths=None):
         B, T, C = log_probs.shape
         if T == 0:
             raise ValueError("CTCLoss: empty emissions (T == 0)")
         if reduction not in ("none", "mean"):  # ctc.py:57-58
             raise ValueError("invalid value for reduction '" + str(reduction) + "'")
+        lens = check_input_lengths(input_lengths, B, T, "CTCLoss", keep_full=log_probs.dtype != torch.float32)
         dev = E.require_gpu()
-        x = E.as_device_f32(log_probs.detach(), dev)
+        if lens is None:
+            x = E.as_device_f32(log_probs.detach(), dev)
+        else:
+            if not log_probs.dtype.is_floating_point:
+                raise TypeError(f"expected a floating point tensor, got {log_probs.dtype}")
+            x = log_probs.detach().to(device=dev, dtype=torch.float32).contiguous()
         tg = E.targets_on_device(targets, dev)
         if tg.B != B:
             raise ValueError(f"got {tg.B} targets for a batch of {B}")
@@ -51,6 +105,19 @@ class CTCLossFunction(torch.autograd.Function):
         if not 0 <= int(blank_idx) < C:
             raise ValueError(f"CTCLoss: blank index {blank_idx} is outside [0, {C})")
         need_grad = log_probs.requires_grad
+        xlen = ctx.xlen = ctx.launch_xlen = None
+        if lens is not None:
+            xlen = ctx.xlen = E.input_lengths_on_device(lens, dev)
+            if (need_grad and tg.max_len <= E.CTC_LENGTHS_MAX_LEN and E.ctc_fast_path_ok(tg.max_len, C)
+                    and log_probs.is_cuda and log_probs.dtype == torch.float32):
+                # the step's launches read the lengths themselves (wfl_ctc_call.input_lengths: the stagers of the
+                # meet-in-the-middle launch, the log-domain chain and gradient bodies): no copy of the emissions
+                ctx.launch_xlen = xlen
+            else:
+                # everything else -- longer targets, the lattice engine, no gradient, emissions that are not float32
+                # or not on the device -- sweeps T frames of a copy whose pad rows are the identity frames; the chains,
+                # the gradient blocks and the lattice engine score a -inf arc as the reference's intersect does
+                x = E.ctc_pad_frames(x, xlen, int(blank_idx))
         if E.ctc_fast_path_ok(tg.max_len, C) and need_grad:
             # loss and gradient in ONE pipelined launch (gradient waves run behind the chains); backward
             # only applies the upstream scalar.  Like torch's own CTC, the gradient is produced eagerly.
@@ -59,7 +126,9 @@ class CTCLossFunction(torch.autograd.Function):
             dx = torch.empty_like(x)
             lse = E.row_lse(x) if ctx_log_softmax(ctx) else None
             _, _, loss = E.ctc_forward_backward(x, tg, int(blank_idx), coef, None, dx, loss_scale=scale, want_loss=True,
-                                                lse=lse, shared_ws=True)
+                                                lse=lse, shared_ws=True, xlen=ctx.launch_xlen)
+            if xlen is not None:  # (the eager gradient: zeroed here, on the launch's stream, before anything can hand it out)
+                E.zero_pad_rows(dx, xlen)
             ctx.aux = ("pipelined", x, tg, int(blank_idx), dx, coef, lse)
         elif ctx_log_softmax(ctx):
             raise RuntimeError("fused log_softmax CTC is only used on the pipelined path")
@@ -77,7 +146,7 @@ class CTCLossFunction(torch.autograd.Function):
             st = E.lattice_forward(x, pack, need_beta=need_grad)
             loss = E.reduce_loss(st.logz, scale, -1.0)
             ctx.aux = ("lattice", x, st, coef)
-        ctx.in_device = log_probs.device
+        ctx.in_device, ctx.in_dtype = log_probs.device, log_probs.dtype
         return loss if log_probs.is_cuda else loss.cpu()
 
     @staticmethod
@@ -92,7 +161,9 @@ class CTCLossFunction(torch.autograd.Function):
                 # place) by the first one, so run the same launch again -- with the same row log-sum-exps when
                 # the log_softmax is fused -- into a fresh buffer, the upstream scalar applied by the kernel
                 dx = torch.empty_like(x)
-                E.ctc_forward_backward(x, tg, blank, coef, gout, dx, lse=lse, shared_ws=True)
+                E.ctc_forward_backward(x, tg, blank, coef, gout, dx, lse=lse, shared_ws=True, xlen=ctx.launch_xlen)
+                if ctx.xlen is not None:
+                    E.zero_pad_rows(dx, ctx.xlen)
             else:
                 E.scale_inplace(dx, gout)
                 ctx.aux = ("pipelined", x, tg, blank, None, coef, lse)
@@ -102,9 +173,13 @@ class CTCLossFunction(torch.autograd.Function):
             dx = torch.empty_like(x)
             _, _, st, coef = ctx.aux
             E.lattice_grad(st, coef, gout=gout, dx=dx)
+            if ctx.xlen is not None:
+                E.zero_pad_rows(dx, ctx.xlen)
         if ctx.in_device.type != "cuda":
             dx = dx.to(ctx.in_device)
-        return dx, None, None, None
+        if dx.dtype != ctx.in_dtype:  # (only with input lengths: other dtypes are rejected in forward)
+            dx = dx.to(ctx.in_dtype)
+        return dx, None, None, None, None
 
 
 def ctx_log_softmax(ctx):
@@ -119,9 +194,9 @@ class _FusedLogSoftmaxCTCLoss(CTCLossFunction):
 
     @staticmethod
     @E.on_input_device
-    def forward(ctx, inputs, targets, blank_idx=0, reduction="none"):
+    def forward(ctx, inputs, targets, blank_idx=0, reduction="none", input_lengths=None):
         ctx.fused_log_softmax = True
-        return CTCLossFunction.forward(ctx, inputs, targets, blank_idx, reduction)
+        return CTCLossFunction.forward(ctx, inputs, targets, blank_idx, reduction, input_lengths)
 
 
 class _EagerLoss(torch.Tensor):
@@ -172,11 +247,19 @@ def _native_node():
 
 
 @E.on_input_device
-def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax):
+def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax, input_lengths=None):
     """CTCLossFunction.apply, with the hot case -- float32 device emissions that require grad, targets the fast
     kernels take -- routed through the C++ autograd node: same checks, same staging, same launch, but neither the
     forward nor the backward passes through Python's autograd.Function machinery (which costs more host time than
-    the step's kernels take on the GPU at the benchmark shape)."""
+    the step's kernels take on the GPU at the benchmark shape).  A call with input lengths (a padded batch) goes
+    through CTCLossFunction, which pads a copy and zeroes the gradient's pad rows around the same launches."""
+    if input_lengths is not None and log_probs.dim() == 3:
+        # checked before anything needs a device; lengths that all equal T are the call without lengths
+        input_lengths = check_input_lengths(input_lengths, log_probs.shape[0], log_probs.shape[1], "CTCLoss",
+                                            keep_full=log_probs.dtype != torch.float32)
+    if input_lengths is not None:
+        fn = _FusedLogSoftmaxCTCLoss if fused_log_softmax else CTCLossFunction
+        return fn.apply(log_probs, targets, blank_idx, reduction, input_lengths)
     if (type(log_probs) is torch.Tensor and log_probs.is_cuda and log_probs.requires_grad
             and log_probs.dtype == torch.float32 and log_probs.dim() == 3 and log_probs.is_contiguous()
             and torch.is_grad_enabled() and log_probs.shape[1] > 0 and reduction in ("none", "mean")):
@@ -202,9 +285,12 @@ def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax):
     return fn.apply(log_probs, targets, blank_idx, reduction)
 
 
-def CTCLoss(log_probs, targets, blank_idx=0, reduction="none"):
-    """ctc.py:96 (`CTCLoss = CTCLossFunction.apply`): same call, same result."""
-    return _ctc_loss(log_probs, targets, blank_idx, reduction, False)
+def CTCLoss(log_probs, targets, blank_idx=0, reduction="none", input_lengths=None):
+    """ctc.py:96 (`CTCLoss = CTCLossFunction.apply`): same call, same result.  `input_lengths` (an addition: B integers
+    1 <= T_b <= T, see check_input_lengths): the loss and gradient of the utterances log_probs[b, :T_b] -- the frames
+    behind T_b of a padded batch do not count, their gradient rows are exactly 0; "mean" still divides by the target
+    length.  None, or lengths that all equal T, is the call without them."""
+    return _ctc_loss(log_probs, targets, blank_idx, reduction, False, input_lengths)
 
 
 class CTC(torch.nn.Module):
@@ -214,17 +300,24 @@ class CTC(torch.nn.Module):
         self.use_pt = use_pt  # use torch.nn.functional.ctc_loss instead of the WFST engine
 
     @E.on_input_device
-    def forward(self, inputs, targets):
+    def forward(self, inputs, targets, input_lengths=None):
+        """ctc.py:106-122.  `input_lengths` (an addition, see CTCLoss): the frames of each utterance of a padded batch;
+        with use_pt they go to torch's operator in place of [T] * B."""
+        lens = None
+        if input_lengths is not None:
+            lens = check_input_lengths(input_lengths, inputs.shape[0], inputs.shape[1], "CTC",
+                                       keep_full=inputs.dtype != torch.float32)
         if not self.use_pt and inputs.requires_grad and inputs.dtype == torch.float32 and \
                 E.ctc_fast_path_ok(max((t.numel() for t in targets), default=0), inputs.shape[2]):
-            return _ctc_loss(inputs, targets, self.blank, "mean", True)
+            return _ctc_loss(inputs, targets, self.blank, "mean", True, lens)
         log_probs = torch.nn.functional.log_softmax(inputs, dim=2)
         if self.use_pt:  # ctc.py:109-121
             return torch.nn.functional.ctc_loss(
-                log_probs.permute(1, 0, 2), torch.cat(targets), [inputs.shape[1]] * inputs.shape[0],
+                log_probs.permute(1, 0, 2), torch.cat(targets),
+                [inputs.shape[1]] * inputs.shape[0] if lens is None else list(lens),
                 [t.numel() for t in targets], blank=self.blank, zero_infinity=True,
             )
-        return CTCLoss(log_probs, [t.tolist() for t in targets], self.blank, "mean")
+        return CTCLoss(log_probs, [t.tolist() for t in targets], self.blank, "mean", lens)
 
     def _device_decode(self, outputs):
         """(x, drop, flags) of the device decode viterbi() and errors() take, or None: the host decodes"""
@@ -233,25 +326,41 @@ class CTC(torch.nn.Module):
             return outputs.detach().contiguous(), self.blank, N.DECODE_NAN_IS_MAX
         return None
 
-    def viterbi(self, outputs):
-        """Greedy decode (ctc.py:126-135): argmax, collapse repeats, drop blank."""
+    def viterbi(self, outputs, input_lengths=None):
+        """Greedy decode (ctc.py:126-135): argmax, collapse repeats, drop blank.  `input_lengths` (an addition, see
+        CTCLoss): row b is decoded as outputs[b, :T_b] -- a pad frame is a blank, which the collapse drops."""
+        lens = None
+        if input_lengths is not None:
+            lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.viterbi")
         plan = self._device_decode(outputs)
         if plan is not None:
             # argmax (torch.argmax's rule for NaNs), collapse and drop on the device: only the labels that survive travel
-            return E.decode_emissions(plan[0], plan[1], flags=plan[2], dtype=torch.int64)
+            if lens is None:
+                return E.decode_emissions(plan[0], plan[1], flags=plan[2], dtype=torch.int64)
+            with torch.cuda.device(outputs.device):  # (the lengths are staged through the current device's stream)
+                xlen = E.input_lengths_on_device(lens, outputs.device)
+                return E.decode_emissions(plan[0], plan[1], flags=plan[2], dtype=torch.int64, lengths=xlen)
         best = torch.argmax(outputs, dim=2).to("cpu").numpy()
-        flat, lens = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
-        return E.split_rows(flat, lens, torch.int64)
+        if lens is not None:
+            for b, n in enumerate(lens):
+                best[b, n:] = self.blank
+        flat, kept = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
+        return E.split_rows(flat, kept, torch.int64)
 
     @E.on_input_device
-    def errors(self, outputs, targets, counter):
+    def errors(self, outputs, targets, counter, input_lengths=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
-        the device the count runs behind the same decode and the predictions never reach the host."""
+        the device the count runs behind the same decode and the predictions never reach the host.  `input_lengths`
+        (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s."""
+        lens = None
+        if input_lengths is not None:
+            lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.errors")
         C = outputs.shape[2]
         counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")  # (the blank is never emitted)
         with torch.no_grad():
             plan = self._device_decode(outputs)
             if plan is None:
-                return counter(self.viterbi(outputs), targets)
-            return counter.totals(M.decode_emissions_errors(counter, targets, plan[0], plan[1], flags=plan[2]))
+                return counter(self.viterbi(outputs, lens), targets)
+            xlen = None if lens is None else E.input_lengths_on_device(lens, outputs.device)
+            return counter.totals(M.decode_emissions_errors(counter, targets, plan[0], plan[1], flags=plan[2], lengths=xlen))

@@ -146,6 +146,12 @@ struct CtcArgs {
   long long n_labels;
   // meet-in-the-middle launch: polls a wave waits for a hand-off before it gives up (ctc_mitm.h, mitm_give_up)
   int spin;
+  // per-utterance input lengths of a padded batch, [B] on the device, or NULL (every utterance has T frames): a frame
+  // t >= xlen[b] is read as a certain-blank frame -- 0 for the blank, -inf for every other class, nothing subtracted
+  // under the fused log_softmax -- the identity of the CTC label graph.  Applied where a launch
+  // has a block's raw scores: the stagers of ctc_mitm.h, ctc_log_chain_body, ctc_grad_body.  (Targets of more than 63
+  // labels -- the ctc_long_* bodies -- do not read it: their callers pad a copy, wfl_ctc_pad_frames.)
+  const int32_t* xlen;
 };
 constexpr int kXcStride = 64;
 
@@ -281,6 +287,8 @@ __device__ __forceinline__ void ctc_log_chain_body(const CtcArgs& a, int b, int 
   const bool skip = has_label && lane >= 1 && y != yprev;
   const float* xrow = a.x + (int64_t)b * T * C;
   const int col = has_label ? y : a.blank;
+  const int Tb = a.xlen ? a.xlen[b] : T;  // (one scalar per workgroup)
+  const float xpad = col == a.blank ? 0.f : kNegBig;  // this lane's score in a certain-blank frame
   const CtcWs w = ctc_ws_layout(a.B, T, P);
   const int NB = ctc_blocks(T);
   if (only_flagged && ((const int32_t*)(a.ws + w.flag))[b] == 0) return;  // uniform per workgroup
@@ -322,6 +330,11 @@ __device__ __forceinline__ void ctc_log_chain_body(const CtcArgs& a, int b, int 
     float xs[kBlk];
 #pragma unroll
     for (int j = 0; j < kBlk; ++j) xs[j] = to_score(LSM ? raw[j] - readlane_f(lse_raw, j) : raw[j]);
+    if (k * kBlk + n > Tb) {  // (wave-uniform, never with xlen == NULL) frames behind the utterance's length
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j)
+        if ((dir == 0 ? k * kBlk + j : k * kBlk + n - 1 - j) >= Tb) xs[j] = xpad;
+    }
     const float m = fold16<true>(xs, lane);  // every lane: the largest score of frame lane % 16 (lanes > L hold the blank's)
     const float rr = m > 0.5f * kNegBig ? rintf(m) : 0.f;
 #pragma unroll
@@ -834,6 +847,13 @@ __device__ __forceinline__ void ctc_grad_body(const CtcArgs& a, bool valid, int 
     for (int j = 0; j < kBlk; ++j) xl[j] = xrow[(int64_t)min(t0 + j, T - 1) * C + col];  // all 16 gathers in flight
 #pragma unroll
     for (int j = 0; j < kBlk; ++j) xl[j] = to_score(lsm ? xl[j] - readlane_f(lse_blk, j) : xl[j]);
+    const int Tb = a.xlen ? a.xlen[b] : T;
+    if (t0 + n > Tb) {  // (wave-uniform, never with xlen == NULL) frames behind the utterance's length: certain-blank frames
+      const float xpad = col == a.blank ? 0.f : kNegBig;
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j)
+        if (t0 + j >= Tb) xl[j] = xpad;
+    }
     // The block in the probability domain on doubles, with per-frame references as in the chain (ctc_log_chain_body):
     // alpha'_j beta~'_j = alpha_j beta~_j 2^-R for every frame j < n, R = the sum of the block's references.  The fp32
     // log-add recursions this replaces carried the states that HOLD the posterior mass at ~2^-100 of the wave's largest
@@ -1674,8 +1694,25 @@ int wfl_ctc_workspace_field(int B, int T, int max_len, int field, int64_t* offse
   return WFL_OK;
 }
 
+static int ctc_forward_impl(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                            int blank, int flags, float* ws, float* nll, const int32_t* input_lengths, void* stream);
+
 int wfl_ctc_forward(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
                     int blank, int flags, float* ws, float* nll, void* stream) {
+  return ctc_forward_impl(x, B, T, C, targets, offsets, max_len, blank, flags, ws, nll, nullptr, stream);
+}
+
+int wfl_ctc_forward_lengths(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                            int blank, int flags, float* ws, float* nll, const int32_t* input_lengths, void* stream) {
+  if (!input_lengths || max_len > 63) {
+    set_error("ctc_forward_lengths: needs input_lengths and targets of up to 63 labels (max_len %d)", max_len);
+    return input_lengths ? WFL_ERR_UNSUPPORTED : WFL_ERR_INVALID;
+  }
+  return ctc_forward_impl(x, B, T, C, targets, offsets, max_len, blank, flags, ws, nll, input_lengths, stream);
+}
+
+static int ctc_forward_impl(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                            int blank, int flags, float* ws, float* nll, const int32_t* input_lengths, void* stream) {
   if (int rc = ctc_check(B, T, C, max_len, blank, "ctc_forward")) return rc;
   if (!x || !targets || !offsets || !ws || !nll) {
     set_error("ctc_forward: null buffer");
@@ -1687,6 +1724,7 @@ int wfl_ctc_forward(const float* x, int B, int T, int C, const int32_t* targets,
     return WFL_ERR_UNSUPPORTED;
   }
   CtcArgs a{x, B, T, C, max_len + 1, blank, targets, offsets, ws, nll};
+  a.xlen = input_lengths;
   const int ppl = (max_len + 1 + 63) / 64;  // target positions per lane
   if (ppl > 1) {  // long targets: multi-position lanes
     const dim3 grid((unsigned)B, 2u);
@@ -1734,6 +1772,12 @@ static int ctc_forward_backward_impl(const float* x, int B, int T, int C, const 
   }
   CtcArgs a{x, B, T, C, max_len + 1, blank, targets, offsets, ws, nll, 0ull, loss_scale, loss_out, row_lse};
   a.n_labels = call && call->n_labels > 0 ? call->n_labels : 0;
+  a.xlen = call ? call->input_lengths : nullptr;
+  if (a.xlen && max_len > 63) {
+    set_error("ctc_forward_backward: input_lengths are read by the launches of targets up to 63 labels (max_len %d): pad a "
+              "copy with wfl_ctc_pad_frames", max_len);
+    return WFL_ERR_UNSUPPORTED;
+  }
   // how long a wave of the meet-in-the-middle launch waits for a hand-off before it gives up and the repair launch
   // recomputes the batch (WFL_CTC_MITM_SPIN: polls; tests force the time-out with 1)
   static const int mitm_spin = [] {
@@ -1886,15 +1930,36 @@ static int ctc_forward_backward_impl(const float* x, int B, int T, int C, const 
   return WFL_OK;
 }
 
+static int ctc_grad_impl(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                         int blank, const float* ws, const float* nll, const float* coef, const float* gout, float* dx,
+                         const int32_t* input_lengths, void* stream);
+
 int wfl_ctc_grad(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
                  int blank, const float* ws, const float* nll, const float* coef, const float* gout, float* dx,
                  void* stream) {
+  return ctc_grad_impl(x, B, T, C, targets, offsets, max_len, blank, ws, nll, coef, gout, dx, nullptr, stream);
+}
+
+int wfl_ctc_grad_lengths(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                         int blank, const float* ws, const float* nll, const float* coef, const float* gout, float* dx,
+                         const int32_t* input_lengths, void* stream) {
+  if (!input_lengths || max_len > 63) {
+    set_error("ctc_grad_lengths: needs input_lengths and targets of up to 63 labels (max_len %d)", max_len);
+    return input_lengths ? WFL_ERR_UNSUPPORTED : WFL_ERR_INVALID;
+  }
+  return ctc_grad_impl(x, B, T, C, targets, offsets, max_len, blank, ws, nll, coef, gout, dx, input_lengths, stream);
+}
+
+static int ctc_grad_impl(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets, int max_len,
+                         int blank, const float* ws, const float* nll, const float* coef, const float* gout, float* dx,
+                         const int32_t* input_lengths, void* stream) {
   if (int rc = ctc_check(B, T, C, max_len, blank, "ctc_grad")) return rc;
   if (!x || !targets || !offsets || !ws || !nll || !dx) {
     set_error("ctc_grad: null buffer");
     return WFL_ERR_INVALID;
   }
   CtcArgs a{x, B, T, C, max_len + 1, blank, targets, offsets, (float*)ws, (float*)nll};
+  a.xlen = input_lengths;
   const int64_t items = (int64_t)B * ctc_blocks(T);
   const int ppl = (max_len + 1 + 63) / 64;
   const bool lcompact = ppl == 1 && C > 120;  // (see wfl_ctc_forward_backward)

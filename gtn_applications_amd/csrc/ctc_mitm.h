@@ -628,6 +628,7 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
   const bool skipn = lane + 1 < L && ynext != y;
   const float* xrow = a.x + (int64_t)b * T * C;
   const int col = has_label ? y : a.blank;
+  const int Tb = a.xlen ? a.xlen[b] : T;  // the utterance's frames (CtcArgs.xlen): one scalar per workgroup
   const CtcWs w = ctc_ws_layout(a.B, T, P);
   const int NB = ctc_blocks(T);
   const int H0 = mitm_first_emitted(NB, dir);  // blocks n < H0 are published, blocks n >= H0 emitted
@@ -736,6 +737,20 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
       if (lane == 0)
         __hip_atomic_store(xflag + (int64_t)(b * 2 + dir) * NB + 1 + n, a.token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
+    // Frames behind the utterance's length (CtcArgs.xlen) are certain-blank frames: 0 in the blank's lane(s), -inf
+    // elsewhere, nothing subtracted under LSM -- stage()'s reference / exp2 / NaN filter then give the reference 0 and the
+    // factors 1 and 0.  Before publish_xc, so the partner reads the same values.  The test is wave-uniform and false for
+    // every block when xlen is NULL.
+    auto pad_block = [&](int n, float (&raw)[kBlk], float& lse_blk) {
+      const int k = dir == 0 ? n : NB - 1 - n;
+      const int t0 = k * kBlk, cnt = min(kBlk, T - t0);
+      if (t0 + cnt <= Tb) return;
+      const float xpad = col == a.blank ? 0.f : WFL_NEG_INF;
+#pragma unroll
+      for (int j = 0; j < kBlk; ++j)
+        if ((dir == 0 ? t0 + j : t0 + cnt - 1 - j) >= Tb) raw[j] = xpad;
+      if (LSM && (dir == 0 ? t0 + (lane & 15) : t0 + cnt - 1 - (lane & 15)) >= Tb) lse_blk = 0.f;
+    };
     float lse_raw = 0.f;
     auto issue_lse = [&](int n) {
       if (LSM) {
@@ -799,6 +814,7 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
       wait_slot(n);
       {
         MITM_T0();
+        pad_block(n, ra, la);
         stage(n, ra, la);
         MITM_ACC(st_wait1);
       }
@@ -810,6 +826,7 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
         wait_slot(n2);
         {
           MITM_T0();
+          pad_block(n2, rb, lb);
           stage(n2, rb, lb);
           MITM_ACC(st_wait1);
         }
@@ -839,10 +856,10 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
       __hip_atomic_store((int32_t*)(a.ws + w.zcnt) + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (dir == 0) {
-      // bit 63 of dup[b]: the target cannot be aligned at all -- T < L + adjacent repeats.  Such an utterance has
+      // bit 63 of dup[b]: the target cannot be aligned at all -- T_b < L + adjacent repeats (T_b: the utterance's frames).  Such an utterance has
       // Z = 0 exactly, in any arithmetic: loss inf, zero gradient, nothing for the certificate to doubt
       const int repeats = __builtin_popcountll(__builtin_amdgcn_ballot_w64(has_label && lane >= 1 && y == yprev));
-      if (lane == 0) coherent_store64((unsigned long long*)(a.ws + w.dup) + b, T < L + repeats ? 1ull << 63 : 0ull);
+      if (lane == 0) coherent_store64((unsigned long long*)(a.ws + w.dup) + b, Tb < L + repeats ? 1ull << 63 : 0ull);
     }
     for (int kk = 0; kk < NB; ++kk) {
       {
@@ -1152,7 +1169,7 @@ __device__ __forceinline__ void ctc_mitm_body(const CtcArgs& a, int b, int dir, 
     // (below).  The repair launch evaluates the certificates in full only if it is up (ctc_repair_kernel).
     unsigned long long* suspect = (unsigned long long*)(a.ws + w.suspect);
     if (any_bad && lane == 0) coherent_store64(suspect, a.token);
-    const bool cannot_align = T < L + __builtin_popcountll(__builtin_amdgcn_ballot_w64(has_label && lane >= 1 && y == yprev));
+    const bool cannot_align = Tb < L + __builtin_popcountll(__builtin_amdgcn_ballot_w64(has_label && lane >= 1 && y == yprev));
     if (dir == 0) {
       // Z = alpha_{T-1}[2L] + alpha_{T-1}[2L-1]   (ctc.py:21 accept states), lanes L and L-1
       const float zb = readlane_f(pb, L);

@@ -18,6 +18,11 @@
 //          then the chunk's kept values, replabels expanded, to out -- plain vector stores, so `out` / `out_offsets`
 //          may be pinned host memory.
 // No atomics anywhere: every position is a prefix sum, the result is deterministic.
+// Per-utterance lengths (wfl_decode_emissions_lengths: a padded batch, criterions/ctc.py): the frames t >= lengths[b] are
+// no candidates in the count step -- they are neither read nor kept, and everything behind the count step sees a row
+// that ends at lengths[b].
+#include <type_traits>
+
 #include "device_common.h"
 
 namespace wfl {
@@ -112,11 +117,13 @@ __device__ __forceinline__ void first_max_rows(const float* __restrict__ xb, int
   }
 }
 
-// The count step of one chunk, from its frame labels (lane i: frame t0 + i; prev0: the label of frame t0 - 1).
-__device__ __forceinline__ void decode_count_chunk(int lab, int prev0, int t0, int lane, const DecodeArgs& a,
+// The count step of one chunk, from its frame labels (lane i: frame t0 + i; prev0: the label of frame t0 - 1).  Tb <= a.T:
+// the frames of the utterance (wfl_decode_emissions_lengths) -- a frame t >= Tb is no candidate, so a chunk's kept
+// values, its first / last kept value and what the scan carries across the boundaries are those of a row that ends at Tb.
+__device__ __forceinline__ void decode_count_chunk(int lab, int prev0, int t0, int lane, const DecodeArgs& a, int Tb,
                                                    int32_t* __restrict__ summary, int32_t* __restrict__ values) {
   const int t = t0 + lane;
-  const bool valid = t < a.T;
+  const bool valid = t < Tb;
   int prev = __shfl_up(lab, 1, 64);
   if (lane == 0) prev = prev0;
   const bool keep = valid && (t == 0 || lab != prev) && lab != a.drop;
@@ -136,7 +143,7 @@ __device__ __forceinline__ void decode_count_chunk(int lab, int prev0, int t0, i
   if (valid && (a.flags & WFL_DECODE_BLANK_SEPARATED)) {
     if (t == 0) bad = lab != a.drop;
     else bad = !(lab == a.drop || prev == a.drop || lab == prev);
-    if (t == a.T - 1) bad = bad || lab != a.drop;
+    if (t == Tb - 1) bad = bad || lab != a.drop;
   }
   const int ok = __ballot(bad) == 0ull;
   if (lane == 0) {
@@ -148,15 +155,17 @@ __device__ __forceinline__ void decode_count_chunk(int lab, int prev0, int t0, i
   }
 }
 
-template <int NV, int RU>
+// LEN: per-utterance lengths (wfl_decode_emissions_lengths); without them the kernel is the one it was
+template <int NV, int RU, bool LEN>
 __global__ void __launch_bounds__(256) decode_count_emissions_kernel(const float* __restrict__ x, const float* __restrict__ bias,
-                                                                      int C, DecodeArgs a, int32_t* __restrict__ summaries,
-                                                                      int32_t* __restrict__ values) {
+                                                                      const int32_t* __restrict__ lengths, int C, DecodeArgs a,
+                                                                      int32_t* __restrict__ summaries, int32_t* __restrict__ values) {
   const int lane = threadIdx.x & 63;
   const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (chunk >= (int64_t)a.B * a.nch) return;  // (a whole wave)
   const int b = (int)(chunk / a.nch), t0 = (int)(chunk % a.nch) * kDecodeChunk;
   const float* xb = x + (int64_t)b * a.T * C;
+  const int Tb = LEN ? min(max(lengths[b], 0), a.T) : a.T;  // (wave-uniform; the rows read stay those of [0, T))
   const bool nan_is_max = (a.flags & WFL_DECODE_NAN_IS_MAX) != 0;
   float bv[NV > 0 ? NV : 1];
 #pragma unroll
@@ -165,16 +174,16 @@ __global__ void __launch_bounds__(256) decode_count_emissions_kernel(const float
     bv[i] = (bias && c < C) ? bias[c] : 0.f;
   }
   int prev0 = -1;
-  if (t0 > 0) first_max_rows<NV, 1>(xb, a.T, C, t0 - 1, lane, bv, bias, nan_is_max, &prev0);
+  if (t0 > 0 && t0 < Tb) first_max_rows<NV, 1>(xb, a.T, C, t0 - 1, lane, bv, bias, nan_is_max, &prev0);
   int lab = 0;
-  for (int u0 = 0; u0 < kDecodeChunk && t0 + u0 < a.T; u0 += RU) {
+  for (int u0 = 0; u0 < kDecodeChunk && t0 + u0 < Tb; u0 += RU) {
     int first[RU];
     first_max_rows<NV, RU>(xb, a.T, C, t0 + u0, lane, bv, bias, nan_is_max, first);
 #pragma unroll
     for (int u = 0; u < RU; ++u)
       if (lane == u0 + u) lab = first[u];
   }
-  decode_count_chunk(lab, prev0, t0, lane, a, summaries + chunk * kDecodeSummary, values + chunk * kDecodeChunk);
+  decode_count_chunk(lab, prev0, t0, lane, a, Tb, summaries + chunk * kDecodeSummary, values + chunk * kDecodeChunk);
 }
 
 __global__ void __launch_bounds__(256) decode_count_paths_kernel(const int32_t* __restrict__ paths, int64_t path_stride,
@@ -187,7 +196,7 @@ __global__ void __launch_bounds__(256) decode_count_paths_kernel(const int32_t* 
   const int32_t* row = paths + (int64_t)b * path_stride;
   const int lab = t0 + lane < a.T ? row[t0 + lane] : 0;
   const int prev0 = t0 > 0 ? row[t0 - 1] : -1;
-  decode_count_chunk(lab, prev0, t0, lane, a, summaries + chunk * kDecodeSummary, values + chunk * kDecodeChunk);
+  decode_count_chunk(lab, prev0, t0, lane, a, a.T, summaries + chunk * kDecodeSummary, values + chunk * kDecodeChunk);
 }
 
 // One wave per utterance: what crosses the chunk boundaries.  carry = the last kept value before the chunk (-1: none;
@@ -311,8 +320,9 @@ int wfl_decode_workspace(int B, int T, int num_replabels, int64_t* out_capacity,
   return WFL_OK;
 }
 
-int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C, int drop, int num_replabels, int flags,
-                         void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream) {
+static int decode_emissions_impl(const float* x, const float* bias, const int32_t* lengths, int B, int T, int C, int drop,
+                                 int num_replabels, int flags, void* ws, int32_t* out, int64_t out_capacity,
+                                 int64_t* out_offsets, void* stream) {
   DecodeArgs a;
   if (!x || C < 1 || drop >= C) {
     set_error("decode_emissions: bad arguments (C %d, drop %d)", C, drop);
@@ -324,22 +334,45 @@ int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C,
   int32_t* values = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + w.values);
   const unsigned grid = (unsigned)(((int64_t)B * a.nch + 3) / 4);
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, bias, C, a, summaries, values);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, bias, lengths, C, a, summaries, values);
   };
-  if (C <= 64)
-    launch(decode_count_emissions_kernel<1, 16>);
-  else if (C <= 128)
-    launch(decode_count_emissions_kernel<2, 8>);
-  else if (C <= 256)
-    launch(decode_count_emissions_kernel<4, 4>);
-  else if (C <= 512)
-    launch(decode_count_emissions_kernel<8, 2>);
-  else if (C <= 1024)
-    launch(decode_count_emissions_kernel<16, 1>);
+  auto pick = [&](auto len) {
+    constexpr bool LEN = decltype(len)::value;
+    if (C <= 64)
+      launch(decode_count_emissions_kernel<1, 16, LEN>);
+    else if (C <= 128)
+      launch(decode_count_emissions_kernel<2, 8, LEN>);
+    else if (C <= 256)
+      launch(decode_count_emissions_kernel<4, 4, LEN>);
+    else if (C <= 512)
+      launch(decode_count_emissions_kernel<8, 2, LEN>);
+    else if (C <= 1024)
+      launch(decode_count_emissions_kernel<16, 1, LEN>);
+    else
+      launch(decode_count_emissions_kernel<0, 1, LEN>);
+  };
+  if (lengths)
+    pick(std::true_type{});
   else
-    launch(decode_count_emissions_kernel<0, 1>);
+    pick(std::false_type{});
   WFL_LAUNCH_CHECK();
   return decode_finish(a, ws, out, out_offsets, (hipStream_t)stream);
+}
+
+int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C, int drop, int num_replabels, int flags,
+                         void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream) {
+  return decode_emissions_impl(x, bias, nullptr, B, T, C, drop, num_replabels, flags, ws, out, out_capacity, out_offsets, stream);
+}
+
+int wfl_decode_emissions_lengths(const float* x, const float* bias, const int32_t* lengths, int B, int T, int C, int drop,
+                                 int num_replabels, int flags, void* ws, int32_t* out, int64_t out_capacity,
+                                 int64_t* out_offsets, void* stream) {
+  if (!lengths) {
+    set_error("decode_emissions_lengths: lengths is NULL (wfl_decode_emissions decodes every frame)");
+    return WFL_ERR_INVALID;
+  }
+  return decode_emissions_impl(x, bias, lengths, B, T, C, drop, num_replabels, flags, ws, out, out_capacity, out_offsets,
+                               stream);
 }
 
 int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, int drop, int num_replabels, int flags,

@@ -906,8 +906,9 @@ struct DecodeCall {
   std::function<void(void*, int32_t*, int64_t, int64_t*, void*)> launch;
 };
 
+// lengths: int32 [B] on x's device (wfl_decode_emissions_lengths: a padded batch), or none: every frame is decoded
 DecodeCall emissions_call(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
-                          int64_t flags) {
+                          int64_t flags, const c10::optional<at::Tensor>& lengths = c10::nullopt) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "decode_emissions: x must be a contiguous float32 [B,T,C] device tensor");
   const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
@@ -917,11 +918,23 @@ DecodeCall emissions_call(const at::Tensor& x, const c10::optional<at::Tensor>& 
                 "decode_emissions: bias must be a contiguous float32 [C] tensor on x's device");
     bt = *bias;
   }
+  at::Tensor lt;
+  if (lengths.has_value() && lengths->defined()) {
+    TORCH_CHECK(lengths->device() == x.device() && lengths->scalar_type() == at::kInt && lengths->is_contiguous() &&
+                    lengths->dim() == 1 && lengths->numel() == B,
+                "decode_emissions: lengths must be a contiguous int32 [B] tensor on x's device");
+    lt = *lengths;
+  }
   return {x, B, T, (int)num_replabels, [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
             const float* bp = bt.defined() ? bt.data_ptr<float>() : nullptr;
-            check(wfl_decode_emissions(x.data_ptr<float>(), bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out, cap,
-                                       offs, s),
-                  "decode_emissions");
+            if (lt.defined())
+              check(wfl_decode_emissions_lengths(x.data_ptr<float>(), bp, lt.data_ptr<int32_t>(), B, T, C, (int)drop,
+                                                 (int)num_replabels, (int)flags, ws, out, cap, offs, s),
+                    "decode_emissions_lengths");
+            else
+              check(wfl_decode_emissions(x.data_ptr<float>(), bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out,
+                                         cap, offs, s),
+                    "decode_emissions");
           }};
 }
 
@@ -941,6 +954,14 @@ DecodeCall paths_call(const at::Tensor& paths, int64_t T, int64_t drop, int64_t 
 std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
                                          int64_t num_replabels, int64_t flags, bool as_int64) {
   const DecodeCall c = emissions_call(x, bias, drop, num_replabels, flags);
+  DeviceScope scope(x.device().index());
+  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+}
+
+std::vector<at::Tensor> decode_emissions_lengths(const at::Tensor& x, const c10::optional<at::Tensor>& bias,
+                                                 const at::Tensor& lengths, int64_t drop, int64_t num_replabels, int64_t flags,
+                                                 bool as_int64) {
+  const DecodeCall c = emissions_call(x, bias, drop, num_replabels, flags, lengths);
   DeviceScope scope(x.device().index());
   return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
 }
@@ -1072,6 +1093,15 @@ at::Tensor decode_emissions_errors(const at::Tensor& x, const c10::optional<at::
                        ref_longest, sep);
 }
 
+at::Tensor decode_emissions_lengths_errors(const at::Tensor& x, const c10::optional<at::Tensor>& bias, const at::Tensor& lengths,
+                                           int64_t drop, int64_t num_replabels, int64_t flags,
+                                           const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
+                                           int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table,
+                                           int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  return decode_errors(emissions_call(x, bias, drop, num_replabels, flags, lengths), ref, hyp_table, hyp_V, hyp_longest,
+                       ref_table, ref_V, ref_longest, sep);
+}
+
 at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
                                const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
                                int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table, int64_t ref_V,
@@ -1092,6 +1122,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "token and word error counts (train.py:74-87) of staged predictions against staged targets: int64 CPU [B, 4]");
   m.def("decode_emissions_errors", &decode_emissions_errors,
         "decode_emissions' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
+  m.def("decode_emissions_lengths", &decode_emissions_lengths,
+        "decode_emissions for a padded batch: lengths int32 [B] on x's device, frames t >= lengths[b] are not decoded");
+  m.def("decode_emissions_lengths_errors", &decode_emissions_lengths_errors,
+        "decode_emissions_lengths' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
   m.def("decode_paths_errors", &decode_paths_errors,
         "decode_paths' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
   m.def("ctc_fast_backward", &ctc_fast_backward,

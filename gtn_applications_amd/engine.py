@@ -839,6 +839,7 @@ class CtcTargets:
 
 
 _CTC_WS_SIZES = {}
+CTC_LENGTHS_MAX_LEN = 63  # longest target whose launches read input lengths themselves (beyond: a padded copy)
 CTC_FAST_MAX_LEN = 255  # longest target of the CTC fast path (four positions per lane); beyond: lattice engine
 CTC_FAST_MAX_CLASSES = 16000  # widest emission row of the CTC fast path (compact gradient tiles: 8 x (4 KB + C bytes) of LDS) ...
 CTC_FAST_MAX_CLASSES_LONG = 602  # ... and for targets of more than 63 labels (dense row tiles [17][C] per wave)
@@ -921,18 +922,72 @@ def decode_chunk_frames():
     return int(N.lib.wfl_decode_chunk_frames())
 
 
-def decode_emissions(x, drop, bias=None, num_replabels=0, flags=0, dtype=torch.int32):
+def decode_emissions(x, drop, bias=None, num_replabels=0, flags=0, dtype=torch.int32, lengths=None):
     """viterbi()'s decode from emissions, on the device (wfl_decode_emissions through csrc/torch_ops.cpp): per frame the
     first maximal class of x [B,T,C] (+ bias [C]), runs collapsed, `drop` (None: nothing) dropped, replabels unpacked.
     Returns B CPU tensors of `dtype` (int32 or int64), views of one tensor; only what survives the collapse leaves the
-    device."""
-    return N.ops.decode_emissions(x, bias, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64)
+    device.  lengths (int32 [B] on x's device, input_lengths_on_device): utterance b ends at frame lengths[b]
+    (wfl_decode_emissions_lengths)."""
+    drop = -1 if drop is None else int(drop)
+    if lengths is not None:
+        return N.ops.decode_emissions_lengths(x, bias, lengths, drop, num_replabels, flags, dtype == torch.int64)
+    return N.ops.decode_emissions(x, bias, drop, num_replabels, flags, dtype == torch.int64)
 
 
 def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int32):
     """The same decode from [B, >= T] int32 device label paths (wfl_dense_viterbi's): wfl_decode_paths."""
     T = paths.shape[1] if T is None else T
     return N.ops.decode_paths(paths, T, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64)
+
+
+_LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)
+
+
+def input_lengths_on_device(lengths, device):
+    """int32 [B] device tensor of a padded batch's input lengths (a sequence of B ints, already checked).  A small
+    upload of its own, apart from the targets' stager (whose cache and recognition of a re-used target list it does not
+    touch): the lengths of a training step differ from the last step's, so nothing is cached -- they are written into
+    the next slot of a ring of eight pinned buffers (allocated once; a slot is reused only after the upload that last
+    read it has completed) and a kernel reads them from there (wfl_upload: asynchronous, no synchronisation).  The
+    device buffer comes from torch's caching allocator; the upload and the launches that read it share the current
+    stream."""
+    device = torch.device(device)
+    index = torch.cuda.current_device() if device.index is None else device.index
+    rings = getattr(_LENGTH_RINGS, "by_device", None)
+    if rings is None:
+        rings = _LENGTH_RINGS.by_device = {}
+    ring = rings.get(index)
+    if ring is None:
+        ring = rings[index] = _StagingRing(slots=8, nbytes=1 << 12)
+    n = len(lengths)
+    nbytes = (4 * n + 15) & ~15
+    i, pinned, view = ring.next(nbytes, True)
+    view[:4 * n].view(np.int32)[:] = lengths
+    with torch.cuda.device(index):
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", index))
+        upload(dev, pinned, nbytes)
+        done = ring.events[i]
+        if done is None:
+            done = ring.events[i] = torch.cuda.Event()
+        done.record()
+    return dev[:4 * n].view(torch.int32)
+
+
+def ctc_pad_frames(x, lengths, blank):
+    """A copy of x [B,T,C] (float32, contiguous, on the device) whose rows t >= lengths[b] are certain-blank frames --
+    0 for the blank, -inf for every other class (wfl_ctc_pad_frames): the identity of the CTC label graph."""
+    B, T, C = x.shape
+    out = torch.empty_like(x)
+    N.check(N.lib.wfl_ctc_pad_frames(ptr(x), ptr(lengths), B, T, C, int(blank), ptr(out), stream_ptr()))
+    return out
+
+
+def zero_pad_rows(dx, lengths):
+    """dx[b, t, :] = 0 for t >= lengths[b], in place on the current stream (wfl_zero_pad_rows): behind every CTC
+    gradient taken with input lengths, before it is handed out."""
+    B, T, C = dx.shape
+    N.check(N.lib.wfl_zero_pad_rows(ptr(dx), ptr(lengths), B, T, C, stream_ptr()))
+    return dx
 
 
 def ctc_workspace(x, max_len):
@@ -957,10 +1012,13 @@ def ctc_reset_state():
     N.ops.ctc_reset_host_state()
 
 
-def ctc_forward_backward(x, tg, blank, coef, gout, dx, loss_scale=None, want_loss=False, lse=None, shared_ws=False):
+def ctc_forward_backward(x, tg, blank, coef, gout, dx, loss_scale=None, want_loss=False, lse=None, shared_ws=False,
+                         xlen=None):
     """Loss and gradient in one pipelined launch (wfl_ctc_forward_backward): returns (ws, nll) or,
     with want_loss, (ws, nll, mean_b(loss_scale[b] * nll[b]) as a 0-dim device tensor).  `coef` / `loss_scale`
-    may be tensors or raw device addresses (CtcTargets.addr).  shared_ws: use the per-stream cached workspace."""
+    may be tensors or raw device addresses (CtcTargets.addr).  shared_ws: use the per-stream cached workspace.
+    xlen (int32 [B] on the device, input_lengths_on_device; targets of up to CTC_LENGTHS_MAX_LEN labels): the launch reads
+    the frames t >= xlen[b] as certain-blank frames (wfl_ctc_call.input_lengths); the caller zeroes those rows of dx."""
     B, T, C = x.shape
     if shared_ws:
         ws, nll = ctc_workspace(x, tg.max_len)
@@ -975,7 +1033,7 @@ def ctc_forward_backward(x, tg, blank, coef, gout, dx, loss_scale=None, want_los
         nll = torch.empty(B, dtype=_F32, device=x.device)
     loss = torch.empty((), dtype=_F32, device=x.device) if want_loss else None
     tok = _mark("ctc_step")
-    call = N.CtcCall(tg.n, ctc_host_state(x, tg.max_len) or None)
+    call = N.CtcCall(tg.n, ctc_host_state(x, tg.max_len) or None, ptr(xlen))
     N.check(
         N.lib.wfl_ctc_forward_backward_call(ptr(x), B, T, C, ptr(tg.addr("flat")), ptr(tg.addr("offsets")), tg.max_len,
                                             blank, ptr(ws), ptr(nll), ptr(coef), ptr(gout), ptr(dx), ptr(loss_scale),

@@ -133,13 +133,17 @@ class ErrorCounter:
         return self.totals(self.counts(predictions, targets))
 
 
-def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=0, flags=0):
-    """engine.decode_emissions' launch and the counts behind it, on x's device: [B, 4] int64 on the host and nothing else"""
+def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=0, flags=0, lengths=None):
+    """engine.decode_emissions' launch and the counts behind it, on x's device: [B, 4] int64 on the host and nothing else
+    (lengths: int32 [B] on x's device, the frames of each utterance of a padded batch)"""
     if len(targets) != x.shape[0]:
         raise ValueError(f"errors: {x.shape[0]} utterances for {len(targets)} targets")
     ref = counter.staged_targets(targets, x.device)
-    return N.ops.decode_emissions_errors(x, bias, -1 if drop is None else int(drop), num_replabels, flags, ref._st,
-                                         *counter.tables(x.device))
+    drop = -1 if drop is None else int(drop)
+    if lengths is not None:
+        return N.ops.decode_emissions_lengths_errors(x, bias, lengths, drop, num_replabels, flags, ref._st,
+                                                     *counter.tables(x.device))
+    return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref._st, *counter.tables(x.device))
 
 
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):

@@ -439,6 +439,11 @@ int wfl_ctc_workspace_field(int B, int T, int max_len, int field, int64_t* offse
 int wfl_ctc_forward(const float* x, int B, int T, int C, const int32_t* targets,
                     const int64_t* offsets, int max_len, int blank, int flags, float* ws, float* nll,
                     void* stream);
+/* wfl_ctc_forward for a padded batch: input_lengths int32 [B] on the device (see wfl_ctc_call.input_lengths); targets of up
+ * to 63 labels (WFL_ERR_UNSUPPORTED beyond), WFL_ERR_INVALID for NULL lengths. */
+int wfl_ctc_forward_lengths(const float* x, int B, int T, int C, const int32_t* targets,
+                            const int64_t* offsets, int max_len, int blank, int flags, float* ws, float* nll,
+                            const int32_t* input_lengths, void* stream);
 /* Per-call extras of wfl_ctc_forward_backward_call -- everything the step remembers or assumes beyond its arguments
  * is the CALLER's:
  *   n_labels    the number of labels behind `targets` the caller vouches for (= offsets[B] as the host knows it; 0:
@@ -451,10 +456,17 @@ int wfl_ctc_forward(const float* x, int B, int T, int C, const int32_t* targets,
  *               waits for it), [1] is the step's own counter.  When the LAST lane-exponent step recomputed more than an
  *               eighth of its utterances the call goes straight to the log-domain step, and every 16th such call tries
  *               the lane-exponent step again.  NULL: every call starts with the lane-exponent step.  Results are within
- *               the parity bar on either path (bit-identical only on the same path); zero the words to forget. */
+ *               the parity bar on either path (bit-identical only on the same path); zero the words to forget.
+ *   input_lengths  per-utterance input lengths of a padded batch, int32 [B] on the DEVICE, 1 <= T_b <= T (the caller's
+ *               to check), or NULL: every utterance has T frames.  A frame t >= T_b is read as a certain-blank frame
+ *               (0 for the blank, -inf for every other class, nothing subtracted from it under row_lse): the identity
+ *               of the CTC label graph, so nll[b] and the gradient rows t < T_b are those of x[b, :T_b] alone.  The
+ *               launch still sweeps T frames; the rows t >= T_b of dx hold no gradient -- call wfl_zero_pad_rows behind
+ *               it.  Targets of up to 63 labels only (WFL_ERR_UNSUPPORTED beyond: pad a copy, wfl_ctc_pad_frames). */
 typedef struct wfl_ctc_call {
   int64_t n_labels;
   int32_t* host_state;
+  const int32_t* input_lengths;
 } wfl_ctc_call;
 
 /* wfl_ctc_forward and wfl_ctc_grad as ONE pipelined launch: gradient waves wait for the checkpoints
@@ -489,6 +501,10 @@ int wfl_row_argmax(const float* x, int64_t rows, int C, int32_t* out, void* stre
 int wfl_ctc_grad(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets,
                  int max_len, int blank, const float* ws, const float* nll, const float* coef,
                  const float* gout, float* dx, void* stream);
+/* wfl_ctc_grad behind wfl_ctc_forward_lengths (same lengths); the rows t >= T_b of dx hold no gradient: wfl_zero_pad_rows */
+int wfl_ctc_grad_lengths(const float* x, int B, int T, int C, const int32_t* targets, const int64_t* offsets,
+                         int max_len, int blank, const float* ws, const float* nll, const float* coef,
+                         const float* gout, float* dx, const int32_t* input_lengths, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: the decode behind a best path (csrc/decode_kernels.hip)
@@ -520,6 +536,14 @@ int wfl_decode_workspace(int B, int T, int num_replabels, int64_t* out_capacity,
  * WFL_DECODE_NAN_IS_MAX: torch.argmax's (ctc.py:128).  Replaces ctc.py:126-135 and transducer.py:216-232. */
 int wfl_decode_emissions(const float* x, const float* bias, int B, int T, int C, int drop, int num_replabels, int flags,
                          void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream);
+/* wfl_decode_emissions for a padded batch: lengths [B] int32 on the device, utterance b has the frames [0, lengths[b])
+ * (values are clamped to [0, T]).  A frame t >= lengths[b] is no candidate: it is not read, not kept, and the previous
+ * label / last kept value carried across the chunk boundaries are those of a row that ends at lengths[b] -- the result
+ * for utterance b is wfl_decode_emissions' of x[b, :lengths[b]] alone (WFL_DECODE_BLANK_SEPARATED: its last frame is
+ * lengths[b] - 1).  Same launches, workspace and capacities.  WFL_ERR_INVALID also for lengths == NULL. */
+int wfl_decode_emissions_lengths(const float* x, const float* bias, const int32_t* lengths, int B, int T, int C, int drop,
+                                 int num_replabels, int flags, void* ws, int32_t* out, int64_t out_capacity,
+                                 int64_t* out_offsets, void* stream);
 /* lab[b][t] = paths[b * path_stride + t]: the label paths of wfl_dense_viterbi.  Replaces asg.py:225-234 and
  * transducer.py:216-232 under the bigram transition model. */
 int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, int drop, int num_replabels, int flags,
@@ -560,6 +584,25 @@ int wfl_errors_count(const int32_t* hyp, const int64_t* hyp_off, const int32_t* 
                      const int32_t* hyp_exp_ptr, const int32_t* hyp_exp_sym, int hyp_V, const int32_t* ref_exp_ptr,
                      const int32_t* ref_exp_sym, int ref_V, int sep, int64_t hyp_capacity, int64_t ref_labels, void* ws,
                      int32_t* counts /* [B][4] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device kernels: per-utterance input lengths of a padded CTC batch (csrc/pad_kernels.hip)
+ *   For the CTC label graph (ctc.py:15-29) a frame whose emissions are 0 for the blank and -inf for every other class
+ *   is the identity: from the accepting states only the blank arc into / on the last blank is finite, so the T-frame
+ *   score of x with such frames at t >= T_b is the T_b-frame score of x[:T_b], the posteriors of the frames < T_b are
+ *   unchanged, those of the pad frames sit on the blank, and an utterance that cannot be aligned in T_b frames keeps
+ *   Z = 0.  The constants do not depend on x: the gradient of the pad rows is 0.  The criterion (criterions/ctc.py,
+ *   `input_lengths`) runs the launches that do not read lengths themselves (wfl_ctc_call.input_lengths does, for targets
+ *   of up to 63 labels) on the padded copy, and zeroes the pad rows behind every gradient.  lengths: int32 [B] on the device,
+ *   1 <= lengths[b] <= T is the caller's to check (any value only moves the comparison, nothing is indexed with it).
+ *   One launch each on `stream`, no allocation, no synchronisation.  WFL_ERR_INVALID: a NULL pointer, B, T or C < 1,
+ *   blank outside [0, C), out == x.
+ * ------------------------------------------------------------------------------------------------ */
+/* out [B,T,C] = x [B,T,C] with every row t >= lengths[b] replaced by {0 at blank, -inf elsewhere} */
+int wfl_ctc_pad_frames(const float* x, const int32_t* lengths, int B, int T, int C, int blank, float* out, void* stream);
+/* dx[b, t, :] = 0 for t >= lengths[b]; the rows before are not touched.  Runs behind every CTC gradient taken with
+ * lengths, before the gradient is handed out. */
+int wfl_zero_pad_rows(float* dx, const int32_t* lengths, int B, int T, int C, void* stream);
 
 /* small device utilities used by the Python layer (kept here so the product never needs a
  * torch op inside the timed path) */

@@ -1,0 +1,185 @@
+"""CPU tests (-m "not gpu") of CTC's per-utterance input lengths (criterions/ctc.py `input_lengths`, csrc/pad_kernels.hip,
+wfl_decode_emissions_lengths): the argument is checked before anything needs a device, the header declares the new
+entry points and the library exports them, and the rule the kernels rely on -- a frame that is 0 for the blank and -inf
+for every other class is the identity of the CTC label graph -- holds on the float64 oracle.  No device compute here."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from gtn_applications_amd import _native as N
+from gtn_applications_amd.criterions import ctc
+from oracle import recurrences as OR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("wfl_ctc_pad_frames", "wfl_zero_pad_rows", "wfl_decode_emissions_lengths", "wfl_ctc_forward_lengths",
+               "wfl_ctc_grad_lengths")
+
+B, T, C = 3, 7, 5
+TARGETS = [[1, 2], [3], []]
+
+
+def _x(dtype=torch.float32):
+    return torch.zeros(B, T, C, dtype=dtype)
+
+
+BAD_LENGTHS = [
+    ([7, 7], "got 2 input lengths for a batch of 3"),
+    ([7, 7, 7, 7], "got 4 input lengths for a batch of 3"),
+    (torch.tensor([[7, 7, 7]]), "must be 1-D"),
+    (torch.tensor(7), "must be 1-D"),
+    (torch.tensor([7.0, 7.0, 7.0]), "must be integers"),
+    (torch.tensor([True, True, True]), "must be integers"),
+    ([7, 6.0, 7], "utterance 1 is not an integer"),
+    ([7, 7, "3"], "utterance 2 is not an integer"),
+    ([True, 7, 7], "utterance 0 is not an integer"),
+    ([7, 0, 7], "input length 0 of utterance 1 is outside [1, 7]"),
+    ([7, 7, 8], "input length 8 of utterance 2 is outside [1, 7]"),
+    ((-1, 7, 7), "input length -1 of utterance 0 is outside [1, 7]"),
+    (torch.tensor([7, 7, 9], dtype=torch.int32), "input length 9 of utterance 2 is outside [1, 7]"),
+    (7, "must be a list, a tuple or a 1-D integer tensor"),
+]
+
+
+@pytest.mark.parametrize("lengths,message", BAD_LENGTHS, ids=[str(i) for i in range(len(BAD_LENGTHS))])
+def test_bad_input_lengths_raise_value_error_before_a_device_is_needed(lengths, message):
+    """every public call that takes the argument names the utterance in a ValueError -- on a machine without a GPU,
+    where anything that got past the check would raise RuntimeError (require_gpu) instead"""
+    x = _x()
+    tt = [torch.tensor(t, dtype=torch.long) for t in TARGETS]
+    calls = [
+        lambda: ctc.CTCLoss(x, TARGETS, 0, "mean", lengths),
+        lambda: ctc.CTCLoss(x.clone().requires_grad_(True), TARGETS, 0, "none", input_lengths=lengths),
+        lambda: ctc.CTCLossFunction.apply(x, TARGETS, 0, "mean", lengths),
+        lambda: ctc.CTC(0, False)(x.clone().requires_grad_(True), tt, lengths),
+        lambda: ctc.CTC(0, False)(x, tt, input_lengths=lengths),
+        lambda: ctc.CTC(0, True)(x, tt, lengths),
+        lambda: ctc.CTC(0, False).viterbi(x, lengths),
+        lambda: ctc.CTC(0, False).errors(x, TARGETS, None, lengths),
+    ]
+    for call in calls:
+        with pytest.raises(ValueError) as err:
+            call()
+        assert message in str(err.value), str(err.value)
+
+
+def test_check_input_lengths_normalises_what_it_accepts():
+    chk = ctc.check_input_lengths
+    assert chk(None, 3, 7, "t") is None
+    assert chk([7, 7, 7], 3, 7, "t") is None  # all T: exactly the call without lengths
+    assert chk(torch.tensor([7, 7, 7]), 3, 7, "t") is None
+    assert chk([7, 1, 4], 3, 7, "t") == (7, 1, 4)
+    assert chk((np.int64(7), np.int32(1), 4), 3, 7, "t") == (7, 1, 4)
+    assert chk(torch.tensor([7, 1, 4], dtype=torch.int16), 3, 7, "t") == (7, 1, 4)
+    assert chk([torch.tensor(7), 1, 4], 3, 7, "t") == (7, 1, 4)
+    assert all(type(v) is int for v in chk(torch.tensor([7, 1, 4]), 3, 7, "t"))
+    # emissions that are not float32 are taken with lengths only: there the lengths stay, whatever they are
+    assert chk([7, 7, 7], 3, 7, "t", keep_full=True) == (7, 7, 7)
+    assert chk([5], 1, 5, "t", keep_full=True) == (5,)
+    assert chk(None, 3, 7, "t", keep_full=True) is None
+
+
+def test_host_decode_and_torch_operator_take_the_lengths():
+    """what needs no device: viterbi() of CPU emissions decodes row b as outputs[b, :T_b], and the use_pt branch hands
+    the lengths to torch's operator in place of [T] * B"""
+    rs = np.random.RandomState(3)
+    x = torch.tensor(rs.randn(4, 9, 6).astype(np.float32))
+    lengths = [9, 5, 1, 8]
+    crit = ctc.CTC(5, False)
+    got = crit.viterbi(x, lengths)
+    for b, n in enumerate(lengths):
+        assert got[b].tolist() == crit.viterbi(x[b:b + 1, :n])[0].tolist(), b
+    tt = [torch.tensor(t, dtype=torch.long) for t in ([1, 2], [3], [], [0, 0, 1])]
+    got = ctc.CTC(5, True)(x, tt, lengths)
+    lp = torch.nn.functional.log_softmax(x, dim=2)
+    want = torch.nn.functional.ctc_loss(lp.permute(1, 0, 2), torch.cat(tt), lengths, [t.numel() for t in tt], blank=5,
+                                        zero_infinity=True)
+    assert got.item() == want.item()
+    full = ctc.CTC(5, True)(x, tt, [9] * 4)
+    assert full.item() == ctc.CTC(5, True)(x, tt).item()
+
+
+def test_header_declares_and_library_exports_the_new_entry_points():
+    with open(os.path.join(ROOT, "include", "wfl.h")) as f:
+        text = f.read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(wfl_[a-z0-9_]+)\s*\(", code))
+    fresh = ctypes.CDLL(N.LIB_PATH)  # (a handle of its own: what the library exports, not what the table declared)
+    for name in NEW_SYMBOLS:
+        assert name in declared, name
+        assert hasattr(fresh, name), name
+        assert name in N.EXPORTED_SYMBOLS, name
+        fn = getattr(N.lib, name)
+        assert fn.restype is ctypes.c_int and fn.argtypes is not None, name
+    assert declared == set(N.EXPORTED_SYMBOLS)
+    for fn in ("decode_emissions_lengths", "decode_emissions_lengths_errors"):
+        assert hasattr(N.ops, fn), fn
+    # wfl_ctc_call carries the lengths of a padded batch behind its two older fields, header and binding alike
+    struct = re.search(r"typedef struct wfl_ctc_call \{(.*?)\} wfl_ctc_call;", code, flags=re.S).group(1)
+    assert [f.split()[-1].lstrip("*") for f in struct.split(";") if f.strip()] == ["n_labels", "host_state", "input_lengths"]
+    assert [f[0] for f in N.CtcCall._fields_] == ["n_labels", "host_state", "input_lengths"]
+    assert ctypes.sizeof(N.CtcCall) == 24
+
+
+def test_new_entry_points_reject_bad_arguments_without_a_launch():
+    buf = (ctypes.c_float * 8)()
+    ints = (ctypes.c_int32 * 2)()
+    p, q = ctypes.addressof(buf), ctypes.addressof(ints)
+    assert N.lib.wfl_ctc_pad_frames(None, q, 1, 2, 4, 0, p, None) == N.ERR_INVALID
+    assert N.lib.wfl_ctc_pad_frames(p, None, 1, 2, 4, 0, p + 16, None) == N.ERR_INVALID
+    assert N.lib.wfl_ctc_pad_frames(p, q, 1, 2, 4, 0, p, None) == N.ERR_INVALID  # in place
+    assert N.lib.wfl_ctc_pad_frames(p, q, 1, 2, 4, 4, p + 16, None) == N.ERR_INVALID  # blank outside [0, C)
+    assert N.lib.wfl_ctc_pad_frames(p, q, 0, 2, 4, 0, p + 16, None) == N.ERR_INVALID
+    assert N.lib.wfl_zero_pad_rows(None, q, 1, 2, 4, None) == N.ERR_INVALID
+    assert N.lib.wfl_zero_pad_rows(p, None, 1, 2, 4, None) == N.ERR_INVALID
+    assert N.lib.wfl_zero_pad_rows(p, q, 1, 0, 4, None) == N.ERR_INVALID
+    assert N.lib.wfl_decode_emissions_lengths(p, None, None, 1, 2, 4, 0, 0, 0, p, q, 8, q, None) == N.ERR_INVALID
+    assert "lengths" in N.last_error()
+
+
+# the shape of the issue's own check: lengths at T, T - 1, around the 16-frame blocks, short, and 1
+ID_B, ID_T, ID_C = 7, 37, 9
+ID_LENGTHS = [37, 36, 17, 16, 5, 1, 4]
+ID_TARGETS = [[1, 2, 2, 3], [4, 4], [5, 1, 5, 1, 5], [2], [3, 3, 1], [], [1, 1, 2, 2]]  # the last: 4 labels + 2 repeats > 4 frames
+
+
+@pytest.mark.parametrize("blank", [0, ID_C - 1])
+@pytest.mark.parametrize("reduction", ["none", "mean"])
+def test_certain_blank_frames_are_the_identity_of_the_ctc_graph(blank, reduction):
+    """The rule on the float64 oracle: a padded batch whose pad rows are {0 at the blank, -inf elsewhere} against the
+    per-slice calls -- the same losses (also +inf for the utterance that cannot be aligned in its T_b frames but could in
+    T), the same gradient rows before T_b, zero rows behind, no NaN."""
+    rs = np.random.RandomState(11 + blank)
+    x = rs.randn(ID_B, ID_T, ID_C)
+    x -= np.log(np.exp(x).sum(axis=2, keepdims=True))
+    targets = ID_TARGETS  # (labels 1 .. 5: no blank among them, whichever end the blank sits at)
+    padded = x.copy()
+    for b, n in enumerate(ID_LENGTHS):
+        padded[b, n:, :] = -np.inf
+        padded[b, n:, blank] = 0.0
+    losses, dx = [], np.zeros_like(x)
+    for b in range(ID_B):
+        loss_b, dx_b = OR.ctc_loss_grad(padded[b:b + 1], [targets[b]], blank, reduction)
+        losses.append(loss_b)
+        dx[b] = dx_b[0]
+    assert not np.isnan(dx).any() and not np.isnan(losses).any()
+    # feasible in T = 37 frames, not in T_b = 4
+    full_loss, _ = OR.ctc_loss_grad(x[6:7], [targets[6]], blank, reduction)
+    assert np.isfinite(full_loss) and np.isinf(losses[6]) and losses[6] > 0
+    for b, n in enumerate(ID_LENGTHS):
+        want_loss, want_dx = OR.ctc_loss_grad(x[b:b + 1, :n], [targets[b]], blank, reduction)
+        if np.isinf(want_loss):
+            assert losses[b] == want_loss, b
+        else:
+            assert abs(losses[b] - want_loss) <= 1e-12 * max(1.0, abs(want_loss)), (b, losses[b], want_loss)
+        np.testing.assert_allclose(dx[b, :n], want_dx[0], rtol=0, atol=1e-13, err_msg=str(b))
+        # the pad frames' posteriors sit on the blank only (the oracle's dx is -posterior * scale: w.r.t. the constants,
+        # which do not depend on x -- the criterion's gradient rows there are 0)
+        nonblank = np.delete(dx[b, n:], blank, axis=1)
+        assert (nonblank == 0.0).all(), b
+        if n < ID_T and np.isfinite(want_loss):
+            scale = 1.0 / len(targets[b]) if reduction == "mean" and targets[b] else 1.0
+            assert np.allclose(-dx[b, n:, blank], scale, rtol=0, atol=1e-12), b
