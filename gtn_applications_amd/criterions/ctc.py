@@ -347,12 +347,70 @@ class CTC(torch.nn.Module):
         flat, kept = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
         return E.split_rows(flat, kept, torch.int64)
 
+    def _beam_plan(self, outputs, beam_size, classes_per_frame, nbest, input_lengths, what):
+        """The arguments of a beam search, checked before anything needs a device: (W, K, nbest, lengths or None)"""
+        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
+            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
+        if not outputs.dtype.is_floating_point:
+            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        B, T, C = outputs.shape
+        if C < 1:
+            raise ValueError(f"{what}: outputs have no classes")
+        if not 0 <= self.blank < C:
+            raise ValueError(f"{what}: blank index {self.blank} is outside [0, {C})")
+        W, K, n = E.check_beam_arguments(C, beam_size, classes_per_frame, nbest, what)
+        lens = None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
+        return W, K, n, lens
+
+    @staticmethod
+    def _beam_emissions(outputs):
+        """float32, contiguous, on a GPU: the tensor's own, or the required one (the criteria's rule: no host path)"""
+        dev = outputs.device if outputs.is_cuda else E.require_gpu()
+        return outputs.detach().to(device=dev, dtype=torch.float32).contiguous()
+
     @E.on_input_device
-    def errors(self, outputs, targets, counter, input_lengths=None):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, input_lengths=None, return_scores=False):
+        """CTC prefix beam search (an addition: the reference has the greedy decode only).  viterbi() maximises over
+        frame paths; this maximises over label sequences, whose probability is the sum over all their alignments
+        (DESIGN.md section 17 has the rules; csrc/beam_kernels.hip runs them, in float64).  Per frame only the
+        `classes_per_frame` best classes (default min(C, 32)) and the blank extend a hypothesis; `beam_size` (1..64)
+        hypotheses survive a frame.  nbest == 1: B int64 CPU tensors, what viterbi() returns; otherwise a list of `nbest`
+        such tensors per utterance, best first (a rank beyond the final beam is empty).  return_scores: also a float64
+        CPU tensor [B, nbest] of log P(sequence | outputs[b, :T_b]) under log_softmax(outputs) -- the module's outputs
+        are raw scores --, -inf for an empty rank.  `input_lengths`: see CTCLoss.  CTC only: no language model, no length
+        bonus, no lexicon; ASG and the Transducer's token graphs have no beam search."""
+        W, K, n, lens = self._beam_plan(outputs, beam_size, classes_per_frame, nbest, input_lengths, "CTC.beam_search")
+        B, T, _ = outputs.shape
+        if B == 0 or T == 0:
+            hyps, scores = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)], \
+                torch.zeros((B, n), dtype=torch.float64)
+        else:
+            x = self._beam_emissions(outputs)
+            with torch.cuda.device(x.device), torch.no_grad():
+                xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
+                hyps, scores = E.ctc_beam_search(x, self.blank, W, K, n, lengths=xlen, normalize=True)
+        if n == 1:
+            hyps = [h[0] for h in hyps]
+        return (hyps, scores) if return_scores else hyps
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter, input_lengths=None, beam_size=None, classes_per_frame=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `input_lengths`
-        (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s."""
+        (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s.  `beam_size` (an addition):
+        the predictions are beam_search(outputs, beam_size, classes_per_frame, input_lengths=input_lengths)'s instead,
+        counted behind the beam launch on its device buffers."""
+        if beam_size is not None:
+            W, K, _, lens = self._beam_plan(outputs, beam_size, classes_per_frame, 1, input_lengths, "CTC.errors")
+            C = outputs.shape[2]
+            counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")
+            if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+                return counter(self.beam_search(outputs, W, K, input_lengths=lens), targets)
+            x = self._beam_emissions(outputs)
+            with torch.cuda.device(x.device), torch.no_grad():
+                xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
+                return counter.totals(M.beam_search_errors(counter, targets, x, self.blank, W, K, lengths=xlen))
         lens = None
         if input_lengths is not None:
             lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.errors")

@@ -1,0 +1,498 @@
+// CTC prefix beam search on the device (wfl_ctc_beam_search; the rules are in include/wfl.h and DESIGN.md section 17).
+// The greedy decode of decode_kernels.hip maximises over frame paths; this one over label sequences, whose score is the
+// log-sum over all their alignments.  Three launch families:
+//   candidates (a wave per row (b, t), t < T_b; the only pass over x): the K best classes of the row, ties to the lower
+//              class, in that order, by K rounds of a wave argmax over keys that order (score, class) -- the row in
+//              registers up to 256 classes, re-read (from cache) beyond; slot K holds the blank if it is not among them
+//              (class -1 otherwise).  Also the row's log-sum-exp by wfl_row_lse's rule.
+//   beam       (a workgroup per utterance: the dependent part): the ranked beam {pb, pnb, tot, two prefix hashes, last label,
+//              length, arena node} lives in LDS, double-buffered.  Per frame: where does each hypothesis' last label sit
+//              among the candidates; which hypothesis is the one-label extension of which (hashes, length, last label);
+//              the stay entries with the merged extensions added; the W-th best stay as a lower bound of the W-th best
+//              entry; every entry at or above it into a compact list; rank of each by counting -- the order is (tot
+//              descending, entry index ascending), entry index = stays by rank, then extensions by (parent rank,
+//              candidate position), which is the tie rule; the entries of rank < W are the next beam, a new prefix
+//              appends its (parent node, label) record to the utterance's arena.  All hypothesis arithmetic is float64.
+//   write      (a wave per (b, rank < nbest)): base = the lengths before it summed in a fixed order, then lane 0 walks
+//              the arena back from the final node and stores the labels -- plain vector stores, `out` / `out_offsets` /
+//              `scores` may be pinned host memory.
+// No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
+// compact list, never its rank: the result is deterministic.
+#include "device_common.h"
+
+namespace wfl {
+
+constexpr int kBeamMax = 64;                                    // beam width and classes per frame
+constexpr int kBeamCand = kBeamMax + 1;                         // + the appended blank
+constexpr int kBeamEntries = kBeamMax + kBeamMax * kBeamCand;   // stays + extensions: 4224
+constexpr int kBeamMaxClasses = 16384;
+constexpr unsigned long long kBeamHashMul = 0x9E3779B97F4A7C15ull;  // odd: h' = h * mul + label + 1 (mod 2^64)
+constexpr unsigned long long kBeamHashMul2 = 0xC2B2AE3D27D4EB4Full;  // a second, independent hash of the same form
+constexpr long long kKeyDropped = (long long)0x8000000000000000ull;  // below the key of every finite score
+constexpr unsigned long long kKeySign = 0x8000000000000000ull;       // key ^ sign: the same order, unsigned
+constexpr int kBeamRankAll = 512;  // entries above the bound up to which every one of them is ranked against every other
+
+// workspace: [candidate classes: B T (K+1) int32 | candidate scores: B T (K+1) float | row lse: B T float |
+//             arena: B T W int2 | final node: B nbest int32 | final length: B nbest int32]
+struct BeamWs {
+  int64_t cls, sc, lse, arena, fin_node, fin_len, bytes;
+};
+inline int64_t beam_align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+inline BeamWs beam_ws_layout(int64_t B, int64_t T, int64_t W, int64_t K, int64_t nbest) {
+  BeamWs w;
+  w.cls = 0;
+  w.sc = w.cls + beam_align16(B * T * (K + 1) * 4);
+  w.lse = w.sc + beam_align16(B * T * (K + 1) * 4);
+  w.arena = w.lse + beam_align16(B * T * 4);
+  w.fin_node = w.arena + beam_align16(B * T * W * 8);
+  w.fin_len = w.fin_node + beam_align16(B * nbest * 4);
+  w.bytes = w.fin_len + beam_align16(B * nbest * 4);
+  return w;
+}
+
+// a score as an int whose signed order is the order of the scores: -0 = +0, NaN = -inf (wfl_row_argmax's rule)
+__device__ __forceinline__ int beam_score_key(float v) {
+  if (v != v) return (int)0x807fffff;  // the key of -inf
+  int b = __float_as_int(v);
+  if (b == (int)0x80000000) b = 0;
+  return b >= 0 ? b : b ^ 0x7fffffff;
+}
+
+constexpr int kBeamNoIndex = 0x3fffffff;
+constexpr int kBeamNoKey = -2147483647 - 1;
+
+// NV > 0: the row in NV registers per lane (C <= 64 NV); NV == 0: any C, the row re-read in every round
+template <int NV>
+__global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths,
+                                                               int B, int T, int C, int blank, int K,
+                                                               int32_t* __restrict__ cls_out, float* __restrict__ sc_out,
+                                                               float* __restrict__ lse_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (int64_t)B * T) return;  // (a whole wave)
+  const int b = (int)(row / T), t = (int)(row % T);
+  const int Tb = lengths ? min(max(lengths[b], 0), T) : T;
+  if (t >= Tb) return;  // (wave-uniform: the frames behind the utterance are not read)
+  const float* r = x + row * C;
+  int key[NV > 0 ? NV : 1];
+  float m = WFL_NEG_INF;
+  if constexpr (NV > 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = lane + 64 * i;
+      const float v = c < C ? nan_to_neg(r[c]) : WFL_NEG_INF;
+      key[i] = beam_score_key(v);
+      m = fmaxf(m, v);
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, nan_to_neg(r[c]));
+  }
+  // the row's log-sum-exp (wfl_row_lse's rule: float32, relative to the maximum, -inf for a row without a finite score)
+  m = wave_all_max(m);
+  float sum = 0.f;
+  if (m > WFL_NEG_INF)
+    for (int c = lane; c < C; c += 64) sum += fast_exp(nan_to_neg(r[c]) - m);
+  sum = wave_all_sum(sum);
+  if (lane == 0) lse_out[row] = m > WFL_NEG_INF ? m + fast_log(sum) : WFL_NEG_INF;
+  // K rounds: the best (score, lowest class) behind the previous round's pick; lane k keeps the pick of round k
+  int pk = 0x7fffffff, pi = -1, mine = -1;
+  for (int k = 0; k < K; ++k) {
+    int bk = kBeamNoKey, bi = kBeamNoIndex;
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        const bool behind = key[i] < pk || (key[i] == pk && c > pi);
+        if (c < C && behind && key[i] > bk) bk = key[i], bi = c;  // (ascending c: the first of equals stays)
+      }
+    } else {
+#pragma unroll 4
+      for (int c = lane; c < C; c += 64) {
+        const int kc = beam_score_key(r[c]);
+        const bool behind = kc < pk || (kc == pk && c > pi);
+        if (behind && kc > bk) bk = kc, bi = c;
+      }
+    }
+    pk = wave_all_max_int(bk);
+    pi = -wave_all_max_int(-(bk == pk ? bi : kBeamNoIndex));
+    if (lane == k) mine = pi;
+  }
+  const int64_t o = row * (K + 1);
+  if (lane < K) cls_out[o + lane] = mine, sc_out[o + lane] = nan_to_neg(r[min(max(mine, 0), C - 1)]);
+  const bool found = __ballot(lane < K && mine == blank) != 0ull;
+  if (lane == 0) cls_out[o + K] = found ? -1 : blank, sc_out[o + K] = found ? WFL_NEG_INF : nan_to_neg(r[blank]);
+}
+
+__device__ __forceinline__ int wave_inclusive_scan_int(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// log(exp(a) + exp(b)) in float64, -inf the identity
+__device__ __forceinline__ double beam_lae(double a, double b) {
+  const double ninf = -__builtin_inf();
+  if (a == ninf) return b;
+  if (b == ninf) return a;
+  return fmax(a, b) + log1p(exp(-fabs(a - b)));
+}
+// a total as an int64 whose signed order is the order of the totals; -inf (and NaN): dropped
+__device__ __forceinline__ long long beam_key(double d) {
+  if (!(d > -__builtin_inf())) return kKeyDropped;
+  if (d == 0.0) return 0;
+  const long long b = __double_as_longlong(d);
+  return b >= 0 ? b : b ^ 0x7fffffffffffffffLL;
+}
+
+struct BeamHyp {  // (struct of arrays, one per buffer)
+  double pb[kBeamMax], pnb[kBeamMax], tot[kBeamMax];
+  unsigned long long hash[kBeamMax], hash2[kBeamMax];
+  int last[kBeamMax], len[kBeamMax], node[kBeamMax];
+};
+
+// NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales)
+template <int NT>
+__global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
+                                                           int nbest, int normalize, const int32_t* __restrict__ cand_cls,
+                                                           const float* __restrict__ cand_sc, const float* __restrict__ row_lse,
+                                                           int2* __restrict__ arena, int32_t* __restrict__ fin_node,
+                                                           int32_t* __restrict__ fin_len, double* __restrict__ scores) {
+  __shared__ BeamHyp beam[2];
+  __shared__ long long ckey[kBeamEntries];
+  __shared__ int cidx[kBeamEntries];
+  __shared__ double s_sc[2][kBeamCand];
+  __shared__ int s_cls[2][kBeamCand];
+  __shared__ int s_bpos[2];
+  __shared__ double spb[kBeamMax], spnb[kBeamMax], stot[kBeamMax];
+  __shared__ long long skey[kBeamMax];
+  __shared__ unsigned long long mmask[kBeamMax];
+  __shared__ int lpos[kBeamMax], par[kBeamMax];
+  __shared__ long long s_tau;
+  __shared__ int s_count;
+  __shared__ int hist[256];
+  __shared__ long long wkey[kBeamMax];
+  __shared__ int widx[kBeamMax];
+  __shared__ int s_bin, s_need, s_ties, s_wcount;
+  __shared__ double s_norm;
+
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int KC = K + 1;
+  const int Tb = lengths ? min(max(lengths[b], 0), T) : T;
+  const double ninf = -__builtin_inf();
+  const int32_t* ccls = cand_cls + (int64_t)b * T * KC;
+  const float* csc = cand_sc + (int64_t)b * T * KC;
+  const float* lse = row_lse + (int64_t)b * T;
+  int2* nodes = arena + (int64_t)b * T * W;
+
+  if (tid == 0) {
+    s_bpos[0] = s_bpos[1] = 0;
+    beam[0].pb[0] = 0.0, beam[0].pnb[0] = ninf, beam[0].tot[0] = 0.0;
+    beam[0].hash[0] = 0ull, beam[0].hash2[0] = 0ull, beam[0].last[0] = -1, beam[0].len[0] = 0, beam[0].node[0] = -1;
+  }
+  __syncthreads();
+  // the candidates of frame 0 into buffer 0
+  if (tid < KC && Tb > 0) {
+    const int c = ccls[tid];
+    s_cls[0][tid] = c, s_sc[0][tid] = (double)csc[tid];
+    if (c == blank) s_bpos[0] = tid;
+  }
+  int nbeam = 1;
+  double norm = 0.0;
+  __syncthreads();
+
+  for (int t = 0; t < Tb; ++t) {
+    const int cur = t & 1;
+    const BeamHyp& h = beam[cur];
+    BeamHyp& g = beam[cur ^ 1];
+    const int* cls = s_cls[cur];
+    const double* sc = s_sc[cur];
+    // the next frame's candidates: loads in flight across this frame's work
+    int ncls = -1;
+    float nsc = 0.f, flse = 0.f;
+    if (tid < KC && t + 1 < Tb) ncls = ccls[(int64_t)(t + 1) * KC + tid], nsc = csc[(int64_t)(t + 1) * KC + tid];
+    if (tid == 0) flse = lse[t];
+    const int ncand = K + (cls[K] >= 0 ? 1 : 0);
+    const int bpos = s_bpos[cur];
+
+    // where each hypothesis' last label sits among the candidates
+    if (tid < nbeam) {
+      int p = -1;
+      const int l = h.last[tid];
+      if (l >= 0)
+        for (int q = 0; q < ncand; ++q)
+          if (cls[q] == l) p = q;
+      lpos[tid] = p, par[tid] = -1;
+    }
+    __syncthreads();
+    // which hypothesis j is hypothesis i plus one label: that extension merges into j's stay entry
+    if (tid < nbeam) {
+      unsigned long long mask = 0ull;
+      const unsigned long long hm = h.hash[tid] * kBeamHashMul, hm2 = h.hash2[tid] * kBeamHashMul2;
+      const int l1 = h.len[tid] + 1;
+      for (int j = 0; j < nbeam; ++j)
+        if (lpos[j] >= 0 && h.len[j] == l1 && h.hash[j] == hm + (unsigned long long)(h.last[j] + 1) &&
+            h.hash2[j] == hm2 + (unsigned long long)(h.last[j] + 1))
+          mask |= 1ull << lpos[j], par[j] = tid;
+      mmask[tid] = mask;
+    }
+    __syncthreads();
+    // the stay entries
+    if (tid < nbeam) {
+      const int p = lpos[tid];
+      const double pb = sc[bpos] + h.tot[tid];
+      double pnb = p >= 0 ? sc[p] + h.pnb[tid] : ninf;
+      const int i = par[tid];
+      if (i >= 0) pnb = beam_lae(pnb, sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]));
+      const double tot = beam_lae(pb, pnb);
+      spb[tid] = pb, spnb[tid] = pnb, stot[tid] = tot, skey[tid] = beam_key(tot);
+    }
+    if (tid == 0) s_tau = kKeyDropped, s_count = 0, norm += (double)flse;
+    __syncthreads();
+    // a full beam: the W-th best stay bounds the W-th best entry from below
+    if (tid < nbeam && nbeam == W) {
+      const long long k = skey[tid];
+      int n = 0;
+      for (int j = 0; j < W; ++j) n += (skey[j] > k || (skey[j] == k && j < tid)) ? 1 : 0;
+      if (n == W - 1) s_tau = k;
+    }
+    __syncthreads();
+    // every entry at or above the bound into the compact list
+    const long long tau = s_tau;
+    for (int e = tid; e < nbeam * (1 + ncand); e += NT) {
+      long long k;
+      int idx;
+      if (e < nbeam) {
+        k = skey[e], idx = e;
+      } else {
+        const int q = e - nbeam, i = q / ncand, p = q - i * ncand;
+        const int c = cls[p];
+        idx = kBeamMax + i * kBeamCand + p;
+        if (c == blank || ((mmask[i] >> p) & 1ull))
+          k = kKeyDropped;
+        else
+          k = beam_key(sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]));
+      }
+      if (k != kKeyDropped && k >= tau) {
+        const int slot = atomicAdd(&s_count, 1);
+        ckey[slot] = k, cidx[slot] = idx;
+      }
+    }
+    __syncthreads();
+    const int M = s_count;
+    // entry idx is the hypothesis of rank r of the next beam
+    auto place = [&](int idx, int r) {
+      if (idx < kBeamMax) {
+        g.pb[r] = spb[idx], g.pnb[r] = spnb[idx], g.tot[r] = stot[idx];
+        g.hash[r] = h.hash[idx], g.hash2[r] = h.hash2[idx], g.last[r] = h.last[idx], g.len[r] = h.len[idx], g.node[r] = h.node[idx];
+      } else {
+        const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
+        const int c = cls[p];
+        const double e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
+        const int node = t * W + r;
+        g.pb[r] = ninf, g.pnb[r] = e, g.tot[r] = e;
+        g.hash[r] = h.hash[i] * kBeamHashMul + (unsigned long long)(c + 1);
+        g.hash2[r] = h.hash2[i] * kBeamHashMul2 + (unsigned long long)(c + 1);
+        g.last[r] = c, g.len[r] = h.len[i] + 1, g.node[r] = node;
+        nodes[node] = make_int2(h.node[i], c);
+      }
+    };
+    // A long list: the W-th largest key by a radix select over the keys' bytes, most significant first (a histogram
+    // of the byte among the keys that share the bytes above it, then the bin the W-th largest falls into) -- O(M) per
+    // byte where ranking every entry is O(M^2).  The entries at or above that key are the survivors, unless more keys
+    // tie with it than the beam has room for: then the order among the ties decides, and the full ranking below does it.
+    bool selected = false;
+    if (M > kBeamRankAll) {
+      unsigned long long prefix = 0ull;
+      int need = W;
+      for (int pass = 7; pass >= 0; --pass) {
+        const int shift = 8 * pass;
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (int m = tid; m < M; m += NT) {
+          const unsigned long long u = (unsigned long long)ckey[m] ^ kKeySign;
+          if (pass == 7 || (u >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(int)(u >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (tid < 64) {  // lane l: the bins 255 - 4 l down to 252 - 4 l; the first lane whose running count reaches `need`
+          const int top = 255 - 4 * tid;
+          const int h0 = hist[top], h1 = hist[top - 1], h2 = hist[top - 2], h3 = hist[top - 3];
+          const int incl = wave_inclusive_scan_int(h0 + h1 + h2 + h3, tid);
+          const unsigned long long reach = __ballot(incl >= need);
+          if (reach && tid == __ffsll(reach) - 1) {
+            int left = need - (incl - (h0 + h1 + h2 + h3)), bin = top, n = h0;  // (left >= 1: the lanes above fell short)
+            if (left > n) left -= n, bin = top - 1, n = h1;
+            if (bin == top - 1 && left > n) left -= n, bin = top - 2, n = h2;
+            if (bin == top - 2 && left > n) left -= n, bin = top - 3, n = h3;
+            s_bin = bin, s_need = left, s_ties = n;
+          }
+          if (tid == 0) s_wcount = 0;
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_bin << shift;
+        need = s_need;
+      }
+      selected = s_ties == need;  // (uniform: exactly the W best are at or above the key)
+      if (selected) {
+        for (int m = tid; m < M; m += NT)
+          if (((unsigned long long)ckey[m] ^ kKeySign) >= prefix) {
+            const int slot = atomicAdd(&s_wcount, 1);
+            wkey[slot] = ckey[m], widx[slot] = cidx[m];
+          }
+        __syncthreads();
+        if (tid < W) {
+          const long long k = wkey[tid];
+          const int idx = widx[tid];
+          int r = 0;
+          for (int q = 0; q < W; ++q) r += (wkey[q] > k || (wkey[q] == k && widx[q] < idx)) ? 1 : 0;
+          place(idx, r);
+        }
+      }
+    }
+    // rank by counting; the entries of rank < W are the next beam
+    if (!selected)
+      for (int m = tid; m < M; m += NT) {
+        const long long k = ckey[m];
+        const int idx = cidx[m];
+        int r = 0;
+#pragma unroll 8
+        for (int q = 0; q < M; ++q) {  // (unrolled: the LDS reads of a batch in flight together)
+          const long long kq = ckey[q];
+          r += (kq > k || (kq == k && cidx[q] < idx)) ? 1 : 0;
+        }
+        if (r < W) place(idx, r);
+      }
+    // the next frame's candidates into the other buffer (last read a frame ago)
+    if (tid < KC && t + 1 < Tb) {
+      s_cls[cur ^ 1][tid] = ncls, s_sc[cur ^ 1][tid] = (double)nsc;
+      if (ncls == blank) s_bpos[cur ^ 1] = tid;
+    }
+    nbeam = min(W, M);
+    __syncthreads();
+    if (nbeam == 0) break;  // (uniform: nothing survives, the utterance decodes to nothing)
+  }
+
+  if (tid == 0) s_norm = norm;
+  __syncthreads();
+  const BeamHyp& f = beam[Tb & 1];
+  if (tid < nbest) {
+    const int64_t o = (int64_t)b * nbest + tid;
+    const bool have = tid < nbeam;
+    fin_node[o] = have ? f.node[tid] : -1;
+    fin_len[o] = have ? f.len[tid] : 0;
+    scores[o] = have ? (normalize ? f.tot[tid] - s_norm : f.tot[tid]) : ninf;
+  }
+}
+
+// one wave per (b, rank): the sequences back to back in (b, rank) order
+__global__ void __launch_bounds__(256) beam_write_kernel(int n, int T, int W, int nbest, const int2* __restrict__ arena,
+                                                          const int32_t* __restrict__ fin_node, const int32_t* __restrict__ fin_len,
+                                                          int32_t* __restrict__ out, int64_t* __restrict__ out_offsets) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n) return;
+  long long base = 0;
+  for (int r = lane; r < (int)w; r += 64) base += fin_len[r];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) base += __shfl_xor(base, o, 64);
+  if (lane != 0) return;
+  const int len = min(max(fin_len[w], 0), T);
+  out_offsets[w] = base;
+  if (w == n - 1) out_offsets[n] = base + len;
+  const int2* nodes = arena + (w / nbest) * (int64_t)T * W;
+  int node = fin_node[w];
+  for (int k = len - 1; k >= 0 && node >= 0 && node < T * W; --k) {
+    const int2 rec = nodes[node];
+    out[base + k] = rec.y;
+    node = rec.x;
+  }
+}
+
+}  // namespace wfl
+
+using namespace wfl;
+
+static int beam_check(const char* what, int B, int T, int C, int beam, int K, int nbest) {
+  if (B < 1 || T < 1 || C < 1 || beam < 1 || beam > kBeamMax || K < 1 || K > std::min(C, kBeamMax) || nbest < 1 || nbest > beam) {
+    set_error("%s: bad arguments (B %d, T %d, C %d, beam %d, classes_per_frame %d, nbest %d)", what, B, T, C, beam, K, nbest);
+    return WFL_ERR_INVALID;
+  }
+  if (C > kBeamMaxClasses || (int64_t)T * kBeamMax > 0x7fffffffLL || (int64_t)B * nbest > 0x7fffffffLL ||
+      (int64_t)B * T > 0x7fffffffLL * 4) {
+    set_error("%s: B %d, T %d, C %d is more than the beam search takes (C <= %d)", what, B, T, C, kBeamMaxClasses);
+    return WFL_ERR_UNSUPPORTED;
+  }
+  return WFL_OK;
+}
+
+extern "C" {
+
+int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
+                           int64_t* ws_bytes) {
+  if (!out_capacity || !ws_bytes) {
+    set_error("ctc_beam_workspace: a NULL pointer");
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = beam_check("ctc_beam_workspace", B, T, C, beam, classes_per_frame, nbest)) return rc;
+  *out_capacity = (int64_t)B * nbest * T;
+  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest).bytes;
+  return WFL_OK;
+}
+
+int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
+                        int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                        double* scores, void* stream) {
+  if (!x || !ws || !out || !out_offsets || !scores) {
+    set_error("ctc_beam_search: a NULL pointer");
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = beam_check("ctc_beam_search", B, T, C, beam, classes_per_frame, nbest)) return rc;
+  if (blank < 0 || blank >= C) {
+    set_error("ctc_beam_search: blank %d is outside [0, %d)", blank, C);
+    return WFL_ERR_INVALID;
+  }
+  if (out_capacity < (int64_t)B * nbest * T) {
+    set_error("ctc_beam_search: out holds %lld labels, B nbest T = %lld are needed", (long long)out_capacity,
+              (long long)B * nbest * T);
+    return WFL_ERR_INVALID;
+  }
+  const int K = classes_per_frame;
+  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest);
+  char* base = static_cast<char*>(ws);
+  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
+  float* sc = reinterpret_cast<float*>(base + w.sc);
+  float* lse = reinterpret_cast<float*>(base + w.lse);
+  int2* arena = reinterpret_cast<int2*>(base + w.arena);
+  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
+  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned rows = (unsigned)(((int64_t)B * T + 3) / 4);
+  auto candidates = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(rows), dim3(256), 0, s, x, lengths, B, T, C, blank, K, cls, sc, lse);
+  };
+  if (C <= 64)
+    candidates(beam_candidates_kernel<1>);
+  else if (C <= 128)
+    candidates(beam_candidates_kernel<2>);
+  else if (C <= 256)
+    candidates(beam_candidates_kernel<4>);
+  else
+    candidates(beam_candidates_kernel<0>);
+  WFL_LAUNCH_CHECK();
+  if (beam * (K + 2) <= 1024)
+    hipLaunchKernelGGL(beam_search_kernel<256>, dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls, sc,
+                       lse, arena, fin_node, fin_len, scores);
+  else
+    hipLaunchKernelGGL(beam_search_kernel<1024>, dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls,
+                       sc, lse, arena, fin_node, fin_len, scores);
+  WFL_LAUNCH_CHECK();
+  const int n = B * nbest;
+  hipLaunchKernelGGL(beam_write_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
+                     fin_len, out, out_offsets);
+  WFL_LAUNCH_CHECK();
+  return WFL_OK;
+}
+
+}  // extern "C"

@@ -1110,9 +1110,114 @@ at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop,
                        ref_longest, sep);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// CTC prefix beam search (wfl_ctc_beam_search, csrc/beam_kernels.hip) behind CTC.beam_search() and CTC.errors(beam_size=):
+// the decode the reference does not have.  Collected like the greedy decode: offsets, scores and the surviving labels
+// land in the device's pinned decode buffer behind one event.
+// ------------------------------------------------------------------------------------------------------------
+struct BeamCall {
+  at::Tensor x, lengths;
+  int B = 0, T = 0, C = 0, blank = 0, beam = 0, K = 0, nbest = 0;
+  void launch(int normalize, void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) const {
+    check(wfl_ctc_beam_search(x.data_ptr<float>(), lengths.defined() ? lengths.data_ptr<int32_t>() : nullptr, B, T, C, blank,
+                              beam, K, nbest, normalize, ws, out, cap, offs, scores, s),
+          "ctc_beam_search");
+  }
+};
+
+BeamCall beam_call(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
+                   int64_t nbest) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
+              "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
+  BeamCall c;
+  c.x = x;
+  c.B = (int)x.size(0), c.T = (int)x.size(1), c.C = (int)x.size(2);
+  c.blank = (int)blank, c.beam = (int)beam, c.K = (int)K, c.nbest = (int)nbest;
+  if (lengths.has_value() && lengths->defined()) {
+    TORCH_CHECK(lengths->device() == x.device() && lengths->scalar_type() == at::kInt && lengths->is_contiguous() &&
+                    lengths->dim() == 1 && lengths->numel() == c.B,
+                "ctc_beam_search: lengths must be a contiguous int32 [B] tensor on x's device");
+    c.lengths = *lengths;
+  }
+  return c;
+}
+
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
+                          int64_t nbest, bool normalize) {
+  const BeamCall c = beam_call(x, lengths, blank, beam, K, nbest);
+  const int dev = x.device().index();
+  DeviceScope scope(dev);
+  int64_t capacity = 0, ws_bytes = 0;
+  check(wfl_ctc_beam_workspace(c.B, c.T, c.C, c.beam, c.K, c.nbest, &capacity, &ws_bytes), "ctc_beam_search");
+  const int64_t n = (int64_t)c.B * c.nbest;
+  const int64_t off_bytes = ((n + 1) * 8 + 15) & ~(int64_t)15, sc_bytes = (n * 8 + 15) & ~(int64_t)15;
+  const int64_t need = off_bytes + sc_bytes + capacity * 4;
+  at::Tensor ws = at::empty({ws_bytes}, x.options().dtype(at::kByte));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+  DecodeBuffer& buf = decode_buffer(dev);
+  at::Tensor flat, offs = at::empty({n + 1}, at::TensorOptions().dtype(at::kLong)),
+                   scores = at::empty({(int64_t)c.B, (int64_t)c.nbest}, at::TensorOptions().dtype(at::kDouble));
+  {
+    py::gil_scoped_release nogil;
+    std::lock_guard<std::mutex> lock(buf.mu);
+    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
+      int64_t cap = 1 << 16;
+      while (cap < need) cap <<= 1;
+      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+    }
+    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
+    uint8_t* base = buf.pinned.data_ptr<uint8_t>();
+    const int64_t* offsets = reinterpret_cast<const int64_t*>(base);
+    const double* landed = reinterpret_cast<const double*>(base + off_bytes);
+    const int32_t* labels = reinterpret_cast<const int32_t*>(base + off_bytes + sc_bytes);
+    c.launch(normalize ? 1 : 0, ws.data_ptr(), reinterpret_cast<int32_t*>(base + off_bytes + sc_bytes), capacity,
+             reinterpret_cast<int64_t*>(base), reinterpret_cast<double*>(base + off_bytes), (void*)stream);
+    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess,
+                "ctc_beam_search: ", hipGetErrorString(hipGetLastError()));
+    const int64_t total = offsets[n];
+    TORCH_CHECK(offsets[0] == 0 && total >= 0 && total <= capacity, "ctc_beam_search: the kernels left inconsistent offsets");
+    flat = at::empty({total}, at::TensorOptions().dtype(at::kLong));
+    int64_t* dst = flat.data_ptr<int64_t>();
+    for (int64_t i = 0; i < total; ++i) dst[i] = labels[i];
+    memcpy(offs.data_ptr<int64_t>(), offsets, (size_t)(n + 1) * 8);
+    memcpy(scores.data_ptr<double>(), landed, (size_t)n * 8);
+  }
+  return py::make_tuple(flat, offs, scores);
+}
+
+// the best hypothesis of every utterance into device buffers, the count behind it: the predictions never reach the host
+at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
+                                  int64_t K, const std::shared_ptr<StagedTargets>& ref,
+                                  const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                                  const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  const BeamCall c = beam_call(x, lengths, blank, beam, K, 1);
+  const int dev = x.device().index();
+  if (c.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
+  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
+  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
+  TORCH_CHECK(c.B > 0, "errors: an empty batch of emissions for ", ref ? ref->B : 0, " targets");
+  DeviceScope scope(dev);
+  int64_t capacity = 0, ws_bytes = 0;
+  check(wfl_ctc_beam_workspace(c.B, c.T, c.C, c.beam, c.K, 1, &capacity, &ws_bytes), "ctc_beam_search");
+  const auto bytes = x.options().dtype(at::kByte);
+  at::Tensor ws = at::empty({ws_bytes}, bytes);
+  at::Tensor out = at::empty({capacity}, bytes.dtype(at::kInt));
+  at::Tensor offs = at::empty({c.B + 1}, bytes.dtype(at::kLong));
+  at::Tensor scores = at::empty({c.B}, bytes.dtype(at::kDouble));
+  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+  c.launch(0, ws.data_ptr(), out.data_ptr<int32_t>(), capacity, offs.data_ptr<int64_t>(), scores.data_ptr<double>(), (void*)stream);
+  return errors_collect(dev, c.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, ref, ht, rt, sep);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
+        "CTC prefix beam search on the device: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
+  m.def("ctc_beam_search_errors", &ctc_beam_search_errors,
+        "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"),
         "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors");

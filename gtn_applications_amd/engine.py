@@ -4,6 +4,7 @@ all arithmetic happens in the HIP kernels behind the C ABI (include/wfl.h).
 """
 import ctypes
 import itertools
+import operator
 import sys
 import threading
 from collections import OrderedDict
@@ -938,6 +939,49 @@ def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int3
     """The same decode from [B, >= T] int32 device label paths (wfl_dense_viterbi's): wfl_decode_paths."""
     T = paths.shape[1] if T is None else T
     return N.ops.decode_paths(paths, T, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64)
+
+
+BEAM_MAX, BEAM_MAX_CLASSES = 64, 16384  # wfl_ctc_beam_search: beam width / classes per frame; classes in all
+
+
+def check_beam_arguments(C, beam_size, classes_per_frame, nbest, what):
+    """(beam, classes per frame, nbest) as ints, checked against the limits of wfl_ctc_beam_search for C classes;
+    classes_per_frame None: min(C, 32) -- a default, not a tuned value.  ValueError otherwise; needs no device."""
+    def integer(v):
+        try:
+            return None if isinstance(v, bool) else operator.index(v)
+        except TypeError:
+            return None
+
+    W = integer(beam_size)
+    if W is None or not 1 <= W <= BEAM_MAX:
+        raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+    K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
+    if K is None or not 1 <= K <= min(C, BEAM_MAX):
+        raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
+                         f"got {classes_per_frame!r}")
+    n = integer(nbest)
+    if n is None or not 1 <= n <= W:
+        raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
+    if C > BEAM_MAX_CLASSES:
+        raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
+    return W, K, n
+
+
+def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True):
+    """CTC prefix beam search on the device (wfl_ctc_beam_search through csrc/torch_ops.cpp; the rules: include/wfl.h,
+    DESIGN.md section 17).  x: float32 [B,T,C] on a GPU, contiguous; lengths: int32 [B] on x's device
+    (input_lengths_on_device) or None.  Returns (hyps, scores): hyps[b][r] the int64 CPU label tensor of rank r of
+    utterance b (views of one tensor), scores float64 CPU [B, nbest] -- log mass of the sequence over the frames, minus
+    the frames' log-sum-exps if `normalize`; a rank beyond the final beam is empty with score -inf.  Only the surviving
+    labels and the scores leave the device."""
+    B, T, C = x.shape
+    W, K, n = check_beam_arguments(C, beam_size, classes_per_frame, nbest, "ctc_beam_search")
+    if not 0 <= int(blank) < C:
+        raise ValueError(f"ctc_beam_search: blank index {blank} is outside [0, {C})")
+    flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize))
+    rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
+    return [list(rows[b * n:(b + 1) * n]) for b in range(B)], scores
 
 
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)

@@ -146,6 +146,16 @@ def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=
     return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref._st, *counter.tables(x.device))
 
 
+def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None):
+    """engine.ctc_beam_search's launches (best hypothesis only) and the counts behind them, on x's device: [B, 4] int64
+    on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments)"""
+    if len(targets) != x.shape[0]:
+        raise ValueError(f"errors: {x.shape[0]} utterances for {len(targets)} targets")
+    ref = counter.staged_targets(targets, x.device)
+    return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref._st,
+                                        *counter.tables(x.device))
+
+
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
     if len(targets) != paths.shape[0]:

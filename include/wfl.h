@@ -550,6 +550,48 @@ int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, in
                      void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device kernels: CTC prefix beam search (csrc/beam_kernels.hip)
+ *   wfl_decode_emissions gives the best FRAME PATH (argmax per frame, collapse, drop the blank).  CTC scores a LABEL
+ *   SEQUENCE by the sum over all its alignments; this search maximises that.  Per utterance b, over the frames
+ *   t < T_b of x [B,T,C] float32 (a NaN counts as -inf), with beam width W = beam, K = classes_per_frame:
+ *     - all hypothesis arithmetic is float64 in the log domain, lae(a, b) = max(a, b) + log1p(exp(-|a - b|)), -inf the
+ *       identity;
+ *     - candidates of a frame: its K classes of highest score, ties to the lower class, in that order; the blank is
+ *       appended if it is not among them;
+ *     - a hypothesis is (prefix, pb, pnb): the log mass of the prefix' alignments that end in the blank / do not; the
+ *       search starts from the empty prefix with pb = 0, pnb = -inf; the beam is ranked by tot = lae(pb, pnb), descending;
+ *     - frame t, hypothesis of rank i, candidate c with s = (double)x[b,t,c]: c the blank -- i's stay entry gets
+ *       pb' = s + tot_i; c the last label of i -- the stay entry gets pnb' = s + pnb_i and the extension i + c gets
+ *       e = s + pb_i; any other c -- the extension i + c gets e = s + tot_i;
+ *     - an extension whose prefix is that of a hypothesis j in the beam is merged into j's stay entry,
+ *       pnb'_j = lae(pnb'_j, e) (there is at most one per j); every other extension is a new entry (pb' = -inf, pnb' = e);
+ *     - entries with tot' = -inf are dropped, the W entries of largest tot' survive, in the order: larger tot'; stay
+ *       entries before new ones; the lower parent rank; the lower position of c among the candidates.  Nothing survives:
+ *       the utterance decodes to the empty sequence with score -inf.
+ *   Prefixes are identified by (two 64-bit rolling hashes h' = h * P + c + 1 mod 2^64 with different odd P, length, last
+ *   label).
+ *   Result: the first nbest ranks of the final beam.  out: their labels back to back in (b, rank) order (capacity
+ *   B nbest T int32), out_offsets [B nbest + 1] int64, scores [B nbest] float64 = tot, minus the sum over t < T_b of the
+ *   rows' log-sum-exps over all C classes (wfl_row_lse's rule, added up in float64 in frame order) if normalize != 0.
+ *   Ranks beyond the final beam's size are empty sequences with score -inf.  With nbest == 1, out / out_offsets are what
+ *   wfl_errors_count reads as hyp / hyp_off.  lengths: int32 [B] on the device or NULL (every utterance has T frames);
+ *   values are clamped to [0, T], frames t >= T_b are not read, T_b = 0 gives the empty sequence with score 0.
+ *   out, out_offsets and scores are written by plain stores of a kernel in a fixed order: any device-accessible memory,
+ *   pinned host memory included; the result is deterministic.  ws: device scratch of wfl_ctc_beam_workspace's size,
+ *   16-byte aligned, contents irrelevant before and after.  Three launches on `stream` (candidates: a wave per frame, the
+ *   only pass over x; beam: a workgroup per utterance; write), no allocation, no synchronisation.
+ *   WFL_ERR_INVALID: a NULL required pointer, B, T or C < 1, blank outside [0, C), beam outside [1, 64],
+ *   classes_per_frame outside [1, min(C, 64)], nbest outside [1, beam], out_capacity too small.
+ *   WFL_ERR_UNSUPPORTED: C > 16384.  No language model, length bonus or lexicon; CTC only.
+ * ------------------------------------------------------------------------------------------------ */
+/* out_capacity = B nbest T (int32 elements of `out`), ws_bytes = the device scratch of a call */
+int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
+                           int64_t* ws_bytes);
+int wfl_ctc_beam_search(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank, int beam,
+                        int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity,
+                        int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
  *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
  *   train.py:278-284 and test.py:94-109 -- per utterance b:
