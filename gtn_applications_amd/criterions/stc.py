@@ -63,10 +63,16 @@ class STCLossFunction(torch.autograd.Function):
             raise ValueError(f"got {tg.B} targets for a batch of {B}")
         # "mean" divides by the number of frames, not the target length (stc.py:90-91)
         scale, _, cneg = E.loss_factors(tg, reduction, norm_lens=[T] * B)
-        key = ("stc", Cstar, float(prob))
-        pack = tg.cache.get(key)
-        if pack is None:
-            pack = tg.cache[key] = E.PackedLattice.stc(tg.flat, tg.offsets, Cstar // 2, math.log(prob), Cstar, dev)
+        # ONE pack per (batch, Cstar), kept with the penalty it was built for: in training `prob` moves every step
+        # (STC.forward), and a pack per value would pile up on a recurring batch for as long as the stager holds it.  A
+        # new penalty builds a NEW pack and drops the cache's reference to the old one -- a forward pass whose backward
+        # is still to come keeps its own (LatticeState.pack).
+        key = ("stc", Cstar)
+        hit = tg.cache.get(key)
+        if hit is None or hit[0] != float(prob):
+            hit = tg.cache[key] = (float(prob),
+                                   E.PackedLattice.stc(tg.flat, tg.offsets, Cstar // 2, math.log(prob), Cstar, dev))
+        pack = hit[1]
         st = E.lattice_forward(x, pack, need_beta=inputs.requires_grad)
         loss = E.reduce_loss(st.logz, scale, -1.0)
         ctx.aux = (x, st, cneg)

@@ -4,6 +4,7 @@ C++ graph algebra (compose / remove / project / viterbi_path / pack) agrees with
 No device compute is called here."""
 import ctypes
 import json
+import math
 import os
 import re
 
@@ -283,6 +284,24 @@ def test_bulk_packers_match_generic_packer():
     slow = E.PackedLattice.from_graphs([stc.STCLossFunction.create_stc_graph(t, 5, 0.5) for t in targets], 10, None)
     np.testing.assert_array_equal(fast.host_ints, slow.host_ints)
     np.testing.assert_allclose(fast.host_floats, slow.host_floats, rtol=1e-6)
+    # STC at its edges: only empty targets (Q = 2, the blank state and one <star> state), one label four times (the skip
+    # arc s-2 -> s between equal labels stays: stc.py:35-36), 341 labels (Q = 1025: more states than a sweep workgroup has
+    # threads), a penalty of log(1) = 0 on every <star> arc
+    rs = np.random.RandomState(341)
+    long = rs.randint(1, 5, size=341).tolist()
+    for stc_targets, prob in (([[], []], 0.5), ([[3, 3, 3, 3]], 0.5), ([long], 0.5), ([long[:7], [], [3, 3, 3, 3]], 1.0),
+                              ([long, [], [2]], 1e-38)):
+        flat, off, _ = E.flatten_targets(stc_targets)
+        if flat.size == 0:
+            flat = np.zeros(1, np.int32)  # (a valid address for the packer, which reads nothing from it)
+        fast = E.PackedLattice.stc(flat, off, 5, math.log(prob), 10, None)
+        slow = E.PackedLattice.from_graphs([stc.STCLossFunction.create_stc_graph(t, 5, prob) for t in stc_targets], 10, None)
+        np.testing.assert_array_equal(fast.host_ints, slow.host_ints)
+        np.testing.assert_array_equal(fast.host_floats, slow.host_floats)
+        for f in ("B", "max_states", "max_arcs", "max_labels", "max_levels", "total_states", "total_arcs", "total_labels"):
+            assert getattr(fast.desc, f) == getattr(slow.desc, f), f
+        assert fast.desc.max_states == 3 * max(len(t) for t in stc_targets) + 2
+        assert set(fast.field("arc_w", fast.desc.total_arcs).tolist()) == {0.0, float(np.float32(math.log(prob)))}
     # ASG force alignment: the closed-form packer against the generic one on the same arcs and weight indices
     rs = np.random.RandomState(3)
     C = 7
