@@ -7,7 +7,7 @@ fails loudly -- the product path never routes around the HIP extension.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint, c_uint8, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint, c_uint8, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WFL_LIB_PATH") or os.path.join(_HERE, "libwfl.so")  # (override: A/B builds of the kernels)
@@ -40,6 +40,14 @@ class CtcCall(ctypes.Structure):
     """Mirror of `wfl_ctc_call` (include/wfl.h)."""
 
     _fields_ = [("n_labels", c_int64), ("host_state", c_void_p), ("input_lengths", c_void_p)]
+
+
+class NgramLm(ctypes.Structure):
+    """Mirror of `wfl_ngram_lm` (include/wfl.h): host pointers for wfl_ngram_lm_check, device pointers for a search."""
+
+    _fields_ = [(n, c_int32) for n in ("num_states", "num_arcs", "start", "reserved")] + [
+        ("step_min", c_double), ("step_max", c_double)] + [
+        (n, c_void_p) for n in ("arc_ptr", "arc_label", "arc_next", "arc_w", "bo_next", "bo_w")]
 
 
 class LatticeDesc(ctypes.Structure):
@@ -186,6 +194,9 @@ _SIGS = {
     # device: CTC prefix beam search
     "wfl_ctc_beam_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_ctc_beam_search": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_ngram_lm_check": (c_int, [POINTER(NgramLm), c_int, c_int]),
+    "wfl_ctc_beam_search_lm": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(NgramLm), c_double,
+                                       c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path
     "wfl_errors_workspace": (c_int, [c_int, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wfl_errors_count": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int64, c_int64, _P, _P, _P]),

@@ -6,6 +6,7 @@ on host threads (ctc.py:38-65), this sends the whole batch through the CTC fast-
 (csrc/ctc_kernels.hip; up to four target positions per lane) -- or, for targets longer than 255
 labels, through the generic lattice engine (csrc/lattice_kernels.hip).  Both are HIP paths; there is no CPU path.
 """
+import math
 import operator
 import os
 
@@ -362,6 +363,12 @@ class CTC(torch.nn.Module):
         lens = None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
         return W, K, n, lens
 
+    def _beam_lm(self, outputs, lm, lm_weight, length_bonus, lm_eos, what):
+        """The language model arguments of a beam search, checked like the rest: the keywords of the engine's call,
+        none without an lm (the call it was)"""
+        lm, weight, bonus, eos = E.check_lm_arguments(lm, outputs.shape[2], self.blank, lm_weight, length_bonus, lm_eos, what)
+        return {} if lm is None else dict(lm=lm, lm_weight=weight, length_bonus=bonus, lm_eos=eos)
+
     @staticmethod
     def _beam_emissions(outputs):
         """float32, contiguous, on a GPU: the tensor's own, or the required one (the criteria's rule: no host path)"""
@@ -369,7 +376,8 @@ class CTC(torch.nn.Module):
         return outputs.detach().to(device=dev, dtype=torch.float32).contiguous()
 
     @E.on_input_device
-    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, input_lengths=None, return_scores=False):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, input_lengths=None, return_scores=False,
+                    lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True):
         """CTC prefix beam search (an addition: the reference has the greedy decode only).  viterbi() maximises over
         frame paths; this maximises over label sequences, whose probability is the sum over all their alignments
         (DESIGN.md section 17 has the rules; csrc/beam_kernels.hip runs them, in float64).  Per frame only the
@@ -377,40 +385,62 @@ class CTC(torch.nn.Module):
         hypotheses survive a frame.  nbest == 1: B int64 CPU tensors, what viterbi() returns; otherwise a list of `nbest`
         such tensors per utterance, best first (a rank beyond the final beam is empty).  return_scores: also a float64
         CPU tensor [B, nbest] of log P(sequence | outputs[b, :T_b]) under log_softmax(outputs) -- the module's outputs
-        are raw scores --, -inf for an empty rank.  `input_lengths`: see CTCLoss.  CTC only: no language model, no length
-        bonus, no lexicon; ASG and the Transducer's token graphs have no beam search."""
+        are raw scores --, -inf for an empty rank.  `input_lengths`: see CTCLoss.  `lm`: an lm.NGramLM over this
+        model's classes (NGramLM.from_arpa reads an ARPA file), fused into the search on the device (DESIGN.md section
+        18): extending a hypothesis by a token adds lm_weight * log P_LM(token | history) + length_bonus to its score,
+        a token the LM cannot follow the history with is never emitted, and with `lm_eos` every final hypothesis gets
+        lm_weight * log P_LM(</s> | history) before the ranks are taken; the scores then include these terms.  Without
+        an lm the call is what it was, and lm_weight, length_bonus, lm_eos must be left alone.  CTC only: no lexicon /
+        word-level LM; ASG and the Transducer's token graphs have no beam search."""
         W, K, n, lens = self._beam_plan(outputs, beam_size, classes_per_frame, nbest, input_lengths, "CTC.beam_search")
+        fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.beam_search")
         B, T, _ = outputs.shape
-        if B == 0 or T == 0:
+        if B == 0 or (T == 0 and not fused):
             hyps, scores = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)], \
                 torch.zeros((B, n), dtype=torch.float64)
+        elif T == 0:  # (no frame: the empty sequence, scored by the LM's </s> alone)
+            # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
+            end = 0.0
+            if fused["lm_eos"]:
+                step = fused["lm"].score([], eos=True)
+                end = -math.inf if step == -math.inf else fused["lm_weight"] * step
+            hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)]
+            scores = torch.full((B, n), -math.inf, dtype=torch.float64)
+            scores[:, 0] = end
         else:
             x = self._beam_emissions(outputs)
             with torch.cuda.device(x.device), torch.no_grad():
                 xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
-                hyps, scores = E.ctc_beam_search(x, self.blank, W, K, n, lengths=xlen, normalize=True)
+                hyps, scores = E.ctc_beam_search(x, self.blank, W, K, n, lengths=xlen, normalize=True, **fused)
         if n == 1:
             hyps = [h[0] for h in hyps]
         return (hyps, scores) if return_scores else hyps
 
     @E.on_input_device
-    def errors(self, outputs, targets, counter, input_lengths=None, beam_size=None, classes_per_frame=None):
+    def errors(self, outputs, targets, counter, input_lengths=None, beam_size=None, classes_per_frame=None, lm=None,
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `input_lengths`
         (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s.  `beam_size` (an addition):
         the predictions are beam_search(outputs, beam_size, classes_per_frame, input_lengths=input_lengths)'s instead,
-        counted behind the beam launch on its device buffers."""
+        counted behind the beam launch on its device buffers; `lm`, `lm_weight`, `length_bonus`, `lm_eos` are
+        beam_search's and need a beam_size."""
+        if beam_size is None:
+            if lm is not None:
+                raise ValueError("CTC.errors: lm needs a beam_size")
+            E.check_lm_arguments(None, outputs.shape[2], self.blank, lm_weight, length_bonus, lm_eos, "CTC.errors")
         if beam_size is not None:
             W, K, _, lens = self._beam_plan(outputs, beam_size, classes_per_frame, 1, input_lengths, "CTC.errors")
+            fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.errors")
             C = outputs.shape[2]
             counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
-                return counter(self.beam_search(outputs, W, K, input_lengths=lens), targets)
+                return counter(self.beam_search(outputs, W, K, input_lengths=lens, **fused), targets)
             x = self._beam_emissions(outputs)
             with torch.cuda.device(x.device), torch.no_grad():
                 xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
-                return counter.totals(M.beam_search_errors(counter, targets, x, self.blank, W, K, lengths=xlen))
+                return counter.totals(M.beam_search_errors(counter, targets, x, self.blank, W, K, lengths=xlen, **fused))
         lens = None
         if input_lengths is not None:
             lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.errors")

@@ -16,6 +16,12 @@
 //   write      (a wave per (b, rank < nbest)): base = the lengths before it summed in a fixed order, then lane 0 walks
 //              the arena back from the final node and stores the labels -- plain vector stores, `out` / `out_offsets` /
 //              `scores` may be pinned host memory.
+// wfl_ctc_beam_search_lm is the same three launches with a token-level n-gram LM and a length bonus fused into the beam
+// launch: the beam kernel takes the LM as a parameter pack, the instantiation without one is the
+// code it was; with it a hypothesis carries an LM state, an extension costs one back-off lookup (bounded binary searches
+// in the LM's arrays, which stay in global memory) where its key is formed -- unless it cannot reach the W-th best stay
+// entry even with the LM's largest term --, its next state waits in LDS beside the entry for place(), and the final
+// beam is ranked again with </s>.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
 #include "device_common.h"
@@ -147,19 +153,67 @@ __device__ __forceinline__ long long beam_key(double d) {
   return b >= 0 ? b : b ^ 0x7fffffffffffffffLL;
 }
 
+// the LM of a launch: wfl_ngram_lm's device arrays (a pack that passed wfl_ngram_lm_check) and the scalars of the call
+struct BeamLm {
+  const int32_t *arc_ptr, *arc_label, *arc_next, *bo_next;
+  const double *arc_w, *bo_w;
+  int start, eos;  // eos: the label of </s> = C
+  double alpha, beta;
+  double bound;  // no extension's alpha step + beta is above it (+inf: unknown)
+  int score_eos;
+};
+constexpr int kLmMaxBackoff = WFL_NGRAM_LM_MAX_BACKOFF;
+
+// step(s, c) of include/wfl.h: the log weight of label c from state s, backing off while s has no such arc; -inf if the
+// chain ends without one.  Both loops are bounded: at most kLmMaxBackoff back-offs, 31 halvings of a range of < 2^31 arcs.
+__device__ __forceinline__ double beam_lm_step(const BeamLm& lm, int s, int c, int& next) {
+  double acc = 0.0;
+  for (int d = 0; d <= kLmMaxBackoff; ++d) {
+    const int end = lm.arc_ptr[s + 1];
+    int lo = lm.arc_ptr[s], hi = end;
+    for (int it = 0; it < 31 && lo < hi; ++it) {  // the first arc whose label is not below c
+      const int mid = lo + ((hi - lo) >> 1);
+      if (lm.arc_label[mid] < c)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (lo < end && lm.arc_label[lo] == c) {
+      next = lm.arc_next[lo];
+      return acc + lm.arc_w[lo];
+    }
+    const int bo = lm.bo_next[s];
+    if (bo < 0) break;
+    acc += lm.bo_w[s], s = bo;
+  }
+  next = lm.start;  // (never used: the entry does not exist)
+  return -__builtin_inf();
+}
+// The total a key was made of: beam_key's inverse.  beam_key maps +0 and -0 to the key 0 before it folds the sign, so
+// the key of a zero comes back as +0 -- the one total whose bits may differ, and equal to it.  (Not for kKeyDropped.)
+__device__ __forceinline__ double beam_key_total(long long k) {
+  return __longlong_as_double(k >= 0 ? k : k ^ 0x7fffffffffffffffLL);
+}
+
 struct BeamHyp {  // (struct of arrays, one per buffer)
   double pb[kBeamMax], pnb[kBeamMax], tot[kBeamMax];
   unsigned long long hash[kBeamMax], hash2[kBeamMax];
   int last[kBeamMax], len[kBeamMax], node[kBeamMax];
 };
 
-// NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales)
-template <int NT>
+__device__ __forceinline__ const BeamLm& beam_lm_of(const BeamLm& lm) { return lm; }
+
+// NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales).
+// Lm: nothing -- the search of wfl_ctc_beam_search, its parameters and its code what they were --, or one BeamLm: the
+// n-gram LM and length bonus of wfl_ctc_beam_search_lm.
+template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
                                                            const float* __restrict__ cand_sc, const float* __restrict__ row_lse,
                                                            int2* __restrict__ arena, int32_t* __restrict__ fin_node,
-                                                           int32_t* __restrict__ fin_len, double* __restrict__ scores) {
+                                                           int32_t* __restrict__ fin_len, double* __restrict__ scores,
+                                                           Lm... lm_arg) {
+  constexpr bool LM = sizeof...(Lm) != 0;
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -177,6 +231,15 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   __shared__ int widx[kBeamMax];
   __shared__ int s_bin, s_need, s_ties, s_wcount;
   __shared__ double s_norm;
+  // LM only: the state of every hypothesis (double-buffered like the beam) and the next state of every extension, by
+  // entry index, from where its key is formed to place()
+  int(*lmst)[kBeamMax] = nullptr;
+  int* enext = nullptr;
+  if constexpr (LM) {
+    __shared__ int s_lmst[2][kBeamMax];
+    __shared__ int s_enext[kBeamEntries];
+    lmst = s_lmst, enext = s_enext;
+  }
 
   const int tid = threadIdx.x, b = blockIdx.x;
   const int KC = K + 1;
@@ -191,6 +254,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     s_bpos[0] = s_bpos[1] = 0;
     beam[0].pb[0] = 0.0, beam[0].pnb[0] = ninf, beam[0].tot[0] = 0.0;
     beam[0].hash[0] = 0ull, beam[0].hash2[0] = 0ull, beam[0].last[0] = -1, beam[0].len[0] = 0, beam[0].node[0] = -1;
+    if constexpr (LM) lmst[0][0] = beam_lm_of(lm_arg...).start;
   }
   __syncthreads();
   // the candidates of frame 0 into buffer 0
@@ -245,7 +309,17 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
       const double pb = sc[bpos] + h.tot[tid];
       double pnb = p >= 0 ? sc[p] + h.pnb[tid] : ninf;
       const int i = par[tid];
-      if (i >= 0) pnb = beam_lae(pnb, sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]));
+      if constexpr (LM) {
+        if (i >= 0) {  // the merged extension carries the LM term of the prefix it makes
+          const BeamLm& lm = beam_lm_of(lm_arg...);
+          const double e = sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]);
+          int nx;
+          const double l = e > ninf ? beam_lm_step(lm, lmst[cur][i], h.last[tid], nx) : ninf;
+          if (l > ninf) pnb = beam_lae(pnb, e + (lm.alpha * l + lm.beta));
+        }
+      } else {
+        if (i >= 0) pnb = beam_lae(pnb, sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]));
+      }
       const double tot = beam_lae(pb, pnb);
       spb[tid] = pb, spnb[tid] = pnb, stot[tid] = tot, skey[tid] = beam_key(tot);
     }
@@ -272,7 +346,16 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         idx = kBeamMax + i * kBeamCand + p;
         if (c == blank || ((mmask[i] >> p) & 1ull))
           k = kKeyDropped;
-        else
+        else if constexpr (LM) {
+          const BeamLm& lm = beam_lm_of(lm_arg...);
+          const double ac = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);  // the extension without its LM term
+          int nx = 0;
+          // (an entry below the bound even with the LM's largest term is outside the beam: no lookup; + is monotone)
+          const bool reach = ac > ninf && beam_key(ac + lm.bound) >= tau;
+          const double l = reach ? beam_lm_step(lm, lmst[cur][i], c, nx) : ninf;
+          k = l > ninf ? beam_key(ac + (lm.alpha * l + lm.beta)) : kKeyDropped;
+          enext[idx] = nx;
+        } else
           k = beam_key(sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]));
       }
       if (k != kKeyDropped && k >= tau) {
@@ -282,15 +365,20 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     }
     __syncthreads();
     const int M = s_count;
-    // entry idx is the hypothesis of rank r of the next beam
-    auto place = [&](int idx, int r) {
+    // entry idx (of key k) is the hypothesis of rank r of the next beam
+    auto place = [&](int idx, int r, long long k) {
       if (idx < kBeamMax) {
         g.pb[r] = spb[idx], g.pnb[r] = spnb[idx], g.tot[r] = stot[idx];
         g.hash[r] = h.hash[idx], g.hash2[r] = h.hash2[idx], g.last[r] = h.last[idx], g.len[r] = h.len[idx], g.node[r] = h.node[idx];
+        if constexpr (LM) lmst[cur ^ 1][r] = lmst[cur][idx];
       } else {
         const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
         const int c = cls[p];
-        const double e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
+        double e;
+        if constexpr (LM)
+          e = beam_key_total(k), lmst[cur ^ 1][r] = enext[idx];  // (the total with its LM term: the key holds it)
+        else
+          e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
         const int node = t * W + r;
         g.pb[r] = ninf, g.pnb[r] = e, g.tot[r] = e;
         g.hash[r] = h.hash[i] * kBeamHashMul + (unsigned long long)(c + 1);
@@ -347,7 +435,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const int idx = widx[tid];
           int r = 0;
           for (int q = 0; q < W; ++q) r += (wkey[q] > k || (wkey[q] == k && widx[q] < idx)) ? 1 : 0;
-          place(idx, r);
+          place(idx, r, k);
         }
       }
     }
@@ -362,7 +450,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const long long kq = ckey[q];
           r += (kq > k || (kq == k && cidx[q] < idx)) ? 1 : 0;
         }
-        if (r < W) place(idx, r);
+        if (r < W) place(idx, r, k);
       }
     // the next frame's candidates into the other buffer (last read a frame ago)
     if (tid < KC && t + 1 < Tb) {
@@ -377,7 +465,37 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   if (tid == 0) s_norm = norm;
   __syncthreads();
   const BeamHyp& f = beam[Tb & 1];
-  if (tid < nbest) {
+  if constexpr (LM) {
+    // </s>: every rank's total with the LM's end weight, a rank without one dropped, then the ranks again by counting
+    // (descending, ties to the earlier rank; dropped keys are below every other and come out behind them, empty)
+    const BeamLm& lm = beam_lm_of(lm_arg...);
+    if (tid < nbeam) {
+      double s = f.tot[tid];
+      if (lm.score_eos) {
+        int nx;
+        const double l = beam_lm_step(lm, lmst[Tb & 1][tid], lm.eos, nx);
+        s = l > ninf ? s + lm.alpha * l : ninf;
+      }
+      stot[tid] = s, skey[tid] = beam_key(s);
+    }
+    __syncthreads();
+    if (tid < max(nbeam, nbest)) {
+      int r = tid;
+      bool have = false;
+      if (tid < nbeam) {
+        const long long k = skey[tid];
+        r = 0;
+        for (int j = 0; j < nbeam; ++j) r += (skey[j] > k || (skey[j] == k && j < tid)) ? 1 : 0;
+        have = k != kKeyDropped;
+      }
+      if (r < nbest) {
+        const int64_t o = (int64_t)b * nbest + r;
+        fin_node[o] = have ? f.node[tid] : -1;
+        fin_len[o] = have ? f.len[tid] : 0;
+        scores[o] = have ? (normalize ? stot[tid] - s_norm : stot[tid]) : ninf;
+      }
+    }
+  } else if (tid < nbest) {
     const int64_t o = (int64_t)b * nbest + tid;
     const bool have = tid < nbeam;
     fin_node[o] = have ? f.node[tid] : -1;
@@ -441,21 +559,23 @@ int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame,
   return WFL_OK;
 }
 
-int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
-                        int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
-                        double* scores, void* stream) {
+}  // extern "C"
+
+// the three launches of a search; lm: NULL, or the LM of wfl_ctc_beam_search_lm (already checked)
+static int beam_launch(const char* what, const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                       int classes_per_frame, int nbest, int normalize, const BeamLm* lm, void* ws, int32_t* out,
+                       int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   if (!x || !ws || !out || !out_offsets || !scores) {
-    set_error("ctc_beam_search: a NULL pointer");
+    set_error("%s: a NULL pointer", what);
     return WFL_ERR_INVALID;
   }
-  if (const int rc = beam_check("ctc_beam_search", B, T, C, beam, classes_per_frame, nbest)) return rc;
+  if (const int rc = beam_check(what, B, T, C, beam, classes_per_frame, nbest)) return rc;
   if (blank < 0 || blank >= C) {
-    set_error("ctc_beam_search: blank %d is outside [0, %d)", blank, C);
+    set_error("%s: blank %d is outside [0, %d)", what, blank, C);
     return WFL_ERR_INVALID;
   }
   if (out_capacity < (int64_t)B * nbest * T) {
-    set_error("ctc_beam_search: out holds %lld labels, B nbest T = %lld are needed", (long long)out_capacity,
-              (long long)B * nbest * T);
+    set_error("%s: out holds %lld labels, B nbest T = %lld are needed", what, (long long)out_capacity, (long long)B * nbest * T);
     return WFL_ERR_INVALID;
   }
   const int K = classes_per_frame;
@@ -481,7 +601,14 @@ int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, in
   else
     candidates(beam_candidates_kernel<0>);
   WFL_LAUNCH_CHECK();
-  if (beam * (K + 2) <= 1024)
+  if (lm) {
+    if (beam * (K + 2) <= 1024)
+      hipLaunchKernelGGL((beam_search_kernel<256, BeamLm>), dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls,
+                         sc, lse, arena, fin_node, fin_len, scores, *lm);
+    else
+      hipLaunchKernelGGL((beam_search_kernel<1024, BeamLm>), dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize,
+                         cls, sc, lse, arena, fin_node, fin_len, scores, *lm);
+  } else if (beam * (K + 2) <= 1024)
     hipLaunchKernelGGL(beam_search_kernel<256>, dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls, sc,
                        lse, arena, fin_node, fin_len, scores);
   else
@@ -493,6 +620,118 @@ int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, in
                      fin_len, out, out_offsets);
   WFL_LAUNCH_CHECK();
   return WFL_OK;
+}
+
+extern "C" {
+
+int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
+                        int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                        double* scores, void* stream) {
+  return beam_launch("ctc_beam_search", x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, ws, out,
+                     out_capacity, out_offsets, scores, stream);
+}
+
+static int ngram_lm_shape(const char* what, const wfl_ngram_lm* lm) {
+  if (!lm || !lm->arc_ptr || !lm->arc_label || !lm->arc_next || !lm->arc_w || !lm->bo_next || !lm->bo_w) {
+    set_error("%s: a NULL language model or array of it", what);
+    return WFL_ERR_INVALID;
+  }
+  if (lm->num_states < 1 || lm->num_arcs < 0 || lm->start < 0 || lm->start >= lm->num_states) {
+    set_error("%s: a language model of %d states, %d arcs, start %d", what, lm->num_states, lm->num_arcs, lm->start);
+    return WFL_ERR_INVALID;
+  }
+  return WFL_OK;
+}
+
+int wfl_ngram_lm_check(wfl_ngram_lm* lm, int C, int blank) {
+  const char* what = "ngram_lm_check";
+  if (const int rc = ngram_lm_shape(what, lm)) return rc;
+  if (C < 1 || blank < 0 || blank >= C) {
+    set_error("%s: %d classes, blank %d", what, C, blank);
+    return WFL_ERR_INVALID;
+  }
+  const int S = lm->num_states, A = lm->num_arcs;
+  if (lm->arc_ptr[0] != 0 || lm->arc_ptr[S] != A) {
+    set_error("%s: arc_ptr runs from %d to %d, not from 0 to %d", what, lm->arc_ptr[0], lm->arc_ptr[S], A);
+    return WFL_ERR_INVALID;
+  }
+  for (int s = 0; s < S; ++s)
+    if (lm->arc_ptr[s] > lm->arc_ptr[s + 1] || lm->arc_ptr[s] < 0 || lm->arc_ptr[s + 1] > A) {
+      set_error("%s: arc_ptr descends or leaves [0, %d] at state %d", what, A, s);
+      return WFL_ERR_INVALID;
+    }
+  for (int s = 0; s < S; ++s) {
+    for (int a = lm->arc_ptr[s]; a < lm->arc_ptr[s + 1]; ++a) {
+      const int l = lm->arc_label[a];
+      if (l < 0 || l > C || l == blank) {
+        set_error("%s: arc %d of state %d has label %d (classes [0, %d), %d for </s>, never the blank %d)", what, a, s, l, C, C,
+                  blank);
+        return WFL_ERR_INVALID;
+      }
+      if (a > lm->arc_ptr[s] && lm->arc_label[a - 1] >= l) {
+        set_error("%s: the labels of state %d are not strictly ascending at arc %d", what, s, a);
+        return WFL_ERR_INVALID;
+      }
+      if (lm->arc_next[a] < 0 || lm->arc_next[a] >= S) {
+        set_error("%s: arc %d of state %d leads to state %d of %d", what, a, s, lm->arc_next[a], S);
+        return WFL_ERR_INVALID;
+      }
+      if (!(lm->arc_w[a] < __builtin_inf())) {  // (NaN or +inf)
+        set_error("%s: arc %d of state %d has a weight that is NaN or +inf", what, a, s);
+        return WFL_ERR_INVALID;
+      }
+    }
+    if (lm->bo_next[s] < -1 || lm->bo_next[s] >= S) {
+      set_error("%s: state %d backs off to state %d of %d", what, s, lm->bo_next[s], S);
+      return WFL_ERR_INVALID;
+    }
+    if (lm->bo_next[s] >= 0 && !(lm->bo_w[s] < __builtin_inf())) {
+      set_error("%s: state %d has a back-off weight that is NaN or +inf", what, s);
+      return WFL_ERR_INVALID;
+    }
+  }
+  for (int s = 0; s < S; ++s) {  // a chain longer than the cap: too deep or a cycle, refused alike
+    int t = s, depth = 0;
+    while (lm->bo_next[t] >= 0 && depth <= WFL_NGRAM_LM_MAX_BACKOFF) t = lm->bo_next[t], ++depth;
+    if (depth > WFL_NGRAM_LM_MAX_BACKOFF) {
+      set_error("%s: the back-off chain of state %d is cyclic or deeper than %d", what, s, WFL_NGRAM_LM_MAX_BACKOFF);
+      return WFL_ERR_INVALID;
+    }
+  }
+  {  // the bounds of step(), written into the struct: an arc weight and at most the cap's number of back-off weights
+    double lo = __builtin_inf(), hi = -__builtin_inf(), blo = 0.0, bhi = 0.0;
+    for (int a = 0; a < A; ++a) lo = fmin(lo, lm->arc_w[a]), hi = fmax(hi, lm->arc_w[a]);
+    for (int s = 0; s < S; ++s)
+      if (lm->bo_next[s] >= 0) blo = fmin(blo, lm->bo_w[s]), bhi = fmax(bhi, lm->bo_w[s]);
+    lo += WFL_NGRAM_LM_MAX_BACKOFF * blo, hi += WFL_NGRAM_LM_MAX_BACKOFF * bhi;
+    lm->step_min = A > 0 ? lo : 0.0, lm->step_max = A > 0 ? hi : 0.0;
+  }
+  return WFL_OK;
+}
+
+int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                           int classes_per_frame, int nbest, int normalize, const wfl_ngram_lm* lm, double lm_weight,
+                           double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                           int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lm";
+  if (const int rc = ngram_lm_shape(what, lm)) return rc;
+  if (lm->step_min != lm->step_min || lm->step_max != lm->step_max) {
+    set_error("%s: the language model's step_min or step_max is NaN", what);
+    return WFL_ERR_INVALID;
+  }
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g and length_bonus %g must be finite", what, lm_weight, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  BeamLm d;
+  d.arc_ptr = lm->arc_ptr, d.arc_label = lm->arc_label, d.arc_next = lm->arc_next, d.bo_next = lm->bo_next;
+  d.arc_w = lm->arc_w, d.bo_w = lm->bo_w;
+  d.start = lm->start, d.eos = C, d.alpha = lm_weight, d.beta = length_bonus, d.score_eos = score_eos ? 1 : 0;
+  // the largest LM term of an extension, by the operations the kernel forms a term with (0 * inf: no bound)
+  const double t0 = lm_weight * lm->step_min, t1 = lm_weight * lm->step_max;
+  d.bound = (t0 != t0 || t1 != t1) ? __builtin_inf() : fmax(t0, t1) + length_bonus;
+  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, &d, ws, out, out_capacity,
+                     out_offsets, scores, stream);
 }
 
 }  // extern "C"

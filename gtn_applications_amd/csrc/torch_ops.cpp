@@ -1115,10 +1115,28 @@ at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop,
 // the decode the reference does not have.  Collected like the greedy decode: offsets, scores and the surviving labels
 // land in the device's pinned decode buffer behind one event.
 // ------------------------------------------------------------------------------------------------------------
+// An n-gram LM on the device (wfl_ngram_lm; lm.py's NGramLM.on_device): ints = [arc_ptr (S+1) | arc_label (A) | arc_next (A)
+// | bo_next (S)] int32, weights = [arc_w (A) | bo_w (S)] float64, both contiguous on x's device, from a pack that passed
+// wfl_ngram_lm_check on the host.
+struct BeamLmCall {
+  at::Tensor ints, weights;
+  wfl_ngram_lm lm;
+  double weight = 1.0, bonus = 0.0;
+  int score_eos = 1;
+};
+
 struct BeamCall {
   at::Tensor x, lengths;
   int B = 0, T = 0, C = 0, blank = 0, beam = 0, K = 0, nbest = 0;
+  std::shared_ptr<BeamLmCall> lm;  // (none: wfl_ctc_beam_search, the call it was)
   void launch(int normalize, void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) const {
+    if (lm) {
+      check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lengths.defined() ? lengths.data_ptr<int32_t>() : nullptr, B, T, C,
+                                   blank, beam, K, nbest, normalize, &lm->lm, lm->weight, lm->bonus, lm->score_eos, ws, out,
+                                   cap, offs, scores, s),
+            "ctc_beam_search_lm");
+      return;
+    }
     check(wfl_ctc_beam_search(x.data_ptr<float>(), lengths.defined() ? lengths.data_ptr<int32_t>() : nullptr, B, T, C, blank,
                               beam, K, nbest, normalize, ws, out, cap, offs, scores, s),
           "ctc_beam_search");
@@ -1142,10 +1160,50 @@ BeamCall beam_call(const at::Tensor& x, const c10::optional<at::Tensor>& lengths
   return c;
 }
 
+std::shared_ptr<BeamLmCall> beam_lm_call(const at::Tensor& x, const at::Tensor& ints, const at::Tensor& weights,
+                                         int64_t num_states, int64_t num_arcs, int64_t start, double step_min,
+                                         double step_max, double lm_weight, double length_bonus, bool score_eos) {
+  const int64_t S = num_states, A = num_arcs;
+  TORCH_CHECK(S >= 1 && A >= 0 && S < (1LL << 31) && A < (1LL << 31) && start >= 0 && start < S,
+              "ctc_beam_search_lm: a language model of ", S, " states, ", A, " arcs, start ", start);
+  TORCH_CHECK(ints.device() == x.device() && ints.scalar_type() == at::kInt && ints.is_contiguous() && ints.dim() == 1 &&
+                  ints.numel() == 2 * S + 1 + 2 * A,
+              "ctc_beam_search_lm: the LM's int32 arrays must be one contiguous [2 S + 1 + 2 A] tensor on x's device");
+  TORCH_CHECK(weights.device() == x.device() && weights.scalar_type() == at::kDouble && weights.is_contiguous() &&
+                  weights.dim() == 1 && weights.numel() == A + S,
+              "ctc_beam_search_lm: the LM's float64 weights must be one contiguous [A + S] tensor on x's device");
+  auto c = std::make_shared<BeamLmCall>();
+  c->ints = ints, c->weights = weights;
+  const int32_t* ip = ints.data_ptr<int32_t>();
+  const double* wp = weights.data_ptr<double>();
+  c->lm.num_states = (int32_t)S, c->lm.num_arcs = (int32_t)A, c->lm.start = (int32_t)start, c->lm.reserved = 0;
+  c->lm.arc_ptr = ip, c->lm.arc_label = ip + S + 1, c->lm.arc_next = ip + S + 1 + A, c->lm.bo_next = ip + S + 1 + 2 * A;
+  c->lm.arc_w = wp, c->lm.bo_w = wp + A, c->lm.step_min = step_min, c->lm.step_max = step_max;
+  c->weight = lm_weight, c->bonus = length_bonus, c->score_eos = score_eos ? 1 : 0;
+  return c;
+}
+
+py::tuple beam_search_collect(const BeamCall& c, bool normalize);
+
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
                           int64_t nbest, bool normalize) {
-  const BeamCall c = beam_call(x, lengths, blank, beam, K, nbest);
+  return beam_search_collect(beam_call(x, lengths, blank, beam, K, nbest), normalize);
+}
+
+// the same with an n-gram LM and a length bonus in the beam launch (wfl_ctc_beam_search_lm)
+py::tuple ctc_beam_search_lm(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
+                             int64_t K, int64_t nbest, bool normalize, const at::Tensor& lm_ints, const at::Tensor& lm_weights,
+                             int64_t num_states, int64_t num_arcs, int64_t start, double step_min, double step_max,
+                             double lm_weight, double length_bonus, bool score_eos) {
+  BeamCall c = beam_call(x, lengths, blank, beam, K, nbest);
+  c.lm = beam_lm_call(x, lm_ints, lm_weights, num_states, num_arcs, start, step_min, step_max, lm_weight, length_bonus,
+                      score_eos);
+  return beam_search_collect(c, normalize);
+}
+
+py::tuple beam_search_collect(const BeamCall& c, bool normalize) {
+  const at::Tensor& x = c.x;
   const int dev = x.device().index();
   DeviceScope scope(dev);
   int64_t capacity = 0, ws_bytes = 0;
@@ -1187,11 +1245,10 @@ py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& 
 }
 
 // the best hypothesis of every utterance into device buffers, the count behind it: the predictions never reach the host
-at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
-                                  int64_t K, const std::shared_ptr<StagedTargets>& ref,
-                                  const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                                  const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  const BeamCall c = beam_call(x, lengths, blank, beam, K, 1);
+at::Tensor beam_search_errors(const BeamCall& c, const std::shared_ptr<StagedTargets>& ref,
+                              const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                              const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  const at::Tensor& x = c.x;
   const int dev = x.device().index();
   if (c.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
   const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
@@ -1210,12 +1267,38 @@ at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::T
   return errors_collect(dev, c.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, ref, ht, rt, sep);
 }
 
+at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
+                                  int64_t K, const std::shared_ptr<StagedTargets>& ref,
+                                  const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
+                                  const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  return beam_search_errors(beam_call(x, lengths, blank, beam, K, 1), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
+                            ref_longest, sep);
+}
+
+at::Tensor ctc_beam_search_lm_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
+                                     int64_t K, const at::Tensor& lm_ints, const at::Tensor& lm_weights, int64_t num_states,
+                                     int64_t num_arcs, int64_t start, double step_min, double step_max, double lm_weight,
+                                     double length_bonus, bool score_eos,
+                                     const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
+                                     int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table,
+                                     int64_t ref_V, int64_t ref_longest, int64_t sep) {
+  BeamCall c = beam_call(x, lengths, blank, beam, K, 1);
+  c.lm = beam_lm_call(x, lm_ints, lm_weights, num_states, num_arcs, start, step_min, step_max, lm_weight, length_bonus,
+                      score_eos);
+  return beam_search_errors(c, ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V, ref_longest, sep);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
         "CTC prefix beam search on the device: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
+  m.def("ctc_beam_search_lm", &ctc_beam_search_lm,
+        "ctc_beam_search with an n-gram LM (int32 and float64 device arrays of a checked pack), its weight, a length bonus and "
+        "whether </s> is scored");
+  m.def("ctc_beam_search_lm_errors", &ctc_beam_search_lm_errors,
+        "ctc_beam_search_lm's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("ctc_beam_search_errors", &ctc_beam_search_errors,
         "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),

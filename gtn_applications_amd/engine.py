@@ -4,6 +4,7 @@ all arithmetic happens in the HIP kernels behind the C ABI (include/wfl.h).
 """
 import ctypes
 import itertools
+import math
 import operator
 import sys
 import threading
@@ -968,18 +969,61 @@ def check_beam_arguments(C, beam_size, classes_per_frame, nbest, what):
     return W, K, n
 
 
-def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True):
+def check_lm_arguments(lm, C, blank, lm_weight, length_bonus, lm_eos, what):
+    """(lm, lm_weight, length_bonus, lm_eos) of a beam search over C classes, checked: lm None and the rest at their
+    defaults, or an lm.NGramLM built for these classes and this blank with a finite weight and bonus.  ValueError
+    otherwise; needs no device."""
+    from .lm import NGramLM
+
+    def number(v, name):
+        """a finite float from a Python or numpy number or a one-element tensor (a sweep over numpy weights); never
+        from a bool or a string"""
+        f = math.nan
+        if not isinstance(v, (bool, np.bool_, str, bytes)):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                pass
+        if not math.isfinite(f):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+        return f
+
+    weight, bonus = number(lm_weight, "lm_weight"), number(length_bonus, "length_bonus")
+    if not isinstance(lm_eos, (bool, np.bool_)):
+        raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+    lm_eos = bool(lm_eos)
+    if lm is None:
+        if weight != 1.0 or bonus != 0.0 or lm_eos is not True:
+            raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm")
+        return None, weight, bonus, lm_eos
+    if not isinstance(lm, NGramLM):
+        raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
+    if lm.num_classes != C or lm.blank != blank:
+        raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
+                         f"the emissions have {C} with blank {blank}")
+    return lm, weight, bonus, lm_eos
+
+
+def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True):
     """CTC prefix beam search on the device (wfl_ctc_beam_search through csrc/torch_ops.cpp; the rules: include/wfl.h,
     DESIGN.md section 17).  x: float32 [B,T,C] on a GPU, contiguous; lengths: int32 [B] on x's device
     (input_lengths_on_device) or None.  Returns (hyps, scores): hyps[b][r] the int64 CPU label tensor of rank r of
     utterance b (views of one tensor), scores float64 CPU [B, nbest] -- log mass of the sequence over the frames, minus
     the frames' log-sum-exps if `normalize`; a rank beyond the final beam is empty with score -inf.  Only the surviving
-    labels and the scores leave the device."""
+    labels and the scores leave the device.  lm: an lm.NGramLM -- the search of wfl_ctc_beam_search_lm (DESIGN.md section
+    18): an extension by class c from LM state s adds lm_weight * step(s, c) + length_bonus, lm_eos adds lm_weight *
+    step(s, </s>) after the last frame and ranks again; the scores include these terms.  lm None: the call it was."""
     B, T, C = x.shape
     W, K, n = check_beam_arguments(C, beam_size, classes_per_frame, nbest, "ctc_beam_search")
     if not 0 <= int(blank) < C:
         raise ValueError(f"ctc_beam_search: blank index {blank} is outside [0, {C})")
-    flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize))
+    lm, weight, bonus, eos = check_lm_arguments(lm, C, int(blank), lm_weight, length_bonus, lm_eos, "ctc_beam_search")
+    if lm is None:
+        flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize))
+    else:
+        flat, offsets, scores = N.ops.ctc_beam_search_lm(x, lengths, int(blank), W, K, n, bool(normalize),
+                                                         *lm.device_arguments(x.device), weight, bonus, eos)
     rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
     return [list(rows[b * n:(b + 1) * n]) for b in range(B)], scores
 

@@ -146,12 +146,19 @@ def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=
     return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref._st, *counter.tables(x.device))
 
 
-def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None):
+def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None, lm=None, lm_weight=1.0,
+                       length_bonus=0.0, lm_eos=True):
     """engine.ctc_beam_search's launches (best hypothesis only) and the counts behind them, on x's device: [B, 4] int64
-    on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments)"""
+    on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments).  lm,
+    lm_weight, length_bonus, lm_eos: as in engine.ctc_beam_search."""
     if len(targets) != x.shape[0]:
         raise ValueError(f"errors: {x.shape[0]} utterances for {len(targets)} targets")
+    lm, weight, bonus, eos = E.check_lm_arguments(lm, x.shape[2], int(blank), lm_weight, length_bonus, lm_eos, "errors")
     ref = counter.staged_targets(targets, x.device)
+    if lm is not None:
+        return N.ops.ctc_beam_search_lm_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame),
+                                               *lm.device_arguments(x.device), weight, bonus, eos, ref._st,
+                                               *counter.tables(x.device))
     return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref._st,
                                         *counter.tables(x.device))
 

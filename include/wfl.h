@@ -582,7 +582,8 @@ int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, in
  *   only pass over x; beam: a workgroup per utterance; write), no allocation, no synchronisation.
  *   WFL_ERR_INVALID: a NULL required pointer, B, T or C < 1, blank outside [0, C), beam outside [1, 64],
  *   classes_per_frame outside [1, min(C, 64)], nbest outside [1, beam], out_capacity too small.
- *   WFL_ERR_UNSUPPORTED: C > 16384.  No language model, length bonus or lexicon; CTC only.
+ *   WFL_ERR_UNSUPPORTED: C > 16384.  No lexicon / word-level LM; CTC only.  A token-level n-gram LM and a length
+ *   bonus: wfl_ctc_beam_search_lm below.
  * ------------------------------------------------------------------------------------------------ */
 /* out_capacity = B nbest T (int32 elements of `out`), ws_bytes = the device scratch of a call */
 int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
@@ -590,6 +591,61 @@ int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame,
 int wfl_ctc_beam_search(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank, int beam,
                         int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity,
                         int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same search with a token-level n-gram LM and a length bonus fused in (csrc/beam_kernels.hip).
+ *   Every rule of wfl_ctc_beam_search stands; the additions:
+ *     - LM form: a deterministic back-off acceptor over the emission classes.  State s has the arcs
+ *       [arc_ptr[s], arc_ptr[s+1]) =(arc_label, arc_next, arc_w), labels strictly ascending, w float64 natural log, and
+ *       an optional back-off (bo_next[s], bo_w[s]), bo_next[s] = -1 for none.  Labels are CTC class indices 0 .. C-1,
+ *       never the blank; label C stands for </s> (the next state of such an arc is not used).  `start` is the <s> history.
+ *     - step(s, c): acc = 0; search c among the arcs of s (a binary search, at most 31 steps); found: (acc + w, next);
+ *       s without a back-off: (-inf, none); otherwise acc += bo_w[s], s = bo_next[s], search again.  A chain has at
+ *       most WFL_NGRAM_LM_MAX_BACKOFF = 8 back-offs; the kernel's loop is bounded by the same constant.
+ *     - every hypothesis carries an LM state, the empty prefix has `start`;
+ *     - the extension i + c: (l, nxt) = step(state_i, c); l = -inf: the extension does not exist; otherwise
+ *       e = (s + base) + (lm_weight l + length_bonus), base as above (pb_i if c is i's last label, else tot_i), and the
+ *       new entry has the state nxt.  An extension with s + base = -inf does not exist either (no lookup).  The kernel also
+ *       skips the lookup of an extension that cannot reach the W-th best stay entry even with the LM's largest term,
+ *       max(lm_weight step_min, lm_weight step_max) + length_bonus: such an entry is outside the beam whatever its step.
+ *     - stays add nothing and keep their state; a merged extension carries the same term as a new one (state and LM
+ *       score are functions of the prefix), so unpruned tot(l) = mass(l) + lm_weight LM(l) + length_bonus |l| exactly;
+ *     - candidates (by acoustic score alone), the order of entries, the tie rule and the -inf drop rule do not change;
+ *     - score_eos != 0: after the last frame rank r gets tot_r + lm_weight step(state_r, C); a rank whose step is -inf is
+ *       dropped, the rest are ranked again by the new score, descending, ties to the earlier rank; nbest is taken after
+ *       that.  T_b = 0 gives the empty sequence with score lm_weight step(start, C) (0 without score_eos);
+ *     - normalize still subtracts the rows' log-sum-exps and nothing else.
+ *   lm: a struct in HOST memory of DEVICE pointers to a pack that wfl_ngram_lm_check accepted (with host pointers, for
+ *   the same C and blank), with the step_min / step_max that check wrote -- the kernels trust it: they check no index.
+ *   lm_weight, length_bonus: finite.  The same workspace (wfl_ctc_beam_workspace), outputs, three launches and
+ *   guarantees as wfl_ctc_beam_search; no global atomics, no cross-workgroup waits, every loop bounded by T_b, W, K,
+ *   the back-off cap or 31 search steps.
+ *   WFL_ERR_INVALID: what wfl_ctc_beam_search refuses; lm or one of its arrays NULL, num_states < 1, num_arcs < 0,
+ *   start outside [0, num_states), step_min or step_max NaN, a weight or bonus that is not finite.
+ * ------------------------------------------------------------------------------------------------ */
+#define WFL_NGRAM_LM_MAX_BACKOFF 8
+typedef struct wfl_ngram_lm {
+  int32_t num_states, num_arcs, start, reserved;
+  double step_min, step_max; /* written by wfl_ngram_lm_check: every step(s, c) that is not -inf lies in between */
+  const int32_t* arc_ptr;   /* [num_states + 1], arc_ptr[0] = 0, arc_ptr[num_states] = num_arcs */
+  const int32_t* arc_label; /* [num_arcs] */
+  const int32_t* arc_next;  /* [num_arcs] */
+  const double* arc_w;      /* [num_arcs] */
+  const int32_t* bo_next;   /* [num_states], -1: no back-off */
+  const double* bo_w;       /* [num_states] */
+} wfl_ngram_lm;
+/* The pack check (host arrays, no device): sizes and `start` in range, arc_ptr ascending from 0 to num_arcs, labels
+ * strictly ascending within a state, in [0, C], never the blank; arc_next and bo_next in range (bo_next may be -1); the
+ * back-off chains acyclic and at most WFL_NGRAM_LM_MAX_BACKOFF deep; no weight NaN or +inf.  WFL_ERR_INVALID names the first offence in
+ * wfl_last_error().  On success it WRITES lm->step_min and lm->step_max, the bounds the search prunes lookups with:
+ * [min arc weight + 8 min(0, least back-off weight), max arc weight + 8 max(0, largest back-off weight)], [0, 0]
+ * without arcs; whatever they held before is not read.  A caller copies them into the struct of device pointers it
+ * hands to wfl_ctc_beam_search_lm. */
+int wfl_ngram_lm_check(wfl_ngram_lm* lm, int C, int blank);
+int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank, int beam,
+                           int classes_per_frame, int nbest, int normalize, const wfl_ngram_lm* lm, double lm_weight,
+                           double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                           int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
