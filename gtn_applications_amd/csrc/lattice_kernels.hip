@@ -980,6 +980,7 @@ struct MitmArgs {
   const uint64_t* oth_prog = nullptr;  // its progress word
   int32_t* fmt = nullptr;            // forward sweep: fmt[b] <- kFmtOcc
   uint32_t* mitm_b = nullptr;        // backward sweep: its own flag (0 / 1), where the alpha buffer keeps `bad`
+  uint32_t* dead_b = nullptr;        // forward sweep: the gradient's bad[b] <- token when no path accepts (see the crossing)
   int spins = 1 << 18;
 };
 
@@ -1747,9 +1748,13 @@ __device__ __forceinline__ void run_chain_prob(const wfl_lattice_desc& d, const 
               oo_cur = ld_l2(mm.oth_offs + slot_of(c0, tid & 15));
             }
             if (tid == 0) {
-              if (DIR == 0)
+              if (DIR == 0) {
                 *mm.fmt = kFmtOcc;
-              else
+                // No accepting path: the occupancies are zeros, and the gradient workgroups beside the sweeps, which
+                // normalise nothing in this format, would leave the rows at their base values -cf softmax(x).  Marked as
+                // not served, the utterance gets its rows -- zeros, by log Z -- from wfl_lattice_grad_rest.
+                if (deadz) __hip_atomic_store(mm.dead_b, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              } else
                 __hip_atomic_store(mm.mitm_b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             // (vmcnt(0) as the BUILTIN, which the compiler's wait-count pass sees: the values just requested are used by
@@ -2245,6 +2250,7 @@ __device__ __forceinline__ void prob_chain_body(const wfl_lattice_desc& d, const
     mm.oth_prog = reinterpret_cast<const uint64_t*>((dir == 0 ? offs_b : offs_a) + prog_offset_doubles(d, nch1)) + b;
     mm.fmt = fmt + b;
     mm.mitm_b = occ_header(d, beta, tail, nch1).bad + b;
+    mm.dead_b = occ_header(d, alpha, tail, nch1).bad + b;
   }
   if (dir == 0) {
     if (threadIdx.x == 0) fmt[b] = kFmtProb;
@@ -2767,13 +2773,18 @@ __device__ __forceinline__ void occ_grad_tiles(const wfl_lattice_desc& d, const 
         dead = !(tot > 0.0 && tot < 1.0e300);
         zd = dead ? 0.0 : log2(tot) + ld_l2(offs_a + ts0 + 1) + ld_l2(offs_b + ts0 + 1);
       } else {
-        dead = false;  // (an utterance without a path: its sweeps stored zeros)
+        dead = false;  // (an utterance without a path: zeros, and marked in `bad` by its forward sweep -- rewritten later)
       }
       LIVE_T(t_w2);
       LIVE_ADD(3, t_w1, t_w2);
     }
     LIVE_T(t_p0);
     for (int i = tid; i < nr * Kmax; i += NT) acc[i] = 0.f;
+    // Behind the sweeps (!LIVE) a label's occupancies are summed as 2^-31 fixed-point integers in the accumulator's words
+    // and turned into floats afterwards: integer atomics commute, so the gradient is the same bits from run to run
+    // whatever order the waves arrive in (float atomics are not: a few dozen elements moved by an ulp of the sum).  The
+    // occupancies of a frame sum to one and a word holds sums below 2; a term is rounded to 2.3e-10 of a posterior's scale.
+    uint32_t* accu = reinterpret_cast<uint32_t*>(acc);
     // frame t's arcs end in slot t + 1 of both sweeps: gamma = p_alpha p_beta 2^(offs_a + offs_b - log2 Z) there
     if (tid < nr && !gamma)
       corr[tid] = LIVE ? exp2(ld_l2(offs_a + ts0 + tid + 1) + ld_l2(offs_b + ts0 + tid + 1) - zd)
@@ -2799,7 +2810,12 @@ __device__ __forceinline__ void occ_grad_tiles(const wfl_lattice_desc& d, const 
           const int r = (int)(((float)i + 0.5f) * inv_q), q = i - r * Q;
           if (i < n) {
             const int kk = lab[q];
-            if (kk >= 0 && gv[k] != 0.f) atomicAdd(&acc[r * Kmax + kk], gv[k]);
+            if (kk >= 0 && gv[k] != 0.f) {
+              if constexpr (LIVE)
+                atomicAdd(&acc[r * Kmax + kk], gv[k]);
+              else
+                atomicAdd(&accu[r * Kmax + kk], __float2uint_rn(gv[k] * 2147483648.f));
+            }
           }
         }
       }
@@ -2835,11 +2851,15 @@ __device__ __forceinline__ void occ_grad_tiles(const wfl_lattice_desc& d, const 
           const int r = (int)(((float)i + 0.5f) * inv_q), q = i - r * Q;  // (exact for i < 2^20)
           const double g = asrc[i] * bsrc[i];
           const int k = lab[q];
-          if (k >= 0 && g != 0.0) atomicAdd(&acc[r * Kmax + k], (float)(g * corr[r]));
+          if (k >= 0 && g != 0.0) atomicAdd(&accu[r * Kmax + k], __double2uint_rn(g * corr[r] * 2147483648.0));
         }
       }
     }
     __syncthreads();
+    if (!LIVE && !dead) {  // (block-uniform: `dead` comes from log Z here)
+      for (int i = tid; i < nr * Kmax; i += NT) acc[i] = (float)accu[i] * 4.656612873077393e-10f;
+      __syncthreads();
+    }
     LIVE_T(t_p1);
     // (eight rows a trip for the workgroups beside the sweeps -- stream_grad_rows<8, true>, twice the bytes in flight for the
     // same registers -- changes nothing: a tile's rows 23.9 us either way, the step 0.342 against 0.338 ms)
