@@ -825,18 +825,26 @@ std::pair<std::vector<at::Tensor>, bool> lattice_loss_forward(const at::Tensor& 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The decode behind viterbi() (wfl_decode_emissions / wfl_decode_paths, csrc/decode_kernels.hip): counterpart of
-// the reference's criterions/ctc.py:126-135, asg.py:225-234, transducer.py:216-232.  The kernels store the collapsed
-// result straight into pinned host memory -- ONE buffer per device, grown on demand, held under its lock from the
-// launch until the result has been copied out of it --, the host waits on one event and copies the labels that
-// survived into a fresh CPU tensor: no hipMemcpyAsync, nothing of size B T crosses the link, and what is returned
-// never aliases the buffer.
+// Landing results on the host.  The kernels behind viterbi(), beam_search() and errors() store
+// what the host needs straight into pinned host memory; the host waits on one event and copies it out: no
+// hipMemcpyAsync, nothing of size B T crosses the link.  THE INVARIANT: a landing buffer is held under its lock from
+// the launch until the result has been copied out of it, and what is returned never aliases it.  land() is the one
+// place that keeps it.
 // ------------------------------------------------------------------------------------------------------------
-struct DecodeBuffer {
+struct Landing {
   std::mutex mu;
-  at::Tensor pinned;  // [offsets: (B + 1) int64, padded to 16 bytes | labels: capacity int32]
+  at::Tensor pinned;  // uint8, a power of two bytes; laid out by the caller of land()
   hipEvent_t done = nullptr;
 };
+// Two per device, so that a count does not wait behind another thread's decode:
+//   kLandHypotheses: offsets, scores and labels of the greedy decode and of the beam search; kLandCounts: the [B][4] counts
+enum LandingKind { kLandHypotheses, kLandCounts };
+Landing& landing(int dev, LandingKind kind) {
+  static std::mutex mu;
+  static auto* all = new std::map<std::pair<int, int>, Landing>();  // (never destroyed: see g_targets)
+  std::lock_guard<std::mutex> lock(mu);
+  return (*all)[{dev, (int)kind}];
+}
 struct DeviceScope {  // the input's device current for the launches (viterbi() may be called with another one current)
   int prev = -1;
   explicit DeviceScope(int dev) {
@@ -847,473 +855,387 @@ struct DeviceScope {  // the input's device current for the launches (viterbi() 
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
-DecodeBuffer& decode_buffer(int dev) {
-  static std::mutex mu;
-  static auto* buffers = new std::map<int, DecodeBuffer>();  // (never destroyed: see g_targets)
-  std::lock_guard<std::mutex> lock(mu);
-  return (*buffers)[dev];
-}
 
-// launch(ws, out, capacity, out_offsets, stream) issues the decode; returns the B label sequences as views of one
-// CPU tensor of int32 or (as_int64) int64
-template <class Launch>
-std::vector<at::Tensor> decode_collect(const at::Tensor& on, int B, int T, int R, bool as_int64, const Launch& launch) {
-  const auto cpu = at::TensorOptions().dtype(as_int64 ? at::kLong : at::kInt);
-  if (B == 0) return {};
-  const int dev = on.device().index();
-  int64_t capacity = 0, ws_bytes = 0;
-  check(wfl_decode_workspace(B, T, R, &capacity, &ws_bytes), "decode");
-  const int64_t off_bytes = ((int64_t)(B + 1) * 8 + 15) & ~(int64_t)15, need = off_bytes + capacity * 4;
-  at::Tensor ws = at::empty({ws_bytes}, on.options().dtype(at::kByte));
+// launch(base, stream) issues kernels that store `need` bytes at base; read(base) copies them out once they are there.
+// Without the GIL; `what` prefixes the error of a launch that failed on the device.
+template <class Launch, class Read>
+void land(int dev, LandingKind kind, int64_t need, const char* what, const Launch& launch, const Read& read) {
   hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
-  DecodeBuffer& buf = decode_buffer(dev);
-  at::Tensor flat;
-  std::vector<int64_t> lens((size_t)B);
-  {
-    py::gil_scoped_release nogil;
-    std::lock_guard<std::mutex> lock(buf.mu);
-    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
-      int64_t cap = 1 << 16;
-      while (cap < need) cap <<= 1;
-      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
-    }
-    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
-    uint8_t* base = buf.pinned.data_ptr<uint8_t>();
-    const int64_t* offsets = reinterpret_cast<const int64_t*>(base);
-    const int32_t* labels = reinterpret_cast<const int32_t*>(base + off_bytes);
-    launch(ws.data_ptr(), reinterpret_cast<int32_t*>(base + off_bytes), capacity, reinterpret_cast<int64_t*>(base), (void*)stream);
-    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess, "decode: ",
-                hipGetErrorString(hipGetLastError()));
-    const int64_t total = offsets[B];
-    TORCH_CHECK(offsets[0] == 0 && total >= 0 && total <= capacity, "decode: the kernels left inconsistent offsets");
-    flat = at::empty({total}, cpu);
-    if (as_int64) {
-      int64_t* dst = flat.data_ptr<int64_t>();
-      for (int64_t i = 0; i < total; ++i) dst[i] = labels[i];
-    } else if (total) {
-      memcpy(flat.data_ptr<int32_t>(), labels, (size_t)total * sizeof(int32_t));
-    }
-    for (int b = 0; b < B; ++b) lens[(size_t)b] = offsets[b + 1] - offsets[b];
+  Landing& buf = landing(dev, kind);
+  py::gil_scoped_release nogil;
+  std::lock_guard<std::mutex> lock(buf.mu);
+  if (!buf.pinned.defined() || buf.pinned.numel() < need) {
+    int64_t cap = kind == kLandCounts ? 1 << 14 : 1 << 16;
+    while (cap < need) cap <<= 1;
+    buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
   }
-  return flat.split_with_sizes(lens);
+  if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
+  uint8_t* base = buf.pinned.data_ptr<uint8_t>();
+  launch(base, (void*)stream);
+  TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess, what, ": ",
+              hipGetErrorString(hipGetLastError()));
+  read(base);
 }
 
-// What a decode op checks once and then issues -- launch(ws, out, capacity, out_offsets, stream) --, shared by the op
-// that collects the labels on the host and the one that counts errors behind the same launch.
-struct DecodeCall {
+// ------------------------------------------------------------------------------------------------------------
+// A source of hypotheses: the greedy decode behind viterbi() (wfl_decode_emissions / wfl_decode_paths,
+// csrc/decode_kernels.hip: counterpart of the reference's criterions/ctc.py:126-135, asg.py:225-234,
+// transducer.py:216-232) or the CTC prefix beam search (wfl_ctc_beam_search, csrc/beam_kernels.hip: the decode the
+// reference does not have).  What an op checks once and then issues, shared by the op that collects the labels on the
+// host and the one that counts errors behind the same launch.
+// ------------------------------------------------------------------------------------------------------------
+struct Hypotheses {
   at::Tensor on;  // the input: its device is the launches'
-  int B = 0, T = 0, R = 0;
-  std::function<void(void*, int32_t*, int64_t, int64_t*, void*)> launch;
+  int B = 0;
+  int64_t rows = 0;     // label sequences the launch writes: B, B nbest of a beam search
+  bool scored = false;  // a beam search: a float64 score per row as well (the greedy decode is handed no scores)
+  const char* what = "";
+  std::function<void(int64_t* capacity, int64_t* ws_bytes)> workspace;  // of this shape
+  std::function<void(void* ws, int32_t* out, int64_t capacity, int64_t* offsets, double* scores, void* stream)> launch;
 };
 
-// lengths: int32 [B] on x's device (wfl_decode_emissions_lengths: a padded batch), or none: every frame is decoded
-DecodeCall emissions_call(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
-                          int64_t flags, const c10::optional<at::Tensor>& lengths = c10::nullopt) {
+// lengths: int32 [B] on x's device (a padded batch), or none
+at::Tensor checked_lengths(const c10::optional<at::Tensor>& lengths, const at::Tensor& x, const char* what) {
+  if (!lengths.has_value() || !lengths->defined()) return at::Tensor();
+  TORCH_CHECK(lengths->device() == x.device() && lengths->scalar_type() == at::kInt && lengths->is_contiguous() &&
+                  lengths->dim() == 1 && lengths->numel() == x.size(0),
+              what, ": lengths must be a contiguous int32 [B] tensor on x's device");
+  return *lengths;
+}
+
+// lengths given: wfl_decode_emissions_lengths, frames t >= lengths[b] are not decoded; none: every frame is
+Hypotheses emissions_source(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
+                            int64_t flags, const c10::optional<at::Tensor>& lengths) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "decode_emissions: x must be a contiguous float32 [B,T,C] device tensor");
-  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
+  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2), R = (int)num_replabels;
   at::Tensor bt;
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->device() == x.device() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == C,
                 "decode_emissions: bias must be a contiguous float32 [C] tensor on x's device");
     bt = *bias;
   }
-  at::Tensor lt;
-  if (lengths.has_value() && lengths->defined()) {
-    TORCH_CHECK(lengths->device() == x.device() && lengths->scalar_type() == at::kInt && lengths->is_contiguous() &&
-                    lengths->dim() == 1 && lengths->numel() == B,
-                "decode_emissions: lengths must be a contiguous int32 [B] tensor on x's device");
-    lt = *lengths;
-  }
-  return {x, B, T, (int)num_replabels, [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
+  const at::Tensor lt = checked_lengths(lengths, x, "decode_emissions");
+  return {x, B, B, false, "decode",
+          [=](int64_t* capacity, int64_t* ws_bytes) { check(wfl_decode_workspace(B, T, R, capacity, ws_bytes), "decode"); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double*, void* s) {
             const float* bp = bt.defined() ? bt.data_ptr<float>() : nullptr;
             if (lt.defined())
-              check(wfl_decode_emissions_lengths(x.data_ptr<float>(), bp, lt.data_ptr<int32_t>(), B, T, C, (int)drop,
-                                                 (int)num_replabels, (int)flags, ws, out, cap, offs, s),
+              check(wfl_decode_emissions_lengths(x.data_ptr<float>(), bp, lt.data_ptr<int32_t>(), B, T, C, (int)drop, R,
+                                                 (int)flags, ws, out, cap, offs, s),
                     "decode_emissions_lengths");
             else
-              check(wfl_decode_emissions(x.data_ptr<float>(), bp, B, T, C, (int)drop, (int)num_replabels, (int)flags, ws, out,
-                                         cap, offs, s),
+              check(wfl_decode_emissions(x.data_ptr<float>(), bp, B, T, C, (int)drop, R, (int)flags, ws, out, cap, offs, s),
                     "decode_emissions");
           }};
 }
 
-DecodeCall paths_call(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags) {
+Hypotheses paths_source(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags) {
   TORCH_CHECK(paths.is_cuda() && paths.scalar_type() == at::kInt && paths.dim() == 2 && (paths.size(1) == 0 || paths.stride(1) == 1) &&
                   paths.size(1) >= T,
               "decode_paths: paths must be an int32 [B, >= T] device tensor with unit stride along the frames");
-  const int B = (int)paths.size(0);
+  const int B = (int)paths.size(0), R = (int)num_replabels;
   const int64_t stride = B > 1 ? paths.stride(0) : paths.size(1);
-  return {paths, B, (int)T, (int)num_replabels, [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, void* s) {
-            check(wfl_decode_paths(paths.data_ptr<int32_t>(), stride, B, (int)T, (int)drop, (int)num_replabels, (int)flags, ws, out,
-                                   cap, offs, s),
+  return {paths, B, B, false, "decode",
+          [=](int64_t* capacity, int64_t* ws_bytes) { check(wfl_decode_workspace(B, (int)T, R, capacity, ws_bytes), "decode"); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double*, void* s) {
+            check(wfl_decode_paths(paths.data_ptr<int32_t>(), stride, B, (int)T, (int)drop, R, (int)flags, ws, out, cap, offs, s),
                   "decode_paths");
           }};
 }
 
-std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
-                                         int64_t num_replabels, int64_t flags, bool as_int64) {
-  const DecodeCall c = emissions_call(x, bias, drop, num_replabels, flags);
-  DeviceScope scope(x.device().index());
-  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+// An n-gram LM on the device (wfl_ngram_lm; lm.py's NGramLM.on_device builds one per device): ints = [arc_ptr (S+1) |
+// arc_label (A) | arc_next (A) | bo_next (S)] int32, weights = [arc_w (A) | bo_w (S)] float64, both contiguous on one
+// GPU, from a pack that passed wfl_ngram_lm_check on the host (step_min, step_max: what that check wrote).
+struct DeviceLm {
+  at::Tensor ints, weights;  // (kept alive: lm points into them)
+  wfl_ngram_lm lm;
+  DeviceLm(const at::Tensor& ints_, const at::Tensor& weights_, int64_t S, int64_t A, int64_t start, double step_min,
+           double step_max)
+      : ints(ints_), weights(weights_) {
+    TORCH_CHECK(S >= 1 && A >= 0 && S < (1LL << 31) && A < (1LL << 31) && start >= 0 && start < S,
+                "ctc_beam_search_lm: a language model of ", S, " states, ", A, " arcs, start ", start);
+    TORCH_CHECK(ints.is_cuda() && ints.scalar_type() == at::kInt && ints.is_contiguous() && ints.dim() == 1 &&
+                    ints.numel() == 2 * S + 1 + 2 * A,
+                "ctc_beam_search_lm: the LM's int32 arrays must be one contiguous [2 S + 1 + 2 A] tensor on a GPU");
+    TORCH_CHECK(weights.device() == ints.device() && weights.scalar_type() == at::kDouble && weights.is_contiguous() &&
+                    weights.dim() == 1 && weights.numel() == A + S,
+                "ctc_beam_search_lm: the LM's float64 weights must be one contiguous [A + S] tensor on the device of its "
+                "int32 arrays");
+    const int32_t* ip = ints.data_ptr<int32_t>();
+    const double* wp = weights.data_ptr<double>();
+    lm.num_states = (int32_t)S, lm.num_arcs = (int32_t)A, lm.start = (int32_t)start, lm.reserved = 0;
+    lm.arc_ptr = ip, lm.arc_label = ip + S + 1, lm.arc_next = ip + S + 1 + A, lm.bo_next = ip + S + 1 + 2 * A;
+    lm.arc_w = wp, lm.bo_w = wp + A, lm.step_min = step_min, lm.step_max = step_max;
+  }
+};
+
+// lm none: wfl_ctc_beam_search, the call it was (lm_weight, length_bonus and score_eos are not read);
+// given: wfl_ctc_beam_search_lm
+Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
+                       int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
+                       double length_bonus, bool score_eos) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
+              "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
+  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
+  const at::Tensor lt = checked_lengths(lengths, x, "ctc_beam_search");
+  TORCH_CHECK(!lm || lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
+  return {x, B, (int64_t)B * nbest, true, "ctc_beam_search",
+          [=](int64_t* capacity, int64_t* ws_bytes) {
+            check(wfl_ctc_beam_workspace(B, T, C, (int)beam, (int)K, (int)nbest, capacity, ws_bytes), "ctc_beam_search");
+          },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
+            if (lm)
+              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
+                                           normalize ? 1 : 0, &lm->lm, lm_weight, length_bonus, score_eos ? 1 : 0, ws, out, cap,
+                                           offs, scores, s),
+                    "ctc_beam_search_lm");
+            else
+              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
+                                        normalize ? 1 : 0, ws, out, cap, offs, scores, s),
+                    "ctc_beam_search");
+          }};
 }
 
-std::vector<at::Tensor> decode_emissions_lengths(const at::Tensor& x, const c10::optional<at::Tensor>& bias,
-                                                 const at::Tensor& lengths, int64_t drop, int64_t num_replabels, int64_t flags,
-                                                 bool as_int64) {
-  const DecodeCall c = emissions_call(x, bias, drop, num_replabels, flags, lengths);
-  DeviceScope scope(x.device().index());
-  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+// The launch of `h` into the device's landing buffer -- [offsets: (rows + 1) int64 | scores: rows float64, a scored
+// source | labels: capacity int32], each part padded to 16 bytes -- and from there into fresh CPU tensors: only the
+// labels that survived leave the device.
+struct Collected {
+  at::Tensor labels, offsets, scores;  // [total] int32 or (as_int64) int64; int64 [rows + 1]; float64 [rows] or undefined
+};
+Collected hypotheses_collect(const Hypotheses& h, bool as_int64) {
+  const int dev = h.on.device().index();
+  DeviceScope scope(dev);
+  int64_t capacity = 0, ws_bytes = 0;
+  h.workspace(&capacity, &ws_bytes);
+  const int64_t n = h.rows, off_bytes = ((n + 1) * 8 + 15) & ~(int64_t)15, sc_bytes = h.scored ? (n * 8 + 15) & ~(int64_t)15 : 0;
+  at::Tensor ws = at::empty({ws_bytes}, h.on.options().dtype(at::kByte));
+  Collected r;
+  land(
+      dev, kLandHypotheses, off_bytes + sc_bytes + capacity * 4, h.what,
+      [&](uint8_t* base, void* stream) {
+        h.launch(ws.data_ptr(), reinterpret_cast<int32_t*>(base + off_bytes + sc_bytes), capacity, reinterpret_cast<int64_t*>(base),
+                 h.scored ? reinterpret_cast<double*>(base + off_bytes) : nullptr, stream);
+      },
+      [&](const uint8_t* base) {
+        const int64_t* offsets = reinterpret_cast<const int64_t*>(base);
+        const int32_t* labels = reinterpret_cast<const int32_t*>(base + off_bytes + sc_bytes);
+        const int64_t total = offsets[n];
+        TORCH_CHECK(offsets[0] == 0 && total >= 0 && total <= capacity, h.what, ": the kernels left inconsistent offsets");
+        r.labels = at::empty({total}, at::TensorOptions().dtype(as_int64 ? at::kLong : at::kInt));
+        if (as_int64) {
+          int64_t* dst = r.labels.data_ptr<int64_t>();
+          for (int64_t i = 0; i < total; ++i) dst[i] = labels[i];
+        } else if (total) {
+          memcpy(r.labels.data_ptr<int32_t>(), labels, (size_t)total * sizeof(int32_t));
+        }
+        r.offsets = at::empty({n + 1}, at::TensorOptions().dtype(at::kLong));
+        memcpy(r.offsets.data_ptr<int64_t>(), offsets, (size_t)(n + 1) * 8);
+        if (h.scored) {
+          r.scores = at::empty({n}, at::TensorOptions().dtype(at::kDouble));
+          memcpy(r.scores.data_ptr<double>(), base + off_bytes, (size_t)n * 8);
+        }
+      });
+  return r;
+}
+
+// the B label sequences of a greedy decode as views of one CPU tensor
+std::vector<at::Tensor> decode_rows(const Hypotheses& h, bool as_int64) {
+  if (h.B == 0) return {};
+  const Collected r = hypotheses_collect(h, as_int64);
+  const int64_t* offsets = r.offsets.data_ptr<int64_t>();
+  std::vector<int64_t> lens((size_t)h.B);
+  for (int b = 0; b < h.B; ++b) lens[(size_t)b] = offsets[b + 1] - offsets[b];
+  return r.labels.split_with_sizes(lens);
+}
+
+std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop,
+                                         int64_t num_replabels, int64_t flags, bool as_int64,
+                                         const c10::optional<at::Tensor>& lengths) {
+  return decode_rows(emissions_source(x, bias, drop, num_replabels, flags, lengths), as_int64);
 }
 
 std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
                                      bool as_int64) {
-  const DecodeCall c = paths_call(paths, T, drop, num_replabels, flags);
-  DeviceScope scope(paths.device().index());
-  return decode_collect(c.on, c.B, c.T, c.R, as_int64, c.launch);
+  return decode_rows(paths_source(paths, T, drop, num_replabels, flags), as_int64);
+}
+
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
+                          int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
+                          double length_bonus, bool score_eos) {
+  const Collected r = hypotheses_collect(
+      beam_source(x, lengths, blank, beam, K, nbest, normalize, lm, lm_weight, length_bonus, score_eos), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), nbest}));
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Token and word error counts behind the decode (wfl_errors_count, csrc/error_kernels.hip): counterpart of the
-// reference's compute_edit_distance (train.py:74-87).  Hypotheses and references stay on the device; the B x 4
-// counts land in a small pinned buffer per device behind one event, the way decode_collect lands its labels.
+// Token and word error counts behind the hypotheses (wfl_errors_count, csrc/error_kernels.hip): counterpart of the
+// reference's compute_edit_distance (train.py:74-87).  Hypotheses and references stay on the device; the B x 4 counts
+// land in the device's second landing buffer.
 // ------------------------------------------------------------------------------------------------------------
-struct ErrorTable {  // a side's expansion table on the device: int32 [exp_ptr: V + 1 | exp_sym], or none (identity)
-  const int32_t* ptr = nullptr;
-  const int32_t* sym = nullptr;
+struct ErrorSide {  // a side's expansion table: int32 [exp_ptr: V + 1 | exp_sym], or undefined (a label is its own symbol)
+  at::Tensor table;
   int V = 0, longest = 1;
+  const int32_t* ptr() const { return table.defined() ? table.data_ptr<int32_t>() : nullptr; }
+  const int32_t* sym() const { return table.defined() ? table.data_ptr<int32_t>() + V + 1 : nullptr; }
 };
-ErrorTable error_table(const c10::optional<at::Tensor>& t, int64_t V, int64_t longest, int dev, const char* what) {
-  ErrorTable e;
-  if (!t.has_value() || !t->defined()) return e;
-  TORCH_CHECK(t->is_cuda() && t->device().index() == dev && t->scalar_type() == at::kInt && t->is_contiguous() && V >= 1 &&
-                  t->numel() > V && longest >= 0 && longest <= INT32_MAX,
-              "errors: the ", what, " table must be a contiguous int32 [V + 1 + symbols] tensor on the batch's device");
-  e.ptr = t->data_ptr<int32_t>(), e.sym = e.ptr + V + 1, e.V = (int)V, e.longest = (int)longest;
-  return e;
-}
+using ErrorSideSpec = c10::optional<std::tuple<at::Tensor, int64_t, int64_t>>;  // (table, V, longest expansion), or none
 
-struct ErrorBuffer {
-  std::mutex mu;
-  at::Tensor pinned;  // [B][4] int32
-  hipEvent_t done = nullptr;
+// Both tables and the separator of a metrics.ErrorCounter, uploaded (ErrorCounter.tables builds one per device)
+struct ErrorTables {
+  ErrorSide hyp, ref;
+  int sep = -1;
+  ErrorTables(const ErrorSideSpec& h, const ErrorSideSpec& r, int64_t sep_)
+      : hyp(side(h, "hypothesis")), ref(side(r, "reference")), sep(sep_ < 0 ? -1 : (int)sep_) {}
+
+  static ErrorSide side(const ErrorSideSpec& spec, const char* what) {
+    ErrorSide e;
+    if (!spec.has_value()) return e;
+    const at::Tensor& t = std::get<0>(*spec);
+    const int64_t V = std::get<1>(*spec), longest = std::get<2>(*spec);
+    TORCH_CHECK(t.defined() && t.scalar_type() == at::kInt && t.is_contiguous() && V >= 1 && V < INT32_MAX && t.numel() > V &&
+                    longest >= 0 && longest <= INT32_MAX,
+                "errors: the ", what, " table must be a contiguous int32 [V + 1 + symbols] tensor");
+    e.table = t, e.V = (int)V, e.longest = (int)longest;
+    return e;
+  }
+  // per call: the launches read the tables on device `dev`
+  void check_device(int dev) const {
+    for (const ErrorSide* e : {&hyp, &ref})
+      TORCH_CHECK(!e->table.defined() || (e->table.is_cuda() && e->table.device().index() == dev),
+                  "errors: the ", e == &hyp ? "hypothesis" : "reference", " table must be on the batch's device");
+  }
+  // ValueError for a staged label a table has no entry for (h: null for hypotheses a decode wrote).  Needs no device:
+  // metrics.ErrorCounter calls it on a machine without a GPU, ahead of reporting that.
+  void check_labels(const StagedTargets* h, const StagedTargets* r) const {
+    if (h && hyp.table.defined() && h->n > 0 && (h->label_min < 0 || h->label_max >= hyp.V))
+      throw py::value_error("errors: predicted label " + std::to_string(h->label_min < 0 ? h->label_min : h->label_max) +
+                            " is outside the hypothesis table [0, " + std::to_string(hyp.V) + ")");
+    if (r && ref.table.defined() && r->n > 0 && (r->label_min < 0 || r->label_max >= ref.V))
+      throw py::value_error("errors: target label " + std::to_string(r->label_min < 0 ? r->label_min : r->label_max) +
+                            " is outside the reference table [0, " + std::to_string(ref.V) + ")");
+  }
 };
-ErrorBuffer& error_buffer(int dev) {
-  static std::mutex mu;
-  static auto* buffers = new std::map<int, ErrorBuffer>();  // (never destroyed: see g_targets)
-  std::lock_guard<std::mutex> lock(mu);
-  return (*buffers)[dev];
-}
 
-// the count behind hypotheses that are on device `dev` already; -> int64 CPU tensor [B, 4]
+// the count behind B hypotheses that are on device `dev` already (staged_hyp: where they were staged on the host, or
+// null), every check before the launch; -> int64 CPU tensor [B, 4]
 at::Tensor errors_collect(int dev, int B, const int32_t* hyp, const int64_t* hyp_off, int64_t hyp_capacity,
-                          const std::shared_ptr<StagedTargets>& ref, const ErrorTable& ht, const ErrorTable& rt, int64_t sep) {
+                          const StagedTargets* staged_hyp, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& t) {
   TORCH_CHECK(ref && ref->dev_buf.is_cuda() && ref->dev_buf.device().index() == dev,
               "errors: the targets must be staged on the device of the hypotheses");
   if (ref->B != B) throw py::value_error("errors: " + std::to_string(B) + " predictions for " + std::to_string(ref->B) + " targets");
-  if (rt.ptr && ref->n > 0 && (ref->label_min < 0 || ref->label_max >= rt.V))
-    throw py::value_error("errors: target label " + std::to_string(ref->label_min < 0 ? ref->label_min : ref->label_max) +
-                          " is outside the reference table [0, " + std::to_string(rt.V) + ")");
+  t.check_labels(staged_hyp, ref.get());
+  t.check_device(dev);
   int64_t ws_bytes = 0;
-  check(wfl_errors_workspace(B, hyp_capacity, ref->n, ht.longest, rt.longest, &ws_bytes), "errors");
+  check(wfl_errors_workspace(B, hyp_capacity, ref->n, t.hyp.longest, t.ref.longest, &ws_bytes), "errors");
   at::Tensor ws = at::empty({ws_bytes}, at::TensorOptions().dtype(at::kByte).device(at::Device(at::kCUDA, (c10::DeviceIndex)dev)));
-  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
   ref->wait_upload();
   const char* rbase = static_cast<const char*>(ref->dev_buf.data_ptr());
   at::Tensor counts = at::empty({B, 4}, at::TensorOptions().dtype(at::kLong));
-  ErrorBuffer& buf = error_buffer(dev);
-  {
-    py::gil_scoped_release nogil;
-    std::lock_guard<std::mutex> lock(buf.mu);
-    const int64_t need = (int64_t)B * 4;
-    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
-      int64_t cap = 1 << 12;
-      while (cap < need) cap <<= 1;
-      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kInt).pinned_memory(true));
-    }
-    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
-    int32_t* landed = buf.pinned.data_ptr<int32_t>();
-    check(wfl_errors_count(hyp, hyp_off, reinterpret_cast<const int32_t*>(rbase + ref->off_flat),
-                           reinterpret_cast<const int64_t*>(rbase), B, ht.ptr, ht.sym, ht.V, rt.ptr, rt.sym, rt.V,
-                           sep < 0 ? -1 : (int)sep, hyp_capacity, ref->n, ws.data_ptr(), landed, (void*)stream),
-          "errors_count");
-    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess, "errors: ",
-                hipGetErrorString(hipGetLastError()));
-    int64_t* dst = counts.data_ptr<int64_t>();
-    for (int64_t i = 0; i < need; ++i) dst[i] = landed[i];
-  }
+  land(
+      dev, kLandCounts, (int64_t)B * 4 * sizeof(int32_t), "errors",
+      [&](uint8_t* base, void* stream) {
+        check(wfl_errors_count(hyp, hyp_off, reinterpret_cast<const int32_t*>(rbase + ref->off_flat),
+                               reinterpret_cast<const int64_t*>(rbase), B, t.hyp.ptr(), t.hyp.sym(), t.hyp.V, t.ref.ptr(),
+                               t.ref.sym(), t.ref.V, t.sep, hyp_capacity, ref->n, ws.data_ptr(), reinterpret_cast<int32_t*>(base),
+                               stream),
+              "errors_count");
+      },
+      [&](const uint8_t* base) {
+        const int32_t* landed = reinterpret_cast<const int32_t*>(base);
+        int64_t* dst = counts.data_ptr<int64_t>();
+        for (int64_t i = 0; i < (int64_t)B * 4; ++i) dst[i] = landed[i];
+      });
   return counts;
 }
 
 // hypotheses that are on the host: staged like targets (the one stager), then counted on the device
 at::Tensor errors_count(const std::shared_ptr<StagedTargets>& hyp, const std::shared_ptr<StagedTargets>& ref,
-                        const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                        const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
+                        const ErrorTables& tables) {
   TORCH_CHECK(hyp && hyp->dev_buf.is_cuda(), "errors_count: the predictions must be staged on a GPU");
   const int dev = hyp->dev_buf.device().index();
   if (hyp->B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
-  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
-  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
-  if (ht.ptr && hyp->n > 0 && (hyp->label_min < 0 || hyp->label_max >= ht.V))
-    throw py::value_error("errors: predicted label " + std::to_string(hyp->label_min < 0 ? hyp->label_min : hyp->label_max) +
-                          " is outside the hypothesis table [0, " + std::to_string(ht.V) + ")");
   DeviceScope scope(dev);
   hyp->wait_upload();
   const char* hbase = static_cast<const char*>(hyp->dev_buf.data_ptr());
   return errors_collect(dev, (int)hyp->B, reinterpret_cast<const int32_t*>(hbase + hyp->off_flat),
-                        reinterpret_cast<const int64_t*>(hbase), hyp->n, ref, ht, rt, sep);
+                        reinterpret_cast<const int64_t*>(hbase), hyp->n, hyp.get(), ref, tables);
 }
 
-// the decode's launch into device buffers, the count behind it: the predictions never reach the host
-at::Tensor decode_errors(const DecodeCall& c, const std::shared_ptr<StagedTargets>& ref,
-                         const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                         const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  const int dev = c.on.device().index();
-  if (c.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
-  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
-  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
-  TORCH_CHECK(c.B > 0, "errors: an empty batch of emissions for ", ref ? ref->B : 0, " targets");
+// a source's launch into device buffers (one hypothesis per utterance), the count behind it: the predictions never
+// reach the host
+at::Tensor hypotheses_errors(const Hypotheses& h, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  const int dev = h.on.device().index();
+  if (h.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
+  TORCH_CHECK(h.B > 0 && h.rows == h.B, "errors: an empty batch of emissions for ", ref ? ref->B : 0, " targets");
   DeviceScope scope(dev);
   int64_t capacity = 0, ws_bytes = 0;
-  check(wfl_decode_workspace(c.B, c.T, c.R, &capacity, &ws_bytes), "decode");
-  const auto bytes = c.on.options().dtype(at::kByte);
+  h.workspace(&capacity, &ws_bytes);
+  const auto bytes = h.on.options().dtype(at::kByte);
   at::Tensor ws = at::empty({ws_bytes}, bytes);
   at::Tensor out = at::empty({capacity}, bytes.dtype(at::kInt));
-  at::Tensor offs = at::empty({c.B + 1}, bytes.dtype(at::kLong));
+  at::Tensor offs = at::empty({h.rows + 1}, bytes.dtype(at::kLong));
+  at::Tensor scores = h.scored ? at::empty({h.rows}, bytes.dtype(at::kDouble)) : at::Tensor();
   hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
-  c.launch(ws.data_ptr(), out.data_ptr<int32_t>(), capacity, offs.data_ptr<int64_t>(), (void*)stream);
-  return errors_collect(dev, c.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, ref, ht, rt, sep);
+  h.launch(ws.data_ptr(), out.data_ptr<int32_t>(), capacity, offs.data_ptr<int64_t>(),
+           h.scored ? scores.data_ptr<double>() : nullptr, (void*)stream);
+  return errors_collect(dev, h.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, nullptr, ref, tables);
 }
 
 at::Tensor decode_emissions_errors(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
-                                   int64_t flags, const std::shared_ptr<StagedTargets>& ref,
-                                   const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                                   const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  return decode_errors(emissions_call(x, bias, drop, num_replabels, flags), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
-                       ref_longest, sep);
-}
-
-at::Tensor decode_emissions_lengths_errors(const at::Tensor& x, const c10::optional<at::Tensor>& bias, const at::Tensor& lengths,
-                                           int64_t drop, int64_t num_replabels, int64_t flags,
-                                           const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
-                                           int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table,
-                                           int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  return decode_errors(emissions_call(x, bias, drop, num_replabels, flags, lengths), ref, hyp_table, hyp_V, hyp_longest,
-                       ref_table, ref_V, ref_longest, sep);
+                                   int64_t flags, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables,
+                                   const c10::optional<at::Tensor>& lengths) {
+  return hypotheses_errors(emissions_source(x, bias, drop, num_replabels, flags, lengths), ref, tables);
 }
 
 at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
-                               const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
-                               int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table, int64_t ref_V,
-                               int64_t ref_longest, int64_t sep) {
-  return decode_errors(paths_call(paths, T, drop, num_replabels, flags), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
-                       ref_longest, sep);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// CTC prefix beam search (wfl_ctc_beam_search, csrc/beam_kernels.hip) behind CTC.beam_search() and CTC.errors(beam_size=):
-// the decode the reference does not have.  Collected like the greedy decode: offsets, scores and the surviving labels
-// land in the device's pinned decode buffer behind one event.
-// ------------------------------------------------------------------------------------------------------------
-// An n-gram LM on the device (wfl_ngram_lm; lm.py's NGramLM.on_device): ints = [arc_ptr (S+1) | arc_label (A) | arc_next (A)
-// | bo_next (S)] int32, weights = [arc_w (A) | bo_w (S)] float64, both contiguous on x's device, from a pack that passed
-// wfl_ngram_lm_check on the host.
-struct BeamLmCall {
-  at::Tensor ints, weights;
-  wfl_ngram_lm lm;
-  double weight = 1.0, bonus = 0.0;
-  int score_eos = 1;
-};
-
-struct BeamCall {
-  at::Tensor x, lengths;
-  int B = 0, T = 0, C = 0, blank = 0, beam = 0, K = 0, nbest = 0;
-  std::shared_ptr<BeamLmCall> lm;  // (none: wfl_ctc_beam_search, the call it was)
-  void launch(int normalize, void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) const {
-    if (lm) {
-      check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lengths.defined() ? lengths.data_ptr<int32_t>() : nullptr, B, T, C,
-                                   blank, beam, K, nbest, normalize, &lm->lm, lm->weight, lm->bonus, lm->score_eos, ws, out,
-                                   cap, offs, scores, s),
-            "ctc_beam_search_lm");
-      return;
-    }
-    check(wfl_ctc_beam_search(x.data_ptr<float>(), lengths.defined() ? lengths.data_ptr<int32_t>() : nullptr, B, T, C, blank,
-                              beam, K, nbest, normalize, ws, out, cap, offs, scores, s),
-          "ctc_beam_search");
-  }
-};
-
-BeamCall beam_call(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
-                   int64_t nbest) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
-              "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
-  BeamCall c;
-  c.x = x;
-  c.B = (int)x.size(0), c.T = (int)x.size(1), c.C = (int)x.size(2);
-  c.blank = (int)blank, c.beam = (int)beam, c.K = (int)K, c.nbest = (int)nbest;
-  if (lengths.has_value() && lengths->defined()) {
-    TORCH_CHECK(lengths->device() == x.device() && lengths->scalar_type() == at::kInt && lengths->is_contiguous() &&
-                    lengths->dim() == 1 && lengths->numel() == c.B,
-                "ctc_beam_search: lengths must be a contiguous int32 [B] tensor on x's device");
-    c.lengths = *lengths;
-  }
-  return c;
-}
-
-std::shared_ptr<BeamLmCall> beam_lm_call(const at::Tensor& x, const at::Tensor& ints, const at::Tensor& weights,
-                                         int64_t num_states, int64_t num_arcs, int64_t start, double step_min,
-                                         double step_max, double lm_weight, double length_bonus, bool score_eos) {
-  const int64_t S = num_states, A = num_arcs;
-  TORCH_CHECK(S >= 1 && A >= 0 && S < (1LL << 31) && A < (1LL << 31) && start >= 0 && start < S,
-              "ctc_beam_search_lm: a language model of ", S, " states, ", A, " arcs, start ", start);
-  TORCH_CHECK(ints.device() == x.device() && ints.scalar_type() == at::kInt && ints.is_contiguous() && ints.dim() == 1 &&
-                  ints.numel() == 2 * S + 1 + 2 * A,
-              "ctc_beam_search_lm: the LM's int32 arrays must be one contiguous [2 S + 1 + 2 A] tensor on x's device");
-  TORCH_CHECK(weights.device() == x.device() && weights.scalar_type() == at::kDouble && weights.is_contiguous() &&
-                  weights.dim() == 1 && weights.numel() == A + S,
-              "ctc_beam_search_lm: the LM's float64 weights must be one contiguous [A + S] tensor on x's device");
-  auto c = std::make_shared<BeamLmCall>();
-  c->ints = ints, c->weights = weights;
-  const int32_t* ip = ints.data_ptr<int32_t>();
-  const double* wp = weights.data_ptr<double>();
-  c->lm.num_states = (int32_t)S, c->lm.num_arcs = (int32_t)A, c->lm.start = (int32_t)start, c->lm.reserved = 0;
-  c->lm.arc_ptr = ip, c->lm.arc_label = ip + S + 1, c->lm.arc_next = ip + S + 1 + A, c->lm.bo_next = ip + S + 1 + 2 * A;
-  c->lm.arc_w = wp, c->lm.bo_w = wp + A, c->lm.step_min = step_min, c->lm.step_max = step_max;
-  c->weight = lm_weight, c->bonus = length_bonus, c->score_eos = score_eos ? 1 : 0;
-  return c;
-}
-
-py::tuple beam_search_collect(const BeamCall& c, bool normalize);
-
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
-py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
-                          int64_t nbest, bool normalize) {
-  return beam_search_collect(beam_call(x, lengths, blank, beam, K, nbest), normalize);
-}
-
-// the same with an n-gram LM and a length bonus in the beam launch (wfl_ctc_beam_search_lm)
-py::tuple ctc_beam_search_lm(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
-                             int64_t K, int64_t nbest, bool normalize, const at::Tensor& lm_ints, const at::Tensor& lm_weights,
-                             int64_t num_states, int64_t num_arcs, int64_t start, double step_min, double step_max,
-                             double lm_weight, double length_bonus, bool score_eos) {
-  BeamCall c = beam_call(x, lengths, blank, beam, K, nbest);
-  c.lm = beam_lm_call(x, lm_ints, lm_weights, num_states, num_arcs, start, step_min, step_max, lm_weight, length_bonus,
-                      score_eos);
-  return beam_search_collect(c, normalize);
-}
-
-py::tuple beam_search_collect(const BeamCall& c, bool normalize) {
-  const at::Tensor& x = c.x;
-  const int dev = x.device().index();
-  DeviceScope scope(dev);
-  int64_t capacity = 0, ws_bytes = 0;
-  check(wfl_ctc_beam_workspace(c.B, c.T, c.C, c.beam, c.K, c.nbest, &capacity, &ws_bytes), "ctc_beam_search");
-  const int64_t n = (int64_t)c.B * c.nbest;
-  const int64_t off_bytes = ((n + 1) * 8 + 15) & ~(int64_t)15, sc_bytes = (n * 8 + 15) & ~(int64_t)15;
-  const int64_t need = off_bytes + sc_bytes + capacity * 4;
-  at::Tensor ws = at::empty({ws_bytes}, x.options().dtype(at::kByte));
-  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
-  DecodeBuffer& buf = decode_buffer(dev);
-  at::Tensor flat, offs = at::empty({n + 1}, at::TensorOptions().dtype(at::kLong)),
-                   scores = at::empty({(int64_t)c.B, (int64_t)c.nbest}, at::TensorOptions().dtype(at::kDouble));
-  {
-    py::gil_scoped_release nogil;
-    std::lock_guard<std::mutex> lock(buf.mu);
-    if (!buf.pinned.defined() || buf.pinned.numel() < need) {
-      int64_t cap = 1 << 16;
-      while (cap < need) cap <<= 1;
-      buf.pinned = at::empty({cap}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
-    }
-    if (!buf.done) TORCH_CHECK(hipEventCreateWithFlags(&buf.done, hipEventDisableTiming) == hipSuccess, "hipEventCreate");
-    uint8_t* base = buf.pinned.data_ptr<uint8_t>();
-    const int64_t* offsets = reinterpret_cast<const int64_t*>(base);
-    const double* landed = reinterpret_cast<const double*>(base + off_bytes);
-    const int32_t* labels = reinterpret_cast<const int32_t*>(base + off_bytes + sc_bytes);
-    c.launch(normalize ? 1 : 0, ws.data_ptr(), reinterpret_cast<int32_t*>(base + off_bytes + sc_bytes), capacity,
-             reinterpret_cast<int64_t*>(base), reinterpret_cast<double*>(base + off_bytes), (void*)stream);
-    TORCH_CHECK(hipEventRecord(buf.done, stream) == hipSuccess && hipEventSynchronize(buf.done) == hipSuccess,
-                "ctc_beam_search: ", hipGetErrorString(hipGetLastError()));
-    const int64_t total = offsets[n];
-    TORCH_CHECK(offsets[0] == 0 && total >= 0 && total <= capacity, "ctc_beam_search: the kernels left inconsistent offsets");
-    flat = at::empty({total}, at::TensorOptions().dtype(at::kLong));
-    int64_t* dst = flat.data_ptr<int64_t>();
-    for (int64_t i = 0; i < total; ++i) dst[i] = labels[i];
-    memcpy(offs.data_ptr<int64_t>(), offsets, (size_t)(n + 1) * 8);
-    memcpy(scores.data_ptr<double>(), landed, (size_t)n * 8);
-  }
-  return py::make_tuple(flat, offs, scores);
-}
-
-// the best hypothesis of every utterance into device buffers, the count behind it: the predictions never reach the host
-at::Tensor beam_search_errors(const BeamCall& c, const std::shared_ptr<StagedTargets>& ref,
-                              const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                              const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  const at::Tensor& x = c.x;
-  const int dev = x.device().index();
-  if (c.B == 0 && ref && ref->B == 0) return at::empty({0, 4}, at::TensorOptions().dtype(at::kLong));
-  const ErrorTable ht = error_table(hyp_table, hyp_V, hyp_longest, dev, "hypothesis");
-  const ErrorTable rt = error_table(ref_table, ref_V, ref_longest, dev, "reference");
-  TORCH_CHECK(c.B > 0, "errors: an empty batch of emissions for ", ref ? ref->B : 0, " targets");
-  DeviceScope scope(dev);
-  int64_t capacity = 0, ws_bytes = 0;
-  check(wfl_ctc_beam_workspace(c.B, c.T, c.C, c.beam, c.K, 1, &capacity, &ws_bytes), "ctc_beam_search");
-  const auto bytes = x.options().dtype(at::kByte);
-  at::Tensor ws = at::empty({ws_bytes}, bytes);
-  at::Tensor out = at::empty({capacity}, bytes.dtype(at::kInt));
-  at::Tensor offs = at::empty({c.B + 1}, bytes.dtype(at::kLong));
-  at::Tensor scores = at::empty({c.B}, bytes.dtype(at::kDouble));
-  hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
-  c.launch(0, ws.data_ptr(), out.data_ptr<int32_t>(), capacity, offs.data_ptr<int64_t>(), scores.data_ptr<double>(), (void*)stream);
-  return errors_collect(dev, c.B, out.data_ptr<int32_t>(), offs.data_ptr<int64_t>(), capacity, ref, ht, rt, sep);
+                               const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(paths_source(paths, T, drop, num_replabels, flags), ref, tables);
 }
 
 at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
-                                  int64_t K, const std::shared_ptr<StagedTargets>& ref,
-                                  const c10::optional<at::Tensor>& hyp_table, int64_t hyp_V, int64_t hyp_longest,
-                                  const c10::optional<at::Tensor>& ref_table, int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  return beam_search_errors(beam_call(x, lengths, blank, beam, K, 1), ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V,
-                            ref_longest, sep);
-}
-
-at::Tensor ctc_beam_search_lm_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
-                                     int64_t K, const at::Tensor& lm_ints, const at::Tensor& lm_weights, int64_t num_states,
-                                     int64_t num_arcs, int64_t start, double step_min, double step_max, double lm_weight,
-                                     double length_bonus, bool score_eos,
-                                     const std::shared_ptr<StagedTargets>& ref, const c10::optional<at::Tensor>& hyp_table,
-                                     int64_t hyp_V, int64_t hyp_longest, const c10::optional<at::Tensor>& ref_table,
-                                     int64_t ref_V, int64_t ref_longest, int64_t sep) {
-  BeamCall c = beam_call(x, lengths, blank, beam, K, 1);
-  c.lm = beam_lm_call(x, lm_ints, lm_weights, num_states, num_arcs, start, step_min, step_max, lm_weight, length_bonus,
-                      score_eos);
-  return beam_search_errors(c, ref, hyp_table, hyp_V, hyp_longest, ref_table, ref_V, ref_longest, sep);
+                                  int64_t K, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables,
+                                  const std::shared_ptr<DeviceLm>& lm, double lm_weight, double length_bonus, bool score_eos) {
+  return hypotheses_errors(beam_source(x, lengths, blank, beam, K, 1, false, lm, lm_weight, length_bonus, score_eos), ref, tables);
 }
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  py::class_<DeviceLm, std::shared_ptr<DeviceLm>>(m, "DeviceLm", "an n-gram LM's pack on a GPU (lm.NGramLM.on_device)")
+      .def(py::init<const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, double, double>(), py::arg("ints"),
+           py::arg("weights"), py::arg("num_states"), py::arg("num_arcs"), py::arg("start"), py::arg("step_min"),
+           py::arg("step_max"))
+      .def_readonly("ints", &DeviceLm::ints)
+      .def_readonly("weights", &DeviceLm::weights);
+  py::class_<ErrorTables, std::shared_ptr<ErrorTables>>(m, "ErrorTables",
+                                                        "both tables of a metrics.ErrorCounter, uploaded, and its separator")
+      .def(py::init<const ErrorSideSpec&, const ErrorSideSpec&, int64_t>(), py::arg("hyp"), py::arg("ref"), py::arg("sep"),
+           "hyp, ref: (int32 [exp_ptr: V + 1 | exp_sym] tensor, V, longest expansion) or None: a label is its own symbol")
+      .def("check_labels", &ErrorTables::check_labels, py::arg("hyp"), py::arg("ref"),
+           "ValueError for a staged label (StagedTargets or None) outside its table; needs no device");
   m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
-        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
-        "CTC prefix beam search on the device: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
-  m.def("ctc_beam_search_lm", &ctc_beam_search_lm,
-        "ctc_beam_search with an n-gram LM (int32 and float64 device arrays of a checked pack), its weight, a length bonus and "
-        "whether </s> is scored");
-  m.def("ctc_beam_search_lm_errors", &ctc_beam_search_lm_errors,
-        "ctc_beam_search_lm's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
-  m.def("ctc_beam_search_errors", &ctc_beam_search_errors,
+        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"), py::arg("lm"), py::arg("lm_weight"),
+        py::arg("length_bonus"), py::arg("score_eos"),
+        "CTC prefix beam search on the device, with an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is "
+        "scored) or None: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
+  m.def("ctc_beam_search_errors", &ctc_beam_search_errors, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"), py::arg("lm"), py::arg("lm_weight"),
+        py::arg("length_bonus"), py::arg("score_eos"),
         "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
-        py::arg("flags"), py::arg("as_int64"),
-        "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors");
+        py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),
+        "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors; lengths int32 [B] "
+        "on x's device (a padded batch: frames t >= lengths[b] are not decoded) or None");
   m.def("decode_paths", &decode_paths, py::arg("paths"), py::arg("T"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), "viterbi()'s decode from [B, >= T] int32 device label paths: B CPU tensors");
   m.def("errors_count", &errors_count,
         "token and word error counts (train.py:74-87) of staged predictions against staged targets: int64 CPU [B, 4]");
-  m.def("decode_emissions_errors", &decode_emissions_errors,
+  m.def("decode_emissions_errors", &decode_emissions_errors, py::arg("x"), py::arg("bias"), py::arg("drop"),
+        py::arg("num_replabels"), py::arg("flags"), py::arg("ref"), py::arg("tables"), py::arg("lengths"),
         "decode_emissions' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
-  m.def("decode_emissions_lengths", &decode_emissions_lengths,
-        "decode_emissions for a padded batch: lengths int32 [B] on x's device, frames t >= lengths[b] are not decoded");
-  m.def("decode_emissions_lengths_errors", &decode_emissions_lengths_errors,
-        "decode_emissions_lengths' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
   m.def("decode_paths_errors", &decode_paths_errors,
         "decode_paths' launch into device memory and the error counts behind it: int64 CPU [B, 4]");
   m.def("ctc_fast_backward", &ctc_fast_backward,

@@ -930,10 +930,8 @@ def decode_emissions(x, drop, bias=None, num_replabels=0, flags=0, dtype=torch.i
     Returns B CPU tensors of `dtype` (int32 or int64), views of one tensor; only what survives the collapse leaves the
     device.  lengths (int32 [B] on x's device, input_lengths_on_device): utterance b ends at frame lengths[b]
     (wfl_decode_emissions_lengths)."""
-    drop = -1 if drop is None else int(drop)
-    if lengths is not None:
-        return N.ops.decode_emissions_lengths(x, bias, lengths, drop, num_replabels, flags, dtype == torch.int64)
-    return N.ops.decode_emissions(x, bias, drop, num_replabels, flags, dtype == torch.int64)
+    return N.ops.decode_emissions(x, bias, -1 if drop is None else int(drop), num_replabels, flags, dtype == torch.int64,
+                                  lengths)
 
 
 def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int32):
@@ -1019,11 +1017,8 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     if not 0 <= int(blank) < C:
         raise ValueError(f"ctc_beam_search: blank index {blank} is outside [0, {C})")
     lm, weight, bonus, eos = check_lm_arguments(lm, C, int(blank), lm_weight, length_bonus, lm_eos, "ctc_beam_search")
-    if lm is None:
-        flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize))
-    else:
-        flat, offsets, scores = N.ops.ctc_beam_search_lm(x, lengths, int(blank), W, K, n, bool(normalize),
-                                                         *lm.device_arguments(x.device), weight, bonus, eos)
+    flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize),
+                                                  None if lm is None else lm.on_device(x.device), weight, bonus, eos)
     rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
     return [list(rows[b * n:(b + 1) * n]) for b in range(B)], scores
 

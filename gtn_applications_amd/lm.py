@@ -104,9 +104,10 @@ class NGramLM:
         return total
 
     def on_device(self, device):
-        """(int32 [arc_ptr | arc_label | arc_next | bo_next], float64 [arc_w | bo_w]) on `device`: uploaded once per
-        device and kept (the cache is a plain dict: two threads that make their first call for a device at the same
-        time may both upload, and one copy is dropped -- harmless)"""
+        """the operators' DeviceLm (csrc/torch_ops.cpp) of this pack on `device`: `.ints` int32 [arc_ptr | arc_label |
+        arc_next | bo_next] and `.weights` float64 [arc_w | bo_w] there, and the wfl_ngram_lm that points into them.
+        Uploaded once per device and kept (the cache is a plain dict: two threads that make their first call for a
+        device at the same time may both upload, and one copy is dropped -- harmless)"""
         import torch
 
         device = torch.device(device)
@@ -118,13 +119,10 @@ class NGramLM:
             ints = np.concatenate([self.arc_ptr, self.arc_label, self.arc_next, self.bo_next])
             weights = np.concatenate([self.arc_w, self.bo_w])
             dev = torch.device("cuda", index)
-            held = self._on_device[index] = (torch.from_numpy(ints).to(dev), torch.from_numpy(weights).to(dev))
+            held = self._on_device[index] = N.ops.DeviceLm(torch.from_numpy(ints).to(dev), torch.from_numpy(weights).to(dev),
+                                                           self.num_states, self.num_arcs, self.start, self.step_min,
+                                                           self.step_max)
         return held
-
-    def device_arguments(self, device):
-        """what the operators behind ctc_beam_search_lm take after the search's own arguments"""
-        ints, weights = self.on_device(device)
-        return ints, weights, self.num_states, self.num_arcs, self.start, self.step_min, self.step_max
 
     # ------------------------------------------------------------------------------------------------------------
     @classmethod

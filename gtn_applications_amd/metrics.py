@@ -73,21 +73,17 @@ class ErrorCounter:
         return None if self.ref_table is None else len(self.ref_table[0]) - 1
 
     def tables(self, device):
-        """(hyp table, V, longest, ref table, V, longest, sep) as the operators take them; the tables ([exp_ptr | exp_sym]
-        int32) are uploaded once per device"""
+        """the operators' ErrorTables (csrc/torch_ops.cpp) of this counter on `device`: both tables ([exp_ptr | exp_sym]
+        int32, uploaded once per device) and the separator"""
         device = torch.device(device)
-        if device.index is None:
+        if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        args = self._device_tables.get(device)
-        if args is None:
-            args = ()
-            for t in (self.hyp_table, self.ref_table):
-                if t is None:
-                    args += (None, 0, 1)
-                else:
-                    args += (torch.from_numpy(np.concatenate([t[0], t[1]])).to(device), len(t[0]) - 1, t[2])
-            args = self._device_tables[device] = args + (self.sep,)
-        return args
+        held = self._device_tables.get(device)
+        if held is None:
+            sides = [None if t is None else (torch.from_numpy(np.concatenate(t[:2])).to(device), len(t[0]) - 1, t[2])
+                     for t in (self.hyp_table, self.ref_table)]
+            held = self._device_tables[device] = N.ops.ErrorTables(*sides, self.sep)
+        return held
 
     def check_hypothesis_labels(self, n_labels, what):
         """ValueError unless the hypothesis table covers the labels [0, n_labels) a decode can emit"""
@@ -95,33 +91,22 @@ class ErrorCounter:
             raise ValueError(f"{what}: the decode can emit {n_labels} labels, the counter's hypothesis table has "
                              f"{self.hyp_size} entries")
 
-    def staged_targets(self, targets, device):
-        """the batch's targets on `device` (the stager's cache: free for a batch the criterion has just seen), checked
-        against the reference table"""
-        tg = E.targets_on_device(targets, device)
-        if self.ref_table is not None and tg.n and (tg.label_min < 0 or tg.label_max >= self.ref_size):
-            bad = tg.label_min if tg.label_min < 0 else tg.label_max
-            raise ValueError(f"ErrorCounter: target label {bad} is outside the reference table [0, {self.ref_size})")
-        return tg
-
     def counts(self, predictions, targets):
         """int64 CPU tensor [B, 4]: per utterance (token distance, target tokens, word distance, target words).
         `predictions`: what viterbi() returns (1-D int tensors or int lists); `targets`: what the criterion takes."""
         predictions = list(predictions)
         if len(predictions) != len(targets):
             raise ValueError(f"ErrorCounter: {len(predictions)} predictions for {len(targets)} targets")
-        # (the labels are checked where they are staged, before anything is launched -- and before a missing GPU is reported)
         dev = E.require_gpu() if torch.cuda.is_available() else torch.device("cpu")
         if not predictions:
             return torch.zeros((0, 4), dtype=torch.int64)
-        ref = self.staged_targets(targets, dev)
+        ref = E.targets_on_device(targets, dev)
         hyp = E.CtcTargets([p.cpu() if isinstance(p, torch.Tensor) and p.is_cuda else p for p in predictions], dev)
-        if self.hyp_table is not None and hyp.n and (hyp.label_min < 0 or hyp.label_max >= self.hyp_size):
-            bad = hyp.label_min if hyp.label_min < 0 else hyp.label_max
-            raise ValueError(f"ErrorCounter: predicted label {bad} is outside the hypothesis table [0, {self.hyp_size})")
-        if dev.type != "cuda":
+        tables = self.tables(dev)
+        if dev.type != "cuda":  # (a label outside its table is the caller's error: reported before a missing GPU is)
+            tables.check_labels(hyp._st, ref._st)
             E.require_gpu()
-        return N.ops.errors_count(hyp._st, ref._st, *self.tables(dev))
+        return N.ops.errors_count(hyp._st, ref._st, tables)
 
     @staticmethod
     def totals(counts):
@@ -133,17 +118,19 @@ class ErrorCounter:
         return self.totals(self.counts(predictions, targets))
 
 
+def _staged(counter, targets, batch, drop=None):
+    """(the targets staged on the batch's device, the counter's tables there, `drop` as the operators take it) of a batch
+    of B utterances; the operators check the targets' labels against the reference table before they launch"""
+    if len(targets) != batch.shape[0]:
+        raise ValueError(f"errors: {batch.shape[0]} utterances for {len(targets)} targets")
+    return E.targets_on_device(targets, batch.device)._st, counter.tables(batch.device), -1 if drop is None else int(drop)
+
+
 def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=0, flags=0, lengths=None):
     """engine.decode_emissions' launch and the counts behind it, on x's device: [B, 4] int64 on the host and nothing else
     (lengths: int32 [B] on x's device, the frames of each utterance of a padded batch)"""
-    if len(targets) != x.shape[0]:
-        raise ValueError(f"errors: {x.shape[0]} utterances for {len(targets)} targets")
-    ref = counter.staged_targets(targets, x.device)
-    drop = -1 if drop is None else int(drop)
-    if lengths is not None:
-        return N.ops.decode_emissions_lengths_errors(x, bias, lengths, drop, num_replabels, flags, ref._st,
-                                                     *counter.tables(x.device))
-    return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref._st, *counter.tables(x.device))
+    ref, tables, drop = _staged(counter, targets, x, drop)
+    return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref, tables, lengths)
 
 
 def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None, lm=None, lm_weight=1.0,
@@ -151,23 +138,13 @@ def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame,
     """engine.ctc_beam_search's launches (best hypothesis only) and the counts behind them, on x's device: [B, 4] int64
     on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments).  lm,
     lm_weight, length_bonus, lm_eos: as in engine.ctc_beam_search."""
-    if len(targets) != x.shape[0]:
-        raise ValueError(f"errors: {x.shape[0]} utterances for {len(targets)} targets")
+    ref, tables, _ = _staged(counter, targets, x)
     lm, weight, bonus, eos = E.check_lm_arguments(lm, x.shape[2], int(blank), lm_weight, length_bonus, lm_eos, "errors")
-    ref = counter.staged_targets(targets, x.device)
-    if lm is not None:
-        return N.ops.ctc_beam_search_lm_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame),
-                                               *lm.device_arguments(x.device), weight, bonus, eos, ref._st,
-                                               *counter.tables(x.device))
-    return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref._st,
-                                        *counter.tables(x.device))
+    return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref, tables,
+                                        None if lm is None else lm.on_device(x.device), weight, bonus, eos)
 
 
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
-    if len(targets) != paths.shape[0]:
-        raise ValueError(f"errors: {paths.shape[0]} utterances for {len(targets)} targets")
-    ref = counter.staged_targets(targets, paths.device)
-    T = paths.shape[1] if T is None else T
-    return N.ops.decode_paths_errors(paths, T, -1 if drop is None else int(drop), num_replabels, flags, ref._st,
-                                     *counter.tables(paths.device))
+    ref, tables, drop = _staged(counter, targets, paths, drop)
+    return N.ops.decode_paths_errors(paths, paths.shape[1] if T is None else T, drop, num_replabels, flags, ref, tables)

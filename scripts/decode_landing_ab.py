@@ -1,5 +1,5 @@
 """Where the device decode's result lands (csrc/decode_kernels.hip): the kernels' stores straight into pinned host memory
-and one event wait -- what the operator does (csrc/torch_ops.cpp::decode_collect) -- against a device buffer plus one
+and one event wait -- what the operator does (csrc/torch_ops.cpp::hypotheses_collect) -- against a device buffer plus one
 copy of the offsets and one of the compact region.  CTC's call at the benchmark shape, through the C ABI, alternating."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

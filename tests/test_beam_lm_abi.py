@@ -32,8 +32,11 @@ def test_header_declares_and_library_exports_the_lm_entry_points():
         assert name in N.EXPORTED_SYMBOLS, name
     assert "typedef struct wfl_ngram_lm" in code and "WFL_NGRAM_LM_MAX_BACKOFF 8" in code
     assert ctypes.sizeof(N.NgramLm) == 16 + 16 + 6 * ctypes.sizeof(ctypes.c_void_p)
-    for fn in ("ctc_beam_search_lm", "ctc_beam_search_lm_errors"):
+    # the operators of the search take the model as an argument: a DeviceLm or None
+    assert hasattr(N.ops, "DeviceLm")
+    for fn in ("ctc_beam_search", "ctc_beam_search_errors"):
         assert hasattr(N.ops, fn), fn
+        assert all(f"{arg}: " in getattr(N.ops, fn).__doc__ for arg in ("lm", "lm_weight", "length_bonus", "score_eos")), fn
 
 
 GOOD = dict(B=2, T=5, C=7, blank=0, beam=4, K=3, nbest=2)

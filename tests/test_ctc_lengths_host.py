@@ -115,8 +115,9 @@ def test_header_declares_and_library_exports_the_new_entry_points():
         fn = getattr(N.lib, name)
         assert fn.restype is ctypes.c_int and fn.argtypes is not None, name
     assert declared == set(N.EXPORTED_SYMBOLS)
-    for fn in ("decode_emissions_lengths", "decode_emissions_lengths_errors"):
+    for fn in ("decode_emissions", "decode_emissions_errors"):  # (the lengths are an argument of the decode's operators)
         assert hasattr(N.ops, fn), fn
+        assert "lengths: " in getattr(N.ops, fn).__doc__, fn
     # wfl_ctc_call carries the lengths of a padded batch behind its two older fields, header and binding alike
     struct = re.search(r"typedef struct wfl_ctc_call \{(.*?)\} wfl_ctc_call;", code, flags=re.S).group(1)
     assert [f.split()[-1].lstrip("*") for f in struct.split(";") if f.strip()] == ["n_labels", "host_state", "input_lengths"]
