@@ -50,6 +50,13 @@ class NgramLm(ctypes.Structure):
         (n, c_void_p) for n in ("arc_ptr", "arc_label", "arc_next", "arc_w", "bo_next", "bo_w")]
 
 
+class Lexicon(ctypes.Structure):
+    """Mirror of `wfl_lexicon` (include/wfl.h): host pointers for wfl_lexicon_check, device pointers for a search."""
+
+    _fields_ = [(n, c_int32) for n in ("num_nodes", "num_arcs", "num_words", "reserved")] + [
+        (n, c_void_p) for n in ("arc_ptr", "arc_label", "arc_next")]
+
+
 class LatticeDesc(ctypes.Structure):
     """Mirror of `wfl_lattice_desc` (include/wfl.h) -- field order and types must match."""
 
@@ -197,6 +204,9 @@ _SIGS = {
     "wfl_ngram_lm_check": (c_int, [POINTER(NgramLm), c_int, c_int]),
     "wfl_ctc_beam_search_lm": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(NgramLm), c_double,
                                        c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_lexicon_check": (c_int, [POINTER(Lexicon), c_int, c_int]),
+    "wfl_ctc_beam_search_lexicon": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Lexicon),
+                                            POINTER(NgramLm), c_double, c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path
     "wfl_errors_workspace": (c_int, [c_int, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wfl_errors_count": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int64, c_int64, _P, _P, _P]),

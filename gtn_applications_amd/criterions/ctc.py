@@ -363,11 +363,16 @@ class CTC(torch.nn.Module):
         lens = None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
         return W, K, n, lens
 
-    def _beam_lm(self, outputs, lm, lm_weight, length_bonus, lm_eos, what):
-        """The language model arguments of a beam search, checked like the rest: the keywords of the engine's call,
-        none without an lm (the call it was)"""
-        lm, weight, bonus, eos = E.check_lm_arguments(lm, outputs.shape[2], self.blank, lm_weight, length_bonus, lm_eos, what)
-        return {} if lm is None else dict(lm=lm, lm_weight=weight, length_bonus=bonus, lm_eos=eos)
+    def _beam_lm(self, outputs, lm, lm_weight, length_bonus, lm_eos, what, lexicon=None, word_bonus=0.0):
+        """The language model and lexicon arguments of a beam search, checked like the rest: the keywords of the
+        engine's call, none without an lm or a lexicon (the call it was)"""
+        C = outputs.shape[2]
+        lexicon, omega = E.check_lexicon_arguments(lexicon, C, self.blank, word_bonus, what)
+        lm, weight, bonus, eos = E.check_lm_arguments(lm, C, self.blank, lm_weight, length_bonus, lm_eos, what, lexicon)
+        fused = {} if lm is None else dict(lm=lm, lm_weight=weight, length_bonus=bonus, lm_eos=eos)
+        if lexicon is not None:
+            fused.update(lexicon=lexicon, word_bonus=omega, length_bonus=bonus)
+        return fused
 
     @staticmethod
     def _beam_emissions(outputs):
@@ -377,7 +382,7 @@ class CTC(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, input_lengths=None, return_scores=False,
-                    lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True):
+                    lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
         """CTC prefix beam search (an addition: the reference has the greedy decode only).  viterbi() maximises over
         frame paths; this maximises over label sequences, whose probability is the sum over all their alignments
         (DESIGN.md section 17 has the rules; csrc/beam_kernels.hip runs them, in float64).  Per frame only the
@@ -390,18 +395,23 @@ class CTC(torch.nn.Module):
         18): extending a hypothesis by a token adds lm_weight * log P_LM(token | history) + length_bonus to its score,
         a token the LM cannot follow the history with is never emitted, and with `lm_eos` every final hypothesis gets
         lm_weight * log P_LM(</s> | history) before the ranks are taken; the scores then include these terms.  Without
-        an lm the call is what it was, and lm_weight, length_bonus, lm_eos must be left alone.  CTC only: no lexicon /
-        word-level LM; ASG and the Transducer's token graphs have no beam search."""
+        an lm the call is what it was, and lm_weight, length_bonus, lm_eos must be left alone.  `lexicon`: a
+        lexicon.Lexicon over this model's classes: only sequences of its words are returned (a
+        hypothesis that ends inside a word is dropped after the last frame; nothing left: the empty sequence, -inf),
+        `lm` is then a word-level LM over the lexicon's word ids (NGramLM.from_arpa(path, words, blank=len(words))), a
+        completed word adds lm_weight * log P_LM(word | history) + word_bonus and every label length_bonus; the output
+        is still the token labels, lexicon.words() gives the words.  `word_bonus` needs a lexicon.  CTC only: ASG and
+        the Transducer's token graphs have no beam search."""
         W, K, n, lens = self._beam_plan(outputs, beam_size, classes_per_frame, nbest, input_lengths, "CTC.beam_search")
-        fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.beam_search")
+        fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.beam_search", lexicon, word_bonus)
         B, T, _ = outputs.shape
         if B == 0 or (T == 0 and not fused):
             hyps, scores = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)], \
                 torch.zeros((B, n), dtype=torch.float64)
-        elif T == 0:  # (no frame: the empty sequence, scored by the LM's </s> alone)
+        elif T == 0:  # (no frame: the empty sequence -- no word either --, scored by the LM's </s> alone)
             # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
             end = 0.0
-            if fused["lm_eos"]:
+            if "lm" in fused and fused["lm_eos"]:
                 step = fused["lm"].score([], eos=True)
                 end = -math.inf if step == -math.inf else fused["lm_weight"] * step
             hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)]
@@ -418,21 +428,22 @@ class CTC(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, input_lengths=None, beam_size=None, classes_per_frame=None, lm=None,
-               lm_weight=1.0, length_bonus=0.0, lm_eos=True):
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `input_lengths`
         (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s.  `beam_size` (an addition):
         the predictions are beam_search(outputs, beam_size, classes_per_frame, input_lengths=input_lengths)'s instead,
-        counted behind the beam launch on its device buffers; `lm`, `lm_weight`, `length_bonus`, `lm_eos` are
-        beam_search's and need a beam_size."""
+        counted behind the beam launch on its device buffers; `lm`, `lm_weight`, `length_bonus`, `lm_eos`, `lexicon`,
+        `word_bonus` are beam_search's and need a beam_size."""
         if beam_size is None:
-            if lm is not None:
-                raise ValueError("CTC.errors: lm needs a beam_size")
+            if lm is not None or lexicon is not None:
+                raise ValueError("CTC.errors: lm and lexicon need a beam_size")
+            E.check_lexicon_arguments(None, outputs.shape[2], self.blank, word_bonus, "CTC.errors")
             E.check_lm_arguments(None, outputs.shape[2], self.blank, lm_weight, length_bonus, lm_eos, "CTC.errors")
         if beam_size is not None:
             W, K, _, lens = self._beam_plan(outputs, beam_size, classes_per_frame, 1, input_lengths, "CTC.errors")
-            fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.errors")
+            fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.errors", lexicon, word_bonus)
             C = outputs.shape[2]
             counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:

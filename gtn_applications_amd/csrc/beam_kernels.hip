@@ -22,6 +22,10 @@
 // in the LM's arrays, which stay in global memory) where its key is formed -- unless it cannot reach the W-th best stay
 // entry even with the LM's largest term --, its next state waits in LDS beside the entry for place(), and the final
 // beam is ranked again with </s>.
+// wfl_ctc_beam_search_lexicon is the same three launches again with a lexicon and an optional word-level n-gram LM
+// (DESIGN.md section 20): a third parameter pack, BeamLex, carries the lexicon's trie and a BeamLm over word ids; a
+// hypothesis carries a trie node beside its LM state, an extension costs one bounded binary search among the arcs of
+// its node and, where the arc completes a word, one LM step; the final beam drops the ranks inside a word.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
 #include "device_common.h"
@@ -203,9 +207,88 @@ struct BeamHyp {  // (struct of arrays, one per buffer)
 
 __device__ __forceinline__ const BeamLm& beam_lm_of(const BeamLm& lm) { return lm; }
 
+// the lexicon of a launch: wfl_lexicon's device arrays (a pack that passed wfl_lexicon_check), the word LM or none, and
+// the scalars of the call.  lm.alpha, lm.beta, lm.score_eos are the call's; lm.eos is the word LM's </s> label V + 1;
+// without a word LM (has_lm == 0) lm's pointers are not read and every word's step is 0.
+struct BeamLex {
+  const int32_t *arc_ptr, *arc_label, *arc_next;
+  BeamLm lm;
+  int has_lm;
+  double omega;  // the word bonus
+  double bound;  // no extension's term is above it (+inf: unknown)
+};
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamLex& lx) { return lx; }
+
+// The term of an extension that completes a word whose LM step is l: (alpha l + omega) + beta, each operation rounded
+// on its own -- on the host, where beam_lex_bound forms the largest such term, and on the device alike, so that the
+// bound holds by the monotonicity of the rounded operations (a fused multiply-add would round once and may land above).
+__host__ __device__ inline double beam_lex_word_term(double alpha, double l, double omega, double beta) {
+#pragma clang fp contract(off)
+  const double al = alpha * l;
+  const double t = al + omega;
+  return t + beta;
+}
+// The largest term of an extension: beta inside a word (= 0 + beta), beam_lex_word_term at a word's end with
+// l in [step_min, step_max].  alpha l <= max(alpha step_min, alpha step_max) =: m, so (alpha l + omega) + beta <=
+// (m + omega) + beta <= max(0, m + omega) + beta, and 0 + beta is below the last as well; 0 * inf: no bound.
+inline double beam_lex_bound(double alpha, double step_min, double step_max, double omega, double beta) {
+#pragma clang fp contract(off)
+  const double t0 = alpha * step_min, t1 = alpha * step_max;
+  if (t0 != t0 || t1 != t1) return __builtin_inf();
+  const double m = fmax(t0, t1) + omega;
+  return fmax(0.0, m) + beta;
+}
+
+constexpr int kLexAbsent = -2147483647 - 1;  // no arc_next: word ids are below 2^31 - 1
+
+// The extension of a hypothesis at trie node `node` with LM state `state` by class c: its term, -inf if it does not
+// exist (no such arc, or a word the LM cannot follow the history with).  enc: where the new hypothesis stands -- an
+// inner node n as n >= 0 (the LM state stays), the root behind a word as -(next LM state + 1).  The search among the
+// node's arcs is bounded like the LM's: 31 halvings.
+__device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int state, int c, int& enc) {
+  const int end = lx.arc_ptr[node + 1];
+  int lo = lx.arc_ptr[node], hi = end;
+  for (int it = 0; it < 31 && lo < hi; ++it) {  // the first arc whose label is not below c
+    const int mid = lo + ((hi - lo) >> 1);
+    if (lx.arc_label[mid] < c)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  enc = 0;
+  const int nx = (lo < end && lx.arc_label[lo] == c) ? lx.arc_next[lo] : kLexAbsent;
+  if (nx == kLexAbsent) return -__builtin_inf();
+  if (nx >= 0) {
+    enc = nx;
+    return lx.lm.beta;
+  }
+  double l = 0.0;
+  int ns = 0;
+  if (lx.has_lm) {
+    l = beam_lm_step(lx.lm, state, -(nx + 1), ns);
+    if (!(l > -__builtin_inf())) return -__builtin_inf();
+  }
+  enc = -(ns + 1);
+  return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
+}
+
+template <typename... Lm>
+struct BeamPack {
+  static constexpr bool lm = false, lex = false;
+};
+template <>
+struct BeamPack<BeamLm> {
+  static constexpr bool lm = true, lex = false;
+};
+template <>
+struct BeamPack<BeamLex> {
+  static constexpr bool lm = false, lex = true;
+};
+
 // NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales).
 // Lm: nothing -- the search of wfl_ctc_beam_search, its parameters and its code what they were --, or one BeamLm: the
-// n-gram LM and length bonus of wfl_ctc_beam_search_lm.
+// n-gram LM and length bonus of wfl_ctc_beam_search_lm, or one BeamLex: the lexicon, word LM and bonuses of
+// wfl_ctc_beam_search_lexicon.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -213,7 +296,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
                                                            int2* __restrict__ arena, int32_t* __restrict__ fin_node,
                                                            int32_t* __restrict__ fin_len, double* __restrict__ scores,
                                                            Lm... lm_arg) {
-  constexpr bool LM = sizeof...(Lm) != 0;
+  constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex;
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -240,6 +323,15 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     __shared__ int s_enext[kBeamEntries];
     lmst = s_lmst, enext = s_enext;
   }
+  // lexicon only: the same two, enext holding beam_lex_step's `enc` (node and state of an extension in one int), and
+  // the trie node of every hypothesis
+  int(*tnode)[kBeamMax] = nullptr;
+  if constexpr (LEX) {
+    __shared__ int s_xlmst[2][kBeamMax];
+    __shared__ int s_xtnode[2][kBeamMax];
+    __shared__ int s_xenext[kBeamEntries];
+    lmst = s_xlmst, tnode = s_xtnode, enext = s_xenext;
+  }
 
   const int tid = threadIdx.x, b = blockIdx.x;
   const int KC = K + 1;
@@ -255,6 +347,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     beam[0].pb[0] = 0.0, beam[0].pnb[0] = ninf, beam[0].tot[0] = 0.0;
     beam[0].hash[0] = 0ull, beam[0].hash2[0] = 0ull, beam[0].last[0] = -1, beam[0].len[0] = 0, beam[0].node[0] = -1;
     if constexpr (LM) lmst[0][0] = beam_lm_of(lm_arg...).start;
+    if constexpr (LEX) lmst[0][0] = beam_lex_of(lm_arg...).has_lm ? beam_lex_of(lm_arg...).lm.start : 0, tnode[0][0] = 0;
   }
   __syncthreads();
   // the candidates of frame 0 into buffer 0
@@ -317,6 +410,13 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const double l = e > ninf ? beam_lm_step(lm, lmst[cur][i], h.last[tid], nx) : ninf;
           if (l > ninf) pnb = beam_lae(pnb, e + (lm.alpha * l + lm.beta));
         }
+      } else if constexpr (LEX) {
+        if (i >= 0) {  // the merged extension carries the term of the prefix it makes (node and state: functions of it)
+          const double e = sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]);
+          int enc;
+          const double term = e > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][i], lmst[cur][i], h.last[tid], enc) : ninf;
+          if (term > ninf) pnb = beam_lae(pnb, e + term);
+        }
       } else {
         if (i >= 0) pnb = beam_lae(pnb, sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]));
       }
@@ -355,6 +455,15 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const double l = reach ? beam_lm_step(lm, lmst[cur][i], c, nx) : ninf;
           k = l > ninf ? beam_key(ac + (lm.alpha * l + lm.beta)) : kKeyDropped;
           enext[idx] = nx;
+        } else if constexpr (LEX) {
+          const BeamLex& lx = beam_lex_of(lm_arg...);
+          const double ac = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);  // the extension without its term
+          int enc = 0;
+          // (an entry below the bound even with the largest term is outside the beam: no lookup; + is monotone)
+          const bool reach = ac > ninf && beam_key(ac + lx.bound) >= tau;
+          const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+          k = term > ninf ? beam_key(ac + term) : kKeyDropped;
+          enext[idx] = enc;
         } else
           k = beam_key(sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]));
       }
@@ -371,13 +480,18 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         g.pb[r] = spb[idx], g.pnb[r] = spnb[idx], g.tot[r] = stot[idx];
         g.hash[r] = h.hash[idx], g.hash2[r] = h.hash2[idx], g.last[r] = h.last[idx], g.len[r] = h.len[idx], g.node[r] = h.node[idx];
         if constexpr (LM) lmst[cur ^ 1][r] = lmst[cur][idx];
+        if constexpr (LEX) lmst[cur ^ 1][r] = lmst[cur][idx], tnode[cur ^ 1][r] = tnode[cur][idx];
       } else {
         const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
         const int c = cls[p];
         double e;
         if constexpr (LM)
           e = beam_key_total(k), lmst[cur ^ 1][r] = enext[idx];  // (the total with its LM term: the key holds it)
-        else
+        else if constexpr (LEX) {
+          const int enc = enext[idx];  // (inside a word: the node, the parent's state; behind one: the root, a new state)
+          e = beam_key_total(k);
+          tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
+        } else
           e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
         const int node = t * W + r;
         g.pb[r] = ninf, g.pnb[r] = e, g.tot[r] = e;
@@ -465,16 +579,28 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   if (tid == 0) s_norm = norm;
   __syncthreads();
   const BeamHyp& f = beam[Tb & 1];
-  if constexpr (LM) {
+  if constexpr (LM || LEX) {
     // </s>: every rank's total with the LM's end weight, a rank without one dropped, then the ranks again by counting
-    // (descending, ties to the earlier rank; dropped keys are below every other and come out behind them, empty)
-    const BeamLm& lm = beam_lm_of(lm_arg...);
+    // (descending, ties to the earlier rank; dropped keys are below every other and come out behind them, empty).
+    // With a lexicon a rank inside a word is dropped first, and </s> needs a word LM.
     if (tid < nbeam) {
       double s = f.tot[tid];
-      if (lm.score_eos) {
-        int nx;
-        const double l = beam_lm_step(lm, lmst[Tb & 1][tid], lm.eos, nx);
-        s = l > ninf ? s + lm.alpha * l : ninf;
+      if constexpr (LEX) {
+        const BeamLex& lx = beam_lex_of(lm_arg...);
+        if (tnode[Tb & 1][tid] != 0)
+          s = ninf;
+        else if (lx.has_lm && lx.lm.score_eos) {
+          int nx;
+          const double l = beam_lm_step(lx.lm, lmst[Tb & 1][tid], lx.lm.eos, nx);
+          s = l > ninf ? s + lx.lm.alpha * l : ninf;
+        }
+      } else {
+        const BeamLm& lm = beam_lm_of(lm_arg...);
+        if (lm.score_eos) {
+          int nx;
+          const double l = beam_lm_step(lm, lmst[Tb & 1][tid], lm.eos, nx);
+          s = l > ninf ? s + lm.alpha * l : ninf;
+        }
       }
       stot[tid] = s, skey[tid] = beam_key(s);
     }
@@ -561,10 +687,11 @@ int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame,
 
 }  // extern "C"
 
-// the three launches of a search; lm: NULL, or the LM of wfl_ctc_beam_search_lm (already checked)
+// the three launches of a search; lm: NULL, or the LM of wfl_ctc_beam_search_lm (already checked); lex: NULL, or the
+// lexicon of wfl_ctc_beam_search_lexicon (already checked; never with lm, its word LM is inside it)
 static int beam_launch(const char* what, const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
-                       int classes_per_frame, int nbest, int normalize, const BeamLm* lm, void* ws, int32_t* out,
-                       int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+                       int classes_per_frame, int nbest, int normalize, const BeamLm* lm, const BeamLex* lex, void* ws,
+                       int32_t* out, int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   if (!x || !ws || !out || !out_offsets || !scores) {
     set_error("%s: a NULL pointer", what);
     return WFL_ERR_INVALID;
@@ -601,7 +728,14 @@ static int beam_launch(const char* what, const float* x, const int32_t* lengths,
   else
     candidates(beam_candidates_kernel<0>);
   WFL_LAUNCH_CHECK();
-  if (lm) {
+  if (lex) {
+    if (beam * (K + 2) <= 1024)
+      hipLaunchKernelGGL((beam_search_kernel<256, BeamLex>), dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize,
+                         cls, sc, lse, arena, fin_node, fin_len, scores, *lex);
+    else
+      hipLaunchKernelGGL((beam_search_kernel<1024, BeamLex>), dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize,
+                         cls, sc, lse, arena, fin_node, fin_len, scores, *lex);
+  } else if (lm) {
     if (beam * (K + 2) <= 1024)
       hipLaunchKernelGGL((beam_search_kernel<256, BeamLm>), dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls,
                          sc, lse, arena, fin_node, fin_len, scores, *lm);
@@ -627,8 +761,8 @@ extern "C" {
 int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
                         int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
                         double* scores, void* stream) {
-  return beam_launch("ctc_beam_search", x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, ws, out,
-                     out_capacity, out_offsets, scores, stream);
+  return beam_launch("ctc_beam_search", x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, nullptr, ws,
+                     out, out_capacity, out_offsets, scores, stream);
 }
 
 static int ngram_lm_shape(const char* what, const wfl_ngram_lm* lm) {
@@ -730,8 +864,141 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths, int B, int T,
   // the largest LM term of an extension, by the operations the kernel forms a term with (0 * inf: no bound)
   const double t0 = lm_weight * lm->step_min, t1 = lm_weight * lm->step_max;
   d.bound = (t0 != t0 || t1 != t1) ? __builtin_inf() : fmax(t0, t1) + length_bonus;
-  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, &d, ws, out, out_capacity,
-                     out_offsets, scores, stream);
+  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, &d, nullptr, ws, out,
+                     out_capacity, out_offsets, scores, stream);
+}
+
+static int lexicon_shape(const char* what, const wfl_lexicon* lex) {
+  if (!lex || !lex->arc_ptr || !lex->arc_label || !lex->arc_next) {
+    set_error("%s: a NULL lexicon or array of it", what);
+    return WFL_ERR_INVALID;
+  }
+  if (lex->num_nodes < 1 || lex->num_arcs < 1 || lex->num_words < 1 || lex->num_words == 0x7fffffff) {  // (</s> is V + 1)
+    set_error("%s: a lexicon of %d nodes, %d arcs, %d words", what, lex->num_nodes, lex->num_arcs, lex->num_words);
+    return WFL_ERR_INVALID;
+  }
+  return WFL_OK;
+}
+
+int wfl_lexicon_check(const wfl_lexicon* lex, int C, int blank) {
+  const char* what = "lexicon_check";
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  if (C < 1 || blank < 0 || blank >= C) {
+    set_error("%s: %d classes, blank %d", what, C, blank);
+    return WFL_ERR_INVALID;
+  }
+  const int N = lex->num_nodes, A = lex->num_arcs, V = lex->num_words;
+  if (lex->arc_ptr[0] != 0 || lex->arc_ptr[N] != A) {
+    set_error("%s: arc_ptr runs from %d to %d, not from 0 to %d", what, lex->arc_ptr[0], lex->arc_ptr[N], A);
+    return WFL_ERR_INVALID;
+  }
+  for (int n = 0; n < N; ++n) {
+    if (lex->arc_ptr[n] > lex->arc_ptr[n + 1] || lex->arc_ptr[n] < 0 || lex->arc_ptr[n + 1] > A) {
+      set_error("%s: arc_ptr descends or leaves [0, %d] at node %d", what, A, n);
+      return WFL_ERR_INVALID;
+    }
+    if (lex->arc_ptr[n] == lex->arc_ptr[n + 1]) {
+      set_error("%s: node %d has no arc (a dead end)", what, n);
+      return WFL_ERR_INVALID;
+    }
+  }
+  std::vector<char> entered((size_t)N, 0), spelled((size_t)V, 0);
+  for (int n = 0; n < N; ++n)
+    for (int a = lex->arc_ptr[n]; a < lex->arc_ptr[n + 1]; ++a) {
+      const int l = lex->arc_label[a], nx = lex->arc_next[a];
+      if (l < 0 || l >= C || l == blank) {
+        set_error("%s: arc %d of node %d has label %d (classes [0, %d), never the blank %d)", what, a, n, l, C, blank);
+        return WFL_ERR_INVALID;
+      }
+      if (a > lex->arc_ptr[n] && lex->arc_label[a - 1] >= l) {
+        set_error("%s: the labels of node %d are not strictly ascending at arc %d", what, n, a);
+        return WFL_ERR_INVALID;
+      }
+      if (nx >= 0) {
+        if (nx < 1 || nx >= N) {
+          set_error("%s: arc %d of node %d leads to node %d (inner nodes are 1 .. %d)", what, a, n, nx, N - 1);
+          return WFL_ERR_INVALID;
+        }
+        if (entered[(size_t)nx]) {
+          set_error("%s: node %d is the target of more than one arc (arc %d is the second)", what, nx, a);
+          return WFL_ERR_INVALID;
+        }
+        entered[(size_t)nx] = 1;
+      } else {
+        const int64_t v = -((int64_t)nx + 1);
+        if (v >= V) {
+          set_error("%s: arc %d of node %d completes word %lld of %d", what, a, n, (long long)v, V);
+          return WFL_ERR_INVALID;
+        }
+        if (spelled[(size_t)v]) {
+          set_error("%s: word %lld is completed by more than one arc (arc %d is the second)", what, (long long)v, a);
+          return WFL_ERR_INVALID;
+        }
+        spelled[(size_t)v] = 1;
+      }
+    }
+  for (int n = 1; n < N; ++n)
+    if (!entered[(size_t)n]) {
+      set_error("%s: node %d is the target of no arc", what, n);
+      return WFL_ERR_INVALID;
+    }
+  for (int v = 0; v < V; ++v)
+    if (!spelled[(size_t)v]) {
+      set_error("%s: word %d is completed by no arc", what, v);
+      return WFL_ERR_INVALID;
+    }
+  {  // one arc into every inner node still allows a cycle apart from the root: every node must be reached from it
+    std::vector<int> stack(1, 0);
+    int reached = 0;
+    while (!stack.empty()) {
+      const int n = stack.back();
+      stack.pop_back();
+      ++reached;
+      for (int a = lex->arc_ptr[n]; a < lex->arc_ptr[n + 1]; ++a)
+        if (lex->arc_next[a] >= 0) stack.push_back(lex->arc_next[a]);
+    }
+    if (reached != N) {
+      set_error("%s: %d of %d nodes are reached from the root: the rest form a cycle", what, reached, N);
+      return WFL_ERR_INVALID;
+    }
+  }
+  return WFL_OK;
+}
+
+int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
+                                int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                                double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon";
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  if (word_lm) {
+    if (const int rc = ngram_lm_shape(what, word_lm)) return rc;
+    if (word_lm->step_min != word_lm->step_min || word_lm->step_max != word_lm->step_max) {
+      set_error("%s: the language model's step_min or step_max is NaN", what);
+      return WFL_ERR_INVALID;
+    }
+  }
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  BeamLex d;
+  d.arc_ptr = lex->arc_ptr, d.arc_label = lex->arc_label, d.arc_next = lex->arc_next;
+  d.has_lm = word_lm ? 1 : 0;
+  d.lm.arc_ptr = d.lm.arc_label = d.lm.arc_next = d.lm.bo_next = nullptr, d.lm.arc_w = d.lm.bo_w = nullptr, d.lm.start = 0;
+  if (word_lm) {
+    d.lm.arc_ptr = word_lm->arc_ptr, d.lm.arc_label = word_lm->arc_label, d.lm.arc_next = word_lm->arc_next;
+    d.lm.bo_next = word_lm->bo_next, d.lm.arc_w = word_lm->arc_w, d.lm.bo_w = word_lm->bo_w, d.lm.start = word_lm->start;
+  }
+  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
+  d.lm.eos = lex->num_words + 1, d.lm.alpha = lm_weight, d.lm.beta = length_bonus, d.lm.score_eos = score_eos ? 1 : 0;
+  d.omega = word_bonus;
+  // (without a word LM every word's step is 0: the bounds of step are [0, 0])
+  d.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
+  d.lm.bound = d.bound;
+  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, &d, ws, out,
+                     out_capacity, out_offsets, scores, stream);
 }
 
 }  // extern "C"

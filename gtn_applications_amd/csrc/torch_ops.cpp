@@ -970,23 +970,47 @@ struct DeviceLm {
   }
 };
 
+// A lexicon on the device (wfl_lexicon; lexicon.py's Lexicon.on_device builds one per device): ints = [arc_ptr (N+1) |
+// arc_label (A) | arc_next (A)] int32, contiguous on one GPU, from a pack that passed wfl_lexicon_check on the host.
+struct DeviceLexicon {
+  at::Tensor ints;  // (kept alive: lex points into it)
+  wfl_lexicon lex;
+  DeviceLexicon(const at::Tensor& ints_, int64_t N, int64_t A, int64_t V) : ints(ints_) {
+    TORCH_CHECK(N >= 1 && A >= 1 && V >= 1 && N < (1LL << 31) && A < (1LL << 31) && V < (1LL << 31) - 1,
+                "ctc_beam_search_lexicon: a lexicon of ", N, " nodes, ", A, " arcs, ", V, " words");
+    TORCH_CHECK(ints.is_cuda() && ints.scalar_type() == at::kInt && ints.is_contiguous() && ints.dim() == 1 &&
+                    ints.numel() == N + 1 + 2 * A,
+                "ctc_beam_search_lexicon: the lexicon's int32 arrays must be one contiguous [N + 1 + 2 A] tensor on a GPU");
+    const int32_t* ip = ints.data_ptr<int32_t>();
+    lex.num_nodes = (int32_t)N, lex.num_arcs = (int32_t)A, lex.num_words = (int32_t)V, lex.reserved = 0;
+    lex.arc_ptr = ip, lex.arc_label = ip + N + 1, lex.arc_next = ip + N + 1 + A;
+  }
+};
+
 // lm none: wfl_ctc_beam_search, the call it was (lm_weight, length_bonus and score_eos are not read);
-// given: wfl_ctc_beam_search_lm
+// given: wfl_ctc_beam_search_lm.  lexicon given: wfl_ctc_beam_search_lexicon, lm (or none) its word LM.
 Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
                        int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
-                       double length_bonus, bool score_eos) {
+                       double length_bonus, bool score_eos, const std::shared_ptr<DeviceLexicon>& lexicon, double word_bonus) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
   const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
   const at::Tensor lt = checked_lengths(lengths, x, "ctc_beam_search");
   TORCH_CHECK(!lm || lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
+  TORCH_CHECK(!lexicon || lexicon->ints.device() == x.device(),
+              "ctc_beam_search_lexicon: the lexicon's arrays must be on x's device");
   return {x, B, (int64_t)B * nbest, true, "ctc_beam_search",
           [=](int64_t* capacity, int64_t* ws_bytes) {
             check(wfl_ctc_beam_workspace(B, T, C, (int)beam, (int)K, (int)nbest, capacity, ws_bytes), "ctc_beam_search");
           },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
             const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
-            if (lm)
+            if (lexicon)
+              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
+                                                normalize ? 1 : 0, &lexicon->lex, lm ? &lm->lm : nullptr, lm_weight, word_bonus,
+                                                length_bonus, score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                    "ctc_beam_search_lexicon");
+            else if (lm)
               check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
                                            normalize ? 1 : 0, &lm->lm, lm_weight, length_bonus, score_eos ? 1 : 0, ws, out, cap,
                                            offs, scores, s),
@@ -1064,9 +1088,11 @@ std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
                           int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
-                          double length_bonus, bool score_eos) {
+                          double length_bonus, bool score_eos, const std::shared_ptr<DeviceLexicon>& lexicon,
+                          double word_bonus) {
   const Collected r = hypotheses_collect(
-      beam_source(x, lengths, blank, beam, K, nbest, normalize, lm, lm_weight, length_bonus, score_eos), true);
+      beam_source(x, lengths, blank, beam, K, nbest, normalize, lm, lm_weight, length_bonus, score_eos, lexicon, word_bonus),
+      true);
   return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), nbest}));
 }
 
@@ -1197,8 +1223,10 @@ at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop,
 
 at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
                                   int64_t K, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables,
-                                  const std::shared_ptr<DeviceLm>& lm, double lm_weight, double length_bonus, bool score_eos) {
-  return hypotheses_errors(beam_source(x, lengths, blank, beam, K, 1, false, lm, lm_weight, length_bonus, score_eos), ref, tables);
+                                  const std::shared_ptr<DeviceLm>& lm, double lm_weight, double length_bonus, bool score_eos,
+                                  const std::shared_ptr<DeviceLexicon>& lexicon, double word_bonus) {
+  return hypotheses_errors(
+      beam_source(x, lengths, blank, beam, K, 1, false, lm, lm_weight, length_bonus, score_eos, lexicon, word_bonus), ref, tables);
 }
 
 }  // namespace
@@ -1210,6 +1238,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("step_max"))
       .def_readonly("ints", &DeviceLm::ints)
       .def_readonly("weights", &DeviceLm::weights);
+  py::class_<DeviceLexicon, std::shared_ptr<DeviceLexicon>>(m, "DeviceLexicon",
+                                                            "a lexicon's pack on a GPU (lexicon.Lexicon.on_device)")
+      .def(py::init<const at::Tensor&, int64_t, int64_t, int64_t>(), py::arg("ints"), py::arg("num_nodes"), py::arg("num_arcs"),
+           py::arg("num_words"))
+      .def_readonly("ints", &DeviceLexicon::ints);
   py::class_<ErrorTables, std::shared_ptr<ErrorTables>>(m, "ErrorTables",
                                                         "both tables of a metrics.ErrorCounter, uploaded, and its separator")
       .def(py::init<const ErrorSideSpec&, const ErrorSideSpec&, int64_t>(), py::arg("hyp"), py::arg("ref"), py::arg("sep"),
@@ -1218,12 +1251,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "ValueError for a staged label (StagedTargets or None) outside its table; needs no device");
   m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"), py::arg("lm"), py::arg("lm_weight"),
-        py::arg("length_bonus"), py::arg("score_eos"),
+        py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon") = std::shared_ptr<DeviceLexicon>(),
+        py::arg("word_bonus") = 0.0,
         "CTC prefix beam search on the device, with an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is "
-        "scored) or None: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
+        "scored) or None, and with a lexicon (DeviceLexicon; lm is then its word LM; a word bonus) or None: (labels "
+        "int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
   m.def("ctc_beam_search_errors", &ctc_beam_search_errors, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"), py::arg("lm"), py::arg("lm_weight"),
-        py::arg("length_bonus"), py::arg("score_eos"),
+        py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon") = std::shared_ptr<DeviceLexicon>(),
+        py::arg("word_bonus") = 0.0,
         "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),

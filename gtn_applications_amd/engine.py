@@ -967,43 +967,68 @@ def check_beam_arguments(C, beam_size, classes_per_frame, nbest, what):
     return W, K, n
 
 
-def check_lm_arguments(lm, C, blank, lm_weight, length_bonus, lm_eos, what):
+def _finite_number(v, name, what):
+    """a finite float from a Python or numpy number or a one-element tensor (a sweep over numpy weights); never from a
+    bool or a string"""
+    f = math.nan
+    if not isinstance(v, (bool, np.bool_, str, bytes)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            pass
+    if not math.isfinite(f):
+        raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+    return f
+
+
+def check_lm_arguments(lm, C, blank, lm_weight, length_bonus, lm_eos, what, lexicon=None):
     """(lm, lm_weight, length_bonus, lm_eos) of a beam search over C classes, checked: lm None and the rest at their
-    defaults, or an lm.NGramLM built for these classes and this blank with a finite weight and bonus.  ValueError
-    otherwise; needs no device."""
+    defaults, or an lm.NGramLM built for these classes and this blank with a finite weight and bonus.  With a `lexicon`
+    (already checked, check_lexicon_arguments) the lm is its word LM instead -- the convention of lexicon.py, checked
+    here --, and the length bonus needs no lm: the lexicon search applies it to every label.  ValueError otherwise;
+    needs no device."""
+    from .lexicon import check_word_lm
     from .lm import NGramLM
 
-    def number(v, name):
-        """a finite float from a Python or numpy number or a one-element tensor (a sweep over numpy weights); never
-        from a bool or a string"""
-        f = math.nan
-        if not isinstance(v, (bool, np.bool_, str, bytes)):
-            try:
-                f = float(v)
-            except (TypeError, ValueError):
-                pass
-        if not math.isfinite(f):
-            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-        return f
-
-    weight, bonus = number(lm_weight, "lm_weight"), number(length_bonus, "length_bonus")
+    weight, bonus = _finite_number(lm_weight, "lm_weight", what), _finite_number(length_bonus, "length_bonus", what)
     if not isinstance(lm_eos, (bool, np.bool_)):
         raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
     lm_eos = bool(lm_eos)
     if lm is None:
-        if weight != 1.0 or bonus != 0.0 or lm_eos is not True:
-            raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm")
+        if weight != 1.0 or (bonus != 0.0 and lexicon is None) or lm_eos is not True:
+            raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm" +
+                             ("" if lexicon is None else " (with a lexicon: lm_weight and lm_eos do)"))
         return None, weight, bonus, lm_eos
     if not isinstance(lm, NGramLM):
         raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
-    if lm.num_classes != C or lm.blank != blank:
+    if lexicon is not None:
+        check_word_lm(lexicon, lm, what)
+    elif lm.num_classes != C or lm.blank != blank:
         raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
                          f"the emissions have {C} with blank {blank}")
     return lm, weight, bonus, lm_eos
 
 
+def check_lexicon_arguments(lexicon, C, blank, word_bonus, what):
+    """(lexicon, word_bonus) of a beam search over C classes, checked: lexicon None and the bonus at its default, or a
+    lexicon.Lexicon built for these classes and this blank with a finite bonus.  ValueError otherwise; needs no device."""
+    from .lexicon import Lexicon
+
+    bonus = _finite_number(word_bonus, "word_bonus", what)
+    if lexicon is None:
+        if bonus != 0.0:
+            raise ValueError(f"{what}: word_bonus needs a lexicon")
+        return None, bonus
+    if not isinstance(lexicon, Lexicon):
+        raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
+    if lexicon.num_classes != C or lexicon.blank != blank:
+        raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}, "
+                         f"the emissions have {C} with blank {blank}")
+    return lexicon, bonus
+
+
 def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
-                    lm_weight=1.0, length_bonus=0.0, lm_eos=True):
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
     """CTC prefix beam search on the device (wfl_ctc_beam_search through csrc/torch_ops.cpp; the rules: include/wfl.h,
     DESIGN.md section 17).  x: float32 [B,T,C] on a GPU, contiguous; lengths: int32 [B] on x's device
     (input_lengths_on_device) or None.  Returns (hyps, scores): hyps[b][r] the int64 CPU label tensor of rank r of
@@ -1011,14 +1036,20 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     the frames' log-sum-exps if `normalize`; a rank beyond the final beam is empty with score -inf.  Only the surviving
     labels and the scores leave the device.  lm: an lm.NGramLM -- the search of wfl_ctc_beam_search_lm (DESIGN.md section
     18): an extension by class c from LM state s adds lm_weight * step(s, c) + length_bonus, lm_eos adds lm_weight *
-    step(s, </s>) after the last frame and ranks again; the scores include these terms.  lm None: the call it was."""
+    step(s, </s>) after the last frame and ranks again; the scores include these terms.  lm None: the call it was.
+    lexicon: a lexicon.Lexicon -- the search of wfl_ctc_beam_search_lexicon: only sequences of
+    its words are returned, lm (if given) is the word LM over its word ids, a label adds length_bonus and a completed
+    word lm_weight * step(s, word) + word_bonus on top.  lexicon None: the call it was."""
     B, T, C = x.shape
     W, K, n = check_beam_arguments(C, beam_size, classes_per_frame, nbest, "ctc_beam_search")
     if not 0 <= int(blank) < C:
         raise ValueError(f"ctc_beam_search: blank index {blank} is outside [0, {C})")
-    lm, weight, bonus, eos = check_lm_arguments(lm, C, int(blank), lm_weight, length_bonus, lm_eos, "ctc_beam_search")
+    lexicon, omega = check_lexicon_arguments(lexicon, C, int(blank), word_bonus, "ctc_beam_search")
+    lm, weight, bonus, eos = check_lm_arguments(lm, C, int(blank), lm_weight, length_bonus, lm_eos, "ctc_beam_search", lexicon)
+    # (without a lexicon: the operator's call as it was, its new arguments at their defaults)
+    more = () if lexicon is None else (lexicon.on_device(x.device), omega)
     flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize),
-                                                  None if lm is None else lm.on_device(x.device), weight, bonus, eos)
+                                                  None if lm is None else lm.on_device(x.device), weight, bonus, eos, *more)
     rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
     return [list(rows[b * n:(b + 1) * n]) for b in range(B)], scores
 

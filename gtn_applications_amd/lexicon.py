@@ -1,0 +1,173 @@
+"""Lexicons for CTC.beam_search (host-side data preparation, like lm.py): the vocabulary a grapheme or word-piece CTC
+model may emit, as a trie over the words' spellings.
+
+A Lexicon is the packed trie of include/wfl.h (wfl_lexicon): a CSR of nodes with the root at
+node 0; node n owns the arcs [arc_ptr[n], arc_ptr[n+1]) = (arc_label, arc_next) with strictly ascending labels;
+arc_next >= 0 is an inner node, arc_next = -(v+1) completes word v and leads back to the root; no leaves are stored.
+Nodes are numbered breadth first, the children of a node in label order.
+
+The lexicon must be prefix-free -- no spelling is a proper prefix of another and no two words share one -- so that a
+label sequence has at most one segmentation into words: the search merges hypotheses by their prefix, and the trie node
+and LM state of a hypothesis must be functions of it.  Spellings that end in a separator class (a grapheme model's word
+separator) are prefix-free by construction.
+
+The word LM convention.  A word-level LM needs no class of its own: word v is LM label v, so
+`NGramLM.from_arpa(path, words, blank=len(words))` is a back-off acceptor over word ids -- V + 1 "classes", index V the
+blank that is never used, and </s> the label V + 1 = lm.num_classes.  check_word_lm() verifies exactly that where the
+two objects meet."""
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+
+
+class Lexicon:
+    """spellings[v]: the non-empty sequence of emission classes that spells word v (separator classes included);
+    num_classes: the C of the emissions, blank among them.  ValueError for an empty list, an empty spelling, a class
+    outside [0, C), the blank in a spelling, or a pair of words that breaks prefix-freeness (both are named).
+    words: optional names of the words, for messages."""
+
+    def __init__(self, spellings, num_classes, blank, words=None):
+        self.num_classes, self.blank = int(num_classes), int(blank)
+        spellings = [tuple(int(c) for c in s) for s in spellings]
+        if not spellings:
+            raise ValueError("Lexicon: no words")
+        if words is not None and len(list(words)) != len(spellings):
+            raise ValueError("Lexicon: as many names as spellings are needed")
+        self.word_names = None if words is None else list(words)
+        name = (lambda v: repr(self.word_names[v])) if self.word_names is not None else (lambda v: f"word {v}")
+        if self.num_classes < 1 or not 0 <= self.blank < self.num_classes:
+            raise ValueError(f"Lexicon: {self.num_classes} classes, blank {self.blank}")
+        hint = "; spellings that end in a separator class are prefix-free by construction"
+        children = [{}]  # node -> {label: child node, or ~v for the arc that completes word v}
+        for v, s in enumerate(spellings):
+            if not s:
+                raise ValueError(f"Lexicon: {name(v)} has an empty spelling")
+            for c in s:
+                if not 0 <= c < self.num_classes:
+                    raise ValueError(f"Lexicon: {name(v)} is spelled with class {c}, outside [0, {self.num_classes})")
+                if c == self.blank:
+                    raise ValueError(f"Lexicon: {name(v)} is spelled with the blank {c}")
+            node = 0
+            for c in s[:-1]:
+                nxt = children[node].get(c)
+                if nxt is None:
+                    nxt = children[node][c] = len(children)
+                    children.append({})
+                elif nxt < 0:
+                    raise ValueError(f"Lexicon: the spelling of {name(~nxt)} is a proper prefix of that of {name(v)}: "
+                                     f"the lexicon is not prefix-free{hint}")
+                node = nxt
+            nxt = children[node].get(s[-1])
+            if nxt is not None and nxt < 0:
+                raise ValueError(f"Lexicon: {name(~nxt)} and {name(v)} have the same spelling: a word has one spelling "
+                                 f"and a spelling one word{hint}")
+            if nxt is not None:
+                while nxt >= 0:  # (any word below: the first arc of every node on the way)
+                    nxt = children[nxt][min(children[nxt])]
+                raise ValueError(f"Lexicon: the spelling of {name(v)} is a proper prefix of that of {name(~nxt)}: "
+                                 f"the lexicon is not prefix-free{hint}")
+            children[node][s[-1]] = ~v
+        self.spellings = spellings
+        # breadth first from the root, children in label order
+        order, number = [0], {0: 0}
+        for n in order:
+            for c in sorted(children[n]):
+                k = children[n][c]
+                if k >= 0:
+                    number[k] = len(order)
+                    order.append(k)
+        arc_ptr, arc_label, arc_next = [0], [], []
+        for n in order:
+            for c in sorted(children[n]):
+                k = children[n][c]
+                arc_label.append(c)
+                arc_next.append(number[k] if k >= 0 else -(~k + 1))
+            arc_ptr.append(len(arc_label))
+        self.arc_ptr = np.asarray(arc_ptr, dtype=np.int32)
+        self.arc_label = np.asarray(arc_label, dtype=np.int32)
+        self.arc_next = np.asarray(arc_next, dtype=np.int32)
+        self.num_nodes, self.num_arcs, self.num_words = len(order), len(arc_label), len(spellings)
+        desc = N.Lexicon(self.num_nodes, self.num_arcs, self.num_words, 0, self.arc_ptr.ctypes.data,
+                         self.arc_label.ctypes.data, self.arc_next.ctypes.data)
+        if N.lib.wfl_lexicon_check(ctypes.byref(desc), self.num_classes, self.blank) != N.WFL_OK:
+            raise ValueError(f"Lexicon: {N.last_error()}")
+        self._arcs = [{int(arc_label[a]): int(arc_next[a]) for a in range(arc_ptr[n], arc_ptr[n + 1])}
+                      for n in range(self.num_nodes)]
+        self._on_device = {}
+
+    @classmethod
+    def from_words(cls, words, tokens, blank, wordsep=None, split=None):
+        """words: strings; tokens: the model's tokens in class order without the blank, blank: its class index, so token
+        i is class i below the blank and i + 1 from it on (the convention of NGramLM.from_arpa).  A word is split into
+        its characters, or by split(word) -> list of tokens (word pieces); with `wordsep` that token's class ends every
+        spelling.  ValueError names a word with a piece that is no token."""
+        tokens, blank = list(tokens), int(blank)
+        if not 0 <= blank <= len(tokens):
+            raise ValueError(f"Lexicon.from_words: blank {blank} is outside [0, {len(tokens)}]")
+        if len(set(tokens)) != len(tokens):
+            raise ValueError("Lexicon.from_words: a token appears twice")
+        label = {tok: (i if i < blank else i + 1) for i, tok in enumerate(tokens)}
+        if wordsep is not None and wordsep not in label:
+            raise ValueError(f"Lexicon.from_words: the word separator {wordsep!r} is not one of the model's tokens")
+        words = list(words)
+        spellings = []
+        for w in words:
+            pieces = list(w) if split is None else list(split(w))
+            for p in pieces:
+                if p not in label:
+                    raise ValueError(f"Lexicon.from_words: {p!r} of {w!r} is not one of the model's tokens")
+            spellings.append([label[p] for p in pieces] + ([label[wordsep]] if wordsep is not None else []))
+        return cls(spellings, len(tokens) + 1, blank, words=words)
+
+    # ------------------------------------------------------------------------------------------------------------
+    def walk(self, labels):
+        """(word ids, node): the one segmentation of the label sequence into words and the trie node it ends in (0:
+        at a word boundary); None if the sequence leaves the trie"""
+        found, node = [], 0
+        for c in labels:
+            nxt = self._arcs[node].get(int(c))
+            if nxt is None:
+                return None
+            if nxt < 0:
+                found.append(-(nxt + 1))
+                node = 0
+            else:
+                node = nxt
+        return found, node
+
+    def words(self, labels):
+        """the word ids of a label sequence that is a sequence of whole words; ValueError otherwise"""
+        at = self.walk(labels)
+        if at is None:
+            raise ValueError("Lexicon.words: the labels leave the lexicon")
+        if at[1] != 0:
+            raise ValueError("Lexicon.words: the labels end inside a word")
+        return at[0]
+
+    def on_device(self, device):
+        """the operators' DeviceLexicon (csrc/torch_ops.cpp) of this pack on `device`: `.ints` int32 [arc_ptr |
+        arc_label | arc_next] there and the wfl_lexicon that points into it.  Uploaded once per device and kept, as
+        NGramLM.on_device keeps its pack."""
+        import torch
+
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"Lexicon.on_device: {device} is not a GPU")
+        index = torch.cuda.current_device() if device.index is None else device.index
+        held = self._on_device.get(index)
+        if held is None:
+            ints = np.concatenate([self.arc_ptr, self.arc_label, self.arc_next])
+            held = self._on_device[index] = N.ops.DeviceLexicon(torch.from_numpy(ints).to(torch.device("cuda", index)),
+                                                                self.num_nodes, self.num_arcs, self.num_words)
+        return held
+
+
+def check_word_lm(lexicon, lm, what):
+    """ValueError unless `lm` (an lm.NGramLM) follows the word LM convention above for `lexicon`"""
+    V = lexicon.num_words
+    if lm.num_classes != V + 1 or lm.blank != V:
+        raise ValueError(f"{what}: with a lexicon the lm is a word LM over its {V} words -- num_classes {V + 1}, blank {V} "
+                         f"(NGramLM.from_arpa(path, words, blank=len(words))) --, this one has num_classes "
+                         f"{lm.num_classes}, blank {lm.blank}")

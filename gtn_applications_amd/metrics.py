@@ -134,14 +134,16 @@ def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=
 
 
 def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None, lm=None, lm_weight=1.0,
-                       length_bonus=0.0, lm_eos=True):
+                       length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
     """engine.ctc_beam_search's launches (best hypothesis only) and the counts behind them, on x's device: [B, 4] int64
     on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments).  lm,
-    lm_weight, length_bonus, lm_eos: as in engine.ctc_beam_search."""
+    lm_weight, length_bonus, lm_eos, lexicon, word_bonus: as in engine.ctc_beam_search."""
     ref, tables, _ = _staged(counter, targets, x)
-    lm, weight, bonus, eos = E.check_lm_arguments(lm, x.shape[2], int(blank), lm_weight, length_bonus, lm_eos, "errors")
+    lexicon, omega = E.check_lexicon_arguments(lexicon, x.shape[2], int(blank), word_bonus, "errors")
+    lm, weight, bonus, eos = E.check_lm_arguments(lm, x.shape[2], int(blank), lm_weight, length_bonus, lm_eos, "errors", lexicon)
+    more = () if lexicon is None else (lexicon.on_device(x.device), omega)
     return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref, tables,
-                                        None if lm is None else lm.on_device(x.device), weight, bonus, eos)
+                                        None if lm is None else lm.on_device(x.device), weight, bonus, eos, *more)
 
 
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):

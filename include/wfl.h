@@ -582,8 +582,8 @@ int wfl_decode_paths(const int32_t* paths, int64_t path_stride, int B, int T, in
  *   only pass over x; beam: a workgroup per utterance; write), no allocation, no synchronisation.
  *   WFL_ERR_INVALID: a NULL required pointer, B, T or C < 1, blank outside [0, C), beam outside [1, 64],
  *   classes_per_frame outside [1, min(C, 64)], nbest outside [1, beam], out_capacity too small.
- *   WFL_ERR_UNSUPPORTED: C > 16384.  No lexicon / word-level LM; CTC only.  A token-level n-gram LM and a length
- *   bonus: wfl_ctc_beam_search_lm below.
+ *   WFL_ERR_UNSUPPORTED: C > 16384.  CTC only.  A token-level n-gram LM and a length bonus: wfl_ctc_beam_search_lm
+ *   below; a lexicon and a word-level LM: wfl_ctc_beam_search_lexicon below that.
  * ------------------------------------------------------------------------------------------------ */
 /* out_capacity = B nbest T (int32 elements of `out`), ws_bytes = the device scratch of a call */
 int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
@@ -646,6 +646,61 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths /* or NULL */,
                            int classes_per_frame, int nbest, int normalize, const wfl_ngram_lm* lm, double lm_weight,
                            double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                            int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same search with a lexicon and an optional word-level n-gram LM (csrc/beam_kernels.hip).
+ *   Every rule of wfl_ctc_beam_search stands; with a = lm_weight, o = word_bonus, b = length_bonus the additions:
+ *     - lexicon form: a trie over the words' spellings (sequences of emission classes, never the blank), packed as a CSR
+ *       of nodes with the root at node 0.  Node n has the arcs [arc_ptr[n], arc_ptr[n+1]) = (arc_label, arc_next), labels
+ *       strictly ascending; arc_next >= 0: an inner node; arc_next = -(v+1): the arc completes word v and leads back to
+ *       the root.  No leaves are stored.  The lexicon is prefix-free (no spelling is a prefix of another): a label
+ *       sequence has at most one segmentation into words, so trie node and LM state are functions of the prefix;
+ *     - word LM form: a wfl_ngram_lm over word ids -- word v is label v, V = num_words is its unused blank and V + 1 its
+ *       </s> -- checked by wfl_ngram_lm_check with C = V + 1, blank = V; NULL: every word's step is 0;
+ *     - every hypothesis carries a trie node and an LM state, the empty prefix has the root and the LM's `start`;
+ *     - the extension i + c, base as in wfl_ctc_beam_search (pb_i if c is i's last label, else tot_i): c is searched
+ *       among the arcs of node_i (a binary search, at most 31 steps).  Absent: the extension does not exist.  An inner
+ *       arc: e = (s + base) + b, the new node is the arc's target, the LM state stays.  An arc that completes word v:
+ *       (l, nxt) = step(state_i, v), (0, -) without an LM; l = -inf: the extension does not exist; otherwise
+ *       e = (s + base) + ((a l + o) + b), the new node is the root and the new LM state nxt.  An extension with
+ *       s + base = -inf does not exist and is not looked up.  The kernel also skips the lookup of an extension that
+ *       cannot reach the W-th best stay entry even with the largest term, max(0, max(a step_min, a step_max) + o) + b
+ *       (step_min = step_max = 0 without an LM): such an entry is outside the beam whatever its arc;
+ *     - stays add nothing and keep node and state; a merged extension carries the same term as a new one, so unpruned
+ *       tot(l) = mass(l) + a LM(words(l)) + o #words + b |l| exactly;
+ *     - candidates (by acoustic score alone), the order of entries, the tie rule and the -inf drop rule do not change;
+ *     - after the last frame a rank whose node is not the root is dropped (it ends inside a word); with score_eos != 0
+ *       and an LM a remaining rank gets + a step(state, V + 1) and is dropped if that step is -inf; the remaining ranks
+ *       are ranked again by score, descending, ties to the earlier rank; nbest is taken after that; nothing left: the
+ *       empty sequence with score -inf.  T_b = 0 gives the empty sequence with score a step(start, V + 1), 0 without
+ *       score_eos or without an LM;
+ *     - normalize still subtracts the rows' log-sum-exps and nothing else; out holds the token labels as before.
+ *   lex, word_lm: structs in HOST memory of DEVICE pointers to packs that wfl_lexicon_check (for the same C and blank)
+ *   and wfl_ngram_lm_check (for V + 1 and V) accepted with host pointers -- the kernels trust them: they check no
+ *   index.  The same workspace (wfl_ctc_beam_workspace), outputs, three launches and guarantees as wfl_ctc_beam_search;
+ *   no global atomics, no cross-workgroup waits, every loop bounded by T_b, W, K, the back-off cap or 31 search steps.
+ *   WFL_ERR_INVALID: what wfl_ctc_beam_search refuses; lex or one of its arrays NULL, num_nodes, num_arcs or num_words
+ *   < 1 (or num_words = 2^31 - 1: </s> is V + 1); a weight or bonus that is not finite; for a non-NULL word_lm what wfl_ctc_beam_search_lm refuses.
+ *   Not here: a token-level LM together with a lexicon, LM look-ahead inside words, several spellings of one word,
+ *   out-of-vocabulary arcs.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct wfl_lexicon {
+  int32_t num_nodes, num_arcs, num_words, reserved;
+  const int32_t* arc_ptr;   /* [num_nodes + 1], arc_ptr[0] = 0, arc_ptr[num_nodes] = num_arcs */
+  const int32_t* arc_label; /* [num_arcs] */
+  const int32_t* arc_next;  /* [num_arcs], >= 0 inner node, -(v+1) completes word v */
+} wfl_lexicon;
+/* The pack check (host arrays, no device): sizes >= 1, arc_ptr ascending from 0 to num_arcs; labels strictly ascending
+ * within a node, in [0, C), never the blank; every inner target in [1, num_nodes) and the target of exactly one arc,
+ * every node reached from the root (a tree rooted at node 0); every node, the root included, has at least one arc (no
+ * dead ends); every word id in [0, num_words) is completed by exactly one arc.  WFL_ERR_INVALID names the first offence
+ * in wfl_last_error(). */
+int wfl_lexicon_check(const wfl_lexicon* lex, int C, int blank);
+int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank, int beam,
+                                int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
+                                double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)

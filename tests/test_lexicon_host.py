@@ -1,0 +1,213 @@
+"""CPU tests (-m "not gpu") of gtn_applications_amd/lexicon.py and libwfl's wfl_lexicon_check (include/wfl.h; DESIGN.md
+section 20): spellings from words, the packed trie literally, the walk over it, every refusal of a lexicon that is not
+one, every kind of bad pack handed to the check directly, and the word LM convention."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import beam_lm_reference as LR
+import beam_lexicon_reference as XR
+from gtn_applications_amd import _native as N
+from gtn_applications_amd import engine as E
+from gtn_applications_amd.lexicon import Lexicon, check_word_lm
+from gtn_applications_amd.lm import NGramLM
+
+# five words over classes 1..5 of C = 6 with the blank 0; 5 is the separator of three of them, one word has a single
+# label, one a doubled label
+FIVE = [(1, 5), (1, 2, 5), (2, 5), (3,), (2, 2, 4)]
+FIVE_PTR = [0, 3, 5, 7, 8, 9]
+FIVE_LABEL = [1, 2, 3, 2, 5, 2, 5, 5, 4]
+FIVE_NEXT = [1, 2, -4, 3, -1, 4, -3, -2, -5]
+
+
+def test_the_packed_arrays_of_a_hand_written_lexicon():
+    lex = Lexicon(FIVE, 6, 0)
+    assert (lex.num_nodes, lex.num_arcs, lex.num_words, lex.num_classes, lex.blank) == (5, 9, 5, 6, 0)
+    assert lex.arc_ptr.tolist() == FIVE_PTR and lex.arc_ptr.dtype == np.int32
+    assert lex.arc_label.tolist() == FIVE_LABEL and lex.arc_label.dtype == np.int32
+    assert lex.arc_next.tolist() == FIVE_NEXT and lex.arc_next.dtype == np.int32
+    # the order of the words does not change the trie, only the ids on its completing arcs
+    back = Lexicon(FIVE[::-1], 6, 0)
+    assert back.arc_ptr.tolist() == FIVE_PTR and back.arc_label.tolist() == FIVE_LABEL
+    assert back.arc_next.tolist() == [n if n >= 0 else -(4 - (-n - 1) + 1) for n in FIVE_NEXT]
+    assert ctypes.sizeof(N.Lexicon) == 16 + 3 * ctypes.sizeof(ctypes.c_void_p)
+
+
+def test_walk_and_words():
+    lex = Lexicon(FIVE, 6, 0)
+    assert lex.walk([]) == ([], 0)
+    assert lex.walk([1, 5, 3, 2, 2, 4]) == ([0, 3, 4], 0)
+    assert lex.walk([1, 2, 5, 1, 2]) == ([1], 3)  # (inside "1 2 5": node 3)
+    assert lex.walk([2]) == ([], 2)
+    assert lex.walk([4]) is None and lex.walk([1, 5, 1, 1]) is None and lex.walk([1, 0]) is None
+    assert lex.words([3, 3, 2, 5]) == [3, 3, 2]
+    assert lex.words(np.array([1, 2, 5])) == [1]
+    with pytest.raises(ValueError, match="inside a word"):
+        lex.words([1, 5, 2, 2])
+    with pytest.raises(ValueError, match="leave"):
+        lex.words([1, 5, 5])
+    # the restatement the device tests use segments alike
+    ref = {s: v for v, s in enumerate(FIVE)}
+    rs = np.random.RandomState(0)
+    for _ in range(200):
+        seq = tuple(int(c) for c in rs.randint(1, 6, size=rs.randint(0, 7)))
+        got, want = lex.walk(seq), XR.segment(ref, seq)
+        assert (got is None) == (want is None)
+        if got is not None:
+            assert got[0] == want[0] and (got[1] == 0) == (want[1] == ())
+
+
+@pytest.mark.parametrize("blank", [0, 2, 4])
+def test_from_words(blank):
+    tokens = ["a", "b", "c", "|"]  # four tokens, five classes
+    cls = {t: (i if i < blank else i + 1) for i, t in enumerate(tokens)}
+    words = ["ab", "b", "cab", "bb"]
+    lex = Lexicon.from_words(words, tokens, blank, wordsep="|")
+    assert (lex.num_classes, lex.blank, lex.num_words) == (5, blank, 4)
+    assert lex.spellings == [tuple(cls[ch] for ch in w) + (cls["|"],) for w in words]
+    assert lex.words([cls[ch] for ch in "cab|b|bb|"]) == [2, 1, 3]
+    assert blank not in lex.arc_label.tolist()
+    # without a separator: the characters alone (this vocabulary is prefix-free as it stands)
+    bare = Lexicon.from_words(["ab", "cab", "bb"], tokens, blank)
+    assert bare.spellings == [tuple(cls[ch] for ch in w) for w in ("ab", "cab", "bb")]
+    assert bare.words([cls[ch] for ch in "bbab"]) == [2, 0]
+    # word pieces through split()
+    pieces = ["_a", "b", "_ca", "_b"]
+    pc = {t: (i if i < blank else i + 1) for i, t in enumerate(pieces)}
+    split = {"ab": ["_a", "b"], "cab": ["_ca", "b"], "b": ["_b"]}
+    wp = Lexicon.from_words(["ab", "cab", "b"], pieces, blank, split=split.__getitem__)
+    assert wp.spellings == [(pc["_a"], pc["b"]), (pc["_ca"], pc["b"]), (pc["_b"],)]
+    for kw in (dict(words=["ad"]), dict(words=["ab"], wordsep="#"), dict(words=["ab"], blank=5), dict(words=["ab"], blank=-1),
+               dict(words=["ab"], tokens=["a", "b", "a"])):
+        with pytest.raises(ValueError):
+            Lexicon.from_words(**dict(dict(tokens=tokens, blank=blank, wordsep="|"), **kw))
+
+
+def test_what_is_no_lexicon_is_refused():
+    with pytest.raises(ValueError, match="no words"):
+        Lexicon([], 6, 0)
+    with pytest.raises(ValueError, match="word 1 has an empty spelling"):
+        Lexicon([(1,), ()], 6, 0)
+    with pytest.raises(ValueError, match=r"class 6, outside \[0, 6\)"):
+        Lexicon([(1,), (2, 6)], 6, 0)
+    with pytest.raises(ValueError, match="outside"):
+        Lexicon([(1,), (-1, 2)], 6, 0)
+    with pytest.raises(ValueError, match="blank"):
+        Lexicon([(1,), (2, 0)], 6, 0)
+    with pytest.raises(ValueError):
+        Lexicon([(1,)], 6, 6)
+    # prefix-freeness: both words are named, whichever comes first, and the separator is recommended
+    for spellings, first, second in (([(1, 2), (3,), (1, 2, 4)], "word 0", "word 2"), ([(1, 2, 4), (3,), (1, 2)], "word 2", "word 0"),
+                                     ([(1,), (1, 2, 3, 4)], "word 0", "word 1")):
+        with pytest.raises(ValueError, match=f"{first} is a proper prefix of that of {second}.*prefix-free.*separator"):
+            Lexicon(spellings, 6, 0)
+    with pytest.raises(ValueError, match="word 0 and word 2 have the same spelling.*separator"):
+        Lexicon([(1, 2), (3,), (1, 2)], 6, 0)
+    with pytest.raises(ValueError, match="'a' is a proper prefix of that of 'ab'"):
+        Lexicon.from_words(["ab", "a"], ["a", "b"], 2)
+    with pytest.raises(ValueError, match="'ab' and 'ab' have the same spelling"):
+        Lexicon.from_words(["ab", "b", "ab"], ["a", "b", "|"], 0, wordsep="|")
+    # the same vocabulary with a separator is a lexicon
+    assert Lexicon.from_words(["ab", "a"], ["a", "b", "|"], 3, wordsep="|").num_words == 2
+
+
+def _check(ptr, label, nxt, V, C=6, blank=0, N_=None, A=None, null=None):
+    arrays = dict(ptr=np.asarray(ptr, np.int32), label=np.asarray(label, np.int32), nxt=np.asarray(nxt, np.int32))
+    p = {k: (None if k == null else v.ctypes.data) for k, v in arrays.items()}
+    desc = N.Lexicon(len(ptr) - 1 if N_ is None else N_, len(label) if A is None else A, V, 0, p["ptr"], p["label"], p["nxt"])
+    rc = N.lib.wfl_lexicon_check(ctypes.byref(desc), C, blank)
+    return rc, N.last_error()
+
+
+def _edit(values, at, to):
+    values = list(values)
+    values[at] = to
+    return values
+
+
+BAD_PACKS = [
+    # sizes and pointers
+    (dict(ptr=[0], label=[], nxt=[], N_=0), "0 nodes"),
+    (dict(A=0), "0 arcs"),
+    (dict(V=0), "0 words"),
+    (dict(null="ptr"), "NULL"),
+    (dict(null="label"), "NULL"),
+    (dict(null="nxt"), "NULL"),
+    (dict(C=0), "0 classes"),
+    (dict(blank=6), "blank 6"),
+    (dict(blank=-1), "blank -1"),
+    # arc_ptr
+    (dict(ptr=_edit(FIVE_PTR, 0, 1)), "arc_ptr runs from 1"),
+    (dict(ptr=_edit(FIVE_PTR, 5, 8)), "arc_ptr runs from 0 to 8"),
+    (dict(ptr=_edit(FIVE_PTR, 2, 2)), "arc_ptr descends"),
+    (dict(ptr=_edit(FIVE_PTR, 1, 11)), "arc_ptr descends or leaves"),
+    # dead ends: an inner node, and the root
+    (dict(ptr=[0, 3, 5, 7, 8, 8], label=FIVE_LABEL[:8], nxt=FIVE_NEXT[:8]), "node 4 has no arc"),
+    (dict(ptr=[0, 0, 1], label=[1], nxt=[-1], V=1), "node 0 has no arc"),
+    # labels
+    (dict(label=_edit(FIVE_LABEL, 1, 1)), "not strictly ascending"),
+    (dict(label=_edit(FIVE_LABEL, 4, 1)), "not strictly ascending"),
+    (dict(label=_edit(FIVE_LABEL, 8, 6)), "label 6"),
+    (dict(label=_edit(FIVE_LABEL, 0, -1)), "label -1"),
+    (dict(label=_edit(FIVE_LABEL, 0, 0)), "never the blank 0"),
+    (dict(blank=4), "never the blank 4"),
+    # inner targets: in [1, N), each entered once, all reached
+    (dict(nxt=_edit(FIVE_NEXT, 3, 0)), "leads to node 0"),
+    (dict(nxt=_edit(FIVE_NEXT, 3, 5)), "leads to node 5"),
+    (dict(nxt=_edit(FIVE_NEXT, 3, 2)), "node 2 is the target of more than one arc"),
+    (dict(nxt=_edit(FIVE_NEXT, 3, -6), V=6), "node 3 is the target of no arc"),
+    (dict(ptr=[0, 1, 2, 4], label=[1, 1, 1, 2], nxt=[-1, 2, 1, -2], V=2), "1 of 3 nodes are reached"),
+    # words: in [0, V), each completed once
+    (dict(nxt=_edit(FIVE_NEXT, 2, -7)), "completes word 6 of 5"),
+    (dict(nxt=_edit(FIVE_NEXT, 2, -1)), "word 0 is completed by more than one arc"),
+    (dict(V=6), "word 5 is completed by no arc"),
+    (dict(nxt=_edit(FIVE_NEXT, 8, -(2 ** 31))), "completes word 2147483647"),
+]
+
+
+def test_the_good_pack_passes_the_check():
+    assert _check(FIVE_PTR, FIVE_LABEL, FIVE_NEXT, 5)[0] == N.WFL_OK
+    assert _check([0, 1], [2], [-1], 1, C=3, blank=0)[0] == N.WFL_OK  # one word of one label: a root with a single arc
+
+
+@pytest.mark.parametrize("change,message", BAD_PACKS, ids=[f"{i}-{m[:24]}" for i, (_, m) in enumerate(BAD_PACKS)])
+def test_every_kind_of_bad_pack_is_refused(change, message):
+    args = dict(dict(ptr=FIVE_PTR, label=FIVE_LABEL, nxt=FIVE_NEXT, V=5), **change)
+    rc, error = _check(**args)
+    assert rc == N.ERR_INVALID
+    assert "lexicon_check" in error and message in error, error
+
+
+def test_the_word_lm_convention(tmp_path):
+    words = ["ab", "b", "cab", "bb"]
+    lex = Lexicon.from_words(words, ["a", "b", "c", "|"], 4, wordsep="|")
+
+    def word_lm(names, blank, seed=1):
+        p = tmp_path / f"w{len(names)}_{blank}.arpa"
+        p.write_text(LR.random_arpa(np.random.RandomState(seed), names, 2, 0.7))
+        return NGramLM.from_arpa(str(p), names, blank)
+
+    lm = word_lm(words, len(words))
+    assert (lm.num_classes, lm.blank) == (lex.num_words + 1, lex.num_words)
+    check_word_lm(lex, lm, "t")
+    # word v is label v, </s> the label V + 1: the LM's score of a word sequence is the reference's
+    ref = LR.ArpaLM(LR.random_arpa(np.random.RandomState(1), words, 2, 0.7), words, len(words))
+    ids = lex.words(lex.spellings[2] + lex.spellings[0] + lex.spellings[0])
+    assert ids == [2, 0, 0]
+    assert abs(lm.score(ids) - ref.score(ids)) <= 1e-12 or lm.score(ids) == ref.score(ids)
+    assert lm.step(lm.start, lex.num_words + 1)[0] == ref.step(ref.start, LR.EOS)[0]
+    assert E.check_lm_arguments(lm, 5, 4, 0.5, 0.1, False, "t", lex) == (lm, 0.5, 0.1, False)
+    # the length bonus needs no lm where there is a lexicon; the weight and </s> still do
+    assert E.check_lm_arguments(None, 5, 4, 1.0, 0.3, True, "t", lex) == (None, 1.0, 0.3, True)
+    for kw in (dict(lm_weight=0.5), dict(lm_eos=False)):
+        with pytest.raises(ValueError, match="need an lm"):
+            E.check_lm_arguments(None, 5, 4, **dict(dict(lm_weight=1.0, length_bonus=0.0, lm_eos=True, what="t", lexicon=lex), **kw))
+    # mismatches: an LM over fewer or more words, the blank elsewhere
+    for bad in (word_lm(words[:3], 3), word_lm(words, 0), word_lm(words + ["c"], 5), word_lm(words, 2)):
+        with pytest.raises(ValueError, match="word LM over its 4 words"):
+            check_word_lm(lex, bad, "t")
+        with pytest.raises(ValueError, match="word LM"):
+            E.check_lm_arguments(bad, 5, 4, 1.0, 0.0, True, "t", lex)
+    assert E.check_lexicon_arguments(lex, 5, 4, np.float32(0.5), "t") == (lex, 0.5)
+    assert E.check_lexicon_arguments(None, 5, 4, 0.0, "t") == (None, 0.0)
