@@ -6,7 +6,6 @@ on host threads (ctc.py:38-65), this sends the whole batch through the CTC fast-
 (csrc/ctc_kernels.hip; up to four target positions per lane) -- or, for targets longer than 255
 labels, through the generic lattice engine (csrc/lattice_kernels.hip).  Both are HIP paths; there is no CPU path.
 """
-import math
 import operator
 import os
 
@@ -348,8 +347,9 @@ class CTC(torch.nn.Module):
         flat, kept = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
         return E.split_rows(flat, kept, torch.int64)
 
-    def _beam_plan(self, outputs, beam_size, classes_per_frame, nbest, input_lengths, what):
-        """The arguments of a beam search, checked before anything needs a device: (W, K, nbest, lengths or None)"""
+    def _beam_plan(self, outputs, input_lengths, what, *options):
+        """The arguments of a beam search, checked before anything needs a device: (the E.BeamPlan of `options`, which
+        are BeamPlan.checked's from beam_size to word_bonus; lengths or None)"""
         if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
             raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
         if not outputs.dtype.is_floating_point:
@@ -357,22 +357,8 @@ class CTC(torch.nn.Module):
         B, T, C = outputs.shape
         if C < 1:
             raise ValueError(f"{what}: outputs have no classes")
-        if not 0 <= self.blank < C:
-            raise ValueError(f"{what}: blank index {self.blank} is outside [0, {C})")
-        W, K, n = E.check_beam_arguments(C, beam_size, classes_per_frame, nbest, what)
-        lens = None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
-        return W, K, n, lens
-
-    def _beam_lm(self, outputs, lm, lm_weight, length_bonus, lm_eos, what, lexicon=None, word_bonus=0.0):
-        """The language model and lexicon arguments of a beam search, checked like the rest: the keywords of the
-        engine's call, none without an lm or a lexicon (the call it was)"""
-        C = outputs.shape[2]
-        lexicon, omega = E.check_lexicon_arguments(lexicon, C, self.blank, word_bonus, what)
-        lm, weight, bonus, eos = E.check_lm_arguments(lm, C, self.blank, lm_weight, length_bonus, lm_eos, what, lexicon)
-        fused = {} if lm is None else dict(lm=lm, lm_weight=weight, length_bonus=bonus, lm_eos=eos)
-        if lexicon is not None:
-            fused.update(lexicon=lexicon, word_bonus=omega, length_bonus=bonus)
-        return fused
+        plan = E.BeamPlan.checked(C, self.blank, *options, what)
+        return plan, None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
 
     @staticmethod
     def _beam_emissions(outputs):
@@ -402,27 +388,16 @@ class CTC(torch.nn.Module):
         completed word adds lm_weight * log P_LM(word | history) + word_bonus and every label length_bonus; the output
         is still the token labels, lexicon.words() gives the words.  `word_bonus` needs a lexicon.  CTC only: ASG and
         the Transducer's token graphs have no beam search."""
-        W, K, n, lens = self._beam_plan(outputs, beam_size, classes_per_frame, nbest, input_lengths, "CTC.beam_search")
-        fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.beam_search", lexicon, word_bonus)
-        B, T, _ = outputs.shape
-        if B == 0 or (T == 0 and not fused):
-            hyps, scores = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)], \
-                torch.zeros((B, n), dtype=torch.float64)
-        elif T == 0:  # (no frame: the empty sequence -- no word either --, scored by the LM's </s> alone)
-            # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
-            end = 0.0
-            if "lm" in fused and fused["lm_eos"]:
-                step = fused["lm"].score([], eos=True)
-                end = -math.inf if step == -math.inf else fused["lm_weight"] * step
-            hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)]
-            scores = torch.full((B, n), -math.inf, dtype=torch.float64)
-            scores[:, 0] = end
+        plan, lens = self._beam_plan(outputs, input_lengths, "CTC.beam_search", beam_size, classes_per_frame, nbest, lm,
+                                     lm_weight, length_bonus, lm_eos, lexicon, word_bonus)
+        if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+            hyps, scores = plan.no_frames(outputs.shape[0])
         else:
             x = self._beam_emissions(outputs)
             with torch.cuda.device(x.device), torch.no_grad():
                 xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
-                hyps, scores = E.ctc_beam_search(x, self.blank, W, K, n, lengths=xlen, normalize=True, **fused)
-        if n == 1:
+                hyps, scores = plan.search(x, xlen, normalize=True)
+        if plan.nbest == 1:
             hyps = [h[0] for h in hyps]
         return (hyps, scores) if return_scores else hyps
 
@@ -437,21 +412,18 @@ class CTC(torch.nn.Module):
         counted behind the beam launch on its device buffers; `lm`, `lm_weight`, `length_bonus`, `lm_eos`, `lexicon`,
         `word_bonus` are beam_search's and need a beam_size."""
         if beam_size is None:
-            if lm is not None or lexicon is not None:
-                raise ValueError("CTC.errors: lm and lexicon need a beam_size")
-            E.check_lexicon_arguments(None, outputs.shape[2], self.blank, word_bonus, "CTC.errors")
-            E.check_lm_arguments(None, outputs.shape[2], self.blank, lm_weight, length_bonus, lm_eos, "CTC.errors")
-        if beam_size is not None:
-            W, K, _, lens = self._beam_plan(outputs, beam_size, classes_per_frame, 1, input_lengths, "CTC.errors")
-            fused = self._beam_lm(outputs, lm, lm_weight, length_bonus, lm_eos, "CTC.errors", lexicon, word_bonus)
+            E.BeamPlan.refuse_without_beam(lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, "CTC.errors")
+        else:
+            plan, lens = self._beam_plan(outputs, input_lengths, "CTC.errors", beam_size, classes_per_frame, 1, lm, lm_weight,
+                                         length_bonus, lm_eos, lexicon, word_bonus)
             C = outputs.shape[2]
             counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
-                return counter(self.beam_search(outputs, W, K, input_lengths=lens, **fused), targets)
+                return counter([h[0] for h in plan.no_frames(outputs.shape[0])[0]], targets)
             x = self._beam_emissions(outputs)
             with torch.cuda.device(x.device), torch.no_grad():
                 xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
-                return counter.totals(M.beam_search_errors(counter, targets, x, self.blank, W, K, lengths=xlen, **fused))
+                return counter.totals(M.beam_search_errors(counter, targets, x, plan, lengths=xlen))
         lens = None
         if input_lengths is not None:
             lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.errors")

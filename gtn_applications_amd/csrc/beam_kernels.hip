@@ -843,24 +843,36 @@ int wfl_ngram_lm_check(wfl_ngram_lm* lm, int C, int blank) {
   return WFL_OK;
 }
 
+// The LM terms of a launch, for the two entries below: the shape of `lm` and its step bounds checked (none, where the
+// entry allows that: the lexicon search without a word LM, whose step is 0 and whose arrays are not read), and `d`
+// filled from it and the call's scalars -- all but d->bound, which each entry forms by its own expression.
+static int beam_lm_terms(const char* what, const wfl_ngram_lm* lm, bool optional, int eos, double alpha, double beta,
+                         int score_eos, BeamLm* d) {
+  if (lm || !optional) {
+    if (const int rc = ngram_lm_shape(what, lm)) return rc;
+    if (lm->step_min != lm->step_min || lm->step_max != lm->step_max) {
+      set_error("%s: the language model's step_min or step_max is NaN", what);
+      return WFL_ERR_INVALID;
+    }
+  }
+  const wfl_ngram_lm none = {}, &m = lm ? *lm : none;  // (none: null arrays, start 0)
+  d->arc_ptr = m.arc_ptr, d->arc_label = m.arc_label, d->arc_next = m.arc_next, d->bo_next = m.bo_next;
+  d->arc_w = m.arc_w, d->bo_w = m.bo_w;
+  d->start = m.start, d->eos = eos, d->alpha = alpha, d->beta = beta, d->score_eos = score_eos ? 1 : 0;
+  return WFL_OK;
+}
+
 int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
                            int classes_per_frame, int nbest, int normalize, const wfl_ngram_lm* lm, double lm_weight,
                            double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                            int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "ctc_beam_search_lm";
-  if (const int rc = ngram_lm_shape(what, lm)) return rc;
-  if (lm->step_min != lm->step_min || lm->step_max != lm->step_max) {
-    set_error("%s: the language model's step_min or step_max is NaN", what);
-    return WFL_ERR_INVALID;
-  }
+  BeamLm d;
+  if (const int rc = beam_lm_terms(what, lm, false, C, lm_weight, length_bonus, score_eos, &d)) return rc;
   if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
     set_error("%s: lm_weight %g and length_bonus %g must be finite", what, lm_weight, length_bonus);
     return WFL_ERR_INVALID;
   }
-  BeamLm d;
-  d.arc_ptr = lm->arc_ptr, d.arc_label = lm->arc_label, d.arc_next = lm->arc_next, d.bo_next = lm->bo_next;
-  d.arc_w = lm->arc_w, d.bo_w = lm->bo_w;
-  d.start = lm->start, d.eos = C, d.alpha = lm_weight, d.beta = length_bonus, d.score_eos = score_eos ? 1 : 0;
   // the largest LM term of an extension, by the operations the kernel forms a term with (0 * inf: no bound)
   const double t0 = lm_weight * lm->step_min, t1 = lm_weight * lm->step_max;
   d.bound = (t0 != t0 || t1 != t1) ? __builtin_inf() : fmax(t0, t1) + length_bonus;
@@ -972,27 +984,15 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, i
                                 double* scores, void* stream) {
   const char* what = "ctc_beam_search_lexicon";
   if (const int rc = lexicon_shape(what, lex)) return rc;
-  if (word_lm) {
-    if (const int rc = ngram_lm_shape(what, word_lm)) return rc;
-    if (word_lm->step_min != word_lm->step_min || word_lm->step_max != word_lm->step_max) {
-      set_error("%s: the language model's step_min or step_max is NaN", what);
-      return WFL_ERR_INVALID;
-    }
-  }
+  BeamLex d;
+  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
+  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lm)) return rc;
   if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
     set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
     return WFL_ERR_INVALID;
   }
-  BeamLex d;
   d.arc_ptr = lex->arc_ptr, d.arc_label = lex->arc_label, d.arc_next = lex->arc_next;
   d.has_lm = word_lm ? 1 : 0;
-  d.lm.arc_ptr = d.lm.arc_label = d.lm.arc_next = d.lm.bo_next = nullptr, d.lm.arc_w = d.lm.bo_w = nullptr, d.lm.start = 0;
-  if (word_lm) {
-    d.lm.arc_ptr = word_lm->arc_ptr, d.lm.arc_label = word_lm->arc_label, d.lm.arc_next = word_lm->arc_next;
-    d.lm.bo_next = word_lm->bo_next, d.lm.arc_w = word_lm->arc_w, d.lm.bo_w = word_lm->bo_w, d.lm.start = word_lm->start;
-  }
-  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
-  d.lm.eos = lex->num_words + 1, d.lm.alpha = lm_weight, d.lm.beta = length_bonus, d.lm.score_eos = score_eos ? 1 : 0;
   d.omega = word_bonus;
   // (without a word LM every word's step is 0: the bounds of step are [0, 0])
   d.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);

@@ -987,37 +987,53 @@ struct DeviceLexicon {
   }
 };
 
-// lm none: wfl_ctc_beam_search, the call it was (lm_weight, length_bonus and score_eos are not read);
-// given: wfl_ctc_beam_search_lm.  lexicon given: wfl_ctc_beam_search_lexicon, lm (or none) its word LM.
-Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
-                       int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
-                       double length_bonus, bool score_eos, const std::shared_ptr<DeviceLexicon>& lexicon, double word_bonus) {
+// The options of one beam search as both beam ops take them (engine.py's BeamPlan.on_device binds the values it has
+// checked).  lm none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not read; lexicon: lm is its word LM.
+struct BeamPlan {
+  int blank, beam, K, nbest;
+  std::shared_ptr<DeviceLm> lm;
+  double lm_weight, length_bonus;
+  bool score_eos;
+  std::shared_ptr<DeviceLexicon> lexicon;
+  double word_bonus;
+  BeamPlan(int blank_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
+           double length_bonus_, bool score_eos_, const std::shared_ptr<DeviceLexicon>& lexicon_, double word_bonus_)
+      : blank(blank_), beam(beam_), K(K_), nbest(nbest_), lm(lm_), lm_weight(lm_weight_), length_bonus(length_bonus_),
+        score_eos(score_eos_), lexicon(lexicon_), word_bonus(word_bonus_) {
+    TORCH_CHECK(!lm || !lexicon || lm->ints.device() == lexicon->ints.device(),
+                "ctc_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
+  }
+};
+
+// nothing fused: wfl_ctc_beam_search, the call it was; an lm: wfl_ctc_beam_search_lm; a lexicon: wfl_ctc_beam_search_lexicon
+Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& p, int nbest,
+                       bool normalize) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
               "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
   const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
   const at::Tensor lt = checked_lengths(lengths, x, "ctc_beam_search");
-  TORCH_CHECK(!lm || lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
-  TORCH_CHECK(!lexicon || lexicon->ints.device() == x.device(),
+  TORCH_CHECK(!p.lm || p.lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
+  TORCH_CHECK(!p.lexicon || p.lexicon->ints.device() == x.device(),
               "ctc_beam_search_lexicon: the lexicon's arrays must be on x's device");
   return {x, B, (int64_t)B * nbest, true, "ctc_beam_search",
           [=](int64_t* capacity, int64_t* ws_bytes) {
-            check(wfl_ctc_beam_workspace(B, T, C, (int)beam, (int)K, (int)nbest, capacity, ws_bytes), "ctc_beam_search");
+            check(wfl_ctc_beam_workspace(B, T, C, p.beam, p.K, nbest, capacity, ws_bytes), "ctc_beam_search");
           },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
             const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
-            if (lexicon)
-              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
-                                                normalize ? 1 : 0, &lexicon->lex, lm ? &lm->lm : nullptr, lm_weight, word_bonus,
-                                                length_bonus, score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+            if (p.lexicon)
+              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
+                                                &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus,
+                                                p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
                     "ctc_beam_search_lexicon");
-            else if (lm)
-              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
-                                           normalize ? 1 : 0, &lm->lm, lm_weight, length_bonus, score_eos ? 1 : 0, ws, out, cap,
-                                           offs, scores, s),
+            else if (p.lm)
+              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
+                                           &p.lm->lm, p.lm_weight, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs,
+                                           scores, s),
                     "ctc_beam_search_lm");
             else
-              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, B, T, C, (int)blank, (int)beam, (int)K, (int)nbest,
-                                        normalize ? 1 : 0, ws, out, cap, offs, scores, s),
+              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0, ws, out,
+                                        cap, offs, scores, s),
                     "ctc_beam_search");
           }};
 }
@@ -1086,14 +1102,9 @@ std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t
 }
 
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
-py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam, int64_t K,
-                          int64_t nbest, bool normalize, const std::shared_ptr<DeviceLm>& lm, double lm_weight,
-                          double length_bonus, bool score_eos, const std::shared_ptr<DeviceLexicon>& lexicon,
-                          double word_bonus) {
-  const Collected r = hypotheses_collect(
-      beam_source(x, lengths, blank, beam, K, nbest, normalize, lm, lm_weight, length_bonus, score_eos, lexicon, word_bonus),
-      true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), nbest}));
+py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& plan, bool normalize) {
+  const Collected r = hypotheses_collect(beam_source(x, lengths, plan, plan.nbest, normalize), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1221,12 +1232,10 @@ at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop,
   return hypotheses_errors(paths_source(paths, T, drop, num_replabels, flags), ref, tables);
 }
 
-at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, int64_t blank, int64_t beam,
-                                  int64_t K, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables,
-                                  const std::shared_ptr<DeviceLm>& lm, double lm_weight, double length_bonus, bool score_eos,
-                                  const std::shared_ptr<DeviceLexicon>& lexicon, double word_bonus) {
-  return hypotheses_errors(
-      beam_source(x, lengths, blank, beam, K, 1, false, lm, lm_weight, length_bonus, score_eos, lexicon, word_bonus), ref, tables);
+// (the plan's first rank, unnormalised: nothing reads the scores)
+at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& plan,
+                                  const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(beam_source(x, lengths, plan, 1, false), ref, tables);
 }
 
 }  // namespace
@@ -1249,17 +1258,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "hyp, ref: (int32 [exp_ptr: V + 1 | exp_sym] tensor, V, longest expansion) or None: a label is its own symbol")
       .def("check_labels", &ErrorTables::check_labels, py::arg("hyp"), py::arg("ref"),
            "ValueError for a staged label (StagedTargets or None) outside its table; needs no device");
-  m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
-        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"), py::arg("lm"), py::arg("lm_weight"),
-        py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon") = std::shared_ptr<DeviceLexicon>(),
-        py::arg("word_bonus") = 0.0,
-        "CTC prefix beam search on the device, with an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is "
-        "scored) or None, and with a lexicon (DeviceLexicon; lm is then its word LM; a word bonus) or None: (labels "
-        "int64 CPU, offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])");
-  m.def("ctc_beam_search_errors", &ctc_beam_search_errors, py::arg("x"), py::arg("lengths"), py::arg("blank"), py::arg("beam"),
-        py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"), py::arg("lm"), py::arg("lm_weight"),
-        py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon") = std::shared_ptr<DeviceLexicon>(),
-        py::arg("word_bonus") = 0.0,
+  py::class_<BeamPlan>(m, "BeamPlan", "the options of one CTC beam search, bound (engine.BeamPlan.on_device)")
+      .def(py::init<int, int, int, int, const std::shared_ptr<DeviceLm>&, double, double, bool,
+                    const std::shared_ptr<DeviceLexicon>&, double>(),
+           py::arg("blank"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("lm"), py::arg("lm_weight"),
+           py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon"), py::arg("word_bonus"),
+           "an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is scored) or None, and a lexicon "
+           "(DeviceLexicon; lm is then its word LM; a word bonus) or None");
+  m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("plan"), py::arg("normalize"),
+        "CTC prefix beam search on the device by a BeamPlan: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores "
+        "float64 CPU [B, nbest])");
+  m.def("ctc_beam_search_errors", &ctc_beam_search_errors, py::arg("x"), py::arg("lengths"), py::arg("plan"), py::arg("ref"),
+        py::arg("tables"),
         "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),

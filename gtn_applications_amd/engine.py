@@ -8,7 +8,7 @@ import math
 import operator
 import sys
 import threading
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -943,88 +943,120 @@ def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int3
 BEAM_MAX, BEAM_MAX_CLASSES = 64, 16384  # wfl_ctc_beam_search: beam width / classes per frame; classes in all
 
 
-def check_beam_arguments(C, beam_size, classes_per_frame, nbest, what):
-    """(beam, classes per frame, nbest) as ints, checked against the limits of wfl_ctc_beam_search for C classes;
-    classes_per_frame None: min(C, 32) -- a default, not a tuned value.  ValueError otherwise; needs no device."""
-    def integer(v):
-        try:
-            return None if isinstance(v, bool) else operator.index(v)
-        except TypeError:
-            return None
+class BeamPlan(namedtuple(
+        "BeamPlan", "C blank beam classes_per_frame nbest lm lm_weight length_bonus lm_eos lexicon word_bonus")):
+    """The options of one CTC beam search over C classes, checked once (`checked`, the one constructor) and handed on whole:
+    CTC.beam_search, CTC.errors(beam_size=) and ctc_beam_search build one plan per call, nothing behind them checks or
+    lists the options again.  ints, floats, lm_eos a bool, lm an lm.NGramLM or None, lexicon a lexicon.Lexicon or None
+    (lm is then its word LM).  Only on_device() and search() need a device."""
+    __slots__ = ()
 
-    W = integer(beam_size)
-    if W is None or not 1 <= W <= BEAM_MAX:
-        raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
-    K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
-    if K is None or not 1 <= K <= min(C, BEAM_MAX):
-        raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
-                         f"got {classes_per_frame!r}")
-    n = integer(nbest)
-    if n is None or not 1 <= n <= W:
-        raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
-    if C > BEAM_MAX_CLASSES:
-        raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
-    return W, K, n
+    @classmethod
+    def checked(cls, C, blank, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus,
+                what):
+        """The plan of these arguments, within the limits of wfl_ctc_beam_search, or ValueError (`what`: the call they were
+        given to).  classes_per_frame None: min(C, 32) -- a default, not a tuned value.  lm None: lm_weight and lm_eos at
+        their defaults, and length_bonus unless there is a lexicon, whose search applies it to every label; an lm is built
+        for these classes and this blank, or is the lexicon's word LM (the convention of lexicon.py).  lexicon None: no
+        word_bonus.  Numbers: Python or numpy numbers, one-element tensors (a sweep over weights), never bools or strings."""
+        from .lexicon import Lexicon, check_word_lm
+        from .lm import NGramLM
 
+        def integer(v):
+            try:
+                return None if isinstance(v, bool) else operator.index(v)
+            except TypeError:
+                return None
 
-def _finite_number(v, name, what):
-    """a finite float from a Python or numpy number or a one-element tensor (a sweep over numpy weights); never from a
-    bool or a string"""
-    f = math.nan
-    if not isinstance(v, (bool, np.bool_, str, bytes)):
-        try:
-            f = float(v)
-        except (TypeError, ValueError):
-            pass
-    if not math.isfinite(f):
-        raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-    return f
+        def finite(v, name):
+            f = math.nan
+            if not isinstance(v, (bool, np.bool_, str, bytes)):
+                try:
+                    f = float(v)
+                except (TypeError, ValueError):
+                    pass
+            if not math.isfinite(f):
+                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+            return f
 
+        W = integer(beam_size)
+        if W is None or not 1 <= W <= BEAM_MAX:
+            raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+        K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
+        if K is None or not 1 <= K <= min(C, BEAM_MAX):
+            raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
+                             f"got {classes_per_frame!r}")
+        n = integer(nbest)
+        if n is None or not 1 <= n <= W:
+            raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
+        if C > BEAM_MAX_CLASSES:
+            raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
+        if not 0 <= int(blank) < C:
+            raise ValueError(f"{what}: blank index {blank} is outside [0, {C})")
+        blank = int(blank)
+        omega = finite(word_bonus, "word_bonus")
+        if lexicon is None:
+            if omega != 0.0:
+                raise ValueError(f"{what}: word_bonus needs a lexicon")
+        elif not isinstance(lexicon, Lexicon):
+            raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
+        elif lexicon.num_classes != C or lexicon.blank != blank:
+            raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}, "
+                             f"the emissions have {C} with blank {blank}")
+        weight, bonus = finite(lm_weight, "lm_weight"), finite(length_bonus, "length_bonus")
+        if not isinstance(lm_eos, (bool, np.bool_)):
+            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+        lm_eos = bool(lm_eos)
+        if lm is None:
+            if weight != 1.0 or (bonus != 0.0 and lexicon is None) or lm_eos is not True:
+                raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm" +
+                                 ("" if lexicon is None else " (with a lexicon: lm_weight and lm_eos do)"))
+        elif not isinstance(lm, NGramLM):
+            raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
+        elif lexicon is not None:
+            check_word_lm(lexicon, lm, what)
+        elif lm.num_classes != C or lm.blank != blank:
+            raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
+                             f"the emissions have {C} with blank {blank}")
+        return cls(C, blank, W, K, n, lm, weight, bonus, lm_eos, lexicon, omega)
 
-def check_lm_arguments(lm, C, blank, lm_weight, length_bonus, lm_eos, what, lexicon=None):
-    """(lm, lm_weight, length_bonus, lm_eos) of a beam search over C classes, checked: lm None and the rest at their
-    defaults, or an lm.NGramLM built for these classes and this blank with a finite weight and bonus.  With a `lexicon`
-    (already checked, check_lexicon_arguments) the lm is its word LM instead -- the convention of lexicon.py, checked
-    here --, and the length bonus needs no lm: the lexicon search applies it to every label.  ValueError otherwise;
-    needs no device."""
-    from .lexicon import check_word_lm
-    from .lm import NGramLM
+    @classmethod
+    def refuse_without_beam(cls, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, what):
+        """ValueError for any of a beam search's keywords in a call that runs none: each must be at its default"""
+        if lm is not None or lexicon is not None:
+            raise ValueError(f"{what}: lm and lexicon need a beam_size")
+        cls.checked(1, 0, 1, None, 1, None, lm_weight, length_bonus, lm_eos, None, word_bonus, what)  # (only they can fail)
 
-    weight, bonus = _finite_number(lm_weight, "lm_weight", what), _finite_number(length_bonus, "length_bonus", what)
-    if not isinstance(lm_eos, (bool, np.bool_)):
-        raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
-    lm_eos = bool(lm_eos)
-    if lm is None:
-        if weight != 1.0 or (bonus != 0.0 and lexicon is None) or lm_eos is not True:
-            raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm" +
-                             ("" if lexicon is None else " (with a lexicon: lm_weight and lm_eos do)"))
-        return None, weight, bonus, lm_eos
-    if not isinstance(lm, NGramLM):
-        raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
-    if lexicon is not None:
-        check_word_lm(lexicon, lm, what)
-    elif lm.num_classes != C or lm.blank != blank:
-        raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
-                         f"the emissions have {C} with blank {blank}")
-    return lm, weight, bonus, lm_eos
+    def no_frames(self, B):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
+        empty sequence -- no word either --, the first scored by the LM's </s> alone"""
+        n = self.nbest
+        hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)]
+        if self.lm is None and self.lexicon is None:
+            return hyps, torch.zeros((B, n), dtype=torch.float64)
+        # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
+        end = 0.0
+        if self.lm is not None and self.lm_eos:
+            step = self.lm.score([], eos=True)
+            end = -math.inf if step == -math.inf else self.lm_weight * step
+        scores = torch.full((B, n), -math.inf, dtype=torch.float64)
+        scores[:, 0] = end
+        return hyps, scores
 
+    def on_device(self, device):
+        """The plan as the operators take it (ops.BeamPlan, csrc/torch_ops.cpp), its lm and lexicon on `device` (their
+        own per-device caches: nothing is uploaded twice)"""
+        return N.ops.BeamPlan(blank=self.blank, beam=self.beam, classes_per_frame=self.classes_per_frame, nbest=self.nbest,
+                              lm=None if self.lm is None else self.lm.on_device(device), lm_weight=self.lm_weight,
+                              length_bonus=self.length_bonus, score_eos=self.lm_eos,
+                              lexicon=None if self.lexicon is None else self.lexicon.on_device(device),
+                              word_bonus=self.word_bonus)
 
-def check_lexicon_arguments(lexicon, C, blank, word_bonus, what):
-    """(lexicon, word_bonus) of a beam search over C classes, checked: lexicon None and the bonus at its default, or a
-    lexicon.Lexicon built for these classes and this blank with a finite bonus.  ValueError otherwise; needs no device."""
-    from .lexicon import Lexicon
-
-    bonus = _finite_number(word_bonus, "word_bonus", what)
-    if lexicon is None:
-        if bonus != 0.0:
-            raise ValueError(f"{what}: word_bonus needs a lexicon")
-        return None, bonus
-    if not isinstance(lexicon, Lexicon):
-        raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
-    if lexicon.num_classes != C or lexicon.blank != blank:
-        raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}, "
-                         f"the emissions have {C} with blank {blank}")
-    return lexicon, bonus
+    def search(self, x, lengths=None, normalize=True):
+        """ctc_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's"""
+        flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, self.on_device(x.device), bool(normalize))
+        rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
+        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
 
 
 def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
@@ -1039,19 +1071,10 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     step(s, </s>) after the last frame and ranks again; the scores include these terms.  lm None: the call it was.
     lexicon: a lexicon.Lexicon -- the search of wfl_ctc_beam_search_lexicon: only sequences of
     its words are returned, lm (if given) is the word LM over its word ids, a label adds length_bonus and a completed
-    word lm_weight * step(s, word) + word_bonus on top.  lexicon None: the call it was."""
-    B, T, C = x.shape
-    W, K, n = check_beam_arguments(C, beam_size, classes_per_frame, nbest, "ctc_beam_search")
-    if not 0 <= int(blank) < C:
-        raise ValueError(f"ctc_beam_search: blank index {blank} is outside [0, {C})")
-    lexicon, omega = check_lexicon_arguments(lexicon, C, int(blank), word_bonus, "ctc_beam_search")
-    lm, weight, bonus, eos = check_lm_arguments(lm, C, int(blank), lm_weight, length_bonus, lm_eos, "ctc_beam_search", lexicon)
-    # (without a lexicon: the operator's call as it was, its new arguments at their defaults)
-    more = () if lexicon is None else (lexicon.on_device(x.device), omega)
-    flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, int(blank), W, K, n, bool(normalize),
-                                                  None if lm is None else lm.on_device(x.device), weight, bonus, eos, *more)
-    rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
-    return [list(rows[b * n:(b + 1) * n]) for b in range(B)], scores
+    word lm_weight * step(s, word) + word_bonus on top.  lexicon None: the call it was.  The options are one BeamPlan."""
+    plan = BeamPlan.checked(x.shape[2], blank, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos,
+                            lexicon, word_bonus, "ctc_beam_search")
+    return plan.search(x, lengths, normalize)
 
 
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)

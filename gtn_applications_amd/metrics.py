@@ -133,17 +133,11 @@ def decode_emissions_errors(counter, targets, x, drop, bias=None, num_replabels=
     return N.ops.decode_emissions_errors(x, bias, drop, num_replabels, flags, ref, tables, lengths)
 
 
-def beam_search_errors(counter, targets, x, blank, beam_size, classes_per_frame, lengths=None, lm=None, lm_weight=1.0,
-                       length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
-    """engine.ctc_beam_search's launches (best hypothesis only) and the counts behind them, on x's device: [B, 4] int64
-    on the host and nothing else (beam_size, classes_per_frame: already checked, engine.check_beam_arguments).  lm,
-    lm_weight, length_bonus, lm_eos, lexicon, word_bonus: as in engine.ctc_beam_search."""
+def beam_search_errors(counter, targets, x, plan, lengths=None):
+    """The launches of engine.BeamPlan.search (`plan`: checked; its best hypothesis only) and the counts behind them, on
+    x's device: [B, 4] int64 on the host and nothing else"""
     ref, tables, _ = _staged(counter, targets, x)
-    lexicon, omega = E.check_lexicon_arguments(lexicon, x.shape[2], int(blank), word_bonus, "errors")
-    lm, weight, bonus, eos = E.check_lm_arguments(lm, x.shape[2], int(blank), lm_weight, length_bonus, lm_eos, "errors", lexicon)
-    more = () if lexicon is None else (lexicon.on_device(x.device), omega)
-    return N.ops.ctc_beam_search_errors(x, lengths, int(blank), int(beam_size), int(classes_per_frame), ref, tables,
-                                        None if lm is None else lm.on_device(x.device), weight, bonus, eos, *more)
+    return N.ops.ctc_beam_search_errors(x, lengths, plan.on_device(x.device), ref, tables)
 
 
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):

@@ -40,11 +40,11 @@ def test_header_declares_and_library_exports_the_lexicon_entry_points():
                                                       "arc_next"]
     assert [n for n, _ in N.Lexicon._fields_] == ["num_nodes", "num_arcs", "num_words", "reserved", "arc_ptr", "arc_label",
                                                  "arc_next"]
-    # the operators of the search take the lexicon as an argument: a DeviceLexicon or None
+    # the operators of the search take the lexicon in their plan: a DeviceLexicon or None
     assert hasattr(N.ops, "DeviceLexicon")
+    assert "lexicon: " in N.ops.BeamPlan.__init__.__doc__ and "word_bonus: " in N.ops.BeamPlan.__init__.__doc__
     for fn in ("ctc_beam_search", "ctc_beam_search_errors"):
-        doc = getattr(N.ops, fn).__doc__
-        assert "lexicon: " in doc and "word_bonus: " in doc, fn
+        assert "plan: " in getattr(N.ops, fn).__doc__, fn
 
 
 GOOD = dict(B=2, T=5, C=7, blank=0, beam=4, K=3, nbest=2)

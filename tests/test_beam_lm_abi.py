@@ -32,11 +32,12 @@ def test_header_declares_and_library_exports_the_lm_entry_points():
         assert name in N.EXPORTED_SYMBOLS, name
     assert "typedef struct wfl_ngram_lm" in code and "WFL_NGRAM_LM_MAX_BACKOFF 8" in code
     assert ctypes.sizeof(N.NgramLm) == 16 + 16 + 6 * ctypes.sizeof(ctypes.c_void_p)
-    # the operators of the search take the model as an argument: a DeviceLm or None
+    # the operators of the search take the model in their plan: a DeviceLm or None
     assert hasattr(N.ops, "DeviceLm")
+    assert all(f"{arg}: " in N.ops.BeamPlan.__init__.__doc__ for arg in ("lm", "lm_weight", "length_bonus", "score_eos"))
     for fn in ("ctc_beam_search", "ctc_beam_search_errors"):
         assert hasattr(N.ops, fn), fn
-        assert all(f"{arg}: " in getattr(N.ops, fn).__doc__ for arg in ("lm", "lm_weight", "length_bonus", "score_eos")), fn
+        assert "plan: " in getattr(N.ops, fn).__doc__, fn
 
 
 GOOD = dict(B=2, T=5, C=7, blank=0, beam=4, K=3, nbest=2)
@@ -118,10 +119,14 @@ def test_module_refuses_bad_lm_arguments_before_a_device_is_needed(tmp_path):
     with pytest.raises(ValueError):  # the LM arguments of errors() belong to its beam search
         crit.errors(x, [[1], [2]], None, lm=lm)
     # the defaults without an lm are today's call: accepted by the check, like every finite pair with one
-    assert E.check_lm_arguments(None, 7, 0, 1.0, 0.0, True, "t") == (None, 1.0, 0.0, True)
-    assert E.check_lm_arguments(lm, 7, 0, 0, -3, False, "t") == (lm, 0.0, -3.0, False)
+    def lm_fields(lm, lm_weight, length_bonus, lm_eos):
+        plan = E.BeamPlan.checked(7, 0, 4, None, 1, lm, lm_weight, length_bonus, lm_eos, None, 0.0, "t")
+        return plan.lm, plan.lm_weight, plan.length_bonus, plan.lm_eos
+
+    assert lm_fields(None, 1.0, 0.0, True) == (None, 1.0, 0.0, True)
+    assert lm_fields(lm, 0, -3, False) == (lm, 0.0, -3.0, False)
     # numpy numbers and one-element tensors are numbers too (a sweep over weights); strings and bools are not
-    got = E.check_lm_arguments(lm, 7, 0, np.float32(0.5), torch.tensor(-1.5), np.bool_(False), "t")
+    got = lm_fields(lm, np.float32(0.5), torch.tensor(-1.5), np.bool_(False))
     assert got == (lm, 0.5, -1.5, False) and all(type(v) is t for v, t in zip(got[1:], (float, float, bool)))
     for kw in (dict(lm_weight=np.float64(math.nan)), dict(length_bonus=torch.tensor(math.inf)), dict(lm_weight=True),
                dict(lm_weight=np.ones(2)), dict(length_bonus=b"1")):

@@ -197,17 +197,26 @@ def test_the_word_lm_convention(tmp_path):
     assert ids == [2, 0, 0]
     assert abs(lm.score(ids) - ref.score(ids)) <= 1e-12 or lm.score(ids) == ref.score(ids)
     assert lm.step(lm.start, lex.num_words + 1)[0] == ref.step(ref.start, LR.EOS)[0]
-    assert E.check_lm_arguments(lm, 5, 4, 0.5, 0.1, False, "t", lex) == (lm, 0.5, 0.1, False)
+    def plan(lm, lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=lex, word_bonus=0.0):
+        return E.BeamPlan.checked(5, 4, 4, None, 1, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, "t")
+
+    def lm_fields(*args, **kw):
+        p = plan(*args, **kw)
+        return p.lm, p.lm_weight, p.length_bonus, p.lm_eos
+
+    assert lm_fields(lm, 0.5, 0.1, False) == (lm, 0.5, 0.1, False)
     # the length bonus needs no lm where there is a lexicon; the weight and </s> still do
-    assert E.check_lm_arguments(None, 5, 4, 1.0, 0.3, True, "t", lex) == (None, 1.0, 0.3, True)
+    assert lm_fields(None, 1.0, 0.3, True) == (None, 1.0, 0.3, True)
     for kw in (dict(lm_weight=0.5), dict(lm_eos=False)):
         with pytest.raises(ValueError, match="need an lm"):
-            E.check_lm_arguments(None, 5, 4, **dict(dict(lm_weight=1.0, length_bonus=0.0, lm_eos=True, what="t", lexicon=lex), **kw))
+            plan(None, **kw)
     # mismatches: an LM over fewer or more words, the blank elsewhere
     for bad in (word_lm(words[:3], 3), word_lm(words, 0), word_lm(words + ["c"], 5), word_lm(words, 2)):
         with pytest.raises(ValueError, match="word LM over its 4 words"):
             check_word_lm(lex, bad, "t")
         with pytest.raises(ValueError, match="word LM"):
-            E.check_lm_arguments(bad, 5, 4, 1.0, 0.0, True, "t", lex)
-    assert E.check_lexicon_arguments(lex, 5, 4, np.float32(0.5), "t") == (lex, 0.5)
-    assert E.check_lexicon_arguments(None, 5, 4, 0.0, "t") == (None, 0.0)
+            plan(bad)
+    got = plan(None, word_bonus=np.float32(0.5))
+    assert (got.lexicon, got.word_bonus) == (lex, 0.5) and type(got.word_bonus) is float
+    got = plan(None, lexicon=None)
+    assert (got.lexicon, got.word_bonus) == (None, 0.0)
