@@ -354,11 +354,68 @@ class ASG(torch.nn.Module):
             return E.decode_paths(paths, self.garbage_idx, self.num_replabels)
         return collapse_and_unpack(paths, self.garbage_idx, self.num_replabels)
 
+    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
+        """The arguments of a beam search, checked before anything needs a device: the E.AsgBeamPlan of the options"""
+        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
+            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
+        if not outputs.dtype.is_floating_point:
+            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        if outputs.shape[2] != self.N:
+            raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {self.N}")
+        return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)
+
+    def _beam_inputs(self, outputs):
+        """(emissions, transitions): float32, contiguous, on the emissions' GPU or the required one (no host path)"""
+        dev = outputs.device if outputs.is_cuda else E.require_gpu()
+        return (outputs.detach().to(device=dev, dtype=torch.float32).contiguous(),
+                E.as_device_f32(self.transitions.detach(), dev))
+
     @E.on_input_device
-    def errors(self, outputs, targets, counter):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False):
+        """ASG prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame path
+        under emissions + transitions; the criterion scores a label sequence by the sum over all its alignments (the
+        force-align numerator, asg.py:72-115), and this returns the sequences it rates highest (DESIGN.md section 21 has
+        the rules; csrc/beam_kernels.hip runs them, in float64).  Per frame the `classes_per_frame` classes of highest
+        emission score (default min(N, 32)) extend a hypothesis; `beam_size` (1..64) hypotheses survive a frame.  A
+        hypothesis whose last class is not among a frame's candidates lives on only through its extensions: ASG has
+        no blank to wait in.  Returns what viterbi() returns -- garbage dropped, replabels unpacked, on the device --:
+        nbest == 1: B int64 CPU tensors; otherwise a list of `nbest` such tensors per utterance, best first (a rank
+        beyond the final beam is empty).  The search and its n-best list are over RAW class sequences (tokens shifted by
+        the replabels, replabels, garbage), the criterion's own objects: two raw sequences can give the same output
+        once the garbage is dropped, so an n-best list may name an output twice, each time with the probability of
+        that raw sequence alone.  return_scores: also a float64 CPU tensor [B, nbest] of log-probabilities under the
+        criterion -- the raw sequence's log mass minus the denominator (asg.py:114): minus the ASG loss of that raw
+        sequence where the beam pruned none of its alignments, a lower bound of it otherwise --, -inf for an empty rank.  B == 0 or T == 0: empty sequences with score 0, no device needed."""
+        plan = self._beam_plan(outputs, "ASG.beam_search", beam_size, classes_per_frame, nbest)
+        if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+            hyps, scores = plan.no_frames(outputs.shape[0])
+        else:
+            x, W = self._beam_inputs(outputs)
+            with torch.cuda.device(x.device), torch.no_grad():
+                hyps, scores = plan.search(x, W, True, self.garbage_idx, self.num_replabels)
+        if plan.nbest == 1:
+            hyps = [h[0] for h in hyps]
+        return (hyps, scores) if return_scores else hyps
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
-        the device the count runs behind the same decode and the predictions never reach the host."""
+        the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
+        addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
+        beam launches on their device buffers; `classes_per_frame` needs a beam_size."""
+        if beam_size is None:
+            if classes_per_frame is not None:
+                raise ValueError("ASG.errors: classes_per_frame needs a beam_size")
+        else:
+            plan = self._beam_plan(outputs, "ASG.errors", beam_size, classes_per_frame, 1)
+            counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
+            if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+                return counter([h[0] for h in plan.no_frames(outputs.shape[0])[0]], targets)
+            x, W = self._beam_inputs(outputs)
+            with torch.cuda.device(x.device), torch.no_grad():
+                return counter.totals(M.asg_beam_search_errors(counter, targets, x, W, plan, self.garbage_idx,
+                                                               self.num_replabels))
         counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
         with torch.no_grad():
             if not (outputs.is_cuda and outputs.shape[0] > 0):

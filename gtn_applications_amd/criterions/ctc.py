@@ -386,8 +386,8 @@ class CTC(torch.nn.Module):
         hypothesis that ends inside a word is dropped after the last frame; nothing left: the empty sequence, -inf),
         `lm` is then a word-level LM over the lexicon's word ids (NGramLM.from_arpa(path, words, blank=len(words))), a
         completed word adds lm_weight * log P_LM(word | history) + word_bonus and every label length_bonus; the output
-        is still the token labels, lexicon.words() gives the words.  `word_bonus` needs a lexicon.  CTC only: ASG and
-        the Transducer's token graphs have no beam search."""
+        is still the token labels, lexicon.words() gives the words.  `word_bonus` needs a lexicon.  CTC's search: ASG has
+        its own (ASG.beam_search), the Transducer's token graphs have none."""
         plan, lens = self._beam_plan(outputs, input_lengths, "CTC.beam_search", beam_size, classes_per_frame, nbest, lm,
                                      lm_weight, length_bonus, lm_eos, lexicon, word_bonus)
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:

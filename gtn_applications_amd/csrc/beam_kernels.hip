@@ -26,6 +26,11 @@
 // (DESIGN.md section 20): a third parameter pack, BeamLex, carries the lexicon's trie and a BeamLm over word ids; a
 // hypothesis carries a trie node beside its LM state, an extension costs one bounded binary search among the arcs of
 // its node and, where the arc completes a word, one LM step; the final beam drops the ranks inside a word.
+// wfl_asg_beam_search is the search of the ASG criterion on the same launches: a fourth pack,
+// BeamAsg, carries the transition matrix -- no blank (the candidates launch leaves slot K empty), one mass per
+// hypothesis, the transition weight of an entry gathered where its key is formed; a hypothesis whose last label is no
+// candidate of the frame has no stay entry.  Its write launch can map a result on the way out (garbage dropped, replabels
+// unpacked: what ASG.viterbi does to a path), behind a launch that counts the mapped lengths.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
 #include "device_common.h"
@@ -44,19 +49,21 @@ constexpr int kBeamRankAll = 512;  // entries above the bound up to which every 
 
 // workspace: [candidate classes: B T (K+1) int32 | candidate scores: B T (K+1) float | row lse: B T float |
 //             arena: B T W int2 | final node: B nbest int32 | final length: B nbest int32]
+// asg (wfl_asg_beam_search): no row lse, and behind the rest [mapped length: B nbest int32]
 struct BeamWs {
-  int64_t cls, sc, lse, arena, fin_node, fin_len, bytes;
+  int64_t cls, sc, lse, arena, fin_node, fin_len, out_len, bytes;
 };
 inline int64_t beam_align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
-inline BeamWs beam_ws_layout(int64_t B, int64_t T, int64_t W, int64_t K, int64_t nbest) {
+inline BeamWs beam_ws_layout(int64_t B, int64_t T, int64_t W, int64_t K, int64_t nbest, bool asg = false) {
   BeamWs w;
   w.cls = 0;
   w.sc = w.cls + beam_align16(B * T * (K + 1) * 4);
   w.lse = w.sc + beam_align16(B * T * (K + 1) * 4);
-  w.arena = w.lse + beam_align16(B * T * 4);
+  w.arena = w.lse + (asg ? 0 : beam_align16(B * T * 4));
   w.fin_node = w.arena + beam_align16(B * T * W * 8);
   w.fin_len = w.fin_node + beam_align16(B * nbest * 4);
-  w.bytes = w.fin_len + beam_align16(B * nbest * 4);
+  w.out_len = w.fin_len + beam_align16(B * nbest * 4);
+  w.bytes = w.out_len + (asg ? beam_align16(B * nbest * 4) : 0);
   return w;
 }
 
@@ -98,12 +105,15 @@ __global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __res
     for (int c = lane; c < C; c += 64) m = fmaxf(m, nan_to_neg(r[c]));
   }
   // the row's log-sum-exp (wfl_row_lse's rule: float32, relative to the maximum, -inf for a row without a finite score)
-  m = wave_all_max(m);
-  float sum = 0.f;
-  if (m > WFL_NEG_INF)
-    for (int c = lane; c < C; c += 64) sum += fast_exp(nan_to_neg(r[c]) - m);
-  sum = wave_all_sum(sum);
-  if (lane == 0) lse_out[row] = m > WFL_NEG_INF ? m + fast_log(sum) : WFL_NEG_INF;
+  // (lse_out NULL -- the ASG search, which normalises by its own denominator: no log-sum-exp)
+  if (lse_out) {  // (uniform)
+    m = wave_all_max(m);
+    float sum = 0.f;
+    if (m > WFL_NEG_INF)
+      for (int c = lane; c < C; c += 64) sum += fast_exp(nan_to_neg(r[c]) - m);
+    sum = wave_all_sum(sum);
+    if (lane == 0) lse_out[row] = m > WFL_NEG_INF ? m + fast_log(sum) : WFL_NEG_INF;
+  }
   // K rounds: the best (score, lowest class) behind the previous round's pick; lane k keeps the pick of round k
   int pk = 0x7fffffff, pi = -1, mine = -1;
   for (int k = 0; k < K; ++k) {
@@ -129,7 +139,8 @@ __global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __res
   }
   const int64_t o = row * (K + 1);
   if (lane < K) cls_out[o + lane] = mine, sc_out[o + lane] = nan_to_neg(r[min(max(mine, 0), C - 1)]);
-  const bool found = __ballot(lane < K && mine == blank) != 0ull;
+  // (blank < 0 -- the ASG search, which has none: slot K holds class -1 and nothing is read at index -1)
+  const bool found = blank < 0 || __ballot(lane < K && mine == blank) != 0ull;
   if (lane == 0) cls_out[o + K] = found ? -1 : blank, sc_out[o + K] = found ? WFL_NEG_INF : nan_to_neg(r[blank]);
 }
 
@@ -272,23 +283,45 @@ __device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int
   return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
 }
 
+// the transitions of an ASG launch (wfl_asg_beam_search): Wt [(C+1), C] float32 in the criterion's layout (asg.py:54-69:
+// row 0 start -> c, row 1 + i: j -> i), and the denominator to subtract from the scores or NULL
+struct BeamAsg {
+  const float* Wt;
+  const float* logz;  // [B] float32 (wfl_dense_forward's), or NULL: raw scores
+  int C;
+};
+__device__ __forceinline__ const BeamAsg& beam_asg_of(const BeamAsg& a) { return a; }
+// the transition weight into class c behind last label l (l < 0: from the start), widened exactly, a NaN = -inf: one
+// gather from a matrix that the frames of every utterance share (it stays in L2)
+__device__ __forceinline__ double beam_asg_w(const BeamAsg& a, int l, int c) {
+  const float w = l < 0 ? a.Wt[c] : a.Wt[(int64_t)(1 + c) * a.C + l];
+  return w != w ? -__builtin_inf() : (double)w;
+}
+
 template <typename... Lm>
 struct BeamPack {
-  static constexpr bool lm = false, lex = false;
+  static constexpr bool lm = false, lex = false, asg = false;
 };
 template <>
 struct BeamPack<BeamLm> {
-  static constexpr bool lm = true, lex = false;
+  static constexpr bool lm = true, lex = false, asg = false;
 };
 template <>
 struct BeamPack<BeamLex> {
-  static constexpr bool lm = false, lex = true;
+  static constexpr bool lm = false, lex = true, asg = false;
+};
+template <>
+struct BeamPack<BeamAsg> {
+  static constexpr bool lm = false, lex = false, asg = true;
 };
 
 // NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales).
 // Lm: nothing -- the search of wfl_ctc_beam_search, its parameters and its code what they were --, or one BeamLm: the
 // n-gram LM and length bonus of wfl_ctc_beam_search_lm, or one BeamLex: the lexicon, word LM and bonuses of
-// wfl_ctc_beam_search_lexicon.
+// wfl_ctc_beam_search_lexicon, or one BeamAsg: the search of wfl_asg_beam_search -- no blank
+// (blank = -1, slot K of the candidates empty), one mass per hypothesis (tot; pb = -inf, pnb = tot), a transition weight
+// in every stay and every extension, a hypothesis whose last label is no candidate has no stay entry; lengths and
+// row_lse NULL, normalize != 0: the pack's logz[b] is subtracted.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -296,7 +329,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
                                                            int2* __restrict__ arena, int32_t* __restrict__ fin_node,
                                                            int32_t* __restrict__ fin_len, double* __restrict__ scores,
                                                            Lm... lm_arg) {
-  constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex;
+  constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg;
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -370,7 +403,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     int ncls = -1;
     float nsc = 0.f, flse = 0.f;
     if (tid < KC && t + 1 < Tb) ncls = ccls[(int64_t)(t + 1) * KC + tid], nsc = csc[(int64_t)(t + 1) * KC + tid];
-    if (tid == 0) flse = lse[t];
+    if constexpr (!ASG)
+      if (tid == 0) flse = lse[t];
     const int ncand = K + (cls[K] >= 0 ? 1 : 0);
     const int bpos = s_bpos[cur];
 
@@ -397,7 +431,27 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     }
     __syncthreads();
     // the stay entries
-    if (tid < nbeam) {
+    if constexpr (ASG) {
+      // ASG: a stay repeats the last label l over its self transition l -> l, and exists only where l is a candidate;
+      // the merged extension comes over the transition from its parent's last label into l
+      if (tid < nbeam) {
+        const BeamAsg& a = beam_asg_of(lm_arg...);
+        const int p = lpos[tid], l = h.last[tid], i = par[tid];
+        double m = p >= 0 ? (sc[p] + beam_asg_w(a, l, l)) + h.tot[tid] : ninf;
+        if (i >= 0) m = beam_lae(m, (sc[p] + beam_asg_w(a, h.last[i], l)) + h.tot[i]);  // (par[j] is set only where lpos[j] >= 0)
+        long long rk = beam_key(m);
+        spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = rk;
+        // The bound below wants one entry per hypothesis.  CTC's blank gives every hypothesis a stay; here a hypothesis
+        // whose last label is no candidate has none, and its first extension that is an entry of its own stands in
+        // (l is no candidate, so no candidate is l; a merged extension is part of another hypothesis' stay).
+        if (p < 0) {
+          const unsigned long long own = ~mmask[tid];
+          const int q = own ? __ffsll(own) - 1 : ncand;
+          if (q < ncand) rk = beam_key((sc[q] + beam_asg_w(a, l, cls[q])) + h.tot[tid]);
+        }
+        wkey[tid] = rk;  // (wkey: free until the selection)
+      }
+    } else if (tid < nbeam) {
       const int p = lpos[tid];
       const double pb = sc[bpos] + h.tot[tid];
       double pnb = p >= 0 ? sc[p] + h.pnb[tid] : ninf;
@@ -425,11 +479,13 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     }
     if (tid == 0) s_tau = kKeyDropped, s_count = 0, norm += (double)flse;
     __syncthreads();
-    // a full beam: the W-th best stay bounds the W-th best entry from below
+    // a full beam: the W-th best stay bounds the W-th best entry from below (ASG: of the one entry per hypothesis above)
+    const long long* bkey = skey;
+    if constexpr (ASG) bkey = wkey;
     if (tid < nbeam && nbeam == W) {
-      const long long k = skey[tid];
+      const long long k = bkey[tid];
       int n = 0;
-      for (int j = 0; j < W; ++j) n += (skey[j] > k || (skey[j] == k && j < tid)) ? 1 : 0;
+      for (int j = 0; j < W; ++j) n += (bkey[j] > k || (bkey[j] == k && j < tid)) ? 1 : 0;
       if (n == W - 1) s_tau = k;
     }
     __syncthreads();
@@ -464,6 +520,10 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
           k = term > ninf ? beam_key(ac + term) : kKeyDropped;
           enext[idx] = enc;
+        } else if constexpr (ASG) {
+          // (c the last label of i: that is i's stay, not an extension; the start row of Wt for the empty prefix)
+          const int l = h.last[i];
+          k = c == l ? kKeyDropped : beam_key((sc[p] + beam_asg_w(beam_asg_of(lm_arg...), l, c)) + h.tot[i]);
         } else
           k = beam_key(sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]));
       }
@@ -491,7 +551,9 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const int enc = enext[idx];  // (inside a word: the node, the parent's state; behind one: the root, a new state)
           e = beam_key_total(k);
           tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
-        } else
+        } else if constexpr (ASG)
+          e = beam_key_total(k);  // (the total with its transition weight: the key holds it, no second gather)
+        else
           e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
         const int node = t * W + r;
         g.pb[r] = ninf, g.pnb[r] = e, g.tot[r] = e;
@@ -577,6 +639,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   }
 
   if (tid == 0) s_norm = norm;
+  if constexpr (ASG)
+    if (tid == 0) s_norm = beam_asg_of(lm_arg...).logz ? (double)beam_asg_of(lm_arg...).logz[b] : 0.0;
   __syncthreads();
   const BeamHyp& f = beam[Tb & 1];
   if constexpr (LM || LEX) {
@@ -630,27 +694,72 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   }
 }
 
-// one wave per (b, rank): the sequences back to back in (b, rank) order
+// The mapping of a result on its way out (wfl_asg_beam_search; the meaning of `drop` and R = num_replabels is
+// wfl_decode_paths'): labels equal to `drop` are removed, then a label v >= R becomes v - R and a replabel r < R right
+// behind a label repeats that label r + 1 times, any other replabel is dropped (asg.py:35-49).  A result is walked from
+// its end, so a replabel waits (`pending`) for the value before it: a label takes it, another replabel replaces it.
+// Returns the mapped length; dst: NULL, or the END of the room mapped labels (stored downwards, never below it).
+__device__ __forceinline__ int beam_map_walk(const int2* __restrict__ nodes, int node, int len, int TW, int drop, int R,
+                                             int32_t* dst, int room) {
+  int pending = -1, n = 0;
+  for (int k = len - 1; k >= 0 && node >= 0 && node < TW; --k) {
+    const int2 rec = nodes[node];
+    const int v = rec.y;
+    node = rec.x;
+    if (v == drop) continue;
+    if (v >= R) {
+      const int copies = 1 + (pending >= 0 ? pending + 1 : 0);
+      if (dst)
+        for (int q = 0; q < copies && n + q < room; ++q) *--dst = v - R;
+      n += copies, pending = -1;
+    } else
+      pending = v;
+  }
+  return n;
+}
+
+// a thread per (b, rank): the mapped length of the result (the write launch needs those before it for its offset)
+__global__ void __launch_bounds__(256) beam_map_count_kernel(int n, int T, int W, int nbest, int drop, int R,
+                                                              const int2* __restrict__ arena, const int32_t* __restrict__ fin_node,
+                                                              const int32_t* __restrict__ fin_len, int32_t* __restrict__ out_len) {
+  const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (w >= n) return;
+  const int2* nodes = arena + (w / nbest) * (int64_t)T * W;
+  out_len[w] = beam_map_walk(nodes, fin_node[w], min(max(fin_len[w], 0), T), T * W, drop, R, nullptr, 0);
+}
+
+// one wave per (b, rank): the sequences back to back in (b, rank) order.  MAP: mapped on the way (beam_map_walk), out_len
+// their mapped lengths (beam_map_count_kernel's); without it the kernel is the one it was.
+template <bool MAP>
 __global__ void __launch_bounds__(256) beam_write_kernel(int n, int T, int W, int nbest, const int2* __restrict__ arena,
                                                           const int32_t* __restrict__ fin_node, const int32_t* __restrict__ fin_len,
-                                                          int32_t* __restrict__ out, int64_t* __restrict__ out_offsets) {
+                                                          int32_t* __restrict__ out, int64_t* __restrict__ out_offsets,
+                                                          const int32_t* __restrict__ out_len, int drop, int R) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n) return;
+  const int32_t* lens = MAP ? out_len : fin_len;
   long long base = 0;
-  for (int r = lane; r < (int)w; r += 64) base += fin_len[r];
+  for (int r = lane; r < (int)w; r += 64) base += lens[r];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) base += __shfl_xor(base, o, 64);
   if (lane != 0) return;
   const int len = min(max(fin_len[w], 0), T);
-  out_offsets[w] = base;
-  if (w == n - 1) out_offsets[n] = base + len;
   const int2* nodes = arena + (w / nbest) * (int64_t)T * W;
   int node = fin_node[w];
-  for (int k = len - 1; k >= 0 && node >= 0 && node < T * W; --k) {
-    const int2 rec = nodes[node];
-    out[base + k] = rec.y;
-    node = rec.x;
+  if constexpr (MAP) {
+    const int mapped = max(out_len[w], 0);
+    out_offsets[w] = base;
+    if (w == n - 1) out_offsets[n] = base + mapped;
+    beam_map_walk(nodes, node, len, T * W, drop, R, out + base + mapped, mapped);
+  } else {
+    out_offsets[w] = base;
+    if (w == n - 1) out_offsets[n] = base + len;
+    for (int k = len - 1; k >= 0 && node >= 0 && node < T * W; --k) {
+      const int2 rec = nodes[node];
+      out[base + k] = rec.y;
+      node = rec.x;
+    }
   }
 }
 
@@ -687,6 +796,23 @@ int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame,
 
 }  // extern "C"
 
+// the candidates launch (blank < 0: none, slot K stays empty; lse NULL: no row log-sum-exp)
+static void beam_candidates(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int K, int32_t* cls, float* sc,
+                            float* lse, hipStream_t s) {
+  const unsigned rows = (unsigned)(((int64_t)B * T + 3) / 4);
+  auto candidates = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(rows), dim3(256), 0, s, x, lengths, B, T, C, blank, K, cls, sc, lse);
+  };
+  if (C <= 64)
+    candidates(beam_candidates_kernel<1>);
+  else if (C <= 128)
+    candidates(beam_candidates_kernel<2>);
+  else if (C <= 256)
+    candidates(beam_candidates_kernel<4>);
+  else
+    candidates(beam_candidates_kernel<0>);
+}
+
 // the three launches of a search; lm: NULL, or the LM of wfl_ctc_beam_search_lm (already checked); lex: NULL, or the
 // lexicon of wfl_ctc_beam_search_lexicon (already checked; never with lm, its word LM is inside it)
 static int beam_launch(const char* what, const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
@@ -715,18 +841,7 @@ static int beam_launch(const char* what, const float* x, const int32_t* lengths,
   int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
   int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned rows = (unsigned)(((int64_t)B * T + 3) / 4);
-  auto candidates = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(rows), dim3(256), 0, s, x, lengths, B, T, C, blank, K, cls, sc, lse);
-  };
-  if (C <= 64)
-    candidates(beam_candidates_kernel<1>);
-  else if (C <= 128)
-    candidates(beam_candidates_kernel<2>);
-  else if (C <= 256)
-    candidates(beam_candidates_kernel<4>);
-  else
-    candidates(beam_candidates_kernel<0>);
+  beam_candidates(x, lengths, B, T, C, blank, K, cls, sc, lse, s);
   WFL_LAUNCH_CHECK();
   if (lex) {
     if (beam * (K + 2) <= 1024)
@@ -750,11 +865,100 @@ static int beam_launch(const char* what, const float* x, const int32_t* lengths,
                        sc, lse, arena, fin_node, fin_len, scores);
   WFL_LAUNCH_CHECK();
   const int n = B * nbest;
-  hipLaunchKernelGGL(beam_write_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
-                     fin_len, out, out_offsets);
+  hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
+                     fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
   WFL_LAUNCH_CHECK();
   return WFL_OK;
 }
+
+// what both ASG entries refuse: beam_check's, and the mapping's arguments by wfl_decode_workspace's rule
+static int asg_beam_check(const char* what, int B, int T, int C, int beam, int K, int nbest, int R) {
+  if (const int rc = beam_check(what, B, T, C, beam, K, nbest)) return rc;
+  if (R < 0) {
+    set_error("%s: num_replabels %d is negative", what, R);
+    return WFL_ERR_INVALID;
+  }
+  if ((int64_t)T * std::max(1, R) > 0x7fffffffLL) {
+    set_error("%s: T %d, num_replabels %d is more than the index width of the unpacking takes", what, T, R);
+    return WFL_ERR_UNSUPPORTED;
+  }
+  return WFL_OK;
+}
+
+extern "C" {
+
+// The beam search of the ASG criterion (asg.py:54-69: the transitions; asg.py:72-115: the score of a label sequence, the
+// force-align numerator, and the denominator logz; asg.py:35-49, 225-234: what viterbi() does to a result).  The
+// reference has no such search: it is an addition, like wfl_ctc_beam_search.
+int wfl_asg_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int num_replabels,
+                           int64_t* out_capacity, int64_t* ws_bytes) {
+  if (!out_capacity || !ws_bytes) {
+    set_error("asg_beam_workspace: a NULL pointer");
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = asg_beam_check("asg_beam_workspace", B, T, C, beam, classes_per_frame, nbest, num_replabels)) return rc;
+  *out_capacity = (int64_t)B * nbest * T * std::max(1, num_replabels);  // (wfl_decode_workspace's B T max(1, R), per rank)
+  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest, true).bytes;
+  return WFL_OK;
+}
+
+int wfl_asg_beam_search(const float* x, const float* Wt, const float* logz, int B, int T, int C, int beam, int classes_per_frame,
+                        int nbest, int drop, int num_replabels, void* ws, int32_t* out, int64_t out_capacity,
+                        int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "asg_beam_search";
+  if (!x || !Wt || !ws || !out || !out_offsets || !scores) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  const int K = classes_per_frame, R = num_replabels;
+  if (const int rc = asg_beam_check(what, B, T, C, beam, K, nbest, R)) return rc;
+  if (drop < -1 || drop >= C) {
+    set_error("%s: drop %d is outside [-1, %d)", what, drop, C);
+    return WFL_ERR_INVALID;
+  }
+  if (out_capacity < (int64_t)B * nbest * T * std::max(1, R)) {
+    set_error("%s: out holds %lld labels, B nbest T max(1, num_replabels) = %lld are needed", what, (long long)out_capacity,
+              (long long)B * nbest * T * std::max(1, R));
+    return WFL_ERR_INVALID;
+  }
+  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest, true);
+  char* base = static_cast<char*>(ws);
+  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
+  float* sc = reinterpret_cast<float*>(base + w.sc);
+  int2* arena = reinterpret_cast<int2*>(base + w.arena);
+  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
+  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
+  int32_t* out_len = reinterpret_cast<int32_t*>(base + w.out_len);
+  hipStream_t s = (hipStream_t)stream;
+  // no blank, no lengths, no row log-sum-exp: ASG has none of them
+  beam_candidates(x, nullptr, B, T, C, -1, K, cls, sc, nullptr, s);
+  WFL_LAUNCH_CHECK();
+  const BeamAsg a{Wt, logz, C};
+  const int32_t* no_lengths = nullptr;
+  const float* no_lse = nullptr;
+  if (beam * (K + 2) <= 1024)
+    hipLaunchKernelGGL((beam_search_kernel<256, BeamAsg>), dim3(B), dim3(256), 0, s, no_lengths, T, -1, beam, K, nbest, logz ? 1 : 0,
+                       cls, sc, no_lse, arena, fin_node, fin_len, scores, a);
+  else
+    hipLaunchKernelGGL((beam_search_kernel<1024, BeamAsg>), dim3(B), dim3(1024), 0, s, no_lengths, T, -1, beam, K, nbest, logz ? 1 : 0,
+                       cls, sc, no_lse, arena, fin_node, fin_len, scores, a);
+  WFL_LAUNCH_CHECK();
+  const int n = B * nbest;
+  if (drop < 0 && R == 0) {  // the raw class sequences: the write launch as it is
+    hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
+                       fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
+  } else {  // count first, then store: a result is walked from its end
+    hipLaunchKernelGGL(beam_map_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, beam, nbest, drop, R, arena,
+                       fin_node, fin_len, out_len);
+    WFL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_write_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
+                       fin_len, out, out_offsets, (const int32_t*)out_len, drop, R);
+  }
+  WFL_LAUNCH_CHECK();
+  return WFL_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

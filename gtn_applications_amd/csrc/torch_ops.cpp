@@ -881,7 +881,7 @@ void land(int dev, LandingKind kind, int64_t need, const char* what, const Launc
 // A source of hypotheses: the greedy decode behind viterbi() (wfl_decode_emissions / wfl_decode_paths,
 // csrc/decode_kernels.hip: counterpart of the reference's criterions/ctc.py:126-135, asg.py:225-234,
 // transducer.py:216-232) or the CTC prefix beam search (wfl_ctc_beam_search, csrc/beam_kernels.hip: the decode the
-// reference does not have).  What an op checks once and then issues, shared by the op that collects the labels on the
+// reference does not have) or the ASG one (wfl_asg_beam_search).  What an op checks once and then issues, shared by the op that collects the labels on the
 // host and the one that counts errors behind the same launch.
 // ------------------------------------------------------------------------------------------------------------
 struct Hypotheses {
@@ -1035,6 +1035,35 @@ Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& len
               check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0, ws, out,
                                         cap, offs, scores, s),
                     "ctc_beam_search");
+          }};
+}
+
+// The ASG prefix beam search (wfl_asg_beam_search): the options are engine.AsgBeamPlan's, already
+// checked.  logz: float32 [B] on x's device (wfl_dense_forward's denominator: normalised scores) or none; drop,
+// num_replabels: the mapping of the results on their way out (-1, 0: the raw class sequences).
+Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, int beam, int K,
+                           int nbest, int64_t drop, int64_t num_replabels) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
+              "asg_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
+  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2), R = (int)num_replabels;
+  TORCH_CHECK(Wt.device() == x.device() && Wt.scalar_type() == at::kFloat && Wt.is_contiguous() && Wt.dim() == 2 &&
+                  Wt.size(0) == (int64_t)C + 1 && Wt.size(1) == C,
+              "asg_beam_search: transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+  at::Tensor lz;
+  if (logz.has_value() && logz->defined()) {
+    TORCH_CHECK(logz->device() == x.device() && logz->scalar_type() == at::kFloat && logz->is_contiguous() && logz->dim() == 1 &&
+                    logz->numel() == B,
+                "asg_beam_search: logz must be a contiguous float32 [B] tensor on x's device");
+    lz = *logz;
+  }
+  return {x, B, (int64_t)B * nbest, true, "asg_beam_search",
+          [=](int64_t* capacity, int64_t* ws_bytes) {
+            check(wfl_asg_beam_workspace(B, T, C, beam, K, nbest, R, capacity, ws_bytes), "asg_beam_search");
+          },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            check(wfl_asg_beam_search(x.data_ptr<float>(), Wt.data_ptr<float>(), lz.defined() ? lz.data_ptr<float>() : nullptr, B, T,
+                                      C, beam, K, nbest, (int)drop, R, ws, out, cap, offs, scores, s),
+                  "asg_beam_search");
           }};
 }
 
@@ -1238,6 +1267,19 @@ at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::T
   return hypotheses_errors(beam_source(x, lengths, plan, 1, false), ref, tables);
 }
 
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple asg_beam_search(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, int beam, int K,
+                          int nbest, int64_t drop, int64_t num_replabels) {
+  const Collected r = hypotheses_collect(asg_beam_source(x, Wt, logz, beam, K, nbest, drop, num_replabels), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+}
+
+// (the first rank, unnormalised: nothing reads the scores)
+at::Tensor asg_beam_search_errors(const at::Tensor& x, const at::Tensor& Wt, int beam, int K, int64_t drop, int64_t num_replabels,
+                                  const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(asg_beam_source(x, Wt, c10::nullopt, beam, K, 1, drop, num_replabels), ref, tables);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1271,6 +1313,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ctc_beam_search_errors", &ctc_beam_search_errors, py::arg("x"), py::arg("lengths"), py::arg("plan"), py::arg("ref"),
         py::arg("tables"),
         "ctc_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  m.def("asg_beam_search", &asg_beam_search, py::arg("x"), py::arg("transitions"), py::arg("logz"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("drop"), py::arg("num_replabels"),
+        "ASG prefix beam search on the device (engine.AsgBeamPlan's options): (labels int64 CPU, offsets int64 CPU "
+        "[B nbest + 1], scores float64 CPU [B, nbest]); logz float32 [B] (normalised scores) or None");
+  m.def("asg_beam_search_errors", &asg_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
+        "asg_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),
         "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors; lengths int32 [B] "

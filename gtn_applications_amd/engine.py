@@ -1077,6 +1077,80 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     return plan.search(x, lengths, normalize)
 
 
+class AsgBeamPlan(namedtuple("AsgBeamPlan", "C beam classes_per_frame nbest")):
+    """The options of one ASG beam search over C classes (tokens + replabels + garbage), checked once (`checked`, the one
+    constructor) and handed on whole, as BeamPlan is for CTC: ASG.beam_search, ASG.errors(beam_size=) and asg_beam_search
+    build one plan per call.  ASG has no blank, no input lengths and -- here -- no LM or lexicon, so four ints are all.
+    Only search() and errors() need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, beam_size, classes_per_frame, nbest, what):
+        """The plan of these arguments, within the limits of wfl_asg_beam_search, or ValueError (`what`: the call they
+        were given to).  classes_per_frame None: min(C, 32) -- a default, not a tuned value.  Integers only, no bools."""
+
+        def integer(v):
+            try:
+                return None if isinstance(v, (bool, np.bool_)) else operator.index(v)
+            except TypeError:
+                return None
+
+        C = integer(C)
+        if C is None or C < 1:
+            raise ValueError(f"{what}: the emissions have no classes")
+        W = integer(beam_size)
+        if W is None or not 1 <= W <= BEAM_MAX:
+            raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+        K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
+        if K is None or not 1 <= K <= min(C, BEAM_MAX):
+            raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
+                             f"got {classes_per_frame!r}")
+        n = integer(nbest)
+        if n is None or not 1 <= n <= W:
+            raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
+        if C > BEAM_MAX_CLASSES:
+            raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
+        return cls(C, W, K, n)
+
+    def no_frames(self, B):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
+        empty sequence with score 0"""
+        hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(self.nbest)] for _ in range(B)]
+        return hyps, torch.zeros((B, self.nbest), dtype=torch.float64)
+
+    def search(self, x, W, normalize=True, drop=None, num_replabels=0):
+        """asg_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
+        [C + 1, C] on x's device, contiguous"""
+        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+            logz = dense_forward(x, W, need_beta=False).logz if normalize else None
+        flat, offsets, scores = N.ops.asg_beam_search(x, W, logz, self.beam, self.classes_per_frame, self.nbest,
+                                                      -1 if drop is None else int(drop), int(num_replabels))
+        rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
+        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
+
+
+def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normalize=True, drop=None, num_replabels=0):
+    """ASG prefix beam search on the device (wfl_asg_beam_search through csrc/torch_ops.cpp; the rules: include/wfl.h,
+    DESIGN.md section 21).  x: float32 [B,T,C] on a GPU, contiguous; Wt: float32 [C + 1, C] on x's device, contiguous, the
+    criterion's transitions (row 0: start -> c, row 1 + i: j -> i).  Returns (hyps, scores): hyps[b][r] the int64 CPU
+    label tensor of rank r of utterance b (views of one tensor), scores float64 CPU [B, nbest] -- the log mass of the
+    sequence's alignments, emissions plus transitions, minus the denominator logz_b of dense_forward(x, Wt) if
+    `normalize`: then minus the ASG loss of that sequence (a lower bound of it where the beam pruned); a rank beyond the final beam is empty with score -inf.  With
+    drop None and num_replabels 0 the sequences are the raw class sequences, which the scores are always of; otherwise
+    `drop` is removed and replabels are unpacked on the way out (what ASG.viterbi does to a path).  Only the surviving
+    labels and the scores leave the device.  The options are one AsgBeamPlan."""
+    plan = AsgBeamPlan.checked(x.shape[2], beam_size, classes_per_frame, nbest, "asg_beam_search")
+    if tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"asg_beam_search: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if not isinstance(num_replabels, int) or isinstance(num_replabels, bool) or num_replabels < 0:
+        raise ValueError(f"asg_beam_search: num_replabels must be an integer >= 0, got {num_replabels!r}")
+    if drop is not None and not -1 <= int(drop) < plan.C:
+        raise ValueError(f"asg_beam_search: drop {drop} is outside [0, {plan.C})")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return plan.no_frames(x.shape[0])
+    return plan.search(x, Wt, normalize, drop, num_replabels)
+
+
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)
 
 

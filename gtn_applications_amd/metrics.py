@@ -140,6 +140,13 @@ def beam_search_errors(counter, targets, x, plan, lengths=None):
     return N.ops.ctc_beam_search_errors(x, lengths, plan.on_device(x.device), ref, tables)
 
 
+def asg_beam_search_errors(counter, targets, x, W, plan, drop, num_replabels):
+    """The launches of engine.AsgBeamPlan.search (`plan`: checked; its best hypothesis only, garbage dropped and
+    replabels unpacked on the way out) and the counts behind them, on x's device: [B, 4] int64 on the host and nothing else"""
+    ref, tables, drop = _staged(counter, targets, x, drop)
+    return N.ops.asg_beam_search_errors(x, W, plan.beam, plan.classes_per_frame, drop, num_replabels, ref, tables)
+
+
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
     ref, tables, drop = _staged(counter, targets, paths, drop)

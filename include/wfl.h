@@ -703,6 +703,60 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths /* or NUL
                                 int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device kernels: ASG prefix beam search (csrc/beam_kernels.hip)
+ *   wfl_dense_viterbi gives the best FRAME PATH under emissions + transitions (asg.py:211-224).  The ASG criterion scores a
+ *   LABEL SEQUENCE by the sum over all its alignments -- the force-align numerator, asg.py:72-115 --; this search
+ *   maximises that, on the launches of wfl_ctc_beam_search.  The reference has no such decoder.  Per utterance b, over
+ *   all T frames of x [B,T,C] float32 (a NaN counts as -inf), with the transitions Wt [(C+1), C] float32 in the
+ *   criterion's layout (asg.py:54-69: Wt[0][c] is start -> c, Wt[1+i][j] is j -> i; a NaN counts as -inf, +inf is not a
+ *   weight), beam width W = beam, K = classes_per_frame.  There is no blank and there are no input lengths: ASG has neither.
+ *     1. all hypothesis arithmetic is float64 in the log domain with wfl_ctc_beam_search's lae; scores and transition
+ *        weights are widened from float32 exactly;
+ *     2. candidates of a frame: its K classes of highest EMISSION score, ties to the lower class, in that order;
+ *        transitions do not enter the choice and no class is appended;
+ *     3. a hypothesis is (prefix, p): a class sequence without two equal neighbours and the log mass of all its
+ *        alignments over the frames so far, emissions plus transitions; the search starts from the empty prefix with
+ *        p = 0; the beam is ranked by p, descending;
+ *     4. frame t, hypothesis of rank i with last label l, candidate c with s = (double)x[b,t,c]: c == l -- i's stay entry
+ *        gets p' = (s + Wt[1+l][l]) + p_i; c != l -- the extension i + c gets e = (s + Wt[1+c][l]) + p_i; from the empty
+ *        prefix (only at t = 0) e = (s + Wt[0][c]) + 0.  The empty prefix has no stay entry, and neither has a hypothesis
+ *        whose last label is not among the candidates: it lives on only through its extensions (CTC's blank keeps every
+ *        hypothesis alive; ASG has none);
+ *     5. an extension whose prefix is that of a hypothesis j in the beam is merged into j's stay entry by lae (there is
+ *        at most one per j, and j's last label is then a candidate, so the stay entry exists, possibly at -inf); every
+ *        other extension is a new entry;
+ *     6. selection and order are wfl_ctc_beam_search's: entries at -inf are dropped (an extension over a -inf transition
+ *        among them), the W entries of largest p' survive, in the order: larger p'; stay entries before new ones; the
+ *        lower parent rank; the lower position of c among the candidates.  Nothing survives: the empty sequence, -inf;
+ *     7. result: the first nbest ranks with their p, minus (double)logz[b] if logz is not NULL -- logz [B] float32 on the
+ *        device, the denominator wfl_dense_forward computes (asg.py:114): the normalised score of a sequence is then minus
+ *        its ASG loss where none of its alignments was pruned, a lower bound of that otherwise.  Ranks beyond the final
+ *        beam's size are empty sequences with score -inf.
+ *   Prefixes are identified as in wfl_ctc_beam_search.  drop, num_replabels: the mapping of a result on its way out, with
+ *   the meaning they have in wfl_decode_paths (what ASG.viterbi does to a path, asg.py:225-234): labels equal to drop
+ *   (the garbage class; -1: none) are removed, then a label v >= num_replabels becomes v - num_replabels and a replabel
+ *   right behind a label repeats it (asg.py:35-49).  drop = -1, num_replabels = 0: the raw class sequences.  The search
+ *   and the scores are over raw sequences whatever the mapping.  out: the (mapped) labels back to back in (b, rank) order,
+ *   capacity B nbest T max(1, num_replabels) int32 (wfl_decode_workspace's rule per rank); out_offsets [B nbest + 1] int64;
+ *   scores [B nbest] float64; with nbest == 1, out / out_offsets are what wfl_errors_count reads as hyp / hyp_off.  All
+ *   three are written by plain stores of a kernel in a fixed order: any device-accessible memory, pinned host memory
+ *   included; the result is deterministic.  ws: device scratch of wfl_asg_beam_workspace's size, 16-byte aligned.  Three
+ *   launches on `stream` (candidates; beam: a workgroup per utterance, one gather from Wt per entry; write), four with a
+ *   mapping (the mapped lengths are counted before they are stored: a result is walked from its end); no allocation, no
+ *   synchronisation, no atomics on global memory, no cross-workgroup waits, every loop bounded by T, W, K.
+ *   WFL_ERR_INVALID: a NULL required pointer (logz may be NULL), B, T or C < 1, beam outside [1, 64], classes_per_frame
+ *   outside [1, min(C, 64)], nbest outside [1, beam], drop outside [-1, C), num_replabels < 0, out_capacity too small.
+ *   WFL_ERR_UNSUPPORTED: C > 16384, T max(1, num_replabels) >= 2^31.  Not here: an LM or a lexicon, input lengths.
+ * ------------------------------------------------------------------------------------------------ */
+/* out_capacity = B nbest T max(1, num_replabels) (int32 elements of `out`), ws_bytes = the device scratch of a call */
+int wfl_asg_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int num_replabels,
+                           int64_t* out_capacity, int64_t* ws_bytes);
+int wfl_asg_beam_search(const float* x, const float* Wt /* [(C+1), C] */, const float* logz /* [B] or NULL */, int B, int T,
+                        int C, int beam, int classes_per_frame, int nbest, int drop, int num_replabels, void* ws, int32_t* out,
+                        int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
  *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
  *   train.py:278-284 and test.py:94-109 -- per utterance b:
