@@ -187,6 +187,25 @@ class PackedNumerator:
         self.pack, self.scale, self.cpos, self.cneg, self.B = pack, scale, cpos, cneg, B
 
 
+def _gated_factors(tg, reduction, T):
+    """E.loss_factors(tg, reduction) for emissions of T frames: (scale, +scale/B, -scale/B).  An utterance no alignment
+    fits whatever the scores -- a target longer than T, an empty target (asg.py:75-77: no accepting node) -- has loss
+    +inf by the numerator's log Z, and DESIGN.md section 4 promises it a gradient of exactly zero: the dense gradient
+    kernels weigh the denominator's posteriors by cpos[b] without looking at the numerator, so its two coefficients are
+    zeros here (scale stays: the loss is +inf).  Known before any launch, from the staged lengths; decided once per
+    (batch, reduction, T) -- a batch without such an utterance gets the views E.loss_factors hands out, untouched."""
+    key = ("asg_factors", reduction, T)
+    hit = tg.cache.get(key)
+    if hit is None:
+        hit = E.loss_factors(tg, reduction)
+        dead = [n == 0 or n > T for n in tg.lens]
+        if any(dead):
+            live = torch.tensor([0.0 if d else 1.0 for d in dead], dtype=torch.float32, device=hit[1].device)
+            hit = (hit[0], hit[1] * live, hit[2] * live)
+        tg.cache[key] = hit
+    return hit
+
+
 class ASGLossFunction(torch.autograd.Function):
     @staticmethod
     def create_transitions_graph(transitions, calc_grad=False):
@@ -241,7 +260,7 @@ class ASGLossFunction(torch.autograd.Function):
             tg = E.targets_on_device(targets, dev)
             if tg.B != B:
                 raise ValueError(f"got {tg.B} targets for a batch of {B}")
-            scale, cpos, cneg = E.loss_factors(tg, reduction)
+            scale, cpos, cneg = _gated_factors(tg, reduction, T)
             pack = tg.cache.get(("asg_fal", C))
             if pack is None:
                 pack = tg.cache[("asg_fal", C)] = E.PackedLattice.asg_force_align(tg.flat, tg.offsets, C, dev)

@@ -3606,8 +3606,13 @@ __global__ void reduce_loss_kernel(const float* __restrict__ vals, const float* 
   __shared__ float red[64];
   WFL_LOG(13);
   float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x)
-    s += sign * (scale ? scale[b] : 1.f) * (minus ? vals[b] - minus[b] : vals[b]);
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    float v = vals[b];
+    // two terms: an utterance whose subtrahend is -inf (no accepting path) is +inf whatever vals[b] is -- also -inf, when
+    // a frame without any finite score kills both sums, and the plain difference would be NaN
+    if (minus) v = minus[b] == WFL_NEG_INF ? -WFL_NEG_INF : v - minus[b];
+    s += sign * (scale ? scale[b] : 1.f) * v;
+  }
   s = block_reduce_sum(s, red);
   if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + s / (float)B;
 }
