@@ -211,6 +211,10 @@ _SIGS = {
     "wfl_asg_beam_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_asg_beam_search": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P,
                                     _P]),
+    # device: Transducer prefix beam search
+    "wfl_transducer_beam_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "wfl_transducer_beam_search": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
+                                           c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path
     "wfl_errors_workspace": (c_int, [c_int, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wfl_errors_count": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int64, c_int64, _P, _P, _P]),

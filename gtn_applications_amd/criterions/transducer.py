@@ -364,11 +364,93 @@ class Transducer(torch.nn.Module):
         flat = torch.from_numpy(out)  # (int32: torch.IntTensor, as transducer.py:233)
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
 
+    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
+        """The arguments of a beam search, checked before anything needs a device: (the E.TransducerBeamPlan of the
+        options, the transition model's kind: "none", "unigram" or "bigram")"""
+        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
+            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
+        if not outputs.dtype.is_floating_point:
+            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        self.tokens.arc_sort()
+        n = ctypes.c_int()
+        mode = N.lib.wfl_graph_token_kind(self.tokens._h, ctypes.byref(n))
+        if mode not in (N.TOKENS_FORCED, N.TOKENS_OPTIONAL_NO_REPEATS):
+            graph = {N.TOKENS_NONE: 'blank="none"', N.TOKENS_OPTIONAL: 'blank="optional" with repeats'}.get(mode, "this token graph")
+            raise NotImplementedError(
+                f"{what}: {graph} is ambiguous -- a frame path spells more than one token sequence (a repeated token "
+                "multiplies alignments, so the sum over alignments favours [a, a, ...] over [a]), and a prefix search "
+                'over it is no decoder; blank="optional" with allow_repeats=False and blank="forced" are searched')
+        C = n.value + 1
+        if outputs.shape[2] != C:
+            raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {n.value} tokens and the blank")
+        kind = "none"
+        if self.transitions is not None:
+            kind = _dispatch(self.transitions, C, self.transition_params.numel()).kind
+            if kind == "general":
+                raise NotImplementedError(f"{what}: the transition model is neither make_transitions_graph(1, C) nor "
+                                          "(2, C): only no model, the unigram and the bigram model are searched")
+        plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
+        return plan, kind
+
+    def _beam_inputs(self, outputs, kind):
+        """(emissions, transitions or None) of the search, as the routes of the loss form them (_dispatch): float32,
+        contiguous, on the emissions' GPU or the required one (no host path)"""
+        dev = outputs.device if outputs.is_cuda else E.require_gpu()
+        x = outputs.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if kind == "none":
+            return x, None
+        params = E.as_device_f32(self.transition_params.detach(), dev).reshape(-1)
+        if kind == "unigram":
+            return x + params, None  # (_unigram_route)
+        xd, Wd = _bigram_dense_operands(x, params, x.shape[2])
+        return xd, Wd.contiguous()
+
     @E.on_input_device
-    def errors(self, outputs, targets, counter):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False):
+        """Transducer prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame
+        path; the criterion scores a token sequence by the sum over all its alignments, and this returns the token
+        sequences it rates highest (DESIGN.md section 22 has the rules; csrc/beam_kernels.hip runs them, in float64).
+        Per frame the `classes_per_frame` classes of highest emission score (default min(C, 32)) and the blank extend a
+        hypothesis; `beam_size` (1..64) hypotheses survive a frame.  Only the unambiguous token graphs are searched --
+        blank="optional" with allow_repeats=False, and blank="forced" --, with no transition model or the unigram or
+        bigram one (`ngram` 0, 1, 2); everything else raises NotImplementedError.  Returns token indices with the blank
+        dropped, in viterbi()'s dtype: nbest == 1: B CPU tensors; otherwise a list of `nbest` such tensors per utterance,
+        best first (a rank beyond the result is empty).  return_scores: also a float64 CPU tensor [B, nbest]: the log
+        mass of the token sequence's alignments that the beam kept, minus the normaliser of the loss (-inf for an empty
+        rank).  For tokens that are single graphemes that is minus the criterion's loss of that target where nothing was
+        pruned.  With word pieces the loss also sums over the other decompositions of the same graphemes, so the score
+        is a lower bound of minus the loss; two token sequences that spell the same graphemes are separate hypotheses.
+        B == 0 or T == 0: empty sequences with score 0, no device needed.  No merging by spelling, lexicon, LM or
+        input lengths."""
+        plan, kind = self._beam_plan(outputs, "Transducer.beam_search", beam_size, classes_per_frame, nbest)
+        if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+            hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
+        else:
+            x, Wt = self._beam_inputs(outputs, kind)
+            with torch.cuda.device(x.device), torch.no_grad():
+                hyps, scores = plan.search(x, Wt, True, torch.int32)
+        if plan.nbest == 1:
+            hyps = [h[0] for h in hyps]
+        return (hyps, scores) if return_scores else hyps
+
+    @E.on_input_device
+    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
-        the device the count runs behind the same decode and the predictions never reach the host."""
+        the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
+        addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
+        beam launches on their device buffers; `classes_per_frame` needs a beam_size."""
+        if beam_size is None:
+            if classes_per_frame is not None:
+                raise ValueError("Transducer.errors: classes_per_frame needs a beam_size")
+        else:
+            plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1)
+            counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
+            if outputs.shape[0] == 0 or outputs.shape[1] == 0:
+                return counter([h[0] for h in plan.no_frames(outputs.shape[0], torch.int32)[0]], targets)
+            x, Wt = self._beam_inputs(outputs, kind)
+            with torch.cuda.device(x.device), torch.no_grad():
+                return counter.totals(M.transducer_beam_search_errors(counter, targets, x, Wt, plan))
         C = outputs.shape[2]
         dplan = self._device_decode(C)
         # (a blank in the last column is never emitted)

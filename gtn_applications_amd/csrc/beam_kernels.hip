@@ -31,6 +31,10 @@
 // hypothesis, the transition weight of an entry gathered where its key is formed; a hypothesis whose last label is no
 // candidate of the frame has no stay entry.  Its write launch can map a result on the way out (garbage dropped, replabels
 // unpacked: what ASG.viterbi does to a path), behind a launch that counts the mapped lengths.
+// wfl_transducer_beam_search is the search of the Transducer criterion on the same launches: a
+// fifth pack, BeamTok, carries the frame-level transitions over tokens + blank (or none) and the token graph's topology
+// -- CTC's two masses per hypothesis and a transition weight on every frame-to-frame step: three gathers in a stay, two
+// gathers and a log-add in an extension; the forced topology leaves the blank state only and ranks the result by pb.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
 #include "device_common.h"
@@ -298,21 +302,49 @@ __device__ __forceinline__ double beam_asg_w(const BeamAsg& a, int l, int c) {
   return w != w ? -__builtin_inf() : (double)w;
 }
 
+// the transitions of a Transducer launch (wfl_transducer_beam_search): Wt [(C+1), C] float32 in the dense engine's layout
+// (row 0 start -> c, row 1 + i: j -> i) or NULL (every weight 0), the denominator to subtract or NULL (the row
+// log-sum-exps, as in the plain search), and the topology of the token graph
+struct BeamTok {
+  const float* Wt;
+  const float* logz;  // [B] float32 (wfl_dense_forward's), or NULL
+  int C;
+  int forced;  // 1: a token is entered from the blank state only, and a path ends in the blank
+};
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamTok& a) { return a; }
+// w(p, c): the weight into class c behind frame label p (p < 0: from the start), widened exactly, a NaN = -inf
+__device__ __forceinline__ double beam_tok_w(const BeamTok& a, int p, int c) {
+  if (!a.Wt) return 0.0;
+  const float w = p < 0 ? a.Wt[c] : a.Wt[(int64_t)(1 + c) * a.C + p];
+  return w != w ? -__builtin_inf() : (double)w;
+}
+// rule 4: the extension by candidate c (score s) of a hypothesis (pb, pnb, last label l) whose blank-side state is
+// `brow` (the start in frame 0, the blank behind it)
+__device__ __forceinline__ double beam_tok_ext(const BeamTok& a, double pb, double pnb, int l, int brow, int c, double s) {
+  double m = pb + beam_tok_w(a, brow, c);
+  if (!a.forced && l >= 0 && c != l && pnb > -__builtin_inf()) m = beam_lae(m, pnb + beam_tok_w(a, l, c));
+  return s + m;
+}
+
 template <typename... Lm>
 struct BeamPack {
-  static constexpr bool lm = false, lex = false, asg = false;
+  static constexpr bool lm = false, lex = false, asg = false, tok = false;
 };
 template <>
 struct BeamPack<BeamLm> {
-  static constexpr bool lm = true, lex = false, asg = false;
+  static constexpr bool lm = true, lex = false, asg = false, tok = false;
 };
 template <>
 struct BeamPack<BeamLex> {
-  static constexpr bool lm = false, lex = true, asg = false;
+  static constexpr bool lm = false, lex = true, asg = false, tok = false;
 };
 template <>
 struct BeamPack<BeamAsg> {
-  static constexpr bool lm = false, lex = false, asg = true;
+  static constexpr bool lm = false, lex = false, asg = true, tok = false;
+};
+template <>
+struct BeamPack<BeamTok> {
+  static constexpr bool lm = false, lex = false, asg = false, tok = true;
 };
 
 // NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales).
@@ -321,7 +353,10 @@ struct BeamPack<BeamAsg> {
 // wfl_ctc_beam_search_lexicon, or one BeamAsg: the search of wfl_asg_beam_search -- no blank
 // (blank = -1, slot K of the candidates empty), one mass per hypothesis (tot; pb = -inf, pnb = tot), a transition weight
 // in every stay and every extension, a hypothesis whose last label is no candidate has no stay entry; lengths and
-// row_lse NULL, normalize != 0: the pack's logz[b] is subtracted.
+// row_lse NULL, normalize != 0: the pack's logz[b] is subtracted; or one BeamTok: the search of
+// wfl_transducer_beam_search -- the plain search's two masses with a transition weight on every
+// step (w = 0 without a matrix), the blank-side state the start row in frame 0, the forced topology's extensions from pb
+// alone and none in frame 0, the final beam ranked again by pb there; lengths NULL, row_lse NULL where logz normalises.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -329,7 +364,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
                                                            int2* __restrict__ arena, int32_t* __restrict__ fin_node,
                                                            int32_t* __restrict__ fin_len, double* __restrict__ scores,
                                                            Lm... lm_arg) {
-  constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg;
+  constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg, TOK = BeamPack<Lm...>::tok;
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -403,7 +438,9 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     int ncls = -1;
     float nsc = 0.f, flse = 0.f;
     if (tid < KC && t + 1 < Tb) ncls = ccls[(int64_t)(t + 1) * KC + tid], nsc = csc[(int64_t)(t + 1) * KC + tid];
-    if constexpr (!ASG)
+    if constexpr (TOK) {
+      if (tid == 0 && row_lse) flse = lse[t];
+    } else if constexpr (!ASG)
       if (tid == 0) flse = lse[t];
     const int ncand = K + (cls[K] >= 0 ? 1 : 0);
     const int bpos = s_bpos[cur];
@@ -450,6 +487,21 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           if (q < ncand) rk = beam_key((sc[q] + beam_asg_w(a, l, cls[q])) + h.tot[tid]);
         }
         wkey[tid] = rk;  // (wkey: free until the selection)
+      }
+    } else if constexpr (TOK) {
+      // rule 3: the blank is entered from the blank-side state and from the last label, the last label repeats over its
+      // self transition; the merged extension is rule 4's
+      if (tid < nbeam) {
+        const BeamTok& a = beam_tok_of(lm_arg...);
+        const int p = lpos[tid], l = h.last[tid], i = par[tid], brow = t == 0 ? -1 : blank;
+        double m = h.pb[tid] + beam_tok_w(a, brow, blank);
+        if (l >= 0 && h.pnb[tid] > ninf) m = beam_lae(m, h.pnb[tid] + beam_tok_w(a, l, blank));
+        const double pb = sc[bpos] + m;
+        double pnb = p >= 0 && h.pnb[tid] > ninf ? (sc[p] + h.pnb[tid]) + beam_tok_w(a, l, l) : ninf;
+        if (i >= 0 && !(a.forced && t == 0))
+          pnb = beam_lae(pnb, beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]));  // (par: only where p >= 0)
+        const double tot = beam_lae(pb, pnb);
+        spb[tid] = pb, spnb[tid] = pnb, stot[tid] = tot, skey[tid] = beam_key(tot);
       }
     } else if (tid < nbeam) {
       const int p = lpos[tid];
@@ -524,6 +576,10 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           // (c the last label of i: that is i's stay, not an extension; the start row of Wt for the empty prefix)
           const int l = h.last[i];
           k = c == l ? kKeyDropped : beam_key((sc[p] + beam_asg_w(beam_asg_of(lm_arg...), l, c)) + h.tot[i]);
+        } else if constexpr (TOK) {
+          const BeamTok& a = beam_tok_of(lm_arg...);
+          k = a.forced && t == 0 ? kKeyDropped
+                                 : beam_key(beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], t == 0 ? -1 : blank, c, sc[p]));
         } else
           k = beam_key(sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]));
       }
@@ -551,7 +607,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const int enc = enext[idx];  // (inside a word: the node, the parent's state; behind one: the root, a new state)
           e = beam_key_total(k);
           tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
-        } else if constexpr (ASG)
+        } else if constexpr (ASG || TOK)
           e = beam_key_total(k);  // (the total with its transition weight: the key holds it, no second gather)
         else
           e = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);
@@ -641,15 +697,21 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   if (tid == 0) s_norm = norm;
   if constexpr (ASG)
     if (tid == 0) s_norm = beam_asg_of(lm_arg...).logz ? (double)beam_asg_of(lm_arg...).logz[b] : 0.0;
+  if constexpr (TOK)
+    if (tid == 0 && beam_tok_of(lm_arg...).logz) s_norm = (double)beam_tok_of(lm_arg...).logz[b];
   __syncthreads();
   const BeamHyp& f = beam[Tb & 1];
-  if constexpr (LM || LEX) {
+  if constexpr (LM || LEX || TOK) {
     // </s>: every rank's total with the LM's end weight, a rank without one dropped, then the ranks again by counting
     // (descending, ties to the earlier rank; dropped keys are below every other and come out behind them, empty).
     // With a lexicon a rank inside a word is dropped first, and </s> needs a word LM.
+    // The Transducer's rules 5 and 6 by the same ranking: the optional topology's beam as it stands (ranked by tot); the
+    // forced one by pb alone, a rank whose paths all end in a token dropped.
     if (tid < nbeam) {
       double s = f.tot[tid];
-      if constexpr (LEX) {
+      if constexpr (TOK) {
+        if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];
+      } else if constexpr (LEX) {
         const BeamLex& lx = beam_lex_of(lm_arg...);
         if (tnode[Tb & 1][tid] != 0)
           s = ninf;
@@ -961,6 +1023,77 @@ int wfl_asg_beam_search(const float* x, const float* Wt, const float* logz, int 
 }  // extern "C"
 
 extern "C" {
+
+// The beam search of the Transducer criterion.  The reference has no such search: an addition.
+int wfl_transducer_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
+                                  int64_t* ws_bytes) {
+  if (!out_capacity || !ws_bytes) {
+    set_error("transducer_beam_workspace: a NULL pointer");
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = beam_check("transducer_beam_workspace", B, T, C, beam, classes_per_frame, nbest)) return rc;
+  *out_capacity = (int64_t)B * nbest * T;
+  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest).bytes;  // (the plain search's: it may be the one that runs)
+  return WFL_OK;
+}
+
+int wfl_transducer_beam_search(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank, int forced,
+                               int beam, int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out,
+                               int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search";
+  if (!x || !ws || !out || !out_offsets || !scores) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  const int K = classes_per_frame;
+  if (const int rc = beam_check(what, B, T, C, beam, K, nbest)) return rc;
+  if (blank < 0 || blank >= C) {
+    set_error("%s: blank %d is outside [0, %d)", what, blank, C);
+    return WFL_ERR_INVALID;
+  }
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  if (out_capacity < (int64_t)B * nbest * T) {
+    set_error("%s: out holds %lld labels, B nbest T = %lld are needed", what, (long long)out_capacity, (long long)B * nbest * T);
+    return WFL_ERR_INVALID;
+  }
+  // no transitions, CTC's topology: these are section 17's rules, and its search is the one that runs
+  if (!Wt && !forced)
+    return beam_launch(what, x, nullptr, B, T, C, blank, beam, K, nbest, normalize, nullptr, nullptr, ws, out, out_capacity,
+                       out_offsets, scores, stream);
+  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest);
+  char* base = static_cast<char*>(ws);
+  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
+  float* sc = reinterpret_cast<float*>(base + w.sc);
+  float* lse = Wt ? nullptr : reinterpret_cast<float*>(base + w.lse);  // (with transitions logz normalises, not the rows)
+  int2* arena = reinterpret_cast<int2*>(base + w.arena);
+  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
+  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
+  hipStream_t s = (hipStream_t)stream;
+  beam_candidates(x, nullptr, B, T, C, blank, K, cls, sc, lse, s);
+  WFL_LAUNCH_CHECK();
+  const BeamTok a{Wt, normalize ? logz : nullptr, C, forced};
+  const int32_t* no_lengths = nullptr;
+  const float* row_lse = lse;
+  if (beam * (K + 2) <= 1024)
+    hipLaunchKernelGGL((beam_search_kernel<256, BeamTok>), dim3(B), dim3(256), 0, s, no_lengths, T, blank, beam, K, nbest, normalize,
+                       cls, sc, row_lse, arena, fin_node, fin_len, scores, a);
+  else
+    hipLaunchKernelGGL((beam_search_kernel<1024, BeamTok>), dim3(B), dim3(1024), 0, s, no_lengths, T, blank, beam, K, nbest, normalize,
+                       cls, sc, row_lse, arena, fin_node, fin_len, scores, a);
+  WFL_LAUNCH_CHECK();
+  const int n = B * nbest;
+  hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
+                     fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
+  WFL_LAUNCH_CHECK();
+  return WFL_OK;
+}
 
 int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
                         int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,

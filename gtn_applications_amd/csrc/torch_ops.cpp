@@ -1067,6 +1067,40 @@ Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10:
           }};
 }
 
+// The Transducer prefix beam search (wfl_transducer_beam_search): the options are
+// engine.TransducerBeamPlan's, already checked.  Wt: float32 [C + 1, C] on x's device or none (every weight 0); logz:
+// float32 [B] on x's device (wfl_dense_forward's denominator, with Wt and normalize) or none.
+Hypotheses transducer_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
+                                  int blank, bool forced, int beam, int K, int nbest, bool normalize) {
+  const char* what = "transducer_beam_search";
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
+              "transducer_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
+  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
+  at::Tensor W, lz;
+  if (Wt.has_value() && Wt->defined()) {
+    TORCH_CHECK(Wt->device() == x.device() && Wt->scalar_type() == at::kFloat && Wt->is_contiguous() && Wt->dim() == 2 &&
+                    Wt->size(0) == (int64_t)C + 1 && Wt->size(1) == C,
+                "transducer_beam_search: transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+    W = *Wt;
+  }
+  if (logz.has_value() && logz->defined()) {
+    TORCH_CHECK(logz->device() == x.device() && logz->scalar_type() == at::kFloat && logz->is_contiguous() && logz->dim() == 1 &&
+                    logz->numel() == B,
+                "transducer_beam_search: logz must be a contiguous float32 [B] tensor on x's device");
+    lz = *logz;
+  }
+  return {x, B, (int64_t)B * nbest, true, what,
+          [=](int64_t* capacity, int64_t* ws_bytes) {
+            check(wfl_transducer_beam_workspace(B, T, C, beam, K, nbest, capacity, ws_bytes), what);
+          },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            check(wfl_transducer_beam_search(x.data_ptr<float>(), W.defined() ? W.data_ptr<float>() : nullptr,
+                                             lz.defined() ? lz.data_ptr<float>() : nullptr, B, T, C, blank, forced ? 1 : 0, beam, K,
+                                             nbest, normalize ? 1 : 0, ws, out, cap, offs, scores, s),
+                  what);
+          }};
+}
+
 // The launch of `h` into the device's landing buffer -- [offsets: (rows + 1) int64 | scores: rows float64, a scored
 // source | labels: capacity int32], each part padded to 16 bytes -- and from there into fresh CPU tensors: only the
 // labels that survived leave the device.
@@ -1280,6 +1314,19 @@ at::Tensor asg_beam_search_errors(const at::Tensor& x, const at::Tensor& Wt, int
   return hypotheses_errors(asg_beam_source(x, Wt, c10::nullopt, beam, K, 1, drop, num_replabels), ref, tables);
 }
 
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple transducer_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
+                                 int blank, bool forced, int beam, int K, int nbest, bool normalize) {
+  const Collected r = hypotheses_collect(transducer_beam_source(x, Wt, logz, blank, forced, beam, K, nbest, normalize), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+}
+
+// (the first rank, unnormalised: nothing reads the scores)
+at::Tensor transducer_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, int blank, bool forced, int beam,
+                                         int K, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(transducer_beam_source(x, Wt, c10::nullopt, blank, forced, beam, K, 1, false), ref, tables);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1320,6 +1367,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("asg_beam_search_errors", &asg_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
         "asg_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  m.def("transducer_beam_search", &transducer_beam_search, py::arg("x"), py::arg("transitions"), py::arg("logz"),
+        py::arg("blank"), py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
+        "Transducer prefix beam search on the device (engine.TransducerBeamPlan's options): (labels int64 CPU, offsets int64 "
+        "CPU [B nbest + 1], scores float64 CPU [B, nbest]); transitions float32 [C + 1, C] or None, logz float32 [B] or None");
+  m.def("transducer_beam_search_errors", &transducer_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("blank"),
+        py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"),
+        "transducer_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),
         "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors; lengths int32 [B] "

@@ -1151,6 +1151,67 @@ def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normal
     return plan.search(x, Wt, normalize, drop, num_replabels)
 
 
+class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam classes_per_frame nbest")):
+    """The options of one Transducer beam search over C classes (tokens + the blank), checked once (`checked`, the one
+    constructor) and handed on whole, as BeamPlan is for CTC and AsgBeamPlan for ASG: Transducer.beam_search,
+    Transducer.errors(beam_size=) and transducer_beam_search build one plan per call.  `forced`: the token graph's
+    topology (False: the optional blank without repeats, CTC's; True: the forced blank).  No input lengths, LM or
+    lexicon.  Only search() and errors() need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, blank, forced, beam_size, classes_per_frame, nbest, what):
+        """The plan of these arguments, within the limits of wfl_transducer_beam_search, or ValueError (`what`: the call
+        they were given to): what AsgBeamPlan.checked refuses, a blank outside [0, C), a `forced` that is no bool (or 0 / 1)"""
+        C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
+        try:
+            b = None if isinstance(blank, (bool, np.bool_)) else operator.index(blank)
+        except TypeError:
+            b = None
+        if b is None or not 0 <= b < C:
+            raise ValueError(f"{what}: blank must be an integer in [0, {C}), got {blank!r}")
+        if not isinstance(forced, (bool, np.bool_)) and not (isinstance(forced, (int, np.integer)) and forced in (0, 1)):
+            raise ValueError(f"{what}: forced must be a bool, got {forced!r}")
+        return cls(C, b, bool(forced), W, K, n)
+
+    def no_frames(self, B, dtype=torch.int64):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
+        empty sequence with score 0"""
+        hyps = [[torch.empty(0, dtype=dtype) for _ in range(self.nbest)] for _ in range(B)]
+        return hyps, torch.zeros((B, self.nbest), dtype=torch.float64)
+
+    def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
+        """transducer_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt: float32
+        [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
+        logz = None
+        if Wt is not None and normalize:
+            with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+                logz = dense_forward(x, Wt, need_beta=False).logz
+        flat, offsets, scores = N.ops.transducer_beam_search(x, Wt, logz, self.blank, self.forced, self.beam,
+                                                             self.classes_per_frame, self.nbest, bool(normalize))
+        rows = flat.to(dtype).split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
+        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
+
+
+def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True):
+    """Transducer prefix beam search on the device (wfl_transducer_beam_search through csrc/torch_ops.cpp; the rules:
+    include/wfl.h).  x: float32 [B,T,C] on a GPU, contiguous; Wt: float32 [C + 1, C] on x's device,
+    contiguous, the frame-level transitions over the C classes in the dense engine's layout (row 0: start -> c, row
+    1 + i: j -> i), or None: no transition model; blank: the blank's class; forced: the forced-blank token graph instead
+    of the optional blank without repeats.  Returns (hyps, scores): hyps[b][r] the int64 CPU label tensor of rank r of
+    utterance b (views of one tensor; never the blank), scores float64 CPU [B, nbest] -- the log mass of the sequence's
+    alignments that the beam kept, minus the normaliser if `normalize` (with Wt the logz_b of dense_forward(x, Wt),
+    without it the sum of the rows' log-sum-exps): then minus the criterion's loss of that sequence where nothing was
+    pruned, a lower bound of it otherwise; a rank beyond the result is empty with score -inf.  With Wt None and forced
+    False this is ctc_beam_search, bit for bit.  The options are one TransducerBeamPlan."""
+    plan = TransducerBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, "transducer_beam_search")
+    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"transducer_beam_search: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return plan.no_frames(x.shape[0])
+    return plan.search(x, Wt, normalize)
+
+
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)
 
 

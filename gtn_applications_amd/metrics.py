@@ -147,6 +147,13 @@ def asg_beam_search_errors(counter, targets, x, W, plan, drop, num_replabels):
     return N.ops.asg_beam_search_errors(x, W, plan.beam, plan.classes_per_frame, drop, num_replabels, ref, tables)
 
 
+def transducer_beam_search_errors(counter, targets, x, Wt, plan):
+    """The launches of engine.TransducerBeamPlan.search (`plan`: checked; its best hypothesis only; Wt: the transitions
+    or None) and the counts behind them, on x's device: [B, 4] int64 on the host and nothing else"""
+    ref, tables, _ = _staged(counter, targets, x)
+    return N.ops.transducer_beam_search_errors(x, Wt, plan.blank, plan.forced, plan.beam, plan.classes_per_frame, ref, tables)
+
+
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
     ref, tables, drop = _staged(counter, targets, paths, drop)

@@ -757,6 +757,59 @@ int wfl_asg_beam_search(const float* x, const float* Wt /* [(C+1), C] */, const 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device kernels: Transducer prefix beam search (csrc/beam_kernels.hip)
+ *   wfl_dense_viterbi gives the best FRAME PATH of the Transducer criterion; the criterion scores a TOKEN SEQUENCE by the
+ *   sum over all its alignments under a token graph with a blank and a frame-level transition model over tokens + blank.
+ *   This search maximises that, on the launches of wfl_ctc_beam_search, for the two token graphs in which a frame path
+ *   spells exactly one token sequence: the optional blank without repeats (CTC's topology, forced = 0) and the forced
+ *   blank (forced = 1: every token is entered from the blank state, repeats itself, and returns to the blank; a path
+ *   starts and ends in the blank).  The reference has no such decoder.
+ *   Input, per utterance b over all T frames: x [B,T,C] float32; the blank class; optionally the transitions Wt
+ *   [(C+1), C] float32 in the dense engine's layout (Wt[0][c] is start -> c, Wt[1+i][j] is j -> i) over the same C
+ *   classes, the blank among them.  A NaN counts as -inf in x and Wt; +inf is not a weight.  W = beam in [1, 64],
+ *   K = classes_per_frame in [1, min(C, 64)], nbest in [1, W], C <= 16384.  No input lengths: the Transducer has none.
+ *   w(p, c) is the weight into class c behind frame label p: Wt[1+c][p], Wt[0][c] from the start, 0 if Wt is NULL.
+ *     1. arithmetic (float64, lae), candidates (the K best EMISSION scores, ties to the lower class, the blank appended
+ *        if it is not among them), prefix identity, merging, selection and tie order are wfl_ctc_beam_search's;
+ *     2. a hypothesis is (prefix, pb, pnb): the log mass of its alignments whose last frame is the blank / is the
+ *        prefix' last label l.  The search starts from the empty prefix with pb = 0, pnb = -inf; the state behind pb is
+ *        the START in frame 0 (row 0 of Wt) and the blank from frame 1 on: call it beta;
+ *     3. the stay entry of hypothesis i in frame t, s_c = (double)x[b,t,c]:
+ *          pb'  = s_blank + lae(pb_i + w(beta, blank), pnb_i + w(l, blank)),
+ *          pnb' = (s_l + pnb_i) + w(l, l) if l is a candidate, else -inf;
+ *     4. the extension of i by a candidate c != blank:
+ *          forced = 0, c != l:  e = s_c + lae(pb_i + w(beta, c), pnb_i + w(l, c)),
+ *          forced = 0, c == l:  e = s_c + (pb_i + w(beta, c)),
+ *          forced = 1:          e = s_c + (pb_i + w(beta, c)) for every c, and NO extension in frame 0;
+ *        merged into the stay entry of the hypothesis with that prefix (pnb' = lae(pnb', e)) or a new entry
+ *        (pb' = -inf, pnb' = e); entries are ranked by tot' = lae(pb', pnb') in both topologies;
+ *     5. result, forced = 0: the first nbest ranks of the final beam with tot;
+ *     6. result, forced = 1: a path ends in the blank, so only pb counts: ranks with pb = -inf are dropped, the rest are
+ *        ranked by pb, descending, ties to the earlier rank; ranks beyond those are empty sequences with score -inf;
+ *     7. normalize != 0: minus the normaliser -- with Wt (double)logz[b], logz [B] float32 on the device, the denominator
+ *        wfl_dense_forward computes for x and Wt; without Wt the sum of the rows' log-sum-exps by wfl_ctc_beam_search's
+ *        rule.  The normalised score of a sequence is then minus the criterion's loss of it where nothing was pruned, a
+ *        lower bound otherwise.
+ *   Wt == NULL and forced == 0 are wfl_ctc_beam_search's rules, and its search is what runs: bit-identical results.
+ *   out (capacity B nbest T int32), out_offsets [B nbest + 1] int64, scores [B nbest] float64 as in wfl_ctc_beam_search
+ *   (the blank is never a label of a result); plain stores in a fixed order, any device-accessible memory; deterministic.
+ *   ws: device scratch of wfl_transducer_beam_workspace's size, 16-byte aligned.  Three launches on `stream` (candidates;
+ *   beam: a workgroup per utterance, up to three gathers from Wt per stay and two per extension; write), no allocation,
+ *   no synchronisation, no atomics on global memory, no cross-workgroup waits, every loop bounded by T, W, K.
+ *   WFL_ERR_INVALID: a NULL required pointer (Wt and logz may be NULL), B, T or C < 1, blank outside [0, C), forced not
+ *   0 or 1, beam outside [1, 64], classes_per_frame outside [1, min(C, 64)], nbest outside [1, beam], out_capacity too
+ *   small, normalize != 0 with Wt but without logz, logz without Wt.  WFL_ERR_UNSUPPORTED: C > 16384.
+ *   Not here: the ambiguous token graphs (no blank; the optional blank with repeats), an LM, a lexicon, input lengths.
+ * ------------------------------------------------------------------------------------------------ */
+/* out_capacity = B nbest T (int32 elements of `out`), ws_bytes = the device scratch of a call */
+int wfl_transducer_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
+                                  int64_t* ws_bytes);
+int wfl_transducer_beam_search(const float* x, const float* Wt /* [(C+1), C] or NULL */, const float* logz /* [B] or NULL */,
+                               int B, int T, int C, int blank, int forced, int beam, int classes_per_frame, int nbest,
+                               int normalize, void* ws, int32_t* out, int64_t out_capacity,
+                               int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
  *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
  *   train.py:278-284 and test.py:94-109 -- per utterance b:
