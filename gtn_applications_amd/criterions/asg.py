@@ -375,10 +375,7 @@ class ASG(torch.nn.Module):
 
     def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
         """The arguments of a beam search, checked before anything needs a device: the E.AsgBeamPlan of the options"""
-        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
-            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
-        if not outputs.dtype.is_floating_point:
-            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        E.check_beam_outputs(outputs, what)
         if outputs.shape[2] != self.N:
             raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {self.N}")
         return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)

@@ -350,10 +350,7 @@ class CTC(torch.nn.Module):
     def _beam_plan(self, outputs, input_lengths, what, *options):
         """The arguments of a beam search, checked before anything needs a device: (the E.BeamPlan of `options`, which
         are BeamPlan.checked's from beam_size to word_bonus; lengths or None)"""
-        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
-            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
-        if not outputs.dtype.is_floating_point:
-            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        E.check_beam_outputs(outputs, what)
         B, T, C = outputs.shape
         if C < 1:
             raise ValueError(f"{what}: outputs have no classes")

@@ -367,10 +367,7 @@ class Transducer(torch.nn.Module):
     def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
         """The arguments of a beam search, checked before anything needs a device: (the E.TransducerBeamPlan of the
         options, the transition model's kind: "none", "unigram" or "bigram")"""
-        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
-            raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
-        if not outputs.dtype.is_floating_point:
-            raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+        E.check_beam_outputs(outputs, what)
         self.tokens.arc_sort()
         n = ctypes.c_int()
         mode = N.lib.wfl_graph_token_kind(self.tokens._h, ctypes.byref(n))

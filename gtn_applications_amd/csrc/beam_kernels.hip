@@ -35,6 +35,8 @@
 // fifth pack, BeamTok, carries the frame-level transitions over tokens + blank (or none) and the token graph's topology
 // -- CTC's two masses per hypothesis and a transition weight on every frame-to-frame step: three gathers in a stay, two
 // gathers and a log-add in an extension; the forced topology leaves the blank state only and ranks the result by pb.
+// All five issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
 #include "device_common.h"
@@ -54,6 +56,7 @@ constexpr int kBeamRankAll = 512;  // entries above the bound up to which every 
 // workspace: [candidate classes: B T (K+1) int32 | candidate scores: B T (K+1) float | row lse: B T float |
 //             arena: B T W int2 | final node: B nbest int32 | final length: B nbest int32]
 // asg (wfl_asg_beam_search): no row lse, and behind the rest [mapped length: B nbest int32]
+// (beam_workspace reports its size and beam_run turns it into pointers: nothing else reads it)
 struct BeamWs {
   int64_t cls, sc, lse, arena, fin_node, fin_len, out_len, bytes;
 };
@@ -829,7 +832,14 @@ __global__ void __launch_bounds__(256) beam_write_kernel(int n, int T, int W, in
 
 using namespace wfl;
 
-static int beam_check(const char* what, int B, int T, int C, int beam, int K, int nbest) {
+// ------------------------------------------------------------------------------------------------------------
+// The host side: one launch path (beam_run) and one set of checks (beam_check, beam_call_check) for all five
+// searches.  An entry makes the checks that are its own, builds its pack and calls beam_run; a new search is a new
+// pack (a struct by value, its BeamPack traits, its branches in the kernel) and such an entry.
+// ------------------------------------------------------------------------------------------------------------
+
+// the sizes of a search; R: the replabels of the mapping on the way out, by wfl_decode_workspace's rule (0: none)
+static int beam_check(const char* what, int B, int T, int C, int beam, int K, int nbest, int R = 0) {
   if (B < 1 || T < 1 || C < 1 || beam < 1 || beam > kBeamMax || K < 1 || K > std::min(C, kBeamMax) || nbest < 1 || nbest > beam) {
     set_error("%s: bad arguments (B %d, T %d, C %d, beam %d, classes_per_frame %d, nbest %d)", what, B, T, C, beam, K, nbest);
     return WFL_ERR_INVALID;
@@ -839,24 +849,66 @@ static int beam_check(const char* what, int B, int T, int C, int beam, int K, in
     set_error("%s: B %d, T %d, C %d is more than the beam search takes (C <= %d)", what, B, T, C, kBeamMaxClasses);
     return WFL_ERR_UNSUPPORTED;
   }
-  return WFL_OK;
-}
-
-extern "C" {
-
-int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
-                           int64_t* ws_bytes) {
-  if (!out_capacity || !ws_bytes) {
-    set_error("ctc_beam_workspace: a NULL pointer");
+  if (R < 0) {
+    set_error("%s: num_replabels %d is negative", what, R);
     return WFL_ERR_INVALID;
   }
-  if (const int rc = beam_check("ctc_beam_workspace", B, T, C, beam, classes_per_frame, nbest)) return rc;
-  *out_capacity = (int64_t)B * nbest * T;
-  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest).bytes;
+  if ((int64_t)T * std::max(1, R) > 0x7fffffffLL) {
+    set_error("%s: T %d, num_replabels %d is more than the index width of the unpacking takes", what, T, R);
+    return WFL_ERR_UNSUPPORTED;
+  }
   return WFL_OK;
 }
 
-}  // extern "C"
+// the three workspace queries (asg: its layout; R: per rank wfl_decode_workspace's T max(1, R) labels)
+static int beam_workspace(const char* what, int B, int T, int C, int beam, int K, int nbest, int R, bool asg,
+                          int64_t* out_capacity, int64_t* ws_bytes) {
+  if (!out_capacity || !ws_bytes) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = beam_check(what, B, T, C, beam, K, nbest, R)) return rc;
+  *out_capacity = (int64_t)B * nbest * T * std::max(1, R);
+  *ws_bytes = beam_ws_layout(B, T, beam, K, nbest, asg).bytes;
+  return WFL_OK;
+}
+
+// what the five entries vary in, apart from the pack; the last four as the three CTC entries have them
+struct BeamCall {
+  const float* x;
+  const int32_t* lengths;  // or NULL
+  int B, T, C;
+  int blank;  // -1 with `asg`: none
+  int beam, K, nbest;
+  int normalize;  // as the beam kernel receives it
+  void* ws;
+  int32_t* out;
+  int64_t out_capacity;
+  int64_t* out_offsets;
+  double* scores;
+  void* stream;
+  bool lse = true;       // the candidates launch computes the rows' log-sum-exps and the beam launch reads them
+  bool asg = false;      // the ASG search: no blank; its layout of the workspace, which alone has room for a mapping
+  int drop = -1, R = 0;  // the mapping on the way out; -1, 0: none, beam_write_kernel<false>
+};
+
+// what every entry refuses first, in this order; the room in `out` comes behind it, in beam_run
+static int beam_call_check(const char* what, const BeamCall& c) {
+  if (!c.x || !c.ws || !c.out || !c.out_offsets || !c.scores) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = beam_check(what, c.B, c.T, c.C, c.beam, c.K, c.nbest, c.R)) return rc;
+  if (!c.asg && (c.blank < 0 || c.blank >= c.C)) {
+    set_error("%s: blank %d is outside [0, %d)", what, c.blank, c.C);
+    return WFL_ERR_INVALID;
+  }
+  if (c.drop < -1 || c.drop >= c.C) {
+    set_error("%s: drop %d is outside [-1, %d)", what, c.drop, c.C);
+    return WFL_ERR_INVALID;
+  }
+  return WFL_OK;
+}
 
 // the candidates launch (blank < 0: none, slot K stays empty; lse NULL: no row log-sum-exp)
 static void beam_candidates(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int K, int32_t* cls, float* sc,
@@ -875,75 +927,54 @@ static void beam_candidates(const float* x, const int32_t* lengths, int B, int T
     candidates(beam_candidates_kernel<0>);
 }
 
-// the three launches of a search; lm: NULL, or the LM of wfl_ctc_beam_search_lm (already checked); lex: NULL, or the
-// lexicon of wfl_ctc_beam_search_lexicon (already checked; never with lm, its word LM is inside it)
-static int beam_launch(const char* what, const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
-                       int classes_per_frame, int nbest, int normalize, const BeamLm* lm, const BeamLex* lex, void* ws,
-                       int32_t* out, int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
-  if (!x || !ws || !out || !out_offsets || !scores) {
-    set_error("%s: a NULL pointer", what);
-    return WFL_ERR_INVALID;
-  }
-  if (const int rc = beam_check(what, B, T, C, beam, classes_per_frame, nbest)) return rc;
-  if (blank < 0 || blank >= C) {
-    set_error("%s: blank %d is outside [0, %d)", what, blank, C);
-    return WFL_ERR_INVALID;
-  }
-  if (out_capacity < (int64_t)B * nbest * T) {
-    set_error("%s: out holds %lld labels, B nbest T = %lld are needed", what, (long long)out_capacity, (long long)B * nbest * T);
-    return WFL_ERR_INVALID;
-  }
-  const int K = classes_per_frame;
-  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest);
-  char* base = static_cast<char*>(ws);
-  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
-  float* sc = reinterpret_cast<float*>(base + w.sc);
-  float* lse = reinterpret_cast<float*>(base + w.lse);
-  int2* arena = reinterpret_cast<int2*>(base + w.arena);
-  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
-  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
-  hipStream_t s = (hipStream_t)stream;
-  beam_candidates(x, lengths, B, T, C, blank, K, cls, sc, lse, s);
-  WFL_LAUNCH_CHECK();
-  if (lex) {
-    if (beam * (K + 2) <= 1024)
-      hipLaunchKernelGGL((beam_search_kernel<256, BeamLex>), dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize,
-                         cls, sc, lse, arena, fin_node, fin_len, scores, *lex);
-    else
-      hipLaunchKernelGGL((beam_search_kernel<1024, BeamLex>), dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize,
-                         cls, sc, lse, arena, fin_node, fin_len, scores, *lex);
-  } else if (lm) {
-    if (beam * (K + 2) <= 1024)
-      hipLaunchKernelGGL((beam_search_kernel<256, BeamLm>), dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls,
-                         sc, lse, arena, fin_node, fin_len, scores, *lm);
-    else
-      hipLaunchKernelGGL((beam_search_kernel<1024, BeamLm>), dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize,
-                         cls, sc, lse, arena, fin_node, fin_len, scores, *lm);
-  } else if (beam * (K + 2) <= 1024)
-    hipLaunchKernelGGL(beam_search_kernel<256>, dim3(B), dim3(256), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls, sc,
-                       lse, arena, fin_node, fin_len, scores);
-  else
-    hipLaunchKernelGGL(beam_search_kernel<1024>, dim3(B), dim3(1024), 0, s, lengths, T, blank, beam, K, nbest, normalize, cls,
-                       sc, lse, arena, fin_node, fin_len, scores);
-  WFL_LAUNCH_CHECK();
-  const int n = B * nbest;
-  hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
-                     fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
-  WFL_LAUNCH_CHECK();
-  return WFL_OK;
+template <typename T>
+static T* beam_ws_at(void* ws, int64_t offset) {
+  return reinterpret_cast<T*>(static_cast<char*>(ws) + offset);
 }
 
-// what both ASG entries refuse: beam_check's, and the mapping's arguments by wfl_decode_workspace's rule
-static int asg_beam_check(const char* what, int B, int T, int C, int beam, int K, int nbest, int R) {
-  if (const int rc = beam_check(what, B, T, C, beam, K, nbest)) return rc;
-  if (R < 0) {
-    set_error("%s: num_replabels %d is negative", what, R);
+// A whole search: the checks every entry shares, then the launches -- candidates, beam, write (behind a count, where
+// the results are mapped).  pack: nothing (the plain search), or the one struct the beam kernel takes behind its
+// arguments, already checked by its entry.
+template <typename... Pack>
+static int beam_run(const char* what, const BeamCall& c, Pack... pack) {
+  if (const int rc = beam_call_check(what, c)) return rc;
+  const int B = c.B, T = c.T, W = c.beam, K = c.K, nbest = c.nbest, n = B * nbest;
+  const int64_t need = (int64_t)n * T * std::max(1, c.R);
+  if (c.out_capacity < need) {
+    set_error("%s: out holds %lld labels, B nbest T%s = %lld are needed", what, (long long)c.out_capacity,
+              c.asg ? " max(1, num_replabels)" : "", (long long)need);
     return WFL_ERR_INVALID;
   }
-  if ((int64_t)T * std::max(1, R) > 0x7fffffffLL) {
-    set_error("%s: T %d, num_replabels %d is more than the index width of the unpacking takes", what, T, R);
-    return WFL_ERR_UNSUPPORTED;
+  const BeamWs w = beam_ws_layout(B, T, W, K, nbest, c.asg);
+  int32_t* cls = beam_ws_at<int32_t>(c.ws, w.cls);
+  float* sc = beam_ws_at<float>(c.ws, w.sc);
+  float* lse = c.lse ? beam_ws_at<float>(c.ws, w.lse) : nullptr;
+  int2* arena = beam_ws_at<int2>(c.ws, w.arena);
+  int32_t* fin_node = beam_ws_at<int32_t>(c.ws, w.fin_node);
+  int32_t* fin_len = beam_ws_at<int32_t>(c.ws, w.fin_len);
+  int32_t* out_len = c.asg ? beam_ws_at<int32_t>(c.ws, w.out_len) : nullptr;
+  hipStream_t s = (hipStream_t)c.stream;
+  beam_candidates(c.x, c.lengths, B, T, c.C, c.blank, K, cls, sc, lse, s);
+  WFL_LAUNCH_CHECK();
+  if (W * (K + 2) <= 1024)
+    hipLaunchKernelGGL((beam_search_kernel<256, Pack...>), dim3(B), dim3(256), 0, s, c.lengths, T, c.blank, W, K, nbest, c.normalize,
+                       cls, sc, lse, arena, fin_node, fin_len, c.scores, pack...);
+  else
+    hipLaunchKernelGGL((beam_search_kernel<1024, Pack...>), dim3(B), dim3(1024), 0, s, c.lengths, T, c.blank, W, K, nbest, c.normalize,
+                       cls, sc, lse, arena, fin_node, fin_len, c.scores, pack...);
+  WFL_LAUNCH_CHECK();
+  const dim3 waves((unsigned)((n + 3) / 4));
+  if (c.drop < 0 && c.R == 0) {  // the raw class sequences: the write launch as it is
+    hipLaunchKernelGGL(beam_write_kernel<false>, waves, dim3(256), 0, s, n, T, W, nbest, arena, fin_node, fin_len, c.out,
+                       c.out_offsets, (const int32_t*)nullptr, -1, 0);
+  } else {  // count first, then store: a result is walked from its end
+    hipLaunchKernelGGL(beam_map_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, W, nbest, c.drop, c.R, arena,
+                       fin_node, fin_len, out_len);
+    WFL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_write_kernel<true>, waves, dim3(256), 0, s, n, T, W, nbest, arena, fin_node, fin_len, c.out,
+                       c.out_offsets, (const int32_t*)out_len, c.drop, c.R);
   }
+  WFL_LAUNCH_CHECK();
   return WFL_OK;
 }
 
@@ -954,103 +985,39 @@ extern "C" {
 // reference has no such search: it is an addition, like wfl_ctc_beam_search.
 int wfl_asg_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int num_replabels,
                            int64_t* out_capacity, int64_t* ws_bytes) {
-  if (!out_capacity || !ws_bytes) {
-    set_error("asg_beam_workspace: a NULL pointer");
-    return WFL_ERR_INVALID;
-  }
-  if (const int rc = asg_beam_check("asg_beam_workspace", B, T, C, beam, classes_per_frame, nbest, num_replabels)) return rc;
-  *out_capacity = (int64_t)B * nbest * T * std::max(1, num_replabels);  // (wfl_decode_workspace's B T max(1, R), per rank)
-  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest, true).bytes;
-  return WFL_OK;
+  return beam_workspace("asg_beam_workspace", B, T, C, beam, classes_per_frame, nbest, num_replabels, true, out_capacity, ws_bytes);
 }
 
 int wfl_asg_beam_search(const float* x, const float* Wt, const float* logz, int B, int T, int C, int beam, int classes_per_frame,
                         int nbest, int drop, int num_replabels, void* ws, int32_t* out, int64_t out_capacity,
                         int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "asg_beam_search";
-  if (!x || !Wt || !ws || !out || !out_offsets || !scores) {
+  if (!Wt) {
     set_error("%s: a NULL pointer", what);
     return WFL_ERR_INVALID;
   }
-  const int K = classes_per_frame, R = num_replabels;
-  if (const int rc = asg_beam_check(what, B, T, C, beam, K, nbest, R)) return rc;
-  if (drop < -1 || drop >= C) {
-    set_error("%s: drop %d is outside [-1, %d)", what, drop, C);
-    return WFL_ERR_INVALID;
-  }
-  if (out_capacity < (int64_t)B * nbest * T * std::max(1, R)) {
-    set_error("%s: out holds %lld labels, B nbest T max(1, num_replabels) = %lld are needed", what, (long long)out_capacity,
-              (long long)B * nbest * T * std::max(1, R));
-    return WFL_ERR_INVALID;
-  }
-  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest, true);
-  char* base = static_cast<char*>(ws);
-  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
-  float* sc = reinterpret_cast<float*>(base + w.sc);
-  int2* arena = reinterpret_cast<int2*>(base + w.arena);
-  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
-  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
-  int32_t* out_len = reinterpret_cast<int32_t*>(base + w.out_len);
-  hipStream_t s = (hipStream_t)stream;
-  // no blank, no lengths, no row log-sum-exp: ASG has none of them
-  beam_candidates(x, nullptr, B, T, C, -1, K, cls, sc, nullptr, s);
-  WFL_LAUNCH_CHECK();
-  const BeamAsg a{Wt, logz, C};
-  const int32_t* no_lengths = nullptr;
-  const float* no_lse = nullptr;
-  if (beam * (K + 2) <= 1024)
-    hipLaunchKernelGGL((beam_search_kernel<256, BeamAsg>), dim3(B), dim3(256), 0, s, no_lengths, T, -1, beam, K, nbest, logz ? 1 : 0,
-                       cls, sc, no_lse, arena, fin_node, fin_len, scores, a);
-  else
-    hipLaunchKernelGGL((beam_search_kernel<1024, BeamAsg>), dim3(B), dim3(1024), 0, s, no_lengths, T, -1, beam, K, nbest, logz ? 1 : 0,
-                       cls, sc, no_lse, arena, fin_node, fin_len, scores, a);
-  WFL_LAUNCH_CHECK();
-  const int n = B * nbest;
-  if (drop < 0 && R == 0) {  // the raw class sequences: the write launch as it is
-    hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
-                       fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
-  } else {  // count first, then store: a result is walked from its end
-    hipLaunchKernelGGL(beam_map_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, beam, nbest, drop, R, arena,
-                       fin_node, fin_len, out_len);
-    WFL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_write_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
-                       fin_len, out, out_offsets, (const int32_t*)out_len, drop, R);
-  }
-  WFL_LAUNCH_CHECK();
-  return WFL_OK;
+  // no blank, no lengths, no row log-sum-exp: ASG has none of them, and normalises by the pack's logz
+  const BeamCall c{x, nullptr, B, T, C, -1, beam, classes_per_frame, nbest, logz ? 1 : 0, ws, out, out_capacity, out_offsets,
+                   scores, stream, false, true, drop, num_replabels};
+  return beam_run(what, c, BeamAsg{Wt, logz, C});
 }
-
-}  // extern "C"
-
-extern "C" {
 
 // The beam search of the Transducer criterion.  The reference has no such search: an addition.
 int wfl_transducer_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
                                   int64_t* ws_bytes) {
-  if (!out_capacity || !ws_bytes) {
-    set_error("transducer_beam_workspace: a NULL pointer");
-    return WFL_ERR_INVALID;
-  }
-  if (const int rc = beam_check("transducer_beam_workspace", B, T, C, beam, classes_per_frame, nbest)) return rc;
-  *out_capacity = (int64_t)B * nbest * T;
-  *ws_bytes = beam_ws_layout(B, T, beam, classes_per_frame, nbest).bytes;  // (the plain search's: it may be the one that runs)
-  return WFL_OK;
+  // (the plain search's layout: it may be the one that runs)
+  return beam_workspace("transducer_beam_workspace", B, T, C, beam, classes_per_frame, nbest, 0, false, out_capacity, ws_bytes);
 }
 
 int wfl_transducer_beam_search(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank, int forced,
                                int beam, int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out,
                                int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "transducer_beam_search";
-  if (!x || !ws || !out || !out_offsets || !scores) {
-    set_error("%s: a NULL pointer", what);
-    return WFL_ERR_INVALID;
-  }
-  const int K = classes_per_frame;
-  if (const int rc = beam_check(what, B, T, C, beam, K, nbest)) return rc;
-  if (blank < 0 || blank >= C) {
-    set_error("%s: blank %d is outside [0, %d)", what, blank, C);
-    return WFL_ERR_INVALID;
-  }
+  // no lengths; with transitions logz normalises, not the rows
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own have always come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
   if (forced != 0 && forced != 1) {
     set_error("%s: forced %d is neither 0 nor 1", what, forced);
     return WFL_ERR_INVALID;
@@ -1059,47 +1026,21 @@ int wfl_transducer_beam_search(const float* x, const float* Wt, const float* log
     set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
     return WFL_ERR_INVALID;
   }
-  if (out_capacity < (int64_t)B * nbest * T) {
-    set_error("%s: out holds %lld labels, B nbest T = %lld are needed", what, (long long)out_capacity, (long long)B * nbest * T);
-    return WFL_ERR_INVALID;
-  }
   // no transitions, CTC's topology: these are section 17's rules, and its search is the one that runs
-  if (!Wt && !forced)
-    return beam_launch(what, x, nullptr, B, T, C, blank, beam, K, nbest, normalize, nullptr, nullptr, ws, out, out_capacity,
-                       out_offsets, scores, stream);
-  const BeamWs w = beam_ws_layout(B, T, beam, K, nbest);
-  char* base = static_cast<char*>(ws);
-  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
-  float* sc = reinterpret_cast<float*>(base + w.sc);
-  float* lse = Wt ? nullptr : reinterpret_cast<float*>(base + w.lse);  // (with transitions logz normalises, not the rows)
-  int2* arena = reinterpret_cast<int2*>(base + w.arena);
-  int32_t* fin_node = reinterpret_cast<int32_t*>(base + w.fin_node);
-  int32_t* fin_len = reinterpret_cast<int32_t*>(base + w.fin_len);
-  hipStream_t s = (hipStream_t)stream;
-  beam_candidates(x, nullptr, B, T, C, blank, K, cls, sc, lse, s);
-  WFL_LAUNCH_CHECK();
-  const BeamTok a{Wt, normalize ? logz : nullptr, C, forced};
-  const int32_t* no_lengths = nullptr;
-  const float* row_lse = lse;
-  if (beam * (K + 2) <= 1024)
-    hipLaunchKernelGGL((beam_search_kernel<256, BeamTok>), dim3(B), dim3(256), 0, s, no_lengths, T, blank, beam, K, nbest, normalize,
-                       cls, sc, row_lse, arena, fin_node, fin_len, scores, a);
-  else
-    hipLaunchKernelGGL((beam_search_kernel<1024, BeamTok>), dim3(B), dim3(1024), 0, s, no_lengths, T, blank, beam, K, nbest, normalize,
-                       cls, sc, row_lse, arena, fin_node, fin_len, scores, a);
-  WFL_LAUNCH_CHECK();
-  const int n = B * nbest;
-  hipLaunchKernelGGL(beam_write_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, n, T, beam, nbest, arena, fin_node,
-                     fin_len, out, out_offsets, (const int32_t*)nullptr, -1, 0);
-  WFL_LAUNCH_CHECK();
-  return WFL_OK;
+  if (!Wt && !forced) return beam_run(what, c);
+  return beam_run(what, c, BeamTok{Wt, normalize ? logz : nullptr, C, forced});
+}
+
+int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
+                           int64_t* ws_bytes) {
+  return beam_workspace("ctc_beam_workspace", B, T, C, beam, classes_per_frame, nbest, 0, false, out_capacity, ws_bytes);
 }
 
 int wfl_ctc_beam_search(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam, int classes_per_frame,
                         int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
                         double* scores, void* stream) {
-  return beam_launch("ctc_beam_search", x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, nullptr, ws,
-                     out, out_capacity, out_offsets, scores, stream);
+  return beam_run("ctc_beam_search", {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity,
+                                      out_offsets, scores, stream});
 }
 
 static int ngram_lm_shape(const char* what, const wfl_ngram_lm* lm) {
@@ -1213,8 +1154,8 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths, int B, int T,
   // the largest LM term of an extension, by the operations the kernel forms a term with (0 * inf: no bound)
   const double t0 = lm_weight * lm->step_min, t1 = lm_weight * lm->step_max;
   d.bound = (t0 != t0 || t1 != t1) ? __builtin_inf() : fmax(t0, t1) + length_bonus;
-  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, &d, nullptr, ws, out,
-                     out_capacity, out_offsets, scores, stream);
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
 }
 
 static int lexicon_shape(const char* what, const wfl_lexicon* lex) {
@@ -1334,8 +1275,8 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, i
   // (without a word LM every word's step is 0: the bounds of step are [0, 0])
   d.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
   d.lm.bound = d.bound;
-  return beam_launch(what, x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, nullptr, &d, ws, out,
-                     out_capacity, out_offsets, scores, stream);
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
 }
 
 }  // extern "C"

@@ -894,6 +894,16 @@ struct Hypotheses {
   std::function<void(void* ws, int32_t* out, int64_t capacity, int64_t* offsets, double* scores, void* stream)> launch;
 };
 
+// x: the emissions of a decode or a search; their sizes
+struct Emissions {
+  int B, T, C;
+};
+Emissions checked_emissions(const at::Tensor& x, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3, what,
+              ": x must be a contiguous float32 [B,T,C] device tensor");
+  return {(int)x.size(0), (int)x.size(1), (int)x.size(2)};
+}
+
 // lengths: int32 [B] on x's device (a padded batch), or none
 at::Tensor checked_lengths(const c10::optional<at::Tensor>& lengths, const at::Tensor& x, const char* what) {
   if (!lengths.has_value() || !lengths->defined()) return at::Tensor();
@@ -903,12 +913,29 @@ at::Tensor checked_lengths(const c10::optional<at::Tensor>& lengths, const at::T
   return *lengths;
 }
 
+// transitions: float32 [C + 1, C] on x's device (the dense engine's layout), or none
+at::Tensor checked_transitions(const c10::optional<at::Tensor>& Wt, const at::Tensor& x, const char* what) {
+  if (!Wt.has_value() || !Wt->defined()) return at::Tensor();
+  TORCH_CHECK(Wt->device() == x.device() && Wt->scalar_type() == at::kFloat && Wt->is_contiguous() && Wt->dim() == 2 &&
+                  Wt->size(0) == x.size(2) + 1 && Wt->size(1) == x.size(2),
+              what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+  return *Wt;
+}
+
+// logz: float32 [B] on x's device (wfl_dense_forward's denominator), or none
+at::Tensor checked_logz(const c10::optional<at::Tensor>& logz, const at::Tensor& x, const char* what) {
+  if (!logz.has_value() || !logz->defined()) return at::Tensor();
+  TORCH_CHECK(logz->device() == x.device() && logz->scalar_type() == at::kFloat && logz->is_contiguous() && logz->dim() == 1 &&
+                  logz->numel() == x.size(0),
+              what, ": logz must be a contiguous float32 [B] tensor on x's device");
+  return *logz;
+}
+
 // lengths given: wfl_decode_emissions_lengths, frames t >= lengths[b] are not decoded; none: every frame is
 Hypotheses emissions_source(const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t drop, int64_t num_replabels,
                             int64_t flags, const c10::optional<at::Tensor>& lengths) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
-              "decode_emissions: x must be a contiguous float32 [B,T,C] device tensor");
-  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2), R = (int)num_replabels;
+  const Emissions e = checked_emissions(x, "decode_emissions");
+  const int B = e.B, T = e.T, C = e.C, R = (int)num_replabels;
   at::Tensor bt;
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->device() == x.device() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == C,
@@ -1008,33 +1035,30 @@ struct BeamPlan {
 // nothing fused: wfl_ctc_beam_search, the call it was; an lm: wfl_ctc_beam_search_lm; a lexicon: wfl_ctc_beam_search_lexicon
 Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& p, int nbest,
                        bool normalize) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
-              "ctc_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
-  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
-  const at::Tensor lt = checked_lengths(lengths, x, "ctc_beam_search");
+  const char* what = "ctc_beam_search";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor lt = checked_lengths(lengths, x, what);
   TORCH_CHECK(!p.lm || p.lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
   TORCH_CHECK(!p.lexicon || p.lexicon->ints.device() == x.device(),
               "ctc_beam_search_lexicon: the lexicon's arrays must be on x's device");
-  return {x, B, (int64_t)B * nbest, true, "ctc_beam_search",
-          [=](int64_t* capacity, int64_t* ws_bytes) {
-            check(wfl_ctc_beam_workspace(B, T, C, p.beam, p.K, nbest, capacity, ws_bytes), "ctc_beam_search");
-          },
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_ctc_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
             const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
             if (p.lexicon)
-              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
-                                                &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus,
-                                                p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
+                                                normalize ? 1 : 0, &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
+                                                p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
                     "ctc_beam_search_lexicon");
             else if (p.lm)
-              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
+              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
                                            &p.lm->lm, p.lm_weight, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs,
                                            scores, s),
                     "ctc_beam_search_lm");
             else
-              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, B, T, C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0, ws, out,
-                                        cap, offs, scores, s),
-                    "ctc_beam_search");
+              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0, ws,
+                                        out, cap, offs, scores, s),
+                    what);
           }};
 }
 
@@ -1043,27 +1067,17 @@ Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& len
 // num_replabels: the mapping of the results on their way out (-1, 0: the raw class sequences).
 Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, int beam, int K,
                            int nbest, int64_t drop, int64_t num_replabels) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
-              "asg_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
-  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2), R = (int)num_replabels;
-  TORCH_CHECK(Wt.device() == x.device() && Wt.scalar_type() == at::kFloat && Wt.is_contiguous() && Wt.dim() == 2 &&
-                  Wt.size(0) == (int64_t)C + 1 && Wt.size(1) == C,
-              "asg_beam_search: transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
-  at::Tensor lz;
-  if (logz.has_value() && logz->defined()) {
-    TORCH_CHECK(logz->device() == x.device() && logz->scalar_type() == at::kFloat && logz->is_contiguous() && logz->dim() == 1 &&
-                    logz->numel() == B,
-                "asg_beam_search: logz must be a contiguous float32 [B] tensor on x's device");
-    lz = *logz;
-  }
-  return {x, B, (int64_t)B * nbest, true, "asg_beam_search",
-          [=](int64_t* capacity, int64_t* ws_bytes) {
-            check(wfl_asg_beam_workspace(B, T, C, beam, K, nbest, R, capacity, ws_bytes), "asg_beam_search");
-          },
+  const char* what = "asg_beam_search";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  TORCH_CHECK(W.defined(), what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+  const int R = (int)num_replabels;
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_asg_beam_workspace(e.B, e.T, e.C, beam, K, nbest, R, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_asg_beam_search(x.data_ptr<float>(), Wt.data_ptr<float>(), lz.defined() ? lz.data_ptr<float>() : nullptr, B, T,
-                                      C, beam, K, nbest, (int)drop, R, ws, out, cap, offs, scores, s),
-                  "asg_beam_search");
+            check(wfl_asg_beam_search(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, beam, K, nbest, (int)drop, R, ws, out,
+                                      cap, offs, scores, s),
+                  what);
           }};
 }
 
@@ -1073,29 +1087,12 @@ Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10:
 Hypotheses transducer_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
                                   int blank, bool forced, int beam, int K, int nbest, bool normalize) {
   const char* what = "transducer_beam_search";
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 3,
-              "transducer_beam_search: x must be a contiguous float32 [B,T,C] device tensor");
-  const int B = (int)x.size(0), T = (int)x.size(1), C = (int)x.size(2);
-  at::Tensor W, lz;
-  if (Wt.has_value() && Wt->defined()) {
-    TORCH_CHECK(Wt->device() == x.device() && Wt->scalar_type() == at::kFloat && Wt->is_contiguous() && Wt->dim() == 2 &&
-                    Wt->size(0) == (int64_t)C + 1 && Wt->size(1) == C,
-                "transducer_beam_search: transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
-    W = *Wt;
-  }
-  if (logz.has_value() && logz->defined()) {
-    TORCH_CHECK(logz->device() == x.device() && logz->scalar_type() == at::kFloat && logz->is_contiguous() && logz->dim() == 1 &&
-                    logz->numel() == B,
-                "transducer_beam_search: logz must be a contiguous float32 [B] tensor on x's device");
-    lz = *logz;
-  }
-  return {x, B, (int64_t)B * nbest, true, what,
-          [=](int64_t* capacity, int64_t* ws_bytes) {
-            check(wfl_transducer_beam_workspace(B, T, C, beam, K, nbest, capacity, ws_bytes), what);
-          },
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, beam, K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_transducer_beam_search(x.data_ptr<float>(), W.defined() ? W.data_ptr<float>() : nullptr,
-                                             lz.defined() ? lz.data_ptr<float>() : nullptr, B, T, C, blank, forced ? 1 : 0, beam, K,
+            check(wfl_transducer_beam_search(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, blank, forced ? 1 : 0, beam, K,
                                              nbest, normalize ? 1 : 0, ws, out, cap, offs, scores, s),
                   what);
           }};

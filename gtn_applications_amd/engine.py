@@ -943,6 +943,52 @@ def decode_paths(paths, drop, num_replabels=0, flags=0, T=None, dtype=torch.int3
 BEAM_MAX, BEAM_MAX_CLASSES = 64, 16384  # wfl_ctc_beam_search: beam width / classes per frame; classes in all
 
 
+def beam_integer(v):
+    """v as an int, or None where it is none: a bool (numpy's too), a float, a string"""
+    try:
+        return None if isinstance(v, (bool, np.bool_)) else operator.index(v)
+    except TypeError:
+        return None
+
+
+def beam_widths(C, beam_size, classes_per_frame, nbest, what):
+    """(beam, classes_per_frame, nbest) of a search over C classes within the limits of the beam kernel, or ValueError
+    (`what`: the call they were given to).  classes_per_frame None: min(C, 32) -- a default, not a tuned value."""
+    W = beam_integer(beam_size)
+    if W is None or not 1 <= W <= BEAM_MAX:
+        raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+    K = min(C, 32) if classes_per_frame is None else beam_integer(classes_per_frame)
+    if K is None or not 1 <= K <= min(C, BEAM_MAX):
+        raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
+                         f"got {classes_per_frame!r}")
+    n = beam_integer(nbest)
+    if n is None or not 1 <= n <= W:
+        raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
+    if C > BEAM_MAX_CLASSES:
+        raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
+    return W, K, n
+
+
+def beam_rows(flat, offsets, B, nbest, dtype=None):
+    """hyps[b][r] of a beam op's (flat labels, offsets [B nbest + 1]): views of one CPU tensor, of `dtype` if given"""
+    rows = (flat if dtype is None else flat.to(dtype)).split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
+    return [list(rows[b * nbest:(b + 1) * nbest]) for b in range(B)]
+
+
+def beam_no_frames(B, nbest, dtype=torch.int64):
+    """(hyps, scores) of a search over B utterances without a frame: every rank the empty sequence, with score 0"""
+    hyps = [[torch.empty(0, dtype=dtype) for _ in range(nbest)] for _ in range(B)]
+    return hyps, torch.zeros((B, nbest), dtype=torch.float64)
+
+
+def check_beam_outputs(outputs, what):
+    """ValueError unless `outputs` is what a criterion's beam search takes: a floating point [B, T, C] tensor"""
+    if not isinstance(outputs, torch.Tensor) or outputs.dim() != 3:
+        raise ValueError(f"{what}: outputs must be a [B, T, C] tensor")
+    if not outputs.dtype.is_floating_point:
+        raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
+
+
 class BeamPlan(namedtuple(
         "BeamPlan", "C blank beam classes_per_frame nbest lm lm_weight length_bonus lm_eos lexicon word_bonus")):
     """The options of one CTC beam search over C classes, checked once (`checked`, the one constructor) and handed on whole:
@@ -962,12 +1008,6 @@ class BeamPlan(namedtuple(
         from .lexicon import Lexicon, check_word_lm
         from .lm import NGramLM
 
-        def integer(v):
-            try:
-                return None if isinstance(v, bool) else operator.index(v)
-            except TypeError:
-                return None
-
         def finite(v, name):
             f = math.nan
             if not isinstance(v, (bool, np.bool_, str, bytes)):
@@ -979,18 +1019,7 @@ class BeamPlan(namedtuple(
                 raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
             return f
 
-        W = integer(beam_size)
-        if W is None or not 1 <= W <= BEAM_MAX:
-            raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
-        K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
-        if K is None or not 1 <= K <= min(C, BEAM_MAX):
-            raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
-                             f"got {classes_per_frame!r}")
-        n = integer(nbest)
-        if n is None or not 1 <= n <= W:
-            raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
-        if C > BEAM_MAX_CLASSES:
-            raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
+        W, K, n = beam_widths(C, beam_size, classes_per_frame, nbest, what)
         if not 0 <= int(blank) < C:
             raise ValueError(f"{what}: blank index {blank} is outside [0, {C})")
         blank = int(blank)
@@ -1030,16 +1059,15 @@ class BeamPlan(namedtuple(
     def no_frames(self, B):
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
         empty sequence -- no word either --, the first scored by the LM's </s> alone"""
-        n = self.nbest
-        hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(n)] for _ in range(B)]
+        hyps, scores = beam_no_frames(B, self.nbest)
         if self.lm is None and self.lexicon is None:
-            return hyps, torch.zeros((B, n), dtype=torch.float64)
+            return hyps, scores
         # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
         end = 0.0
         if self.lm is not None and self.lm_eos:
             step = self.lm.score([], eos=True)
             end = -math.inf if step == -math.inf else self.lm_weight * step
-        scores = torch.full((B, n), -math.inf, dtype=torch.float64)
+        scores[:, 1:] = -math.inf
         scores[:, 0] = end
         return hyps, scores
 
@@ -1055,8 +1083,7 @@ class BeamPlan(namedtuple(
     def search(self, x, lengths=None, normalize=True):
         """ctc_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's"""
         flat, offsets, scores = N.ops.ctc_beam_search(x, lengths, self.on_device(x.device), bool(normalize))
-        rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
-        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
+        return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
 def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
@@ -1088,35 +1115,14 @@ class AsgBeamPlan(namedtuple("AsgBeamPlan", "C beam classes_per_frame nbest")):
     def checked(cls, C, beam_size, classes_per_frame, nbest, what):
         """The plan of these arguments, within the limits of wfl_asg_beam_search, or ValueError (`what`: the call they
         were given to).  classes_per_frame None: min(C, 32) -- a default, not a tuned value.  Integers only, no bools."""
-
-        def integer(v):
-            try:
-                return None if isinstance(v, (bool, np.bool_)) else operator.index(v)
-            except TypeError:
-                return None
-
-        C = integer(C)
+        C = beam_integer(C)
         if C is None or C < 1:
             raise ValueError(f"{what}: the emissions have no classes")
-        W = integer(beam_size)
-        if W is None or not 1 <= W <= BEAM_MAX:
-            raise ValueError(f"{what}: beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
-        K = min(C, 32) if classes_per_frame is None else integer(classes_per_frame)
-        if K is None or not 1 <= K <= min(C, BEAM_MAX):
-            raise ValueError(f"{what}: classes_per_frame must be an integer in [1, {min(C, BEAM_MAX)}] for {C} classes, "
-                             f"got {classes_per_frame!r}")
-        n = integer(nbest)
-        if n is None or not 1 <= n <= W:
-            raise ValueError(f"{what}: nbest must be an integer in [1, beam_size = {W}], got {nbest!r}")
-        if C > BEAM_MAX_CLASSES:
-            raise ValueError(f"{what}: {C} classes are more than the beam search takes ({BEAM_MAX_CLASSES})")
-        return cls(C, W, K, n)
+        return cls(C, *beam_widths(C, beam_size, classes_per_frame, nbest, what))
 
     def no_frames(self, B):
-        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
-        empty sequence with score 0"""
-        hyps = [[torch.empty(0, dtype=torch.int64) for _ in range(self.nbest)] for _ in range(B)]
-        return hyps, torch.zeros((B, self.nbest), dtype=torch.float64)
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: beam_no_frames's"""
+        return beam_no_frames(B, self.nbest)
 
     def search(self, x, W, normalize=True, drop=None, num_replabels=0):
         """asg_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
@@ -1125,8 +1131,7 @@ class AsgBeamPlan(namedtuple("AsgBeamPlan", "C beam classes_per_frame nbest")):
             logz = dense_forward(x, W, need_beta=False).logz if normalize else None
         flat, offsets, scores = N.ops.asg_beam_search(x, W, logz, self.beam, self.classes_per_frame, self.nbest,
                                                       -1 if drop is None else int(drop), int(num_replabels))
-        rows = flat.split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
-        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
+        return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
 def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normalize=True, drop=None, num_replabels=0):
@@ -1164,10 +1169,7 @@ class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam c
         """The plan of these arguments, within the limits of wfl_transducer_beam_search, or ValueError (`what`: the call
         they were given to): what AsgBeamPlan.checked refuses, a blank outside [0, C), a `forced` that is no bool (or 0 / 1)"""
         C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
-        try:
-            b = None if isinstance(blank, (bool, np.bool_)) else operator.index(blank)
-        except TypeError:
-            b = None
+        b = beam_integer(blank)
         if b is None or not 0 <= b < C:
             raise ValueError(f"{what}: blank must be an integer in [0, {C}), got {blank!r}")
         if not isinstance(forced, (bool, np.bool_)) and not (isinstance(forced, (int, np.integer)) and forced in (0, 1)):
@@ -1175,10 +1177,8 @@ class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam c
         return cls(C, b, bool(forced), W, K, n)
 
     def no_frames(self, B, dtype=torch.int64):
-        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
-        empty sequence with score 0"""
-        hyps = [[torch.empty(0, dtype=dtype) for _ in range(self.nbest)] for _ in range(B)]
-        return hyps, torch.zeros((B, self.nbest), dtype=torch.float64)
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: beam_no_frames's"""
+        return beam_no_frames(B, self.nbest, dtype)
 
     def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
         """transducer_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt: float32
@@ -1189,8 +1189,7 @@ class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam c
                 logz = dense_forward(x, Wt, need_beta=False).logz
         flat, offsets, scores = N.ops.transducer_beam_search(x, Wt, logz, self.blank, self.forced, self.beam,
                                                              self.classes_per_frame, self.nbest, bool(normalize))
-        rows = flat.to(dtype).split_with_sizes((offsets[1:] - offsets[:-1]).tolist())
-        return [list(rows[b * self.nbest:(b + 1) * self.nbest]) for b in range(x.shape[0])], scores
+        return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
 
 
 def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True):
