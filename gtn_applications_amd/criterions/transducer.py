@@ -256,6 +256,10 @@ class Transducer(torch.nn.Module):
         self.tokens = make_token_graph(tokens, blank=blank, allow_repeats=allow_repeats)
         self.lexicon = make_lexicon_graph(tokens, graphemes_to_idx)
         self._num_emission_classes = len(tokens) + int(blank != "none")  # (width of the emissions: prepare())
+        # the graphemes every token spells, as indices: what beam_search(merge_spellings=True) identifies hypotheses by
+        # (plain attributes, no buffers: the state_dict is what it was)
+        self.token_spellings = [tuple(graphemes_to_idx[g] for g in wp) for wp in tokens]
+        self._spelling_table = None
         self.ngram = ngram
         if ngram > 0 and transitions is not None:
             raise ValueError("Only one of ngram and transitions may be specified")
@@ -389,6 +393,27 @@ class Transducer(torch.nn.Module):
         plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
         return plan, kind
 
+    def _spelling(self, plan, what):
+        """The E.Spelling of the plan's classes (the tokens' spellings, the blank's none), checked once and kept: ValueError
+        for a token that spells nothing or more than E.SPELL_MAX graphemes.  Needs no device."""
+        held = self._spelling_table
+        rows = list(self.token_spellings)
+        if held is None or held[0] != rows:
+            for i, s in enumerate(rows):
+                if not 1 <= len(s) <= E.SPELL_MAX:
+                    raise ValueError(f"{what}: token {i} spells {len(s)} graphemes, merge_spellings takes tokens of 1 to "
+                                     f"{E.SPELL_MAX}")
+            table = E.Spelling.checked(rows[:plan.blank] + [None] + rows[plan.blank:], plan.blank, what)
+            held = self._spelling_table = (rows, table)
+        E.check_spelling(held[1], plan, what)
+        return held[1]
+
+    @staticmethod
+    def _merge_flag(merge_spellings, what):
+        if not isinstance(merge_spellings, (bool, np.bool_)):
+            raise ValueError(f"{what}: merge_spellings must be True or False, got {merge_spellings!r}")
+        return bool(merge_spellings)
+
     def _beam_inputs(self, outputs, kind):
         """(emissions, transitions or None) of the search, as the routes of the loss form them (_dispatch): float32,
         contiguous, on the emissions' GPU or the required one (no host path)"""
@@ -403,7 +428,8 @@ class Transducer(torch.nn.Module):
         return xd, Wd.contiguous()
 
     @E.on_input_device
-    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False,
+                    merge_spellings=False):
         """Transducer prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame
         path; the criterion scores a token sequence by the sum over all its alignments, and this returns the token
         sequences it rates highest (DESIGN.md section 22 has the rules; csrc/beam_kernels.hip runs them, in float64).
@@ -416,37 +442,54 @@ class Transducer(torch.nn.Module):
         mass of the token sequence's alignments that the beam kept, minus the normaliser of the loss (-inf for an empty
         rank).  For tokens that are single graphemes that is minus the criterion's loss of that target where nothing was
         pruned.  With word pieces the loss also sums over the other decompositions of the same graphemes, so the score
-        is a lower bound of minus the loss; two token sequences that spell the same graphemes are separate hypotheses.
-        B == 0 or T == 0: empty sequences with score 0, no device needed.  No merging by spelling, lexicon, LM or
-        input lengths."""
-        plan, kind = self._beam_plan(outputs, "Transducer.beam_search", beam_size, classes_per_frame, nbest)
+        is a lower bound of minus the loss; two token sequences that spell the same graphemes are separate hypotheses
+        unless `merge_spellings`.
+        merge_spellings=True: hypotheses are identified by the graphemes they spell (and their
+        last token), and the masses of all decompositions of those graphemes into tokens are summed inside the beam
+        launch.  A returned sequence is then a REPRESENTATIVE -- one token sequence that spells the result --, and the
+        score belongs to its spelling: the kept log mass of every alignment of every decomposition, minus the
+        normaliser -- minus the criterion's loss of that grapheme target where nothing was pruned, a lower bound
+        otherwise, and never below the score of any single decomposition.  No two ranks spell the same graphemes.  The
+        return types do not change.  A token that spells nothing, or more than 64 graphemes, raises ValueError.
+        B == 0 or T == 0: empty sequences with score 0, no device needed.  No lexicon, LM or input lengths."""
+        what = "Transducer.beam_search"
+        plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest)
+        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what) else None
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
         else:
             x, Wt = self._beam_inputs(outputs, kind)
             with torch.cuda.device(x.device), torch.no_grad():
-                hyps, scores = plan.search(x, Wt, True, torch.int32)
+                if spelling is not None:
+                    hyps, scores = E.transducer_merged_search(plan, x, Wt, spelling, True, torch.int32)
+                else:
+                    hyps, scores = plan.search(x, Wt, True, torch.int32)
         if plan.nbest == 1:
             hyps = [h[0] for h in hyps]
         return (hyps, scores) if return_scores else hyps
 
     @E.on_input_device
-    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None):
+    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, merge_spellings=False):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
-        beam launches on their device buffers; `classes_per_frame` needs a beam_size."""
+        beam launches on their device buffers; `classes_per_frame` and `merge_spellings` (beam_search's: the predictions
+        are the representatives of the best spellings) need a beam_size."""
+        merge = self._merge_flag(merge_spellings, "Transducer.errors")
         if beam_size is None:
-            if classes_per_frame is not None:
-                raise ValueError("Transducer.errors: classes_per_frame needs a beam_size")
+            if classes_per_frame is not None or merge:
+                raise ValueError("Transducer.errors: classes_per_frame and merge_spellings need a beam_size")
         else:
             plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1)
+            spelling = self._spelling(plan, "Transducer.errors") if merge else None
             counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
                 return counter([h[0] for h in plan.no_frames(outputs.shape[0], torch.int32)[0]], targets)
             x, Wt = self._beam_inputs(outputs, kind)
             with torch.cuda.device(x.device), torch.no_grad():
+                if merge:
+                    return counter.totals(M.transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling))
                 return counter.totals(M.transducer_beam_search_errors(counter, targets, x, Wt, plan))
         C = outputs.shape[2]
         dplan = self._device_decode(C)

@@ -35,7 +35,10 @@
 // fifth pack, BeamTok, carries the frame-level transitions over tokens + blank (or none) and the token graph's topology
 // -- CTC's two masses per hypothesis and a transition weight on every frame-to-frame step: three gathers in a stay, two
 // gathers and a log-add in an extension; the forced topology leaves the blank state only and ranks the result by pb.
-// All five issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_transducer_beam_search_merged is that search with hypotheses identified by the graphemes they spell and their last
+// token: a sixth pack, BeamSpell, adds the spelling table of the classes; the token sequences
+// that spell the same graphemes share one hypothesis, their masses summed inside the beam launch.
+// All six issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -329,25 +332,49 @@ __device__ __forceinline__ double beam_tok_ext(const BeamTok& a, double pb, doub
   return s + m;
 }
 
+// the Transducer launch that merges by spelling (wfl_transducer_beam_search_merged): BeamTok's
+// fields and the spelling table over the C classes -- class c spells the graphemes spell_sym[spell_ptr[c] ..
+// spell_ptr[c + 1]), none for the blank, 1 .. WFL_SPELL_MAX for every other class (wfl_spelling_check)
+struct BeamSpell {
+  BeamTok tok;
+  const int32_t *spell_ptr, *spell_sym;
+};
+__device__ __forceinline__ const BeamSpell& beam_spell_of(const BeamSpell& a) { return a; }
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamSpell& a) { return a.tok; }
+constexpr int kSpellMax = WFL_SPELL_MAX;
+// the inverse of an odd multiplier mod 2^64 (Newton: every round doubles the correct low bits, a itself has three)
+constexpr unsigned long long beam_inverse(unsigned long long a) {
+  unsigned long long v = a;
+  for (int i = 0; i < 6; ++i) v *= 2ull - a * v;
+  return v;
+}
+constexpr unsigned long long kBeamHashInv = beam_inverse(kBeamHashMul), kBeamHashInv2 = beam_inverse(kBeamHashMul2);
+static_assert(kBeamHashInv * kBeamHashMul == 1ull && kBeamHashInv2 * kBeamHashMul2 == 1ull, "the hash multipliers' inverses");
+
 template <typename... Lm>
 struct BeamPack {
-  static constexpr bool lm = false, lex = false, asg = false, tok = false;
+  static constexpr bool lm = false, lex = false, asg = false, tok = false, spell = false;
 };
 template <>
 struct BeamPack<BeamLm> {
-  static constexpr bool lm = true, lex = false, asg = false, tok = false;
+  static constexpr bool lm = true, lex = false, asg = false, tok = false, spell = false;
 };
 template <>
 struct BeamPack<BeamLex> {
-  static constexpr bool lm = false, lex = true, asg = false, tok = false;
+  static constexpr bool lm = false, lex = true, asg = false, tok = false, spell = false;
 };
 template <>
 struct BeamPack<BeamAsg> {
-  static constexpr bool lm = false, lex = false, asg = true, tok = false;
+  static constexpr bool lm = false, lex = false, asg = true, tok = false, spell = false;
 };
 template <>
 struct BeamPack<BeamTok> {
-  static constexpr bool lm = false, lex = false, asg = false, tok = true;
+  static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = false;
+};
+// (tok: what the two Transducer searches share -- the normaliser, the frame's log-sum-exp, the forced topology's result)
+template <>
+struct BeamPack<BeamSpell> {
+  static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = true;
 };
 
 // NT threads: 256 where a frame has at most 1024 entries, 1024 beyond (the ranking is the work that scales).
@@ -359,7 +386,15 @@ struct BeamPack<BeamTok> {
 // row_lse NULL, normalize != 0: the pack's logz[b] is subtracted; or one BeamTok: the search of
 // wfl_transducer_beam_search -- the plain search's two masses with a transition weight on every
 // step (w = 0 without a matrix), the blank-side state the start row in frame 0, the forced topology's extensions from pb
-// alone and none in frame 0, the final beam ranked again by pb there; lengths NULL, row_lse NULL where logz normalises.
+// alone and none in frame 0, the final beam ranked again by pb there; lengths NULL, row_lse NULL where logz normalises;
+// or one BeamSpell: the search of wfl_transducer_beam_search_merged -- BeamTok's arithmetic per
+// hypothesis, but a hypothesis is identified by (the graphemes it spells, its last token): the hashes run over
+// graphemes, len counts them and a token count rides along for the write launch; per frame the hypotheses of one
+// spelling form a class (a member mask, the leader its lowest rank), an extension entry exists for leaders only and
+// sums the extensions of the members in rank order, and the parent class of a hypothesis is found by un-appending
+// the spelling of its last token from its hashes (the multipliers are odd: one multiplication by the inverse per
+// grapheme, once per hypothesis -- cheaper than extending every class by it); the result merges the ranks of one
+// spelling before it is ranked.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -368,6 +403,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
                                                            int32_t* __restrict__ fin_len, double* __restrict__ scores,
                                                            Lm... lm_arg) {
   constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg, TOK = BeamPack<Lm...>::tok;
+  constexpr bool SPELL = BeamPack<Lm...>::spell;  // (TOK as well)
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -403,6 +439,15 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     __shared__ int s_xenext[kBeamEntries];
     lmst = s_xlmst, tnode = s_xtnode, enext = s_xenext;
   }
+  // merging by spelling only: the token count of every hypothesis (len counts graphemes there), and per frame the
+  // member mask of every hypothesis' spelling class
+  int(*ntok)[kBeamMax] = nullptr;
+  unsigned long long* cmask = nullptr;
+  if constexpr (SPELL) {
+    __shared__ int s_ntok[2][kBeamMax];
+    __shared__ unsigned long long s_cmask[kBeamMax];
+    ntok = s_ntok, cmask = s_cmask;
+  }
 
   const int tid = threadIdx.x, b = blockIdx.x;
   const int KC = K + 1;
@@ -419,6 +464,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     beam[0].hash[0] = 0ull, beam[0].hash2[0] = 0ull, beam[0].last[0] = -1, beam[0].len[0] = 0, beam[0].node[0] = -1;
     if constexpr (LM) lmst[0][0] = beam_lm_of(lm_arg...).start;
     if constexpr (LEX) lmst[0][0] = beam_lex_of(lm_arg...).has_lm ? beam_lex_of(lm_arg...).lm.start : 0, tnode[0][0] = 0;
+    if constexpr (SPELL) ntok[0][0] = 0;
   }
   __syncthreads();
   // the candidates of frame 0 into buffer 0
@@ -458,8 +504,42 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
       lpos[tid] = p, par[tid] = -1;
     }
     __syncthreads();
-    // which hypothesis j is hypothesis i plus one label: that extension merges into j's stay entry
-    if (tid < nbeam) {
+    if constexpr (SPELL) {
+      // the spelling class of every hypothesis (its members' ranks as a mask; the leader is the lowest), and the leader
+      // of its parent class: the class that spells what it spells without its last token
+      const BeamSpell& sp = beam_spell_of(lm_arg...);
+      if (tid < nbeam) {
+        const unsigned long long hh = h.hash[tid], hh2 = h.hash2[tid];
+        const int ln = h.len[tid], l = h.last[tid];
+        unsigned long long m = 0ull;
+        for (int j = 0; j < nbeam; ++j)
+          if (h.len[j] == ln && h.hash[j] == hh && h.hash2[j] == hh2) m |= 1ull << j;
+        cmask[tid] = m;
+        int pl = -1;
+        if (lpos[tid] >= 0 && !(sp.tok.forced && t == 0)) {  // (only a candidate extends anything; lpos >= 0: l >= 0)
+          const int s0 = sp.spell_ptr[l], n = min(sp.spell_ptr[l + 1] - s0, kSpellMax);
+          unsigned long long ph = hh, ph2 = hh2;
+          for (int q = n - 1; q >= 0; --q) {  // h = h_parent mul^n + ...: taken off from the end
+            const unsigned long long gq = (unsigned long long)(sp.spell_sym[s0 + q] + 1);
+            ph = (ph - gq) * kBeamHashInv, ph2 = (ph2 - gq) * kBeamHashInv2;
+          }
+          const int plen = ln - n;
+          for (int j = nbeam - 1; j >= 0; --j)
+            if (h.len[j] == plen && h.hash[j] == ph && h.hash2[j] == ph2) pl = j;
+        }
+        par[tid] = pl;
+      }
+      __syncthreads();
+      // every member's extension by the last token of a hypothesis whose parent class it is in merges into that stay
+      if (tid < nbeam) {
+        const int lead = __ffsll(cmask[tid]) - 1;
+        unsigned long long mask = 0ull;
+        for (int j = 0; j < nbeam; ++j)
+          if (par[j] == lead) mask |= 1ull << lpos[j];  // (par[j] >= 0 only where lpos[j] >= 0)
+        mmask[tid] = mask;
+      }
+    } else if (tid < nbeam) {
+      // which hypothesis j is hypothesis i plus one label: that extension merges into j's stay entry
       unsigned long long mask = 0ull;
       const unsigned long long hm = h.hash[tid] * kBeamHashMul, hm2 = h.hash2[tid] * kBeamHashMul2;
       const int l1 = h.len[tid] + 1;
@@ -490,6 +570,26 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           if (q < ncand) rk = beam_key((sc[q] + beam_asg_w(a, l, cls[q])) + h.tot[tid]);
         }
         wkey[tid] = rk;  // (wkey: free until the selection)
+      }
+    } else if constexpr (SPELL) {
+      // section 22's stay; behind its own term the extensions of every member of the parent class, in rank order
+      if (tid < nbeam) {
+        const BeamTok& a = beam_tok_of(lm_arg...);
+        const int p = lpos[tid], l = h.last[tid], pl = par[tid], brow = t == 0 ? -1 : blank;
+        double m = h.pb[tid] + beam_tok_w(a, brow, blank);
+        if (l >= 0 && h.pnb[tid] > ninf) m = beam_lae(m, h.pnb[tid] + beam_tok_w(a, l, blank));
+        const double pb = sc[bpos] + m;
+        double pnb = p >= 0 && h.pnb[tid] > ninf ? (sc[p] + h.pnb[tid]) + beam_tok_w(a, l, l) : ninf;
+        if (pl >= 0) {  // (par: only where p >= 0, and never in the forced topology's frame 0)
+          unsigned long long mm = cmask[pl];
+          for (int it = 0; it < kBeamMax && mm; ++it) {
+            const int i = __ffsll(mm) - 1;
+            mm &= mm - 1ull;
+            pnb = beam_lae(pnb, beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]));
+          }
+        }
+        const double tot = beam_lae(pb, pnb);
+        spb[tid] = pb, spnb[tid] = pnb, stot[tid] = tot, skey[tid] = beam_key(tot);
       }
     } else if constexpr (TOK) {
       // rule 3: the blank is entered from the blank-side state and from the last label, the last label repeats over its
@@ -579,6 +679,21 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           // (c the last label of i: that is i's stay, not an extension; the start row of Wt for the empty prefix)
           const int l = h.last[i];
           k = c == l ? kKeyDropped : beam_key((sc[p] + beam_asg_w(beam_asg_of(lm_arg...), l, c)) + h.tot[i]);
+        } else if constexpr (SPELL) {
+          // one entry per spelling class and candidate, at the leader: the members' extensions summed in rank order
+          const BeamTok& a = beam_tok_of(lm_arg...);
+          unsigned long long mm = cmask[i];
+          if ((a.forced && t == 0) || __ffsll(mm) - 1 != i)
+            k = kKeyDropped;
+          else {
+            double m = ninf;
+            for (int it = 0; it < kBeamMax && mm; ++it) {
+              const int j = __ffsll(mm) - 1;
+              mm &= mm - 1ull;
+              m = beam_lae(m, beam_tok_ext(a, h.pb[j], h.pnb[j], h.last[j], t == 0 ? -1 : blank, c, sc[p]));
+            }
+            k = beam_key(m);
+          }
         } else if constexpr (TOK) {
           const BeamTok& a = beam_tok_of(lm_arg...);
           k = a.forced && t == 0 ? kKeyDropped
@@ -600,6 +715,36 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         g.hash[r] = h.hash[idx], g.hash2[r] = h.hash2[idx], g.last[r] = h.last[idx], g.len[r] = h.len[idx], g.node[r] = h.node[idx];
         if constexpr (LM) lmst[cur ^ 1][r] = lmst[cur][idx];
         if constexpr (LEX) lmst[cur ^ 1][r] = lmst[cur][idx], tnode[cur ^ 1][r] = tnode[cur][idx];
+        if constexpr (SPELL) ntok[cur ^ 1][r] = ntok[cur][idx];
+      } else if constexpr (SPELL) {
+        // a new (spelling, last token): the class' sum is in the key; the representative token sequence is that of
+        // the lowest-ranked member whose own extension is finite (there is one: the sum is), with c behind it
+        const BeamSpell& sp = beam_spell_of(lm_arg...);
+        const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
+        const int c = cls[p];
+        const double e = beam_key_total(k);
+        unsigned long long mm = cmask[i];
+        int rep = i;
+        for (int it = 0; it < kBeamMax && mm; ++it) {
+          const int j = __ffsll(mm) - 1;
+          mm &= mm - 1ull;
+          if (beam_tok_ext(sp.tok, h.pb[j], h.pnb[j], h.last[j], t == 0 ? -1 : blank, c, sc[p]) > ninf) {
+            rep = j;
+            break;
+          }
+        }
+        const int s0 = sp.spell_ptr[c], n = min(sp.spell_ptr[c + 1] - s0, kSpellMax);
+        unsigned long long nh = h.hash[i], nh2 = h.hash2[i];
+        for (int q = 0; q < n; ++q) {
+          const unsigned long long gq = (unsigned long long)(sp.spell_sym[s0 + q] + 1);
+          nh = nh * kBeamHashMul + gq, nh2 = nh2 * kBeamHashMul2 + gq;
+        }
+        const int node = t * W + r;
+        g.pb[r] = ninf, g.pnb[r] = e, g.tot[r] = e;
+        g.hash[r] = nh, g.hash2[r] = nh2;
+        g.last[r] = c, g.len[r] = h.len[i] + n, g.node[r] = node;
+        ntok[cur ^ 1][r] = ntok[cur][rep] + 1;
+        nodes[node] = make_int2(h.node[rep], c);
       } else {
         const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
         const int c = cls[p];
@@ -710,9 +855,25 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     // With a lexicon a rank inside a word is dropped first, and </s> needs a word LM.
     // The Transducer's rules 5 and 6 by the same ranking: the optional topology's beam as it stands (ranked by tot); the
     // forced one by pb alone, a rank whose paths all end in a token dropped.
+    // Merging by spelling (section 23 rule 4): the ranks of one spelling are one result -- their scores added in rank
+    // order, at the place (and with the token sequence) of the first of them whose score is finite.
+    if constexpr (SPELL) {
+      if (tid < nbeam) spb[tid] = beam_tok_of(lm_arg...).forced ? f.pb[tid] : f.tot[tid];  // (spb: free behind the frames)
+      __syncthreads();
+    }
     if (tid < nbeam) {
       double s = f.tot[tid];
-      if constexpr (TOK) {
+      if constexpr (SPELL) {
+        bool owner = spb[tid] > ninf;
+        s = ninf;
+        for (int j = 0; j < nbeam; ++j)
+          if (f.len[j] == f.len[tid] && f.hash[j] == f.hash[tid] && f.hash2[j] == f.hash2[tid]) {
+            const double sj = spb[j];
+            if (j < tid && sj > ninf) owner = false;
+            s = beam_lae(s, sj);
+          }
+        if (!owner) s = ninf;
+      } else if constexpr (TOK) {
         if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];
       } else if constexpr (LEX) {
         const BeamLex& lx = beam_lex_of(lm_arg...);
@@ -746,7 +907,10 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
       if (r < nbest) {
         const int64_t o = (int64_t)b * nbest + r;
         fin_node[o] = have ? f.node[tid] : -1;
-        fin_len[o] = have ? f.len[tid] : 0;
+        if constexpr (SPELL)
+          fin_len[o] = have ? ntok[Tb & 1][tid] : 0;  // (the write launch walks tokens; len counts graphemes)
+        else
+          fin_len[o] = have ? f.len[tid] : 0;
         scores[o] = have ? (normalize ? stot[tid] - s_norm : stot[tid]) : ninf;
       }
     }
@@ -1029,6 +1193,68 @@ int wfl_transducer_beam_search(const float* x, const float* Wt, const float* log
   // no transitions, CTC's topology: these are section 17's rules, and its search is the one that runs
   if (!Wt && !forced) return beam_run(what, c);
   return beam_run(what, c, BeamTok{Wt, normalize ? logz : nullptr, C, forced});
+}
+
+int wfl_spelling_check(const int32_t* spell_ptr, const int32_t* spell_sym, int C, int blank) {
+  const char* what = "spelling_check";
+  if (!spell_ptr || !spell_sym) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  if (C < 1 || blank < 0 || blank >= C) {
+    set_error("%s: %d classes, blank %d", what, C, blank);
+    return WFL_ERR_INVALID;
+  }
+  if (spell_ptr[0] != 0) {
+    set_error("%s: spell_ptr starts at %d, not at 0", what, spell_ptr[0]);
+    return WFL_ERR_INVALID;
+  }
+  for (int c = 0; c < C; ++c) {  // (every range before any symbol: nothing is read outside [0, spell_ptr[C]))
+    const int64_t n = (int64_t)spell_ptr[c + 1] - spell_ptr[c];
+    if (n < 0) {
+      set_error("%s: spell_ptr descends at class %d", what, c);
+      return WFL_ERR_INVALID;
+    }
+    if (c == blank ? n != 0 : (n < 1 || n > WFL_SPELL_MAX)) {
+      if (c == blank)
+        set_error("%s: the blank %d spells %lld graphemes, not none", what, c, (long long)n);
+      else
+        set_error("%s: class %d spells %lld graphemes, not 1 .. %d", what, c, (long long)n, WFL_SPELL_MAX);
+      return WFL_ERR_INVALID;
+    }
+  }
+  for (int c = 0; c < C; ++c)
+    for (int q = spell_ptr[c]; q < spell_ptr[c + 1]; ++q)
+      if (spell_sym[q] < 0) {
+        set_error("%s: grapheme %d of class %d is %d (graphemes are >= 0)", what, q - spell_ptr[c], c, spell_sym[q]);
+        return WFL_ERR_INVALID;
+      }
+  return WFL_OK;
+}
+
+// The Transducer search with hypotheses merged by spelling: wfl_transducer_beam_search's checks
+// in its order, then this entry's own; always the BeamSpell kernel, also where the plain search would do.
+int wfl_transducer_beam_search_merged(const float* x, const float* Wt, const float* logz, const int32_t* spell_ptr,
+                                      const int32_t* spell_sym, int B, int T, int C, int blank, int forced, int beam,
+                                      int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out,
+                                      int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_merged";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if (!spell_ptr || !spell_sym) {
+    set_error("%s: a NULL spelling table", what);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  return beam_run(what, c, BeamSpell{BeamTok{Wt, normalize ? logz : nullptr, C, forced}, spell_ptr, spell_sym});
 }
 
 int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,

@@ -1098,6 +1098,29 @@ Hypotheses transducer_beam_source(const at::Tensor& x, const c10::optional<at::T
           }};
 }
 
+// The same search with hypotheses merged by spelling (wfl_transducer_beam_search_merged).
+// spelling: int32 [spell_ptr: C + 1 | spell_sym: num_symbols] on x's device, one contiguous tensor, a table that
+// wfl_spelling_check passed on the host (engine.Spelling.on_device).
+Hypotheses transducer_merged_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
+                                         const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
+                                         int blank, bool forced, int beam, int K, int nbest, bool normalize) {
+  const char* what = "transducer_beam_search_merged";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  TORCH_CHECK(spelling.device() == x.device() && spelling.scalar_type() == at::kInt && spelling.is_contiguous() &&
+                  spelling.dim() == 1 && num_symbols >= 0 && spelling.numel() == (int64_t)e.C + 1 + num_symbols,
+              what, ": the spelling table must be one contiguous int32 [C + 1 + symbols] tensor on x's device");
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, beam, K, nbest, cap, bytes), what); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            const int32_t* sp = spelling.data_ptr<int32_t>();
+            check(wfl_transducer_beam_search_merged(x.data_ptr<float>(), fptr(W), fptr(lz), sp, sp + e.C + 1, e.B, e.T, e.C, blank,
+                                                    forced ? 1 : 0, beam, K, nbest, normalize ? 1 : 0, ws, out, cap, offs, scores,
+                                                    s),
+                  what);
+          }};
+}
+
 // The launch of `h` into the device's landing buffer -- [offsets: (rows + 1) int64 | scores: rows float64, a scored
 // source | labels: capacity int32], each part padded to 16 bytes -- and from there into fresh CPU tensors: only the
 // labels that survived leave the device.
@@ -1324,6 +1347,23 @@ at::Tensor transducer_beam_search_errors(const at::Tensor& x, const c10::optiona
   return hypotheses_errors(transducer_beam_source(x, Wt, c10::nullopt, blank, forced, beam, K, 1, false), ref, tables);
 }
 
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple transducer_beam_search_merged(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
+                                        const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
+                                        int blank, bool forced, int beam, int K, int nbest, bool normalize) {
+  const Collected r = hypotheses_collect(
+      transducer_merged_beam_source(x, Wt, logz, spelling, num_symbols, blank, forced, beam, K, nbest, normalize), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+}
+
+// (the first rank, unnormalised: nothing reads the scores)
+at::Tensor transducer_beam_search_merged_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const at::Tensor& spelling,
+                                                int64_t num_symbols, int blank, bool forced, int beam, int K,
+                                                const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(
+      transducer_merged_beam_source(x, Wt, c10::nullopt, spelling, num_symbols, blank, forced, beam, K, 1, false), ref, tables);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1371,6 +1411,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transducer_beam_search_errors", &transducer_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("blank"),
         py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"),
         "transducer_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  m.def("transducer_beam_search_merged", &transducer_beam_search_merged, py::arg("x"), py::arg("transitions"), py::arg("logz"),
+        py::arg("spelling"), py::arg("num_symbols"), py::arg("blank"), py::arg("forced"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
+        "transducer_beam_search with hypotheses merged by spelling (DESIGN.md section 23); spelling: int32 [spell_ptr: C + 1 | "
+        "spell_sym: num_symbols] on x's device (engine.Spelling.on_device)");
+  m.def("transducer_beam_search_merged_errors", &transducer_beam_search_merged_errors, py::arg("x"), py::arg("transitions"),
+        py::arg("spelling"), py::arg("num_symbols"), py::arg("blank"), py::arg("forced"), py::arg("beam"),
+        py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"),
+        "transducer_beam_search_merged's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("decode_emissions", &decode_emissions, py::arg("x"), py::arg("bias"), py::arg("drop"), py::arg("num_replabels"),
         py::arg("flags"), py::arg("as_int64"), py::arg("lengths"),
         "viterbi()'s decode from emissions (argmax, collapse, drop, unpack) on the device: B CPU tensors; lengths int32 [B] "

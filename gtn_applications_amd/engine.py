@@ -1192,7 +1192,81 @@ class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam c
         return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
 
 
-def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True):
+SPELL_MAX = 64  # include/wfl.h: WFL_SPELL_MAX, the graphemes of one class
+
+
+class Spelling:
+    """The spelling table of C classes for the Transducer search that merges by spelling, checked
+    once (`checked`, the one constructor: wfl_spelling_check on the host arrays) and uploaded once per device
+    (`on_device`, cached as metrics.ErrorCounter.tables is).  ptr: int32 [C + 1], sym: int32 [ptr[C]] -- class c spells
+    the graphemes sym[ptr[c]:ptr[c + 1]], the blank nothing, every other class 1 .. SPELL_MAX non-negative integers."""
+
+    def __init__(self, ptr, sym, blank):
+        self.ptr, self.sym, self.blank = ptr, sym, blank
+        self.num_classes, self.num_symbols = len(ptr) - 1, len(sym)
+        self._device = {}
+
+    @classmethod
+    def checked(cls, spellings, blank, what="Spelling"):
+        """The table of `spellings` -- a sequence over the C classes of grapheme index sequences, the blank's empty or
+        None -- or ValueError (`what`: the call they were given to).  Needs no device."""
+        C = len(spellings)
+        b = beam_integer(blank)
+        if b is None or not 0 <= b < C:
+            raise ValueError(f"{what}: blank must be an integer in [0, {C}), got {blank!r}")
+        rows = []
+        for c, s in enumerate(spellings):
+            row = [] if s is None else [beam_integer(g) for g in s]
+            if any(g is None or not -2 ** 31 <= g < 2 ** 31 for g in row):
+                raise ValueError(f"{what}: the spelling of class {c} must be a sequence of integers, got {s!r}")
+            if c != b and not 1 <= len(row) <= SPELL_MAX:
+                raise ValueError(f"{what}: class {c} spells {len(row)} graphemes, a class that is not the blank spells 1 to "
+                                 f"{SPELL_MAX}")
+            rows.append(row)
+        ptr = np.zeros(C + 1, np.int32)
+        np.cumsum([len(r) for r in rows], out=ptr[1:])
+        sym = np.ascontiguousarray([g for r in rows for g in r], dtype=np.int32)
+        pad = sym if len(sym) else np.zeros(1, np.int32)  # (a valid address for a table without a symbol)
+        if N.lib.wfl_spelling_check(ptr.ctypes.data, pad.ctypes.data, C, b) != 0:
+            raise ValueError(f"{what}: {N.last_error()}")
+        return cls(ptr, sym, b)
+
+    def on_device(self, device):
+        """int32 [ptr | sym] on `device`, uploaded once"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        held = self._device.get(device)
+        if held is None:
+            held = self._device[device] = torch.from_numpy(np.concatenate([self.ptr, self.sym])).to(device)
+        return held
+
+
+def transducer_merged_search(plan, x, Wt, spelling, normalize=True, dtype=torch.int64):
+    """TransducerBeamPlan.search for the search that merges by spelling (wfl_transducer_beam_search_merged): `plan` a
+    checked TransducerBeamPlan, `spelling` the Spelling of its classes and blank; x, Wt, the result: as search()'s, a
+    hypothesis a representative token sequence of its spelling"""
+    logz = None
+    if Wt is not None and normalize:
+        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+            logz = dense_forward(x, Wt, need_beta=False).logz
+    flat, offsets, scores = N.ops.transducer_beam_search_merged(x, Wt, logz, spelling.on_device(x.device), spelling.num_symbols,
+                                                                plan.blank, plan.forced, plan.beam, plan.classes_per_frame,
+                                                                plan.nbest, bool(normalize))
+    return beam_rows(flat, offsets, x.shape[0], plan.nbest, dtype), scores
+
+
+def check_spelling(spelling, plan, what):
+    """ValueError unless `spelling` is a Spelling of the plan's classes and blank"""
+    if not isinstance(spelling, Spelling):
+        raise ValueError(f"{what}: spelling must be an engine.Spelling, got {type(spelling).__name__}")
+    if spelling.num_classes != plan.C or spelling.blank != plan.blank:
+        raise ValueError(f"{what}: the spelling table was built for {spelling.num_classes} classes with blank {spelling.blank}, "
+                         f"the emissions have {plan.C} with blank {plan.blank}")
+
+
+def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True,
+                           spelling=None):
     """Transducer prefix beam search on the device (wfl_transducer_beam_search through csrc/torch_ops.cpp; the rules:
     include/wfl.h).  x: float32 [B,T,C] on a GPU, contiguous; Wt: float32 [C + 1, C] on x's device,
     contiguous, the frame-level transitions over the C classes in the dense engine's layout (row 0: start -> c, row
@@ -1202,12 +1276,19 @@ def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per
     alignments that the beam kept, minus the normaliser if `normalize` (with Wt the logz_b of dense_forward(x, Wt),
     without it the sum of the rows' log-sum-exps): then minus the criterion's loss of that sequence where nothing was
     pruned, a lower bound of it otherwise; a rank beyond the result is empty with score -inf.  With Wt None and forced
-    False this is ctc_beam_search, bit for bit.  The options are one TransducerBeamPlan."""
+    False this is ctc_beam_search, bit for bit.  The options are one TransducerBeamPlan.  spelling: a Spelling of the C
+    classes -- the search of wfl_transducer_beam_search_merged: hypotheses are identified by the
+    graphemes they spell, a result is a representative token sequence of its spelling and its score the kept mass of
+    every decomposition of that spelling; no two ranks spell the same.  spelling None: the call it was."""
     plan = TransducerBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, "transducer_beam_search")
     if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
         raise ValueError(f"transducer_beam_search: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if spelling is not None:
+        check_spelling(spelling, plan, "transducer_beam_search")
     if x.shape[0] == 0 or x.shape[1] == 0:
         return plan.no_frames(x.shape[0])
+    if spelling is not None:
+        return transducer_merged_search(plan, x, Wt, spelling, normalize)
     return plan.search(x, Wt, normalize)
 
 

@@ -154,6 +154,14 @@ def transducer_beam_search_errors(counter, targets, x, Wt, plan):
     return N.ops.transducer_beam_search_errors(x, Wt, plan.blank, plan.forced, plan.beam, plan.classes_per_frame, ref, tables)
 
 
+def transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling):
+    """transducer_beam_search_errors with hypotheses merged by spelling (`spelling`: the engine.Spelling of the plan's
+    classes and blank): the launches of engine.transducer_merged_search and the counts behind them"""
+    ref, tables, _ = _staged(counter, targets, x)
+    return N.ops.transducer_beam_search_merged_errors(x, Wt, spelling.on_device(x.device), spelling.num_symbols, plan.blank,
+                                                      plan.forced, plan.beam, plan.classes_per_frame, ref, tables)
+
+
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
     ref, tables, drop = _staged(counter, targets, paths, drop)

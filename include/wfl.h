@@ -810,6 +810,56 @@ int wfl_transducer_beam_search(const float* x, const float* Wt /* [(C+1), C] or 
                                int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device kernels: Transducer prefix beam search, hypotheses merged by spelling (csrc/beam_kernels.hip)
+ *   With word pieces the criterion's targets are GRAPHEME sequences and its loss sums over every alignment of every
+ *   decomposition of the graphemes into tokens.  wfl_transducer_beam_search stops at the token sequence: two sequences
+ *   that spell the same graphemes compete.  This search identifies a hypothesis by what it spells and sums the mass of
+ *   the decompositions inside the beam launch.  The rules extend those above and keep their symbols.
+ *   Additional input, the spelling table over the C classes: spell_ptr int32 [C+1], spell_sym int32 [spell_ptr[C]];
+ *   class c spells the graphemes spell_sym[spell_ptr[c] .. spell_ptr[c+1]); the blank's range is empty, every other
+ *   class has 1 .. WFL_SPELL_MAX graphemes, each >= 0.
+ *     1. arithmetic, candidates, stay entries (rule 3), the mass of an extension (rule 4), the frame-0 start row, the
+ *        forced topology's "no extension in frame 0", selection and tie order are unchanged, per hypothesis;
+ *     2. a hypothesis is (S, l, pb, pnb, rho): S the grapheme sequence spelt so far, l the last token, rho a
+ *        REPRESENTATIVE token sequence with spelling S and last token l.  Its identity is the pair (S, l) -- what its
+ *        future depends on: the stay, "c = l extends from pb only" and every w(l, .) need l, the blank-side state is the
+ *        blank whatever l was.  The search starts from ((), none) with pb = 0, pnb = -inf;
+ *     3. the extension of hypothesis i by a candidate c != blank has the key (S_i ++ spell(c), c).  All extensions of a
+ *        frame with the same key are ONE entry (their parents share S and differ in l); their masses are added with lae
+ *        in the order of the parents' ranks.  If the key is the identity of a beam hypothesis j (then l_j = c is a
+ *        candidate and j has a stay) the sum goes into j's pnb' by lae, behind j's own stay term, and j keeps rho_j.
+ *        Otherwise the sum is a new entry: its place in the tie order is (rank of its lowest-ranked parent, candidate
+ *        position), whether or not that parent's own contribution is finite; rho = rho_p ++ c, p the lowest-ranked
+ *        parent whose contribution is finite; an entry at -inf is dropped, as always;
+ *     4. result: each hypothesis of the final beam scores lae(pb, pnb) (forced = 0) or pb (forced = 1; -inf dropped);
+ *        hypotheses with the same S are merged -- scores added with lae in rank order, at the place and with the rho of
+ *        the best-ranked member with a finite score --, the merged ones ranked by score descending, ties to the earlier
+ *        place; the first nbest are returned as rho (token indices, never the blank) with their score, minus the
+ *        normaliser of rule 7 above if normalize != 0.  No two ranks spell the same graphemes; ranks beyond the result
+ *        are empty with score -inf;
+ *     5. the beam is ranked per (S, l), not per S: a stated pruning choice.
+ *   A score is the mass, kept by the beam, of all alignments of all decompositions of S, minus the normaliser: minus the
+ *   criterion's loss of target S where nothing is pruned, a lower bound of it otherwise.  Where every token is a single
+ *   grapheme and the graphemes are distinct, (S, l) and the token sequence determine each other and the results are
+ *   those of wfl_transducer_beam_search's rules (lae is applied in the same order).
+ *   wfl_spelling_check (HOST arrays, once per table): WFL_ERR_INVALID for a NULL pointer, C < 1, blank outside [0, C),
+ *   spell_ptr[0] != 0, descending pointers, a blank that spells something, another class with no grapheme or more than
+ *   WFL_SPELL_MAX, a negative grapheme; the message names the first offence.
+ *   wfl_transducer_beam_search_merged: wfl_transducer_beam_search's arguments with the table's two DEVICE pointers behind
+ *   logz; the workspace is wfl_transducer_beam_workspace's; the same refusals in the same order, a NULL table refused
+ *   behind `forced`; the same three launches -- always with the merging beam kernel, also for Wt == NULL, forced == 0 --,
+ *   the beam launch reading the table from global memory; every loop bounded by T, W, K, WFL_SPELL_MAX.
+ *   Not here: a lexicon, an LM, input lengths, graphemes in the place of tokens as the result.
+ * ------------------------------------------------------------------------------------------------ */
+#define WFL_SPELL_MAX 64
+int wfl_spelling_check(const int32_t* spell_ptr /* [C+1] */, const int32_t* spell_sym /* [spell_ptr[C]] */, int C, int blank);
+int wfl_transducer_beam_search_merged(const float* x, const float* Wt /* [(C+1), C] or NULL */,
+                                      const float* logz /* [B] or NULL */, const int32_t* spell_ptr, const int32_t* spell_sym,
+                                      int B, int T, int C, int blank, int forced, int beam, int classes_per_frame, int nbest,
+                                      int normalize, void* ws, int32_t* out, int64_t out_capacity,
+                                      int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
  *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
  *   train.py:278-284 and test.py:94-109 -- per utterance b:
