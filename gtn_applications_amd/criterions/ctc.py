@@ -9,6 +9,7 @@ labels, through the generic lattice engine (csrc/lattice_kernels.hip).  Both are
 import operator
 import os
 
+import numpy as np
 import torch
 
 from .. import _native as N
@@ -55,6 +56,16 @@ def check_input_lengths(input_lengths, B, T, what, keep_full=False):
     return None if not keep_full and all(n == T for n in lens) else tuple(lens)
 
 
+class BlankLabelUnderLengths(ValueError):
+    """CTCLossFunction.forward met input lengths and a target label equal to the blank index.  It is the autograd node
+    and cannot widen its input; `targets` are the staged targets (labels inside [0, C)) for the caller that can."""
+
+    def __init__(self, targets):
+        super().__init__("CTCLossFunction: input_lengths with a target label equal to the blank index: call CTCLoss, "
+                         "which gives such labels a column of their own")
+        self.targets = targets
+
+
 class CTCLossFunction(torch.autograd.Function):
     """`input_lengths` (padded batches; an addition to the reference's call): utterance b has the frames [0, T_b), the
     frames behind them are read as certain-blank frames -- 0 for the blank, -inf for every other class -- which are the
@@ -63,7 +74,10 @@ class CTCLossFunction(torch.autograd.Function):
     every other route runs unchanged on a copy of the emissions padded that way (wfl_ctc_pad_frames).  The pad rows of
     every gradient are set to exactly 0 (wfl_zero_pad_rows) before it is handed out.  Whenever `input_lengths` is passed, emissions of
     another floating dtype are taken too (the padded copy is float32, the gradient comes back in their dtype) -- also
-    when all the lengths equal T; float32 emissions with such lengths take exactly the path without lengths."""
+    when all the lengths equal T; float32 emissions with such lengths take exactly the path without lengths.  The
+    identity needs targets without the blank index among their labels: with lengths, such a target is refused here
+    (BlankLabelUnderLengths, a ValueError) and served by CTCLoss and the CTC module, which catch that
+    (_lengths_with_blank_labels)."""
 
     @staticmethod
     def create_ctc_graph(target, blank_idx):
@@ -104,6 +118,11 @@ class CTCLossFunction(torch.autograd.Function):
         E.check_labels(tg, C, "CTCLoss")
         if not 0 <= int(blank_idx) < C:
             raise ValueError(f"CTCLoss: blank index {blank_idx} is outside [0, {C})")
+        if lens is not None and tg.label_min <= int(blank_idx) <= tg.label_max and bool((tg.flat == int(blank_idx)).any()):
+            # a certain-blank frame is the identity only while no LABEL state reads the blank's column (DESIGN.md
+            # section 16): CTCLoss and the CTC module catch this and give such labels a column of their own -- with
+            # the staged targets at hand, whose labels were checked against the caller's C just above
+            raise BlankLabelUnderLengths(tg)
         need_grad = log_probs.requires_grad
         xlen = ctx.xlen = ctx.launch_xlen = None
         if lens is not None:
@@ -259,7 +278,14 @@ def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax, input
                                             keep_full=log_probs.dtype != torch.float32)
     if input_lengths is not None:
         fn = _FusedLogSoftmaxCTCLoss if fused_log_softmax else CTCLossFunction
-        return fn.apply(log_probs, targets, blank_idx, reduction, input_lengths)
+        try:
+            return fn.apply(log_probs, targets, blank_idx, reduction, input_lengths)
+        except BlankLabelUnderLengths as met:
+            # (found by the node on the targets it staged and checked: lists, tensors or staged targets alike, and no
+            # second pass over the labels for the batches without such a label)
+            tg = met.targets
+        return _lengths_with_blank_labels(log_probs, tg.flat, tg.offsets, int(blank_idx), reduction, fused_log_softmax,
+                                          input_lengths)
     if (type(log_probs) is torch.Tensor and log_probs.is_cuda and log_probs.requires_grad
             and log_probs.dtype == torch.float32 and log_probs.dim() == 3 and log_probs.is_contiguous()
             and torch.is_grad_enabled() and log_probs.shape[1] > 0 and reduction in ("none", "mean")):
@@ -283,6 +309,27 @@ def _ctc_loss(log_probs, targets, blank_idx, reduction, fused_log_softmax, input
             return loss
     fn = _FusedLogSoftmaxCTCLoss if fused_log_softmax else CTCLossFunction
     return fn.apply(log_probs, targets, blank_idx, reduction)
+
+
+def _lengths_with_blank_labels(log_probs, flat, offsets, blank, reduction, fused_log_softmax, lens):
+    """A padded batch whose targets hold the blank index as a LABEL.  In a certain-blank frame such a label's state has
+    the finite score 0 as well, so the pad frames are no identity of its graph: paths move on, or wait, between a blank
+    state and the blank-labelled state beside it, and where the target ends in such a label they are accepted -- Z grows
+    (tests/test_ctc_lengths_host.py shows it on the oracle).  The labels get a column of their own
+    instead -- class C, a copy of the blank's column, which a pad frame scores -inf like every other label -- and keep
+    their place in the skip rule (they equal each other and no other label).  torch's cat and log_softmax carry the
+    gradient back: the copy's into the blank's column, and through the normalisation when it was asked fused."""
+    C = log_probs.shape[2]
+    flat = np.asarray(flat)
+    if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= C):  # (the caller's C, not the widened row's)
+        bad = int(flat.min()) if int(flat.min()) < 0 else int(flat.max())
+        raise ValueError(f"CTCLoss: target label {bad} is outside [0, {C}) (emissions have {C} classes)")
+    if fused_log_softmax:  # (a NaN is an impossible arc here as in the fused launch)
+        log_probs = torch.nn.functional.log_softmax(log_probs.masked_fill(torch.isnan(log_probs), float("-inf")), dim=2)
+    wide = torch.cat((log_probs, log_probs[:, :, blank:blank + 1]), dim=2)
+    flat = np.where(flat == blank, C, flat)
+    targets = [flat[offsets[b]:offsets[b + 1]].tolist() for b in range(len(offsets) - 1)]
+    return CTCLossFunction.apply(wide, targets, blank, reduction, lens)
 
 
 def CTCLoss(log_probs, targets, blank_idx=0, reduction="none", input_lengths=None):

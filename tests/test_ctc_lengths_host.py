@@ -184,3 +184,50 @@ def test_certain_blank_frames_are_the_identity_of_the_ctc_graph(blank, reduction
         if n < ID_T and np.isfinite(want_loss):
             scale = 1.0 / len(targets[b]) if reduction == "mean" and targets[b] else 1.0
             assert np.allclose(-dx[b, n:, blank], scale, rtol=0, atol=1e-12), b
+
+
+@pytest.mark.parametrize("blank", [0, 4, ID_C - 1])
+def test_a_blank_label_needs_a_column_of_its_own_under_certain_blank_frames(blank):
+    """A target label equal to the blank index breaks the identity: in a pad frame its state scores 0 as the blank states
+    do, so paths wait or move on there, and where the target ends in such a label they are accepted: Z grows.  Shown on
+    the oracle; and the remedy of criterions/ctc.py
+    (_lengths_with_blank_labels): the blank labels relabelled to a class C whose column copies the blank's in the real
+    frames and is -inf in the pad frames -- that padded batch equals the per-slice calls again, and folding column C's
+    gradient into the blank's column gives the slices' gradient."""
+    rs = np.random.RandomState(23 + blank)
+    x = rs.randn(4, 12, ID_C)
+    lengths = [12, 9, 5, 7]
+    others = [c for c in range(ID_C) if c != blank]
+    targets = [[others[0], blank, others[1]], [blank, blank], [blank], [others[2], others[2], blank, others[2]]]
+    wide = np.concatenate([x, x[:, :, blank:blank + 1]], axis=2)
+    relabelled = [[ID_C if c == blank else c for c in t] for t in targets]
+    for pad_in, tg in ((x, targets), (wide, relabelled)):
+        padded = pad_in.copy()
+        for b, n in enumerate(lengths):
+            padded[b, n:, :] = -np.inf
+            padded[b, n:, blank] = 0.0
+        for b, n in enumerate(lengths):
+            want_loss, want_dx = OR.ctc_loss_grad(x[b:b + 1, :n], [targets[b]], blank, "mean")
+            loss, dx = OR.ctc_loss_grad(padded[b:b + 1], [tg[b]], blank, "mean")
+            if pad_in is x:
+                # more paths, a smaller loss -- where the target ENDS in the blank label: only there does the mass that
+                # waits in a blank-labelled state reach an accepting one
+                assert (loss < want_loss - 1e-3) == (n < 12 and targets[b][-1] == blank), (b, loss, want_loss)
+                assert loss <= want_loss + 1e-12
+                continue
+            assert abs(loss - want_loss) <= 1e-12 * max(1.0, abs(want_loss)), (b, loss, want_loss)
+            folded = dx[0, :, :ID_C].copy()
+            folded[:, blank] += dx[0, :, ID_C]
+            np.testing.assert_allclose(folded[:n], want_dx[0], rtol=0, atol=1e-13, err_msg=str(b))
+            assert (np.delete(folded[n:], blank, axis=1) == 0.0).all() and (dx[0, n:, ID_C] == 0.0).all(), b
+
+
+def test_the_widened_route_checks_labels_against_the_callers_classes():
+    """criterions/ctc.py::_lengths_with_blank_labels relabels blank labels to class C of a row of C + 1 classes: a label
+    C (or beyond, or negative) in the caller's targets is refused with the caller's class count before the row is
+    widened and before anything needs a device -- it must not be read as a relabelled blank"""
+    x = torch.zeros(2, 3, 4)
+    for bad in (4, 5, -1):
+        with pytest.raises(ValueError, match=rf"target label {bad} is outside \[0, 4\) \(emissions have 4 classes\)"):
+            ctc._lengths_with_blank_labels(x, np.array([1, 0, bad], dtype=np.int32), np.array([0, 2, 3]), 0, "none", False,
+                                           (3, 2))
