@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "lattice_layout.h"
 
 namespace wfl {
 
@@ -795,13 +796,10 @@ __device__ void run_chain(const wfl_lattice_desc& d, const UttView& u, const Cha
 //   out[slot][q] (double) relative to offs[slot] in LOG2 units:  log2 value = log2 out + offs[slot]
 // ------------------------------------------------------------------------------------------------
 constexpr int kFmtLog = 0, kFmtProb = 1;
-__device__ __forceinline__ int64_t xg_main_dev(const wfl_lattice_desc& d, int T) {
-  return (((int64_t)d.B * T * d.max_labels) + 3) & ~(int64_t)3;
-}
 constexpr double kLog2e_d = 1.4426950408889634074;
 #define WFL_SWEEP_STORE(ptr, v) (*(ptr) = (v))
 // ---- progress words of the sweeps (the in-launch gradient, prob_chain_occ_kernel) ---------------------------------
-// One 64-bit word per (utterance, direction) behind the dump area of the alpha / beta tails:
+// One 64-bit word per (utterance, direction) in the alpha / beta tails (AbTail::prog):
 //     [63:32] launch token   [31:28] XCC id of the sweep's workgroup   [27:0] chunks whose stores have reached L2
 // written by thread 0 of the sweep with one write-through store, polled by the gradient workgroups of the same launch.
 // The token (a per-launch counter from the host) makes words left by earlier launches read as "not yet".
@@ -828,58 +826,23 @@ __device__ __forceinline__ void prog_publish(uint64_t* w, uint32_t token, uint32
   __hip_atomic_store(w, ((uint64_t)token << 32) | ((uint64_t)xcc_id() << 28) | chunks, __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
-__host__ __device__ inline int64_t prog_offset_doubles(const wfl_lattice_desc& d, int nch1) {  // from the tail's start
-  return (int64_t)d.B * nch1 + 2 * (int64_t)d.B + 1024 + 1;
-}
-constexpr int kLiveTile = 32;  // frames per job of the gradient beside the sweeps (at least: T / tiles, rounded up)
-                               // (40 / 48 / 56 / 64 with the gradient in two phases, same box, three runs each: 0.324-0.326 / 0.307-0.317 /
-                               //  0.307-0.310 / 0.335-0.337 against 0.309-0.335 -- inside the runs' own spread)
-// header of the in-flight gradient, behind the progress words and `bad` of the alpha tail (int32 units)
-struct OccHeader {
-  uint32_t* bad;    // [B]
-  int32_t* nx;      // [8]  utterances whose sweeps run on XCD x
-  uint32_t* next;   // [8]  next job of XCD x
-  int32_t* list;    // [8][B]
-  uint32_t* busy;   // [8][256]  == token while a sweep runs on CU (xcc, HW_ID[15:8])
-  uint32_t* meta;   // [2]       the launch's token and its tiles per utterance (for served_beside_the_sweeps)
-  uint32_t* next_base;  // [8]   next base-row job of XCD x (occ_live_kernel, first phase)
-  uint32_t* based;  // [B][tiles] == token once the tile's base rows are written
-};
 // Did the gradient workgroups that ran beside the sweeps write utterance b's rows?  Not if one of them gave up on it
 // (`bad`), nor if jobs of its XCD were left undrawn (an XCD that hosted sweeps but no gradient workgroup).  Read by the
 // general gradient kernel of wfl_lattice_grad_rest, launches later.
-__device__ __forceinline__ bool served_beside_the_sweeps(const wfl_lattice_desc& d, const float* alpha, int64_t tail, int nch1,
-                                                         int b);
 __device__ __forceinline__ uint32_t cu_key() {  // this wave's CU among the 8 x 256 the ids can name
   uint32_t v;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
   return (xcc_id() & 7u) * 256u + ((v >> 8) & 255u);
 }
-__device__ __forceinline__ OccHeader occ_header(const wfl_lattice_desc& d, float* alpha, int64_t tail, int nch1) {
-  OccHeader h;
-  double* ta = reinterpret_cast<double*>(alpha + tail) + prog_offset_doubles(d, nch1);
-  h.bad = reinterpret_cast<uint32_t*>(ta + d.B);
-  h.nx = reinterpret_cast<int32_t*>(h.bad + ((d.B + 1) & ~1));
-  h.next = reinterpret_cast<uint32_t*>(h.nx + 8);
-  h.list = h.nx + 16;
-  h.busy = reinterpret_cast<uint32_t*>(h.list + 8 * (int64_t)d.B);
-  h.meta = h.busy + 8 * 256;
-  h.next_base = h.meta + 2;
-  h.based = h.next_base + 8;
-  return h;
-}
-
-__device__ __forceinline__ bool served_beside_the_sweeps(const wfl_lattice_desc& d, const float* alpha, int64_t tail, int nch1,
-                                                         int b) {
-  const OccHeader h = occ_header(d, const_cast<float*>(alpha), tail, nch1);
+__device__ __forceinline__ bool served_beside_the_sweeps(const AbTail& lay, const float* alpha, int b) {
+  const OccHeader h = lay.occ_header(const_cast<float*>(alpha));
   const uint32_t token = h.meta[0], ntiles = h.meta[1];
   if (h.bad[b] == token) return false;
-  const uint64_t va = reinterpret_cast<const uint64_t*>(reinterpret_cast<const double*>(alpha + tail) + prog_offset_doubles(d, nch1))[b];
+  const uint64_t va = *lay.prog(const_cast<float*>(alpha), b);
   if ((uint32_t)(va >> 32) != token || ((uint32_t)va & 0x0fffffffu) == kProgSkip) return false;
   const uint32_t x = ((uint32_t)va >> 28) & 7u;
   return h.next[x] >= (uint32_t)h.nx[x] * ntiles;
 }
-constexpr int kDumpDoubles = 1024;  // scratch behind the alpha / beta tails (see run_chain_prob)
 constexpr int kBandDepth = 4;
 // floats of the probability-domain sweeps' row tile: two chunks of the tile path, or the banded sweep's two tiles of
 // 16 rows (+ their references)
@@ -2202,15 +2165,15 @@ __device__ __forceinline__ void prob_chain_body(const wfl_lattice_desc& d, const
                                                 float* __restrict__ logz, int64_t tail, int nch1, int b, int dir, char* smem,
                                                 uint32_t token, int mitm_req = 0) {
   const UttView u = make_view(d, ints, floats, b, T);
-  double* offs_a = reinterpret_cast<double*>(alpha + tail);  // (tail layout: see chain_kernel)
-  double* offs_b = beta ? reinterpret_cast<double*>(beta + tail) : nullptr;
-  double* za = offs_a + (int64_t)d.B * nch1;
-  double* zb = offs_b ? offs_b + (int64_t)d.B * nch1 : nullptr;
-  int32_t* fmt = reinterpret_cast<int32_t*>(za + d.B);
-  float* wrefs = reinterpret_cast<float*>(fmt + d.B);
-  uint64_t* prog = PUB ? reinterpret_cast<uint64_t*>((dir == 0 ? offs_a : offs_b) + prog_offset_doubles(d, nch1)) + b : nullptr;
-  const float* fg = xg + xg_main_dev(d, T);
-  const float* rmax = fg + xg_main_dev(d, T);
+  const AbTail lay(d, tail, nch1);
+  double *offs_a = lay.offs(alpha, 0), *offs_b = beta ? lay.offs(beta, 0) : nullptr;  // (forward only: no beta buffer)
+  double *za = lay.z(alpha, 0), *zb = beta ? lay.z(beta, 0) : nullptr, *verdict = beta ? lay.verdict(beta, b) : nullptr;
+  int32_t* fmt = lay.fmt(alpha, 0);
+  float* wrefs = lay.wref(alpha, 0);
+  float *mine = dir == 0 ? alpha : beta, *other = dir == 0 ? beta : alpha;  // this sweep's buffer, its partner's
+  uint64_t* prog = PUB ? lay.prog(mine, b) : nullptr;
+  const float* fg = xg + xg_main(d, T);
+  const float* rmax = fg + xg_main(d, T);
   if (!prob_eligible(u, blockDim.x)) {
     if (PUB) {  // (the launch with the gradient beside the sweeps: left to the log-domain launch that follows)
       if (threadIdx.x == 0) {
@@ -2223,11 +2186,11 @@ __device__ __forceinline__ void prob_chain_body(const wfl_lattice_desc& d, const
     if (dir == 0) {
       if (threadIdx.x == 0) fmt[b] = kFmtProb;
       run_chain_prob_general<0, MAXT != 1024>(d, u, smem, T, rows_per_chunk, fg, rmax, weights, reinterpret_cast<double*>(alpha), logz, b,
-                                offs_a + (int64_t)b * nch1, za, wrefs);
+                                offs_a + lay.offs(b), za, wrefs);
     } else {
-      if (threadIdx.x == 0) zb[d.B + b] = 0.0;
+      if (threadIdx.x == 0) *verdict = 0.0;
       run_chain_prob_general<1, MAXT != 1024>(d, u, smem, T, rows_per_chunk, fg, rmax, weights, reinterpret_cast<double*>(beta), nullptr, b,
-                                offs_b + (int64_t)b * nch1, zb, nullptr);
+                                offs_b + lay.offs(b), zb, nullptr);
     }
     return;
   }
@@ -2243,26 +2206,26 @@ __device__ __forceinline__ void prob_chain_body(const wfl_lattice_desc& d, const
   MitmArgs mm;
   if (PUB && beta) {
     // (the partner: the other direction's rows, offsets and progress word; the backward sweep's own flag sits in the
-    // beta buffer where the alpha buffer keeps the gradient's `bad` words: occ_header)
+    // beta buffer where the alpha buffer keeps the gradient's `bad` words: AbTail)
     mm.req = mitm_req;
-    mm.oth = reinterpret_cast<double*>(dir == 0 ? beta : alpha) + u.ab_base;
-    mm.oth_offs = (dir == 0 ? offs_b : offs_a) + (int64_t)b * nch1;
-    mm.oth_prog = reinterpret_cast<const uint64_t*>((dir == 0 ? offs_b : offs_a) + prog_offset_doubles(d, nch1)) + b;
+    mm.oth = reinterpret_cast<double*>(other) + u.ab_base;
+    mm.oth_offs = lay.offs(other, b);
+    mm.oth_prog = lay.prog(other, b);
     mm.fmt = fmt + b;
-    mm.mitm_b = occ_header(d, beta, tail, nch1).bad + b;
-    mm.dead_b = occ_header(d, alpha, tail, nch1).bad + b;
+    mm.mitm_b = lay.occ_header(beta).bad + b;
+    mm.dead_b = lay.occ_header(alpha).bad + b;
   }
   if (dir == 0) {
     if (threadIdx.x == 0) fmt[b] = kFmtProb;
     run_chain_prob<0, MAXT == 128, MAXT <= 512, PUB>(d, u, P, T, rows_per_chunk, fg, rmax, weights, reinterpret_cast<double*>(alpha), logz, b,
-                      offs_a + (int64_t)b * nch1, za, wrefs, offs_a + (int64_t)d.B * nch1 + 2 * (int64_t)d.B, prog, token, mm);
+                      offs_a + lay.offs(b), za, wrefs, lay.dump(alpha), prog, token, mm);
   } else {
     if (threadIdx.x == 0) {
-      zb[d.B + b] = 0.0;  // the certificate's verdict: raised by prob_certify_kernel
+      *verdict = 0.0;  // the certificate's verdict: raised by prob_certify_kernel
       if (PUB) __hip_atomic_store(mm.mitm_b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     run_chain_prob<1, MAXT == 128, MAXT <= 512, PUB>(d, u, P, T, rows_per_chunk, fg, rmax, weights, reinterpret_cast<double*>(beta), nullptr, b,
-                      offs_b + (int64_t)b * nch1, zb, nullptr, offs_b + (int64_t)d.B * nch1 + 2 * (int64_t)d.B, prog, token, mm);
+                      offs_b + lay.offs(b), zb, nullptr, lay.dump(beta), prog, token, mm);
   }
 }
 
@@ -2299,13 +2262,11 @@ __global__ void __launch_bounds__(256)
   WFL_MARK_BEGIN(0);
   WFL_LOG(10);
   const UttView u = make_view(d, ints, floats, b, T);
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  double* tail_b = reinterpret_cast<double*>(beta + tail);
-  const double* offs_b = tail_b + (int64_t)b * nch1;
-  const double za = (reinterpret_cast<const double*>(alpha + tail) + (int64_t)d.B * nch1)[b];
-  const double zbv = (tail_b + (int64_t)d.B * nch1)[b];
-  double* verdict = tail_b + (int64_t)d.B * (nch1 + 1) + b;
-  const int32_t* fmt = reinterpret_cast<const int32_t*>(reinterpret_cast<const double*>(alpha + tail) + (int64_t)d.B * (nch1 + 1));
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
+  const double za = *lay.z(alpha, b), zbv = *lay.z(beta, b);
+  double* verdict = lay.verdict(beta, b);
+  const int32_t* fmt = lay.fmt(alpha, 0);
   if (fmt[b] != kFmtProb && fmt[b] != kFmtOcc) {
     if (tid == 0) *verdict = 1.0;  // (not swept in the probability domain at all: the log-domain launch takes it)
     return;
@@ -2322,7 +2283,7 @@ __global__ void __launch_bounds__(256)
   // total, at slot 0 to the backward sweep's).  One sweep that did and one that did not (a crossing that gave up
   // waiting) leave neither format: re-run in the log domain.
   const bool occ_a = fmt[b] == kFmtOcc;
-  const bool occ_b = pub && occ_header(d, beta, tail, nch1).bad[b] == 1u;
+  const bool occ_b = pub && lay.occ_header(beta).bad[b] == 1u;
   if (occ_a != occ_b) {
     if (tid == 0) *verdict = 1.0;
     return;
@@ -2373,24 +2334,15 @@ __global__ void chain_kernel(wfl_lattice_desc d, const int32_t* __restrict__ int
   WFL_MARK_BEGIN(1);
   WFL_LOG(11);
   const UttView u = make_view(d, ints, floats, b, T);
-  // behind the score arrays (wfl_lattice_workspace reserves the room):
-  //   alpha + tail: double offs[B][nch1], double Z[B] (ln Z; log2 Z for probability-domain utterances),
-  //                 int32 fmt[B], float wref[B]
-  //   beta + tail:  double offs[B][nch1], double Z[B] as the backward sweep sees it (probability domain), double
-  //                 verdict[B] of prob_certify_kernel (0: certified, 1: re-run in the log domain)
-  double* offs_a = reinterpret_cast<double*>(alpha + tail);
-  double* offs_b = beta ? reinterpret_cast<double*>(beta + tail) : nullptr;
-  double* za = offs_a + (int64_t)d.B * nch1;
-  double* zb = offs_b ? offs_b + (int64_t)d.B * nch1 : nullptr;
-  int32_t* fmt = reinterpret_cast<int32_t*>(za + d.B);
-  float* wrefs = reinterpret_cast<float*>(fmt + d.B);
+  const AbTail lay(d, tail, nch1);
+  int32_t* fmt = lay.fmt(alpha, 0);
   // mode: 1 = every utterance in the log domain (WFL_LATTICE_DOMAIN=log, tropical semiring);
   //       2 = the launch after prob_chain_kernel: the log-domain sweeps of what that launch left -- utterances whose
   //           acceptor it does not take, and those whose two probability-domain sweeps disagree about Z
   if (SR == WFL_SEMIRING_LOG && mode == 2) {
     if (fmt[b] == kFmtProb || fmt[b] == kFmtOcc) {  // swept in the probability domain by the launch before
-      if (!zb) return;                 // (forward only: nothing to compare)
-      if (zb[d.B + b] == 0.0) return;  // certified by prob_certify_kernel
+      if (!beta) return;                        // (forward only: nothing to compare)
+      if (*lay.verdict(beta, b) == 0.0) return;  // certified by prob_certify_kernel
     }
   }
   if (SR == WFL_SEMIRING_LOG && dir == 0 && threadIdx.x == 0) fmt[b] = kFmtLog;
@@ -2407,10 +2359,9 @@ __global__ void chain_kernel(wfl_lattice_desc d, const int32_t* __restrict__ int
   L.lvl = (int*)p, p += (size_t)(d.max_levels + 1) * 4;
   L.heavy = (int*)p;
   if (dir == 0)
-    run_chain<SR, 0>(d, u, L, T, rows_per_chunk, xg, weights, alpha, bptr, logz, b, offs_a + (int64_t)b * nch1, za);
+    run_chain<SR, 0>(d, u, L, T, rows_per_chunk, xg, weights, alpha, bptr, logz, b, lay.offs(alpha, b), lay.z(alpha, 0));
   else
-    run_chain<SR, 1>(d, u, L, T, rows_per_chunk, xg, weights, beta, nullptr, nullptr, b, offs_b + (int64_t)b * nch1,
-                     nullptr);
+    run_chain<SR, 1>(d, u, L, T, rows_per_chunk, xg, weights, beta, nullptr, nullptr, b, lay.offs(beta, b), nullptr);
 }
 
 // threads of the sweep workgroups: one state per thread up to 1024 states (the lean frame paths need it); beyond
@@ -2420,11 +2371,12 @@ static int chain_threads(const wfl_lattice_desc& d) {
   while (nt < 256 && nt * kPre < 2 * d.max_labels) nt += 64;  // two rows per chunk must fit the prefetch registers
   return nt;
 }
+// LDS of the probability-domain sweeps (ProbLds, carved in prob_chain_body)
+static size_t prob_lds_bytes(const wfl_lattice_desc& d, int rows_per_chunk, int nt) {
+  return (size_t)std::max(d.max_states, nt) * 16 + 64 * 4 + prob_rows_floats(d, rows_per_chunk, nt) * 4 + (size_t)2 * nt * 4 + 64;
+}
 static size_t chain_lds_bytes(const wfl_lattice_desc& d, int rows_per_chunk) {
-  const int nt = chain_threads(d);
-  const size_t prob = (size_t)std::max(d.max_states, nt) * 16 + 64 * 4 + prob_rows_floats(d, rows_per_chunk, nt) * 4 +
-                      (size_t)2 * nt * 4 + 64;
-  return std::max(prob, (size_t)d.max_arcs * 8 + (size_t)d.max_eps * 8 + (size_t)(d.max_states + 1) * 8 + (size_t)d.max_states * 16 +
+  return std::max(prob_lds_bytes(d, rows_per_chunk, chain_threads(d)), (size_t)d.max_arcs * 8 + (size_t)d.max_eps * 8 + (size_t)(d.max_states + 1) * 8 + (size_t)d.max_states * 16 +
          (size_t)2 * rows_per_chunk * d.max_labels * 4 + 64 * 4 + (size_t)(d.max_levels + 1) * 4 +
          (size_t)(d.max_states + 1) * 4 + (size_t)2 * rows_per_chunk * 4 + 64);
 }
@@ -2703,8 +2655,8 @@ __device__ __forceinline__ void occ_grad_tiles(const wfl_lattice_desc& d, const 
   int16_t* lab = (int16_t*)(corr + TS);                       // [Qmax]: label slot of the state (-1: no in-arc)
   int16_t* colmap = lab + ((d.max_states + 3) & ~3);          // [C]
   int32_t* colk = reinterpret_cast<int32_t*>(colmap + ((C + 3) & ~3));  // [Kmax]: the column of a label slot
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  const double* offs_b = reinterpret_cast<const double*>(beta + tail) + (int64_t)b * nch1;
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
   double zd = 0.0;
   bool dead = false;
   // gamma: the sweeps met in the middle and stored occupancies (floats) -- slots <= m in the beta buffer's rows, slots > m in
@@ -2712,10 +2664,10 @@ __device__ __forceinline__ void occ_grad_tiles(const wfl_lattice_desc& d, const 
   bool gamma = false;
   const int mid = mitm_middle(T);
   if (!LIVE) {
-    zd = reinterpret_cast<const double*>(alpha + tail)[(int64_t)d.B * nch1 + b];  // log2 Z
-    const int32_t* fmt = reinterpret_cast<const int32_t*>(reinterpret_cast<const double*>(alpha + tail) + (int64_t)d.B * (nch1 + 1));
-    gamma = fmt[b] == kFmtOcc;
-    if (!occ_eligible(u, fmt[b] == kFmtProb || gamma)) return;
+    zd = *lay.z(alpha, b);  // log2 Z
+    const int32_t fmt = *lay.fmt(alpha, b);
+    gamma = fmt == kFmtOcc;
+    if (!occ_eligible(u, fmt == kFmtProb || gamma)) return;
     const float z = logz[b];
     dead = !(z > WFL_NEG_INF) || !(z < __builtin_inff());  // no accepting path: zero gradient
   } else if (!occ_eligible(u, true)) {
@@ -2949,7 +2901,7 @@ __global__ void __launch_bounds__(MAXT)
   if (b >= d.B) return;
   __builtin_amdgcn_s_setprio(2);
   // the gradient workgroups leave a CU alone while a sweep runs on it (occ_live_kernel)
-  uint32_t* busy = occ_header(d, alpha, tail, nch1).busy + cu_key();
+  uint32_t* busy = AbTail(d, tail, nch1).occ_header(alpha).busy + cu_key();
   if (threadIdx.x == 0) __hip_atomic_store(busy, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef WFL_LIVE_STATS
   if (threadIdx.x == 0 && blockIdx.x < 512) g_sweep[blockIdx.x][0] = wall_clock64();
@@ -2972,9 +2924,9 @@ __global__ void __launch_bounds__(64)
                     uint32_t token, int force_bad, uint32_t* __restrict__ host_words, uint32_t* __restrict__ verdict,
                     int ntiles, int max_spins) {
   const int lane = threadIdx.x;
-  const uint64_t* pa = reinterpret_cast<const uint64_t*>(reinterpret_cast<double*>(alpha + tail) + prog_offset_doubles(d, nch1));
-  const uint64_t* pb = reinterpret_cast<const uint64_t*>(reinterpret_cast<double*>(beta + tail) + prog_offset_doubles(d, nch1));
-  const OccHeader h = occ_header(d, alpha, tail, nch1);
+  const AbTail lay(d, tail, nch1);
+  const uint64_t *pa = lay.prog(alpha, 0), *pb = lay.prog(beta, 0);
+  const OccHeader h = lay.occ_header(alpha);
   // First every sweep of the launch must have announced itself -- until then NOTHING is written to alpha / beta: the
   // buffers may be a previous call's, whose gradient kernel (wfl_lattice_grad_rest) may read its header until the
   // stream reaches this call's sweeps.  The wait is bounded (max_spins polls of ~2 us: the side stream was forked
@@ -3050,11 +3002,10 @@ __global__ void __launch_bounds__(256, 3)  // (three waves a SIMD, i.e. three wo
   // (the gate in front of this kernel on the side stream: anything but the launch's token means it gave up and the
   // header is not this launch's -- nothing to do here, wfl_lattice_grad_rest computes every row)
   if (__hip_atomic_load(verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != token) return;
-  const OccHeader h = occ_header(d, alpha, tail, nch1);
+  const AbTail lay(d, tail, nch1);
+  const OccHeader h = lay.occ_header(alpha);
   const uint32_t me = xcc_id() & 7u;
   const int nx = h.nx[me];
-  const double* ta = reinterpret_cast<const double*>(alpha + tail) + prog_offset_doubles(d, nch1);
-  const double* tb = reinterpret_cast<const double*>(beta + tail) + prog_offset_doubles(d, nch1);
   // middle-out: mid, mid - 1, mid + 1, mid - 2, ... and the rest of the longer side
   const int mid = ntiles / 2, nlo = mid, nhi = ntiles - mid, pair = min(nlo, nhi);
 #ifndef WFL_LIVE_SHARE_CU
@@ -3093,19 +3044,13 @@ __global__ void __launch_bounds__(256, 3)  // (three waves a SIMD, i.e. three wo
   const uint32_t total = (uint32_t)nx * (uint32_t)ntiles;
   auto live_of = [&](int b, int tile) {
     OccLive live;
-    live.prog_a = reinterpret_cast<const uint64_t*>(ta) + b;
-    live.prog_b = reinterpret_cast<const uint64_t*>(tb) + b;
+    live.prog_a = lay.prog(alpha, b);
+    live.prog_b = lay.prog(beta, b);
     live.bad = h.bad + b;
     live.token = token, live.R = rows_per_chunk, live.force_bad = 0, live.mitm = mitm_req;
     live.based = two_phase ? h.based + (int64_t)b * ntiles + tile : nullptr;
     return live;
   };
-  // ---- first phase: the rows' base values.  A row of the gradient is -cf softmax(x) plus the occupancies of its label
-  // columns, and only the latter wait for the sweeps: the workgroups stream the former -- the step's gradient traffic --
-  // while the sweeps are in their first half and there is nothing else for them to do (the first occupancies appear at
-  // the crossing, 85 us into the launch), and mark each tile in `based`.  With whole rows written per tile behind the
-  // sweeps the gradient ran at the capacity of its workgroups from the crossing on and was 80 us behind when the sweeps
-  // ended (B = 64: 858 of 1 600 tiles; profiles/r06_live_timeline.txt).
   // (Every base job is drawn before any occupancy job: a tile that waits for its base rows waits for a workgroup that
   // is writing them.  Occupancy jobs first where they are ready -- a look at the head job, then a ticket or a
   // compare-and-swap -- was built twice: the looks cost more than the order gains, 0.40 ms and 2.1 ms a step.)
@@ -3186,17 +3131,16 @@ __global__ void __launch_bounds__(256)
   int16_t* colmap = (int16_t*)(corr_eps + 34);  // [C] (only if dx)
   // scores are stored relative to per-chunk double offsets (run_chain): slot s of alpha belongs to chunk (s-1)/R of
   // the forward sweep, slot s of beta to chunk (T-1-s)/R of the backward sweep, the boundary slots to offset 0
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  const double* offs_b = reinterpret_cast<const double*>(beta + tail) + (int64_t)b * nch1;
-  const double zd = reinterpret_cast<const double*>(alpha + tail)[(int64_t)d.B * nch1 + b];  // ln Z | log2 Z (prob)
-  const int32_t* fmt = reinterpret_cast<const int32_t*>(reinterpret_cast<const double*>(alpha + tail) + (int64_t)d.B * (nch1 + 1));
-  const float* wrefs = reinterpret_cast<const float*>(fmt + d.B);
-  const bool prob = fmt[b] == kFmtProb;
-  if (fmt[b] == kFmtOcc) {
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
+  const double zd = *lay.z(alpha, b);  // ln Z | log2 Z (prob)
+  const int32_t fmt = *lay.fmt(alpha, b);
+  const bool prob = fmt == kFmtProb;
+  if (fmt == kFmtOcc) {
     // sweeps that met in the middle left occupancies, not both vectors (run_chain_prob): only the occupancy gradient reads
     // them -- the workgroups beside the sweeps (skip_occ == 2, unless they say otherwise) or occ_grad_kernel in this call
     // (skip_occ == 1); what neither served is computed right here, the same tiles
-    if (skip_occ == 1 || (skip_occ == 2 && served_beside_the_sweeps(d, alpha, tail, nch1, b)) || !dx) return;
+    if (skip_occ == 1 || (skip_occ == 2 && served_beside_the_sweeps(lay, alpha, b)) || !dx) return;
     const int tb = blockIdx.x * rows_per_block;
     occ_grad_tiles<false>(d, u, b, T, C, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, tb, min(T, tb + rows_per_block),
                           TS, tail, nch1, smem, OccLive{});
@@ -3208,10 +3152,10 @@ __global__ void __launch_bounds__(256)
   }
   // occ_grad_kernel served this utterance (the same test decides there); skip_occ == 2: the gradient workgroups beside
   // the sweeps did, unless they say otherwise
-  if (skip_occ && occ_eligible(u, prob) && (skip_occ != 2 || served_beside_the_sweeps(d, alpha, tail, nch1, b))) return;
-  const float wref = prob ? wrefs[b] : 0.f;
-  const float* fgp = xg + xg_main_dev(d, T);                    // probability-domain factors of the gathered rows
-  const float* rmaxp = fgp + xg_main_dev(d, T) + (int64_t)b * T;  // their references
+  if (skip_occ && occ_eligible(u, prob) && (skip_occ != 2 || served_beside_the_sweeps(lay, alpha, b))) return;
+  const float wref = prob ? *lay.wref(alpha, b) : 0.f;
+  const float* fgp = xg + xg_main(d, T);                    // probability-domain factors of the gathered rows
+  const float* rmaxp = fgp + xg_main(d, T) + (int64_t)b * T;  // their references
   const double* alpha_d = reinterpret_cast<const double*>(alpha);
   const double* beta_d = reinterpret_cast<const double*>(beta);
   const float g0 = gout ? gout[0] : 1.f;
@@ -3438,13 +3382,12 @@ __global__ void __launch_bounds__(256)
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const UttView u = make_view(d, ints, floats, b, T);
   const int Q = u.Q, Kmax = d.max_labels;
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  const double* offs_b = reinterpret_cast<const double*>(beta + tail) + (int64_t)b * nch1;
-  const double zd = reinterpret_cast<const double*>(alpha + tail)[(int64_t)d.B * nch1 + b];  // log2 Z
-  const int32_t* fmt = reinterpret_cast<const int32_t*>(reinterpret_cast<const double*>(alpha + tail) + (int64_t)d.B * (nch1 + 1));
-  const float wref = reinterpret_cast<const float*>(fmt + d.B)[b];
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
+  const double zd = *lay.z(alpha, b);  // log2 Z
+  const float wref = *lay.wref(alpha, b);
   const BandArcs arcs = band_in_arcs(u, weights, lane);
-  const bool shape = fmt[b] == kFmtProb && band_shape(d, u);
+  const bool shape = *lay.fmt(alpha, b) == kFmtProb && band_shape(d, u);
   if (!__syncthreads_and(arcs.ok) || !shape) return;  // the general kernel takes this utterance (same test there)
   float* acc = reinterpret_cast<float*>(smem) + (size_t)wave * RB * Kmax;  // [RB][Kmax], this wave's
   int16_t* colmap = reinterpret_cast<int16_t*>(reinterpret_cast<float*>(smem) + (size_t)4 * RB * Kmax);  // [C]
@@ -3466,8 +3409,8 @@ __global__ void __launch_bounds__(256)
   // for those lanes only)
   const double* A_ = reinterpret_cast<const double*>(alpha) + u.ab_base + min(lane, Q - 1);
   const double* B_ = reinterpret_cast<const double*>(beta) + u.ab_base + min(lane, Q - 1);
-  const float* fgu = xg + xg_main_dev(d, T) + u.xg_base;                         // factors of the gathered rows
-  const float* rmu = xg + 2 * xg_main_dev(d, T) + (int64_t)b * T;                // their references
+  const float* fgu = xg + xg_main(d, T) + u.xg_base;                         // factors of the gathered rows
+  const float* rmu = xg + 2 * xg_main(d, T) + (int64_t)b * T;                // their references
   const bool one_slot = arcs.slot_self == arcs.slot_adj;
   double sum_s = 0.0, sum_a = 0.0;
   const int nblk = (T + RB - 1) / RB, nw = gridDim.x * 4;
@@ -3767,32 +3710,11 @@ using namespace wfl;
 
 extern "C" {
 
-static int64_t xg_main(const wfl_lattice_desc& d, int T) { return (((int64_t)d.B * T * d.max_labels) + 3) & ~(int64_t)3; }
-
 // Launch shape of the chain kernel: threads per workgroup and emission rows per chunk (also the renormalisation
 // interval, so the gradient kernel needs the same number).
 static void chain_config(const wfl_lattice_desc& d, int& nt, int& rpc) {
   nt = chain_threads(d);
   rpc = std::max(2, std::min(16, nt * kPre / std::max(1, d.max_labels)) & ~1);  // even (run_chain)
-}
-// scores (float | double) [..] | double offs[B][nch1] | double Z[B] | int32 fmt[B] | float wref[B]   (see chain_kernel)
-static int64_t ab_main_elems(const wfl_lattice_desc& d, int T) {  // (float units; room for doubles)
-  return 2 * (d.shared ? (int64_t)d.B * (T + 1) * d.max_states : (int64_t)(T + 1) * d.total_states);
-}
-static void ab_tail(const wfl_lattice_desc& d, int T, int64_t& tail, int& nch1) {
-  nch1 = T + 1;  // one offset per time slot (probability domain); the log domain uses one per chunk
-  tail = ab_main_elems(d, T);
-}
-
-static int64_t ab_tuned_elems(const wfl_lattice_desc& d, int T) {
-  int64_t tail;
-  int nch1;
-  ab_tail(d, T, tail, nch1);
-  // (+ kDumpDoubles doubles behind the tail: where the lanes without a state of the unrolled sweeps "store")
-  // (+ behind that: a progress word per utterance, and -- alpha only -- `bad` and the OccHeader lists)
-  // (... + the in-flight gradient's header: OccHeader, its per-tile words last)
-  return tail + 2 * ((int64_t)d.B * nch1 + d.B) + 2 * (int64_t)d.B + 2 + 2 * kDumpDoubles + 12 * (int64_t)d.B + 32 + 2048 + 4 +
-         16 + (int64_t)d.B * (T / kLiveTile + 2);
 }
 
 // ---- streamed sweeps (lattice_streamed.h): acceptors whose arcs do not fit LDS ----------------------------------
@@ -3825,7 +3747,7 @@ static int stream_mode(const wfl_lattice_desc& d) {
   return env != 2 && stream_lds_bytes(d, true) <= (size_t)kLdsBytes ? 1 : 2;
 }
 // where the streamed area starts in the alpha buffer (float units, behind the tuned layout; 16-byte aligned)
-static int64_t stream_area_off(const wfl_lattice_desc& d, int T) { return (ab_tuned_elems(d, T) + 3) & ~(int64_t)3; }
+static int64_t stream_area_off(const wfl_lattice_desc& d, int T) { return (ab_tail(d, T).total_floats() + 3) & ~(int64_t)3; }
 static std::atomic<uint64_t> g_streamed_launches{0};  // wfl_lattice_diagnostics out[8]
 
 int wfl_lattice_workspace(const wfl_lattice_desc* d, int T, int64_t* xg_elems, int64_t* ab_elems) {
@@ -3835,7 +3757,7 @@ int wfl_lattice_workspace(const wfl_lattice_desc* d, int T, int64_t* xg_elems, i
   }
   // xg: log-domain rows | probability-domain factors of the same rows | one reference per row
   if (xg_elems) *xg_elems = 2 * xg_main(*d, T) + (int64_t)d->B * T;
-  if (ab_elems) *ab_elems = stream_mode(*d) ? stream_area_off(*d, T) + stream_area_words(*d) : ab_tuned_elems(*d, T);
+  if (ab_elems) *ab_elems = stream_mode(*d) ? stream_area_off(*d, T) + stream_area_words(*d) : ab_tail(*d, T).total_floats();
   return WFL_OK;
 }
 
@@ -3851,9 +3773,7 @@ static int lattice_forward_streamed(const wfl_lattice_desc* d, const int32_t* in
     set_error("lattice_forward: tropical semiring needs a back-pointer buffer");
     return WFL_ERR_INVALID;
   }
-  int64_t tail;
-  int nch1;
-  ab_tail(*d, T, tail, nch1);
+  const AbTail lay = ab_tail(*d, T);
   const hipStream_t s = (hipStream_t)stream;
   const int work = 3 * d->max_arcs + 2 * d->max_eps;
   const unsigned bx = (unsigned)std::max(1, std::min(256, (work + 255) / 256));
@@ -3867,7 +3787,7 @@ static int lattice_forward_streamed(const wfl_lattice_desc* d, const int32_t* in
   auto launch = [&](auto kern) -> int {
     if (lds > 48 * 1024) WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)kern, (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(kStreamThreads), lds, s, *d, ints, floats, xg, T, R, alpha, log ? beta : nullptr,
-                       log ? nullptr : bptr, logz, tail, nch1, stream_area_off(*d, T));
+                       log ? nullptr : bptr, logz, lay.tail, lay.nch1, stream_area_off(*d, T));
     return WFL_OK;
   };
   int rc;
@@ -3887,9 +3807,7 @@ static int lattice_grad_streamed(const wfl_lattice_desc* d, const int32_t* ints,
                                  int C, const float* weights, const float* alpha, const float* beta, const float* logz,
                                  const float* coef, const float* coef_w, const float* gout, int accumulate, const float* x,
                                  const float* row_lse, float* dx, float* dW, void* stream) {
-  int64_t tail;
-  int nch1;
-  ab_tail(*d, T, tail, nch1);
+  const AbTail lay = ab_tail(*d, T);
   const hipStream_t s = (hipStream_t)stream;
   const int R = stream_rpc(*d);
   if (dx) {
@@ -3903,14 +3821,14 @@ static int lattice_grad_streamed(const wfl_lattice_desc* d, const int32_t* ints,
     }
     if (lds > 48 * 1024) WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)stream_grad_kernel, (int)lds));
     hipLaunchKernelGGL(stream_grad_kernel, dim3((unsigned)((T + TS - 1) / TS), (unsigned)d->B), dim3(256), lds, s, *d, ints,
-                       floats, xg, T, C, R, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, TS, tail, nch1,
+                       floats, xg, T, C, R, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, TS, lay.tail, lay.nch1,
                        stream_area_off(*d, T));
     WFL_LAUNCH_CHECK();
   }
   const int nba = (d->max_arcs + 255) / 256, nbe = (d->max_eps + 255) / 256;
   if (dW && nba + nbe > 0) {
     hipLaunchKernelGGL(stream_dw_kernel, dim3((unsigned)(nba + nbe), (unsigned)d->B), dim3(256), 0, s, *d, ints, floats, xg,
-                       T, R, weights, alpha, beta, logz, coef_w, gout, dW, nba, tail, nch1);
+                       T, R, weights, alpha, beta, logz, coef_w, gout, dW, nba, lay.tail, lay.nch1);
     WFL_LAUNCH_CHECK();
   }
   g_streamed_launches.fetch_add(1);
@@ -3923,10 +3841,8 @@ int wfl_lattice_formats_offset(const wfl_lattice_desc* d, int T, int64_t* offset
     set_error("lattice_formats_offset: bad arguments");
     return WFL_ERR_INVALID;
   }
-  int64_t tail;
-  int nch1;
-  ab_tail(*d, T, tail, nch1);
-  *offset = tail + 2 * ((int64_t)d->B * nch1 + d->B);  // behind offs[B][nch1] and Z[B] (doubles)
+  const AbTail lay = ab_tail(*d, T);
+  *offset = lay.tail + lay.fmt(0);
   return WFL_OK;
 }
 
@@ -4121,10 +4037,9 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
   }
   if (const int mode = stream_mode(*d))
     return lattice_forward_streamed(d, ints, floats, xg, T, weights, semiring, alpha, beta, bptr, logz, stream, mode);
-  int nt, rpc, nch1;
-  int64_t tail;
+  int nt, rpc;
   chain_config(*d, nt, rpc);
-  ab_tail(*d, T, tail, nch1);
+  const AbTail lay = ab_tail(*d, T);
   const size_t lds = chain_lds_bytes(*d, rpc);
   if (lds > (size_t)kLdsBytes) {
     set_error("lattice_forward: acceptor needs %zu B of LDS (limit %d): %d arcs, %d states", lds, kLdsBytes,
@@ -4147,13 +4062,13 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
         if (lds > 48 * 1024)
           (void)wfl::set_max_dynamic_lds((const void*)kern, (int)lds);
         hipLaunchKernelGGL(kern, grid, dim3(nt), lds, (hipStream_t)stream, *d, ints, floats, xg, T, rpc, weights, alpha,
-                           beta, logz, tail, nch1);
+                           beta, logz, lay.tail, lay.nch1);
       };
       // The occupancy gradient beside the sweeps (prob_chain_pub_kernel + occ_gate_kernel + occ_live_kernel): uniform-
       // label acceptors without epsilon arcs, full 16-frame chunks (the sweeps' publication counts on them).
       // WFL_LATTICE_FUSED_BADXCD=1: every utterance is reported as swept on two XCDs (tests of the fall-back).
       constexpr int fused_env = 1;
-      constexpr int fused_tile = kLiveTile;  // frames per gradient job (16 / 24 / 48 re-measured in round 5 with the sweeps at 160 us: all within 1 %)
+      constexpr int fused_tile = kLiveTile;  // frames per gradient job: AbTail::live_tiles() sizes `based` by it (16 / 24 / 48 re-measured in round 5: all within 1 %)
       // persistent gradient workgroups per CU: as many as are resident at once (four waves of 130 VGPRs each: three per
       // CU).  More only queue behind those and start when the jobs are gone; measured at the Transducer benchmark with
       // the sweeps at 160 us: 2 -> 0.399 ms, 3 -> 0.362, 4 -> 0.364, 5 (the value until then) -> 0.369, 8 -> 0.37
@@ -4168,7 +4083,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
         const int ntiles = (T + fused_tile - 1) / fused_tile;
         const int rows_o = (T + ntiles - 1) / ntiles;
         nt_o = (T + rows_o - 1) / rows_o;
-        const size_t plds = (size_t)std::max(d->max_states, nt) * 16 + 64 * 4 + prob_rows_floats(*d, rpc, nt) * 4 + (size_t)2 * nt * 4 + 64;
+        const size_t plds = prob_lds_bytes(*d, rpc, nt);
         const size_t olds = occ_lds_bytes(*d, rows_o, g->C);
         // (not while the stream is being captured into a graph: the side stream's launches would not be part of it)
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -4200,7 +4115,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
             WFL_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
           }
           auto launch_gate = [&]() {
-            hipLaunchKernelGGL(occ_gate_kernel, dim3(1), dim3(64), 0, gate_s, *d, alpha, beta, tail, nch1, token,
+            hipLaunchKernelGGL(occ_gate_kernel, dim3(1), dim3(64), 0, gate_s, *d, alpha, beta, lay.tail, lay.nch1, token,
                                bad_env && atoi(bad_env) == 1 ? 1 : 0, ls.host, verdict, nt_o, ls.max_spins);
           };
           if (serial_test) launch_gate();
@@ -4220,7 +4135,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
           auto launch_pub = [&](auto kern) {
             if (plds > 48 * 1024) (void)wfl::set_max_dynamic_lds((const void*)kern, (int)plds);
             hipLaunchKernelGGL(kern, dim3((unsigned)(2 * Bp)), dim3(nt), plds, main_s, *d, ints, floats, xg, T, rpc, weights,
-                               alpha, beta, logz, tail, nch1, Bp, token, mitm_req);
+                               alpha, beta, logz, lay.tail, lay.nch1, Bp, token, mitm_req);
           };
           if (nt <= 256)
             launch_pub(prob_chain_pub_kernel<256>);
@@ -4231,7 +4146,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
           const int64_t jobs = (int64_t)d->B * nt_o;
           const unsigned wgs = (unsigned)std::max<int64_t>(8, std::min<int64_t>(jobs, (int64_t)fused_wgs * device_cus()));
           hipLaunchKernelGGL(occ_live_kernel, dim3(wgs), dim3(256), olds, side->stream, *d, ints, floats, T, g->C, alpha, beta,
-                             g->coef, g->x, g->row_lse, g->dx, rows_o, nt_o, rpc, tail, nch1, token, verdict, mitm_req, two_phase);
+                             g->coef, g->x, g->row_lse, g->dx, rows_o, nt_o, rpc, lay.tail, lay.nch1, token, verdict, mitm_req, two_phase);
           WFL_HIP_CHECK(hipEventRecord(side->join, side->stream));
           join_side = side;  // (joined below, behind the certificate: it and the log-domain launch overlap the gradient's tail)
           g->done = 1;
@@ -4248,11 +4163,11 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
         launch_prob(prob_chain_kernel<1024>);
       if (beta)
         hipLaunchKernelGGL(prob_certify_kernel, dim3((unsigned)d->B, 8u), dim3(256), 0, (hipStream_t)stream, *d, ints,
-                           floats, T, alpha, beta, tail, nch1, nt, (g && g->done) ? 1 : 0, weights);
+                           floats, T, alpha, beta, lay.tail, lay.nch1, nt, (g && g->done) ? 1 : 0, weights);
     }
     // ... then the log-domain sweeps of the rest (and of utterances whose two sweeps disagree: the certificate)
     hipLaunchKernelGGL(k, grid, dim3(nt), lds, (hipStream_t)stream, *d, ints, floats, xg, T, rpc, weights, alpha,
-                       beta, (int32_t*)nullptr, logz, tail, nch1, log_only ? 1 : 2);
+                       beta, (int32_t*)nullptr, logz, lay.tail, lay.nch1, log_only ? 1 : 2);
     // (the gradient beside the sweeps: joined only here -- the certificate and the log-domain launch, which normally
     // finds nothing to do, ran under its tail.  An utterance the log-domain launch re-sweeps while gradient workgroups
     // still read its alpha / beta gets rows of garbage from them; wfl_lattice_grad_rest overwrites exactly those.)
@@ -4267,7 +4182,7 @@ static int lattice_forward_impl(const wfl_lattice_desc* d, const int32_t* ints, 
     if (lds > 48 * 1024)
       WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)k, (int)lds));
     hipLaunchKernelGGL(k, grid, dim3(nt), lds, (hipStream_t)stream, *d, ints, floats, xg, T, rpc, weights, alpha,
-                       (float*)nullptr, bptr, logz, tail, nch1, 1);
+                       (float*)nullptr, bptr, logz, lay.tail, lay.nch1, 1);
   } else {
     set_error("lattice_forward: unknown semiring %d", semiring);
     return WFL_ERR_INVALID;
@@ -4333,10 +4248,9 @@ static int lattice_grad_impl(const wfl_lattice_desc* d, const int32_t* ints, con
     set_error("lattice_grad: %d distinct labels per utterance (limit 32767)", d->max_labels);
     return WFL_ERR_UNSUPPORTED;
   }
-  int nt_chain, rpc, nch1;
-  int64_t tail;
+  int nt_chain, rpc;
   chain_config(*d, nt_chain, rpc);
-  ab_tail(*d, T, tail, nch1);
+  const AbTail lay = ab_tail(*d, T);
   constexpr size_t budget = 40 * 1024;  // LDS per workgroup that sizes the tiles
   int TS = fixed + row_bytes < budget ? (int)((budget - fixed) / row_bytes) : 1;
   TS = std::max(1, std::min(TS, 32));
@@ -4374,7 +4288,7 @@ static int lattice_grad_impl(const wfl_lattice_desc* d, const int32_t* ints, con
     const unsigned bx = (unsigned)std::max(1, std::min((nblk + 3) / 4, (1024 + d->B - 1) / d->B));
     const size_t blds = (size_t)4 * 16 * d->max_labels * 4 + (size_t)2 * C + 16;
     hipLaunchKernelGGL(band_grad_kernel, dim3(bx, (unsigned)d->B), dim3(256), blds, (hipStream_t)stream, *d, ints, floats,
-                       xg, T, C, weights, alpha, beta, logz, coef, coef_w, gout, accumulate, dx, dW, tail, nch1);
+                       xg, T, C, weights, alpha, beta, logz, coef, coef_w, gout, accumulate, dx, dW, lay.tail, lay.nch1);
     WFL_LAUNCH_CHECK();
   }
   // uniform-label acceptors without learnable weights (the Transducer's alignment graphs, long CTC targets): the
@@ -4390,8 +4304,8 @@ static int lattice_grad_impl(const wfl_lattice_desc* d, const int32_t* ints, con
     if (olds <= (size_t)kLdsBytes) {
       if (olds > 48 * 1024) WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)occ_grad_kernel, (int)olds));
       hipLaunchKernelGGL(occ_grad_kernel, dim3((unsigned)blocks_o, (unsigned)d->B), dim3(256), olds, (hipStream_t)stream, *d,
-                         ints, floats, T, C, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, rows_o, ts_o, tail,
-                         nch1);
+                         ints, floats, T, C, alpha, beta, logz, coef, gout, accumulate, x, row_lse, dx, rows_o, ts_o, lay.tail,
+                         lay.nch1);
       WFL_LAUNCH_CHECK();
       occ_done = 1;
     }
@@ -4400,7 +4314,7 @@ static int lattice_grad_impl(const wfl_lattice_desc* d, const int32_t* ints, con
     WFL_HIP_CHECK(wfl::set_max_dynamic_lds((const void*)grad_kernel, (int)lds));
   hipLaunchKernelGGL(grad_kernel, dim3((unsigned)blocks_t, (unsigned)d->B), dim3(256), lds, (hipStream_t)stream, *d,
                      ints, floats, xg, T, C, weights, alpha, beta, logz, coef, coef_w, gout, accumulate, x, row_lse,
-                     dx, dW, rows_per_block, TS, tail, nch1, rpc, band, occ_done);
+                     dx, dW, rows_per_block, TS, lay.tail, lay.nch1, rpc, band, occ_done);
   WFL_LAUNCH_CHECK();
   return WFL_OK;
 }

@@ -412,8 +412,7 @@ __device__ void run_stream(const wfl_lattice_desc& d, const UttView& u, const St
   }
 }
 
-// grid (B, directions).  Behind the score arrays the tuned layout (chain_kernel): alpha + tail: double offs[B][nch1],
-// double Z[B], int32 fmt[B]; beta + tail: double offs[B][nch1].  The area of stream_stage_kernel at alpha + area_off.
+// grid (B, directions).  Behind the score arrays the tuned layout (AbTail), stream_stage_kernel's area at alpha + area_off.
 template <int SR, bool LDSST>
 __global__ void __launch_bounds__(kStreamThreads)
     stream_chain_kernel(wfl_lattice_desc d, const int32_t* __restrict__ ints, const float* __restrict__ floats,
@@ -425,15 +424,12 @@ __global__ void __launch_bounds__(kStreamThreads)
   const int g = d.shared ? 0 : b;
   const int s0 = ints[d.state_off + g];
   const StreamArea S = stream_area(d, reinterpret_cast<int32_t*>(alpha + area_off));
-  double* offs_a = reinterpret_cast<double*>(alpha + tail);
-  double* za = offs_a + (int64_t)d.B * nch1;
-  int32_t* fmt = reinterpret_cast<int32_t*>(za + d.B);
-  if (SR == WFL_SEMIRING_LOG && dir == 0 && threadIdx.x == 0) fmt[b] = kFmtLog;
+  const AbTail lay(d, tail, nch1);
+  if (SR == WFL_SEMIRING_LOG && dir == 0 && threadIdx.x == 0) *lay.fmt(alpha, b) = kFmtLog;
   if (dir == 0)
-    run_stream<SR, 0, LDSST>(d, u, S, g, s0, smem, T, R, xg, alpha, bptr, logz, b, offs_a + (int64_t)b * nch1, za);
+    run_stream<SR, 0, LDSST>(d, u, S, g, s0, smem, T, R, xg, alpha, bptr, logz, b, lay.offs(alpha, b), lay.z(alpha, 0));
   else
-    run_stream<SR, 1, LDSST>(d, u, S, g, s0, smem, T, R, xg, beta, nullptr, nullptr, b,
-                             reinterpret_cast<double*>(beta + tail) + (int64_t)b * nch1, nullptr);
+    run_stream<SR, 1, LDSST>(d, u, S, g, s0, smem, T, R, xg, beta, nullptr, nullptr, b, lay.offs(beta, b), nullptr);
 }
 
 // offset index of a slot: alpha slot s belongs to chunk (s-1)/R of the forward sweep, beta slot s to chunk (T-1-s)/R of
@@ -455,9 +451,9 @@ __global__ void __launch_bounds__(256)
   const int Q = u.Q, K = u.K, A = u.A, Kmax = d.max_labels;
   const StreamArea S = stream_area(d, const_cast<int32_t*>(reinterpret_cast<const int32_t*>(alpha + area_off)));
   const int2* __restrict__ sarc = S.sarc + u.a0;
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  const double* offs_b = reinterpret_cast<const double*>(beta + tail) + (int64_t)b * nch1;
-  const double zd = reinterpret_cast<const double*>(alpha + tail)[(int64_t)d.B * nch1 + b];
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
+  const double zd = *lay.z(alpha, b);
   float* acc = reinterpret_cast<float*>(smem);
   double* corr = reinterpret_cast<double*>(acc + (((size_t)TS * Kmax + 1) & ~(size_t)1));
   int* sptr = reinterpret_cast<int*>(corr + TS);
@@ -525,9 +521,9 @@ __global__ void __launch_bounds__(256)
   if (!(z > WFL_NEG_INF) || !(z < __builtin_inff())) return;  // no accepting path: zero gradient
   const UttView u = make_view(d, ints, floats, b, T);
   const int Q = u.Q, Kmax = d.max_labels;
-  const double* offs_a = reinterpret_cast<const double*>(alpha + tail) + (int64_t)b * nch1;
-  const double* offs_b = reinterpret_cast<const double*>(beta + tail) + (int64_t)b * nch1;
-  const double zd = reinterpret_cast<const double*>(alpha + tail)[(int64_t)d.B * nch1 + b];
+  const AbTail lay(d, tail, nch1);
+  const double *offs_a = lay.offs(alpha, b), *offs_b = lay.offs(beta, b);
+  const double zd = *lay.z(alpha, b);
   const double* alpha_d = reinterpret_cast<const double*>(alpha) + u.ab_base;
   const double* beta_d = reinterpret_cast<const double*>(beta) + u.ab_base;
   const float cw = (coef_w ? coef_w[b] : 1.f) * (gout ? gout[0] : 1.f);

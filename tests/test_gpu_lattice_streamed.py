@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 from oracle import recurrences as OR  # noqa: E402
 
 from test_gpu_configs import check, STATS, RTOL, _word_piece_setup  # noqa: E402,F401
+from lattice_workspace import tuned_workspace as _tuned_workspace  # noqa: E402
 from test_gpu_ngram import check_dparams, _oracle, _run  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,16 +55,6 @@ def _workspace(pack, T):
     n_xg, n_ab = ctypes.c_int64(), ctypes.c_int64()
     N.check(N.lib.wfl_lattice_workspace(pack._desc_ref, T, ctypes.byref(n_xg), ctypes.byref(n_ab)))
     return n_xg.value, n_ab.value
-
-
-def _tuned_workspace(d, T):
-    """wfl_lattice_workspace of the tuned sweeps, restated: xg rows | factors | references, and the alpha / beta
-    scores followed by offsets, Z, formats and the bookkeeping of the probability-domain launches"""
-    xg_main = (d.B * T * d.max_labels + 3) & ~3
-    nch1 = T + 1
-    tail = 2 * (d.B * (T + 1) * d.max_states if d.shared else (T + 1) * d.total_states)
-    ab = tail + 2 * (d.B * nch1 + d.B) + 2 * d.B + 2 + 2 * 1024 + 12 * d.B + 32 + 2048 + 4 + 16 + d.B * (T // 32 + 2)
-    return 2 * xg_main + d.B * T, ab
 
 
 @functools.lru_cache(maxsize=None)
