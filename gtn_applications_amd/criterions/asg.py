@@ -8,6 +8,7 @@ transitions tensor is the graph.
 """
 import ctypes
 import itertools
+import numbers
 import os
 
 import torch
@@ -326,6 +327,17 @@ def ASGLoss(*args):
     return E.make_eager(ASGLossFunction.apply(*args))
 
 
+def _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus):
+    """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default"""
+    if lm is not None:
+        raise ValueError(f"{what}: lm needs a lexicon (the lm of an ASG search is a word LM)")
+    for name, v, default in (("lm_weight", lm_weight, 1.0), ("length_bonus", length_bonus, 0.0), ("word_bonus", word_bonus, 0.0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or float(v) != default:  # (numpy's numbers are Real too)
+            raise ValueError(f"{what}: {name} needs a lexicon, got {v!r}")
+    if lm_eos is not True:
+        raise ValueError(f"{what}: lm_eos needs a lexicon, got {lm_eos!r}")
+
+
 class ASG(torch.nn.Module):
     def __init__(self, num_classes, num_replabels=1, use_garbage=True):
         super(ASG, self).__init__()
@@ -373,12 +385,71 @@ class ASG(torch.nn.Module):
             return E.decode_paths(paths, self.garbage_idx, self.num_replabels)
         return collapse_and_unpack(paths, self.garbage_idx, self.num_replabels)
 
-    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
-        """The arguments of a beam search, checked before anything needs a device: the E.AsgBeamPlan of the options"""
+    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest, lexicon=None, lm=None, lm_weight=1.0,
+                   length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+        """The arguments of a beam search, checked before anything needs a device: the E.AsgBeamPlan of the options, with
+        a lexicon the E.AsgLexiconBeamPlan; without one every keyword of the lexicon search must be at its default"""
         E.check_beam_outputs(outputs, what)
         if outputs.shape[2] != self.N:
             raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {self.N}")
-        return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)
+        if lexicon is None:
+            _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)
+        return E.AsgLexiconBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, self.garbage_idx, lexicon, lm,
+                                            lm_weight, word_bonus, length_bonus, lm_eos, what)
+
+    def lexicon(self, words, tokens, wordsep=None, split=None):
+        """The lexicon.Lexicon of `words` for beam_search(lexicon=): a trie over the RAW class
+        sequences the criterion trains on.  tokens: the model's num_classes tokens in class order (token i is raw class
+        i + num_replabels); a word is split into its characters, or by split(word) -> list of tokens; with `wordsep`
+        that token ends every spelling.  A spelling is pack_replabels(token indices, num_replabels): "aa|" with one
+        replabel is [a + 1, 0, sep + 1].  The garbage class is never spelled: the search treats it as transparent.  The
+        Lexicon is built for (N, garbage) where the module has a garbage class, else for (N + 1, N): a phantom class that
+        is never a label stands in for the blank a Lexicon wants.  ValueError names a word with a piece that is no token,
+        and two words where the last token of one equals the first token of the other: the criterion packs a target as a
+        whole, so that pair would be packed across the word boundary and no trie over single words spells it."""
+        tokens = list(tokens)
+        what = "ASG.lexicon"
+        if len(tokens) != self.num_classes:
+            raise ValueError(f"{what}: {len(tokens)} tokens for a criterion of {self.num_classes} classes")
+        if len(set(tokens)) != len(tokens):
+            raise ValueError(f"{what}: a token appears twice")
+        index = {tok: i for i, tok in enumerate(tokens)}
+        if wordsep is not None and wordsep not in index:
+            raise ValueError(f"{what}: the word separator {wordsep!r} is not one of the model's tokens")
+        words = list(words)
+        pieces_of = []
+        for w in words:
+            pieces = list(w) if split is None else list(split(w))
+            for p in pieces:
+                if p not in index:
+                    raise ValueError(f"{what}: {p!r} of {w!r} is not one of the model's tokens")
+            pieces = [index[p] for p in pieces] + ([index[wordsep]] if wordsep is not None else [])
+            if not pieces:
+                raise ValueError(f"{what}: {w!r} has an empty spelling")
+            pieces_of.append(pieces)
+        first = {}
+        for w, pieces in zip(words, pieces_of):
+            first.setdefault(pieces[0], w)
+        for w, pieces in zip(words, pieces_of):
+            if pieces[-1] in first:
+                raise ValueError(f"{what}: {w!r} ends in the token {tokens[pieces[-1]]!r} that {first[pieces[-1]]!r} starts "
+                                 f"with: replabels would pack the pair across the word boundary, which a lexicon of single "
+                                 f"words cannot spell; spellings that end in a separator (wordsep) no word starts with "
+                                 f"satisfy this by construction")
+        from ..lexicon import Lexicon
+
+        spellings = [pack_replabels(pieces, self.num_replabels) for pieces in pieces_of]
+        if self.garbage_idx is not None:
+            return Lexicon(spellings, self.N, self.garbage_idx, words=words)
+        return Lexicon(spellings, self.N + 1, self.N, words=words)
+
+    def words(self, lexicon, labels):
+        """The word ids of a label sequence that beam_search(lexicon=) returned (mapped: garbage dropped, replabels
+        unpacked): lexicon.words of the sequence packed again.  No word ends in a token a word starts with (lexicon()
+        checks that), so packing the whole sequence packs every word as the lexicon spells it."""
+        labels = labels.tolist() if hasattr(labels, "tolist") else list(labels)
+        return lexicon.words(pack_replabels([int(v) for v in labels], self.num_replabels))
 
     def _beam_inputs(self, outputs):
         """(emissions, transitions): float32, contiguous, on the emissions' GPU or the required one (no host path)"""
@@ -387,7 +458,8 @@ class ASG(torch.nn.Module):
                 E.as_device_f32(self.transitions.detach(), dev))
 
     @E.on_input_device
-    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False):
+    def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False, lexicon=None, lm=None,
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
         """ASG prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame path
         under emissions + transitions; the criterion scores a label sequence by the sum over all its alignments (the
         force-align numerator, asg.py:72-115), and this returns the sequences it rates highest (DESIGN.md section 21 has
@@ -401,8 +473,20 @@ class ASG(torch.nn.Module):
         once the garbage is dropped, so an n-best list may name an output twice, each time with the probability of
         that raw sequence alone.  return_scores: also a float64 CPU tensor [B, nbest] of log-probabilities under the
         criterion -- the raw sequence's log mass minus the denominator (asg.py:114): minus the ASG loss of that raw
-        sequence where the beam pruned none of its alignments, a lower bound of it otherwise --, -inf for an empty rank.  B == 0 or T == 0: empty sequences with score 0, no device needed."""
-        plan = self._beam_plan(outputs, "ASG.beam_search", beam_size, classes_per_frame, nbest)
+        sequence where the beam pruned none of its alignments, a lower bound of it otherwise --, -inf for an empty rank.  B == 0 or T == 0: empty sequences with score 0, no device needed.
+
+        lexicon (an addition): a lexicon.Lexicon built by self.lexicon() -- only sequences of its
+        words are returned, and lm (optional) is a word LM over its word ids (NGramLM.from_arpa(path, words,
+        blank=len(words))).  A raw class other than the garbage adds length_bonus, a completed word lm_weight * step(s,
+        word) + word_bonus on top, and lm_eos lm_weight * step(s, </s>) after the last frame; the scores include these
+        terms.  The garbage class is transparent: it may stand anywhere between the classes of a word.  The search and
+        the n-best list are still over raw sequences, and only the raw forms the criterion is trained on are returned: a
+        word spelled `a a` is found as raw `a, replabel 0`, never as raw `a, garbage, a`, which unpacks to the same
+        tokens but does not walk the trie.  Without a lexicon the call is what it was, and lm, lm_weight, length_bonus,
+        lm_eos and word_bonus must be at their defaults (ValueError).  B == 0 or T == 0 with a lexicon: the empty
+        sequence, scored by the LM's </s> alone."""
+        plan = self._beam_plan(outputs, "ASG.beam_search", beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight,
+                               length_bonus, lm_eos, word_bonus)
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0])
         else:
@@ -414,24 +498,31 @@ class ASG(torch.nn.Module):
         return (hyps, scores) if return_scores else hyps
 
     @E.on_input_device
-    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None):
+    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, lexicon=None, lm=None,
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
-        beam launches on their device buffers; `classes_per_frame` needs a beam_size."""
+        beam launches on their device buffers; `classes_per_frame` needs a beam_size.  lexicon, lm, lm_weight,
+        length_bonus, lm_eos, word_bonus: beam_search's, with a beam_size: the predictions are those of the search with
+        a lexicon."""
         if beam_size is None:
             if classes_per_frame is not None:
                 raise ValueError("ASG.errors: classes_per_frame needs a beam_size")
+            if lexicon is not None:
+                raise ValueError("ASG.errors: lexicon needs a beam_size")
+            _refuse_without_lexicon("ASG.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
         else:
-            plan = self._beam_plan(outputs, "ASG.errors", beam_size, classes_per_frame, 1)
+            plan = self._beam_plan(outputs, "ASG.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
+                                   length_bonus, lm_eos, word_bonus)
             counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
                 return counter([h[0] for h in plan.no_frames(outputs.shape[0])[0]], targets)
             x, W = self._beam_inputs(outputs)
+            count = M.asg_beam_search_errors if lexicon is None else M.asg_beam_search_lexicon_errors
             with torch.cuda.device(x.device), torch.no_grad():
-                return counter.totals(M.asg_beam_search_errors(counter, targets, x, W, plan, self.garbage_idx,
-                                                               self.num_replabels))
+                return counter.totals(count(counter, targets, x, W, plan, self.garbage_idx, self.num_replabels))
         counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
         with torch.no_grad():
             if not (outputs.is_cuda and outputs.shape[0] > 0):

@@ -38,7 +38,10 @@
 // wfl_transducer_beam_search_merged is that search with hypotheses identified by the graphemes they spell and their last
 // token: a sixth pack, BeamSpell, adds the spelling table of the classes; the token sequences
 // that spell the same graphemes share one hypothesis, their masses summed inside the beam launch.
-// All six issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_asg_beam_search_lexicon is the ASG search with the lexicon and word LM of the CTC one: a
+// seventh pack, BeamAsgLex, holds a BeamAsg, a BeamLex over raw class sequences and the garbage class, which the trie
+// does not see -- ASG's one mass and transition gather per entry, the lexicon's node and state per hypothesis.
+// All seven issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -308,6 +311,18 @@ __device__ __forceinline__ double beam_asg_w(const BeamAsg& a, int l, int c) {
   return w != w ? -__builtin_inf() : (double)w;
 }
 
+// the ASG launch with a lexicon (wfl_asg_beam_search_lexicon): BeamAsg's transitions and BeamLex's
+// trie, word LM and bonuses -- the trie over RAW class sequences (replabels included) --, and the garbage class, which
+// no spelling contains: an extension by it keeps node and state and costs no lookup (-1: the criterion has none)
+struct BeamAsgLex {
+  BeamAsg asg;
+  BeamLex lex;
+  int garbage;
+};
+__device__ __forceinline__ const BeamAsgLex& beam_asg_lex_of(const BeamAsgLex& a) { return a; }
+__device__ __forceinline__ const BeamAsg& beam_asg_of(const BeamAsgLex& a) { return a.asg; }
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamAsgLex& a) { return a.lex; }
+
 // the transitions of a Transducer launch (wfl_transducer_beam_search): Wt [(C+1), C] float32 in the dense engine's layout
 // (row 0 start -> c, row 1 + i: j -> i) or NULL (every weight 0), the denominator to subtract or NULL (the row
 // log-sum-exps, as in the plain search), and the topology of the token graph
@@ -367,6 +382,11 @@ template <>
 struct BeamPack<BeamAsg> {
   static constexpr bool lm = false, lex = false, asg = true, tok = false, spell = false;
 };
+// (asg and lex: ASG's single mass and transition gather, the lexicon's node / state arrays and final drop-and-rerank)
+template <>
+struct BeamPack<BeamAsgLex> {
+  static constexpr bool lm = false, lex = true, asg = true, tok = false, spell = false;
+};
 template <>
 struct BeamPack<BeamTok> {
   static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = false;
@@ -394,7 +414,9 @@ struct BeamPack<BeamSpell> {
 // sums the extensions of the members in rank order, and the parent class of a hypothesis is found by un-appending
 // the spelling of its last token from its hashes (the multipliers are odd: one multiplication by the inverse per
 // grapheme, once per hypothesis -- cheaper than extending every class by it); the result merges the ranks of one
-// spelling before it is ranked.
+// spelling before it is ranked; or one BeamAsgLex: the search of wfl_asg_beam_search_lexicon --
+// BeamAsg's arithmetic with BeamLex's node and state per hypothesis, term per extension and final drop-and-rerank; an
+// extension by the garbage class keeps node and state.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -558,16 +580,48 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         const BeamAsg& a = beam_asg_of(lm_arg...);
         const int p = lpos[tid], l = h.last[tid], i = par[tid];
         double m = p >= 0 ? (sc[p] + beam_asg_w(a, l, l)) + h.tot[tid] : ninf;
-        if (i >= 0) m = beam_lae(m, (sc[p] + beam_asg_w(a, h.last[i], l)) + h.tot[i]);  // (par[j] is set only where lpos[j] >= 0)
-        long long rk = beam_key(m);
-        spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = rk;
-        // The bound below wants one entry per hypothesis.  CTC's blank gives every hypothesis a stay; here a hypothesis
-        // whose last label is no candidate has none, and its first extension that is an entry of its own stands in
-        // (l is no candidate, so no candidate is l; a merged extension is part of another hypothesis' stay).
-        if (p < 0) {
-          const unsigned long long own = ~mmask[tid];
-          const int q = own ? __ffsll(own) - 1 : ncand;
-          if (q < ncand) rk = beam_key((sc[q] + beam_asg_w(a, l, cls[q])) + h.tot[tid]);
+        long long rk;
+        if constexpr (LEX) {
+          // With a lexicon one extension per hypothesis is looked up here: the one merged into this stay (p >= 0, i >= 0),
+          // which carries the term of the prefix it makes (node and state: functions of it), or -- where there is no
+          // stay (p < 0, and then i < 0: par is set only where lpos is) -- the own extension that stands in for the
+          // bound below.  The garbage is transparent to the trie: term 0, no lookup.
+          // The bound wants one entry per hypothesis that EXISTS (arc present, LM step finite): the garbage extension
+          // where the garbage is a candidate (no lookup), else the first own extension, looked up; absent, the
+          // hypothesis contributes kKeyDropped and the frame's bound prunes nothing.
+          const int garbage = beam_asg_lex_of(lm_arg...).garbage;
+          int src = i, c = l, q = p;
+          if (p < 0) {
+            const unsigned long long own = ~mmask[tid];
+            q = own ? __ffsll(own) - 1 : ncand;
+            for (int j = 0; j < ncand; ++j)
+              if (cls[j] == garbage && ((own >> j) & 1ull)) q = j;
+            if (q < ncand) src = tid, c = cls[q];
+          }
+          double e = ninf;
+          if (src >= 0) {
+            const double ac = (sc[q] + beam_asg_w(a, h.last[src], c)) + h.tot[src];
+            double term = 0.0;
+            int enc;
+            if (c != garbage)
+              term = ac > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][src], lmst[cur][src], c, enc) : ninf;
+            if (term > ninf) e = ac + term;
+          }
+          if (p >= 0) m = beam_lae(m, e);
+          rk = beam_key(p >= 0 ? m : e);
+          spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = beam_key(m);
+        } else {
+          if (i >= 0) m = beam_lae(m, (sc[p] + beam_asg_w(a, h.last[i], l)) + h.tot[i]);  // (par[j] is set only where lpos[j] >= 0)
+          rk = beam_key(m);
+          spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = rk;
+          // The bound below wants one entry per hypothesis.  CTC's blank gives every hypothesis a stay; here a hypothesis
+          // whose last label is no candidate has none, and its first extension that is an entry of its own stands in
+          // (l is no candidate, so no candidate is l; a merged extension is part of another hypothesis' stay).
+          if (p < 0) {
+            const unsigned long long own = ~mmask[tid];
+            const int q = own ? __ffsll(own) - 1 : ncand;
+            if (q < ncand) rk = beam_key((sc[q] + beam_asg_w(a, l, cls[q])) + h.tot[tid]);
+          }
         }
         wkey[tid] = rk;  // (wkey: free until the selection)
       }
@@ -657,7 +711,27 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         idx = kBeamMax + i * kBeamCand + p;
         if (c == blank || ((mmask[i] >> p) & 1ull))
           k = kKeyDropped;
-        else if constexpr (LM) {
+        else if constexpr (ASG && LEX) {
+          // ASG's extension (one mass, the transition gathered here) with the lexicon's term: the garbage keeps node and
+          // state (enc = the node: >= 0, the state stays) and is not looked up; a trie extension is the lexicon
+          // search's, its skip test included (the garbage has term 0: nothing to skip)
+          const BeamLex& lx = beam_lex_of(lm_arg...);
+          const int l = h.last[i];
+          int enc = 0;
+          if (c == l)
+            k = kKeyDropped;  // (i's stay, not an extension)
+          else {
+            const double ac = (sc[p] + beam_asg_w(beam_asg_of(lm_arg...), l, c)) + h.tot[i];
+            if (c == beam_asg_lex_of(lm_arg...).garbage) {
+              k = beam_key(ac), enc = tnode[cur][i];
+            } else {
+              const bool reach = ac > ninf && beam_key(ac + lx.bound) >= tau;
+              const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+              k = term > ninf ? beam_key(ac + term) : kKeyDropped;
+            }
+          }
+          enext[idx] = enc;
+        } else if constexpr (LM) {
           const BeamLm& lm = beam_lm_of(lm_arg...);
           const double ac = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);  // the extension without its LM term
           int nx = 0;
@@ -752,7 +826,9 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         if constexpr (LM)
           e = beam_key_total(k), lmst[cur ^ 1][r] = enext[idx];  // (the total with its LM term: the key holds it)
         else if constexpr (LEX) {
-          const int enc = enext[idx];  // (inside a word: the node, the parent's state; behind one: the root, a new state)
+          // (inside a word: the node, the parent's state; behind one: the root, a new state; ASG's garbage: the
+          // parent's node as enc, so both stay -- and the total with its transition weight is in the key there too)
+          const int enc = enext[idx];
           e = beam_key_total(k);
           tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
         } else if constexpr (ASG || TOK)
@@ -1503,6 +1579,44 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, i
   d.lm.bound = d.bound;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
+}
+
+// The ASG search with a lexicon and an optional word LM: wfl_asg_beam_search's call and checks,
+// wfl_ctc_beam_search_lexicon's checks of the lexicon, the LM and the three constants, and the garbage class.
+int wfl_asg_beam_search_lexicon(const float* x, const float* Wt, const float* logz, int B, int T, int C, int beam,
+                                int classes_per_frame, int nbest, int drop, int num_replabels, int garbage, const wfl_lexicon* lex,
+                                const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
+                                int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, double* scores,
+                                void* stream) {
+  const char* what = "asg_beam_search_lexicon";
+  if (!Wt) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  const BeamCall c{x, nullptr, B, T, C, -1, beam, classes_per_frame, nbest, logz ? 1 : 0, ws, out, out_capacity, out_offsets,
+                   scores, stream, false, true, drop, num_replabels};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (garbage < -1 || garbage >= C) {
+    set_error("%s: garbage %d is outside [-1, %d)", what, garbage, C);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  BeamAsgLex d;
+  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
+  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lex.lm)) return rc;
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  d.asg = BeamAsg{Wt, logz, C};
+  d.lex.arc_ptr = lex->arc_ptr, d.lex.arc_label = lex->arc_label, d.lex.arc_next = lex->arc_next;
+  d.lex.has_lm = word_lm ? 1 : 0;
+  d.lex.omega = word_bonus;
+  d.lex.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
+  d.lex.lm.bound = d.lex.bound;
+  d.garbage = garbage;
+  return beam_run(what, c, d);
 }
 
 }  // extern "C"

@@ -1081,6 +1081,45 @@ Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10:
           }};
 }
 
+// The options of the ASG search with a lexicon as both of its ops take them (engine.AsgLexiconBeamPlan.on_device binds
+// the values it has checked): asg_beam_source's, the garbage class (-1: none), and the lexicon, word LM (or none) and
+// constants of the CTC lexicon search.
+struct AsgLexiconPlan {
+  int beam, K, nbest, garbage;
+  std::shared_ptr<DeviceLexicon> lexicon;
+  std::shared_ptr<DeviceLm> lm;
+  double lm_weight, word_bonus, length_bonus;
+  bool score_eos;
+  AsgLexiconPlan(int beam_, int K_, int nbest_, int garbage_, const std::shared_ptr<DeviceLexicon>& lexicon_,
+                 const std::shared_ptr<DeviceLm>& lm_, double lm_weight_, double word_bonus_, double length_bonus_,
+                 bool score_eos_)
+      : beam(beam_), K(K_), nbest(nbest_), garbage(garbage_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
+        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_) {
+    TORCH_CHECK(lexicon, "asg_beam_search_lexicon: a lexicon is needed");
+    TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
+                "asg_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
+  }
+};
+
+// The ASG search with a lexicon (wfl_asg_beam_search_lexicon): asg_beam_source with the plan above.
+Hypotheses asg_lexicon_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz,
+                                   const AsgLexiconPlan& p, int nbest, int64_t drop, int64_t num_replabels) {
+  const char* what = "asg_beam_search_lexicon";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  TORCH_CHECK(W.defined(), what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+  TORCH_CHECK(p.lexicon->ints.device() == x.device(), what, ": the lexicon's arrays must be on x's device");
+  const int R = (int)num_replabels;
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_asg_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, R, cap, bytes), what); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            check(wfl_asg_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.beam, p.K, nbest, (int)drop,
+                                              R, p.garbage, &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
+                                              p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                  what);
+          }};
+}
+
 // The Transducer prefix beam search (wfl_transducer_beam_search): the options are
 // engine.TransducerBeamPlan's, already checked.  Wt: float32 [C + 1, C] on x's device or none (every weight 0); logz:
 // float32 [B] on x's device (wfl_dense_forward's denominator, with Wt and normalize) or none.
@@ -1335,6 +1374,20 @@ at::Tensor asg_beam_search_errors(const at::Tensor& x, const at::Tensor& Wt, int
 }
 
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple asg_beam_search_lexicon(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz,
+                                  const AsgLexiconPlan& plan, int64_t drop, int64_t num_replabels) {
+  const Collected r = hypotheses_collect(asg_lexicon_beam_source(x, Wt, logz, plan, plan.nbest, drop, num_replabels), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+}
+
+// (the plan's first rank, unnormalised: nothing reads the scores)
+at::Tensor asg_beam_search_lexicon_errors(const at::Tensor& x, const at::Tensor& Wt, const AsgLexiconPlan& plan, int64_t drop,
+                                          int64_t num_replabels, const std::shared_ptr<StagedTargets>& ref,
+                                          const ErrorTables& tables) {
+  return hypotheses_errors(asg_lexicon_beam_source(x, Wt, c10::nullopt, plan, 1, drop, num_replabels), ref, tables);
+}
+
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
                                  int blank, bool forced, int beam, int K, int nbest, bool normalize) {
   const Collected r = hypotheses_collect(transducer_beam_source(x, Wt, logz, blank, forced, beam, K, nbest, normalize), true);
@@ -1404,6 +1457,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("asg_beam_search_errors", &asg_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
         "asg_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  py::class_<AsgLexiconPlan>(m, "AsgLexiconPlan",
+                             "the options of one ASG beam search with a lexicon, bound (engine.AsgLexiconBeamPlan.on_device)")
+      .def(py::init<int, int, int, int, const std::shared_ptr<DeviceLexicon>&, const std::shared_ptr<DeviceLm>&, double, double,
+                    double, bool>(),
+           py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("garbage"), py::arg("lexicon"), py::arg("lm"),
+           py::arg("lm_weight"), py::arg("word_bonus"), py::arg("length_bonus"), py::arg("score_eos"),
+           "the garbage class (-1: none), a lexicon over raw class sequences (DeviceLexicon), its word LM (DeviceLm) or None, "
+           "and the constants of the CTC lexicon search");
+  m.def("asg_beam_search_lexicon", &asg_beam_search_lexicon, py::arg("x"), py::arg("transitions"), py::arg("logz"),
+        py::arg("plan"), py::arg("drop"), py::arg("num_replabels"),
+        "ASG prefix beam search with a lexicon on the device by an AsgLexiconPlan: (labels int64 CPU, offsets int64 CPU "
+        "[B nbest + 1], scores float64 CPU [B, nbest]); logz float32 [B] (normalised scores) or None");
+  m.def("asg_beam_search_lexicon_errors", &asg_beam_search_lexicon_errors, py::arg("x"), py::arg("transitions"), py::arg("plan"),
+        py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
+        "asg_beam_search_lexicon's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("transducer_beam_search", &transducer_beam_search, py::arg("x"), py::arg("transitions"), py::arg("logz"),
         py::arg("blank"), py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
         "Transducer prefix beam search on the device (engine.TransducerBeamPlan's options): (labels int64 CPU, offsets int64 "

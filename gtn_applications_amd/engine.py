@@ -1156,6 +1156,118 @@ def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normal
     return plan.search(x, Wt, normalize, drop, num_replabels)
 
 
+class AsgLexiconBeamPlan(namedtuple(
+        "AsgLexiconBeamPlan", "C beam classes_per_frame nbest garbage lexicon lm lm_weight word_bonus length_bonus lm_eos")):
+    """The options of one ASG beam search with a lexicon (wfl_asg_beam_search_lexicon) over C raw
+    classes (tokens + replabels + garbage), checked once (`checked`, the one constructor) and handed on whole:
+    AsgBeamPlan's four ints, the garbage class (None: the criterion has none), a lexicon.Lexicon over raw class
+    sequences (ASG.lexicon builds one), its word LM (an lm.NGramLM by the convention of lexicon.py) or None, and the
+    constants of the CTC lexicon search.  Only on_device(), search() and errors need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, beam_size, classes_per_frame, nbest, garbage, lexicon, lm, lm_weight, word_bonus, length_bonus, lm_eos,
+                what):
+        """The plan of these arguments, within the limits of wfl_asg_beam_search_lexicon, or ValueError (`what`: the call
+        they were given to): what AsgBeamPlan.checked refuses; a garbage outside [0, C); a lexicon that is none or was not
+        built for (C, garbage) -- with a garbage class -- or (C + 1, C) -- without one: a phantom blank that is never a
+        label --; an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an lm; a
+        number that is not finite."""
+        from .lexicon import Lexicon, check_word_lm
+        from .lm import NGramLM
+
+        def finite(v, name):
+            f = math.nan
+            if not isinstance(v, (bool, np.bool_, str, bytes)):
+                try:
+                    f = float(v)
+                except (TypeError, ValueError):
+                    pass
+            if not math.isfinite(f):
+                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+            return f
+
+        C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
+        if garbage is not None:
+            g = beam_integer(garbage)
+            if g is None or not 0 <= g < C:
+                raise ValueError(f"{what}: the garbage class {garbage!r} is outside [0, {C})")
+            garbage = g
+        if not isinstance(lexicon, Lexicon):
+            raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
+        want = (C, garbage) if garbage is not None else (C + 1, C)
+        if (lexicon.num_classes, lexicon.blank) != want:
+            raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}; "
+                             f"for {C} raw classes " + (f"with the garbage class {garbage}" if garbage is not None else
+                                                        "without a garbage class") +
+                             f" it must have {want[0]} with blank {want[1]} (ASG.lexicon builds it)")
+        weight, omega, bonus = finite(lm_weight, "lm_weight"), finite(word_bonus, "word_bonus"), finite(length_bonus, "length_bonus")
+        if not isinstance(lm_eos, (bool, np.bool_)):
+            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+        lm_eos = bool(lm_eos)
+        if lm is None:
+            if weight != 1.0 or lm_eos is not True:
+                raise ValueError(f"{what}: lm_weight and lm_eos need an lm")
+        elif not isinstance(lm, NGramLM):
+            raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
+        else:
+            check_word_lm(lexicon, lm, what)
+        return cls(C, W, K, n, garbage, lexicon, lm, weight, omega, bonus, lm_eos)
+
+    def no_frames(self, B):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
+        BeamPlan.no_frames: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
+        hyps, scores = beam_no_frames(B, self.nbest)
+        end = 0.0
+        if self.lm is not None and self.lm_eos:
+            step = self.lm.score([], eos=True)
+            end = -math.inf if step == -math.inf else self.lm_weight * step
+        scores[:, 1:] = -math.inf
+        scores[:, 0] = end
+        return hyps, scores
+
+    def on_device(self, device):
+        """The plan as the operators take it (ops.AsgLexiconPlan, csrc/torch_ops.cpp), its lexicon and lm on `device`"""
+        return N.ops.AsgLexiconPlan(beam=self.beam, classes_per_frame=self.classes_per_frame, nbest=self.nbest,
+                                    garbage=-1 if self.garbage is None else self.garbage,
+                                    lexicon=self.lexicon.on_device(device),
+                                    lm=None if self.lm is None else self.lm.on_device(device), lm_weight=self.lm_weight,
+                                    word_bonus=self.word_bonus, length_bonus=self.length_bonus, score_eos=self.lm_eos)
+
+    def search(self, x, W, normalize=True, drop=None, num_replabels=0):
+        """asg_beam_search_lexicon's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
+        [C + 1, C] on x's device, contiguous"""
+        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+            logz = dense_forward(x, W, need_beta=False).logz if normalize else None
+            flat, offsets, scores = N.ops.asg_beam_search_lexicon(x, W, logz, self.on_device(x.device),
+                                                                  -1 if drop is None else int(drop), int(num_replabels))
+        return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
+
+
+def asg_beam_search_lexicon(x, Wt, lexicon, garbage=None, beam_size=16, classes_per_frame=None, nbest=1, normalize=True,
+                            drop=None, num_replabels=0, lm=None, lm_weight=1.0, word_bonus=0.0, length_bonus=0.0, lm_eos=True):
+    """asg_beam_search with a lexicon and an optional word LM (wfl_asg_beam_search_lexicon through csrc/torch_ops.cpp; the
+    rules: include/wfl.h).  x, Wt, drop, num_replabels and the result: asg_beam_search's.  lexicon: a
+    lexicon.Lexicon over RAW class sequences (replabels packed in, the garbage never spelled; ASG.lexicon builds one) for
+    (C, garbage), or for (C + 1, C) where garbage is None; garbage: the class that is transparent to the trie.  Only
+    sequences of the lexicon's words are returned, garbage anywhere between their classes; lm (if given) is the word LM
+    over its word ids; a class other than the garbage adds length_bonus and a completed word lm_weight * step(s, word) +
+    word_bonus on top; lm_eos adds lm_weight * step(s, </s>) after the last frame.  The scores include these terms.  The
+    options are one AsgLexiconBeamPlan."""
+    what = "asg_beam_search_lexicon"
+    plan = AsgLexiconBeamPlan.checked(x.shape[2], beam_size, classes_per_frame, nbest, garbage, lexicon, lm, lm_weight,
+                                      word_bonus, length_bonus, lm_eos, what)
+    if tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if not isinstance(num_replabels, int) or isinstance(num_replabels, bool) or num_replabels < 0:
+        raise ValueError(f"{what}: num_replabels must be an integer >= 0, got {num_replabels!r}")
+    if drop is not None and not -1 <= int(drop) < plan.C:
+        raise ValueError(f"{what}: drop {drop} is outside [0, {plan.C})")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return plan.no_frames(x.shape[0])
+    return plan.search(x, Wt, normalize, drop, num_replabels)
+
+
 class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam classes_per_frame nbest")):
     """The options of one Transducer beam search over C classes (tokens + the blank), checked once (`checked`, the one
     constructor) and handed on whole, as BeamPlan is for CTC and AsgBeamPlan for ASG: Transducer.beam_search,

@@ -147,6 +147,13 @@ def asg_beam_search_errors(counter, targets, x, W, plan, drop, num_replabels):
     return N.ops.asg_beam_search_errors(x, W, plan.beam, plan.classes_per_frame, drop, num_replabels, ref, tables)
 
 
+def asg_beam_search_lexicon_errors(counter, targets, x, W, plan, drop, num_replabels):
+    """asg_beam_search_errors for the search with a lexicon (`plan`: a checked engine.AsgLexiconBeamPlan): the launches
+    of its search() and the counts behind them"""
+    ref, tables, drop = _staged(counter, targets, x, drop)
+    return N.ops.asg_beam_search_lexicon_errors(x, W, plan.on_device(x.device), drop, num_replabels, ref, tables)
+
+
 def transducer_beam_search_errors(counter, targets, x, Wt, plan):
     """The launches of engine.TransducerBeamPlan.search (`plan`: checked; its best hypothesis only; Wt: the transitions
     or None) and the counts behind them, on x's device: [B, 4] int64 on the host and nothing else"""

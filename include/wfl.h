@@ -757,6 +757,61 @@ int wfl_asg_beam_search(const float* x, const float* Wt /* [(C+1), C] */, const 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The ASG search with a lexicon and an optional word-level n-gram LM (csrc/beam_kernels.hip).
+ *   Every rule of wfl_asg_beam_search stands.  a = lm_weight, o = word_bonus, b = length_bonus, all finite float64 (the
+ *   names of wfl_ctc_beam_search_lexicon); R = num_replabels; C = the classes of x (tokens + R + the garbage, if any).
+ *     1. raw classes: replabel k is class k (k < R), token i is class i + R, the garbage class -- if the criterion has
+ *        one -- is `garbage` = tokens + R (-1: none).  The lexicon is a wfl_lexicon over RAW class sequences: a word's
+ *        spelling is its token sequence (separator token included, if there is one) packed as the criterion packs its
+ *        targets (asg.py:13-32), so "aa|" with R = 1 is [a + R, 0, sep + R].  A spelling never contains the garbage;
+ *     2. every hypothesis carries a trie node and, with a word LM, an LM state; the empty prefix has the root and the
+ *        LM's `start`.  Both are functions of the raw prefix, so merging by prefix identity (rule 5 of the ASG search)
+ *        stays exact, and a merged extension carries the same term as a new one;
+ *     3. the extension of hypothesis i (last label l, the start for the empty prefix) by candidate c != l, with
+ *        ac = (s + Wt[1+c][l]) + p_i as in rule 4 of the ASG search: c == garbage -- the garbage is transparent: e = ac,
+ *        node and state stay, nothing is looked up and nothing is added.  Otherwise c is searched among the arcs of
+ *        node_i (a binary search, at most 31 steps).  Absent: the extension does not exist.  An inner arc: e = ac + b,
+ *        the node becomes the arc's target, the state stays.  An arc that completes word v: (l, nxt) = step(state_i, v),
+ *        (0, -) without an LM; l = -inf: the extension does not exist; otherwise e = ac + ((a l + o) + b), each
+ *        operation rounded on its own, the new node is the root and the new state nxt.  An extension with ac = -inf does
+ *        not exist and is not looked up;
+ *     4. stays add nothing and keep node and state, for the garbage as for any other class; candidates (by emission
+ *        score alone), the order of entries, the tie rule and the -inf drop rule are the ASG search's;
+ *     5. after the last frame (rule 5 of wfl_ctc_beam_search_lexicon) a rank whose node is not the root is dropped; with
+ *        score_eos != 0 and an LM a remaining rank gets + a step(state, V + 1) and is dropped if that step is -inf; the
+ *        remaining ranks are ranked again by score, descending, ties to the earlier rank; nbest is taken after that;
+ *        nothing left: the empty sequence with score -inf;
+ *     6. where nothing is pruned, score(l) = mass_ASG(l) + a LM(words(l)) + o #words + b #(classes of l other than the
+ *        garbage), plus the </s> term; logz[b] is subtracted if logz is given;
+ *     7. the labels are mapped on the way out as in wfl_asg_beam_search (drop, num_replabels).  The search and the
+ *        n-best list are over raw sequences: a word spelled `a a` is found as raw `a, r0` only -- raw `a, garbage, a`
+ *        unpacks to the same tokens but does not walk the trie, which holds the packed form the criterion trains on.
+ *   The bound.  The kernel ranks only the entries at or above a lower bound of the W-th best entry, formed from one entry
+ *   per hypothesis of a full beam: its stay, or -- where its last label is no candidate -- an extension of its own, which
+ *   may serve only if it EXISTS (arc present, LM step finite): the garbage extension where the garbage is a candidate,
+ *   else the first own extension, looked up; if that is absent the hypothesis contributes nothing and the frame's bound
+ *   is -inf.  The lookup of a trie extension that cannot reach the bound even with the largest term (that of
+ *   wfl_ctc_beam_search_lexicon) is skipped; garbage extensions have term 0.  The bound decides what is ranked, never
+ *   the result.
+ *   lex, word_lm: structs in HOST memory of DEVICE pointers, as for wfl_ctc_beam_search_lexicon; lex passed
+ *   wfl_lexicon_check for (C, garbage) with a garbage class, for (C + 1, C) without one (a phantom blank that is never a
+ *   label); word_lm passed wfl_ngram_lm_check for V + 1 and V.  The kernels trust them.  The same workspace
+ *   (wfl_asg_beam_workspace), outputs, launches (three, four with a mapping) and guarantees as wfl_asg_beam_search: no
+ *   allocation, no synchronisation, no global atomics, no cross-workgroup waits, every loop bounded by T, W, K, the
+ *   back-off cap or 31 search steps.
+ *   WFL_ERR_INVALID: what wfl_asg_beam_search refuses; garbage outside [-1, C); lex or one of its arrays NULL, num_nodes,
+ *   num_arcs or num_words < 1 (or num_words = 2^31 - 1); a weight or bonus that is not finite; for a non-NULL word_lm
+ *   what wfl_ctc_beam_search_lm refuses.  Not here: a token-level LM, LM look-ahead inside words, several spellings of
+ *   one word, out-of-vocabulary arcs, input lengths.
+ * ------------------------------------------------------------------------------------------------ */
+int wfl_asg_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] */, const float* logz /* [B] or NULL */, int B,
+                                int T, int C, int beam, int classes_per_frame, int nbest, int drop, int num_replabels,
+                                int garbage /* -1: none */, const wfl_lexicon* lex, const wfl_ngram_lm* word_lm /* or NULL */,
+                                double lm_weight, double word_bonus, double length_bonus, int score_eos, void* ws,
+                                int32_t* out, int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: Transducer prefix beam search (csrc/beam_kernels.hip)
  *   wfl_dense_viterbi gives the best FRAME PATH of the Transducer criterion; the criterion scores a TOKEN SEQUENCE by the
  *   sum over all its alignments under a token graph with a blank and a frame-level transition model over tokens + blank.
