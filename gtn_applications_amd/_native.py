@@ -219,6 +219,9 @@ _SIGS = {
     "wfl_transducer_beam_search": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
                                            c_int64, _P, _P, _P]),
     "wfl_spelling_check": (c_int, [_P, _P, c_int, c_int]),
+    "wfl_transducer_beam_search_lexicon": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                   POINTER(Lexicon), POINTER(NgramLm), c_double, c_double, c_double, c_int, _P,
+                                                   _P, c_int64, _P, _P, _P]),
     "wfl_transducer_beam_search_merged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path

@@ -10,6 +10,7 @@ transducer.py:265-281) runs in the C++ host library; everything that touches the
 import collections
 import ctypes
 import itertools
+import numbers
 import os
 import threading
 
@@ -238,6 +239,17 @@ def _alignment_graph(target, tokens, lexicon, transitions, direct=False):
 _DENSE_NGRAM = os.environ.get("WFL_DENSE_NGRAM", "1") != "0"
 
 
+def _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus):
+    """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default"""
+    if lm is not None:
+        raise ValueError(f"{what}: lm needs a lexicon (the lm of a Transducer search is a word LM)")
+    for name, v, default in (("lm_weight", lm_weight, 1.0), ("length_bonus", length_bonus, 0.0), ("word_bonus", word_bonus, 0.0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or float(v) != default:  # (numpy's numbers are Real too)
+            raise ValueError(f"{what}: {name} needs a lexicon, got {v!r}")
+    if lm_eos is not True:
+        raise ValueError(f"{what}: lm_eos needs a lexicon, got {lm_eos!r}")
+
+
 class Transducer(torch.nn.Module):
     """A generic transducer loss (transducer.py:126-234).
 
@@ -260,6 +272,9 @@ class Transducer(torch.nn.Module):
         # (plain attributes, no buffers: the state_dict is what it was)
         self.token_spellings = [tuple(graphemes_to_idx[g] for g in wp) for wp in tokens]
         self._spelling_table = None
+        # the tokens as tuples of their elements: what word_lexicon() compares the pieces of a word against (plain too)
+        self._token_pieces = [tuple(wp) for wp in tokens]
+        self._has_blank = blank != "none"
         self.ngram = ngram
         if ngram > 0 and transitions is not None:
             raise ValueError("Only one of ngram and transitions may be specified")
@@ -368,9 +383,11 @@ class Transducer(torch.nn.Module):
         flat = torch.from_numpy(out)  # (int32: torch.IntTensor, as transducer.py:233)
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
 
-    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest):
+    def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest, lexicon=None, lm=None, lm_weight=1.0,
+                   length_bonus=0.0, lm_eos=True, word_bonus=0.0):
         """The arguments of a beam search, checked before anything needs a device: (the E.TransducerBeamPlan of the
-        options, the transition model's kind: "none", "unigram" or "bigram")"""
+        options -- with a lexicon the E.TransducerLexiconBeamPlan; without one every keyword of the lexicon search must
+        be at its default --, the transition model's kind: "none", "unigram" or "bigram")"""
         E.check_beam_outputs(outputs, what)
         self.tokens.arc_sort()
         n = ctypes.c_int()
@@ -390,8 +407,54 @@ class Transducer(torch.nn.Module):
             if kind == "general":
                 raise NotImplementedError(f"{what}: the transition model is neither make_transitions_graph(1, C) nor "
                                           "(2, C): only no model, the unigram and the bigram model are searched")
-        plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
+        if lexicon is None:
+            _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
+        else:
+            plan = E.TransducerLexiconBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest,
+                                                       lexicon, lm, lm_weight, word_bonus, length_bonus, lm_eos, what)
         return plan, kind
+
+    def word_lexicon(self, words, wordsep=None, split=None):
+        """The lexicon.Lexicon of `words` for beam_search(lexicon=): a trie over sequences of the
+        module's own tokens, for (n_tokens + 1, n_tokens) -- the emission classes and the blank of a token graph with a
+        blank, which the module must have.  A word is split into its characters, or by split(word) into pieces; each
+        piece must be one of the module's tokens, compared as tuple(piece) against tuple(token); with `wordsep` that
+        token ends every spelling.  split= fixes ONE decomposition per word: the other decompositions of the same
+        graphemes into word pieces are not in the trie.  ValueError names a word and its piece that is no token.
+        (`Transducer.lexicon` is the criterion's token-to-grapheme graph, hence the name.)"""
+        what = "Transducer.word_lexicon"
+        if not self._has_blank:
+            raise ValueError(f'{what}: blank="none" has no class for the blank a Lexicon is built around, and no beam search')
+        index = {}
+        for i, tok in enumerate(self._token_pieces):
+            index.setdefault(tok, i)
+        sep = None
+        if wordsep is not None:
+            sep = index.get(tuple(wordsep))
+            if sep is None:
+                raise ValueError(f"{what}: the word separator {wordsep!r} is not one of the module's tokens")
+        words = list(words)
+        spellings = []
+        for w in words:
+            pieces = list(w) if split is None else list(split(w))
+            ids = []
+            for piece in pieces:
+                i = index.get(tuple(piece))
+                if i is None:
+                    raise ValueError(f"{what}: {piece!r} of {w!r} is not one of the module's tokens")
+                ids.append(i)
+            spellings.append(ids + ([sep] if sep is not None else []))
+        from ..lexicon import Lexicon
+
+        n = len(self._token_pieces)
+        return Lexicon(spellings, n + 1, n, words=words)
+
+    @staticmethod
+    def words(lexicon, labels):
+        """The word ids of a token sequence that beam_search(lexicon=) returned: lexicon.words(labels)"""
+        labels = labels.tolist() if hasattr(labels, "tolist") else list(labels)
+        return lexicon.words([int(v) for v in labels])
 
     def _spelling(self, plan, what):
         """The E.Spelling of the plan's classes (the tokens' spellings, the blank's none), checked once and kept: ValueError
@@ -409,9 +472,14 @@ class Transducer(torch.nn.Module):
         return held[1]
 
     @staticmethod
-    def _merge_flag(merge_spellings, what):
+    def _merge_flag(merge_spellings, what, lexicon=None):
         if not isinstance(merge_spellings, (bool, np.bool_)):
             raise ValueError(f"{what}: merge_spellings must be True or False, got {merge_spellings!r}")
+        if merge_spellings and lexicon is not None:
+            raise NotImplementedError(
+                f"{what}: merge_spellings=True with a lexicon -- the merged search identifies a hypothesis by the graphemes "
+                "it spells, so one hypothesis stands for several token prefixes, while the trie node (and with it the LM "
+                "state) is a function of the token prefix: the members of a merged hypothesis stand at different nodes")
         return bool(merge_spellings)
 
     def _beam_inputs(self, outputs, kind):
@@ -429,7 +497,7 @@ class Transducer(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False,
-                    merge_spellings=False):
+                    merge_spellings=False, lexicon=None, lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
         """Transducer prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame
         path; the criterion scores a token sequence by the sum over all its alignments, and this returns the token
         sequences it rates highest (DESIGN.md section 22 has the rules; csrc/beam_kernels.hip runs them, in float64).
@@ -451,10 +519,22 @@ class Transducer(torch.nn.Module):
         normaliser -- minus the criterion's loss of that grapheme target where nothing was pruned, a lower bound
         otherwise, and never below the score of any single decomposition.  No two ranks spell the same graphemes.  The
         return types do not change.  A token that spells nothing, or more than 64 graphemes, raises ValueError.
-        B == 0 or T == 0: empty sequences with score 0, no device needed.  No lexicon, LM or input lengths."""
+        B == 0 or T == 0: empty sequences with score 0, no device needed.
+        lexicon: a lexicon.Lexicon built by self.word_lexicon() -- only sequences of its words are
+        returned (every result is a whole number of words; self.words(lexicon, labels) names them), and lm (optional) is
+        a word LM over its word ids (NGramLM.from_arpa(path, words, blank=len(words))).  A token adds length_bonus, a
+        completed word lm_weight * step(s, word) + word_bonus on top, and lm_eos lm_weight * step(s, </s>) after the last
+        frame; the scores include these terms.  With word pieces a lexicon built with split= fixes one decomposition per
+        word: the score is the kept mass of that token sequence's alignments, a lower bound of minus the loss as
+        without a lexicon, and the criterion's other decompositions of the same graphemes are not searched.  A lexicon
+        with merge_spellings=True raises NotImplementedError.  Without a lexicon the call is what it was, and lm,
+        lm_weight, length_bonus, lm_eos and word_bonus must be at their defaults (ValueError).  B == 0 or T == 0 with a
+        lexicon: the empty sequence, scored by the LM's </s> alone.  No token-level LM, LM look-ahead, several spellings
+        per word or input lengths."""
         what = "Transducer.beam_search"
-        plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest)
-        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what) else None
+        plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, length_bonus,
+                                     lm_eos, word_bonus)
+        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what, lexicon) else None
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
         else:
@@ -469,19 +549,25 @@ class Transducer(torch.nn.Module):
         return (hyps, scores) if return_scores else hyps
 
     @E.on_input_device
-    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, merge_spellings=False):
+    def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, merge_spellings=False, lexicon=None,
+               lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
         beam launches on their device buffers; `classes_per_frame` and `merge_spellings` (beam_search's: the predictions
-        are the representatives of the best spellings) need a beam_size."""
-        merge = self._merge_flag(merge_spellings, "Transducer.errors")
+        are the representatives of the best spellings) need a beam_size.  lexicon, lm, lm_weight, length_bonus, lm_eos,
+        word_bonus: beam_search's, with a beam_size: the predictions are those of the search with a lexicon."""
+        merge = self._merge_flag(merge_spellings, "Transducer.errors", lexicon)
         if beam_size is None:
             if classes_per_frame is not None or merge:
                 raise ValueError("Transducer.errors: classes_per_frame and merge_spellings need a beam_size")
+            if lexicon is not None:
+                raise ValueError("Transducer.errors: lexicon needs a beam_size")
+            _refuse_without_lexicon("Transducer.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
         else:
-            plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1)
+            plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
+                                         length_bonus, lm_eos, word_bonus)
             spelling = self._spelling(plan, "Transducer.errors") if merge else None
             counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
@@ -490,6 +576,8 @@ class Transducer(torch.nn.Module):
             with torch.cuda.device(x.device), torch.no_grad():
                 if merge:
                     return counter.totals(M.transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling))
+                if lexicon is not None:
+                    return counter.totals(M.transducer_beam_search_lexicon_errors(counter, targets, x, Wt, plan))
                 return counter.totals(M.transducer_beam_search_errors(counter, targets, x, Wt, plan))
         C = outputs.shape[2]
         dplan = self._device_decode(C)

@@ -41,7 +41,10 @@
 // wfl_asg_beam_search_lexicon is the ASG search with the lexicon and word LM of the CTC one: a
 // seventh pack, BeamAsgLex, holds a BeamAsg, a BeamLex over raw class sequences and the garbage class, which the trie
 // does not see -- ASG's one mass and transition gather per entry, the lexicon's node and state per hypothesis.
-// All seven issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_transducer_beam_search_lexicon is the Transducer search with that lexicon and word LM: an
+// eighth pack, BeamTokLex, holds a BeamTok and a BeamLex -- the Transducer's two masses and transition gathers per
+// entry, the lexicon's node and state per hypothesis.
+// All eight issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -347,6 +350,15 @@ __device__ __forceinline__ double beam_tok_ext(const BeamTok& a, double pb, doub
   return s + m;
 }
 
+// the Transducer launch with a lexicon (wfl_transducer_beam_search_lexicon): BeamTok's transitions
+// and topology, BeamLex's trie over token sequences, word LM and bonuses
+struct BeamTokLex {
+  BeamTok tok;
+  BeamLex lex;
+};
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamTokLex& a) { return a.tok; }
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamTokLex& a) { return a.lex; }
+
 // the Transducer launch that merges by spelling (wfl_transducer_beam_search_merged): BeamTok's
 // fields and the spelling table over the C classes -- class c spells the graphemes spell_sym[spell_ptr[c] ..
 // spell_ptr[c + 1]), none for the blank, 1 .. WFL_SPELL_MAX for every other class (wfl_spelling_check)
@@ -391,7 +403,13 @@ template <>
 struct BeamPack<BeamTok> {
   static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = false;
 };
-// (tok: what the two Transducer searches share -- the normaliser, the frame's log-sum-exp, the forced topology's result)
+// (tok and lex: the Transducer's two masses and transition gathers, the lexicon's node / state arrays, term per
+// extension and final drop, ahead of the ranking the Transducer's result shares with it)
+template <>
+struct BeamPack<BeamTokLex> {
+  static constexpr bool lm = false, lex = true, asg = false, tok = true, spell = false;
+};
+// (tok: what the three Transducer searches share -- the normaliser, the frame's log-sum-exp, the forced topology's result)
 template <>
 struct BeamPack<BeamSpell> {
   static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = true;
@@ -416,7 +434,9 @@ struct BeamPack<BeamSpell> {
 // grapheme, once per hypothesis -- cheaper than extending every class by it); the result merges the ranks of one
 // spelling before it is ranked; or one BeamAsgLex: the search of wfl_asg_beam_search_lexicon --
 // BeamAsg's arithmetic with BeamLex's node and state per hypothesis, term per extension and final drop-and-rerank; an
-// extension by the garbage class keeps node and state.
+// extension by the garbage class keeps node and state; or one BeamTokLex: the search of
+// wfl_transducer_beam_search_lexicon -- BeamTok's arithmetic with BeamLex's node and state per
+// hypothesis, term per extension (the merged one inside a stay included) and final drop ahead of the ranking.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -655,7 +675,16 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         if (l >= 0 && h.pnb[tid] > ninf) m = beam_lae(m, h.pnb[tid] + beam_tok_w(a, l, blank));
         const double pb = sc[bpos] + m;
         double pnb = p >= 0 && h.pnb[tid] > ninf ? (sc[p] + h.pnb[tid]) + beam_tok_w(a, l, l) : ninf;
-        if (i >= 0 && !(a.forced && t == 0))
+        if constexpr (LEX) {
+          // (section 25 rule 3: the merged extension carries the term of the prefix it makes -- node and state are
+          // functions of it --, and does not exist where the trie or the LM has none)
+          if (i >= 0 && !(a.forced && t == 0)) {
+            const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]);
+            int enc;
+            const double term = ac > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][i], lmst[cur][i], l, enc) : ninf;
+            if (term > ninf) pnb = beam_lae(pnb, ac + term);
+          }
+        } else if (i >= 0 && !(a.forced && t == 0))
           pnb = beam_lae(pnb, beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]));  // (par: only where p >= 0)
         const double tot = beam_lae(pb, pnb);
         spb[tid] = pb, spnb[tid] = pnb, stot[tid] = tot, skey[tid] = beam_key(tot);
@@ -730,6 +759,18 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
               k = term > ninf ? beam_key(ac + term) : kKeyDropped;
             }
           }
+          enext[idx] = enc;
+        } else if constexpr (TOK && LEX) {
+          // the Transducer's extension (section 22 rule 4: both masses, the transitions gathered here; none in the forced
+          // topology's frame 0) with the lexicon's term and skip test; (ahead of the LEX and TOK branches, which each
+          // take the other for unset)
+          const BeamLex& lx = beam_lex_of(lm_arg...);
+          const BeamTok& a = beam_tok_of(lm_arg...);
+          const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], t == 0 ? -1 : blank, c, sc[p]);
+          int enc = 0;
+          const bool reach = !(a.forced && t == 0) && ac > ninf && beam_key(ac + lx.bound) >= tau;
+          const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+          k = term > ninf ? beam_key(ac + term) : kKeyDropped;
           enext[idx] = enc;
         } else if constexpr (LM) {
           const BeamLm& lm = beam_lm_of(lm_arg...);
@@ -827,7 +868,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           e = beam_key_total(k), lmst[cur ^ 1][r] = enext[idx];  // (the total with its LM term: the key holds it)
         else if constexpr (LEX) {
           // (inside a word: the node, the parent's state; behind one: the root, a new state; ASG's garbage: the
-          // parent's node as enc, so both stay -- and the total with its transition weight is in the key there too)
+          // parent's node as enc, so both stay -- and the total with its transition weight is in the key there too,
+          // as with the Transducer's transitions)
           const int enc = enext[idx];
           e = beam_key_total(k);
           tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
@@ -933,6 +975,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     // forced one by pb alone, a rank whose paths all end in a token dropped.
     // Merging by spelling (section 23 rule 4): the ranks of one spelling are one result -- their scores added in rank
     // order, at the place (and with the token sequence) of the first of them whose score is finite.
+    // The Transducer with a lexicon (section 25 rule 5): the lexicon's drop of a rank inside a word, the topology's
+    // score, </s> on top of it.
     if constexpr (SPELL) {
       if (tid < nbeam) spb[tid] = beam_tok_of(lm_arg...).forced ? f.pb[tid] : f.tot[tid];  // (spb: free behind the frames)
       __syncthreads();
@@ -949,10 +993,12 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
             s = beam_lae(s, sj);
           }
         if (!owner) s = ninf;
-      } else if constexpr (TOK) {
+      } else if constexpr (TOK && !LEX) {
         if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];
       } else if constexpr (LEX) {
         const BeamLex& lx = beam_lex_of(lm_arg...);
+        if constexpr (TOK)
+          if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];  // (-inf: dropped below, with or without </s>)
         if (tnode[Tb & 1][tid] != 0)
           s = ninf;
         else if (lx.has_lm && lx.lm.score_eos) {
@@ -1579,6 +1625,45 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, i
   d.lm.bound = d.bound;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
+}
+
+// The Transducer search with a lexicon and an optional word LM: wfl_transducer_beam_search's call
+// and checks in its order, then wfl_ctc_beam_search_lexicon's checks of the lexicon, the LM and the three constants.
+int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                                       int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                       const wfl_lexicon* lex, const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                       double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                       int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  BeamTokLex d;
+  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
+  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lex.lm)) return rc;
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
+  d.lex.arc_ptr = lex->arc_ptr, d.lex.arc_label = lex->arc_label, d.lex.arc_next = lex->arc_next;
+  d.lex.has_lm = word_lm ? 1 : 0;
+  d.lex.omega = word_bonus;
+  d.lex.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
+  d.lex.lm.bound = d.lex.bound;
+  // no transitions, CTC's topology: these are section 20's rules without lengths, and its search is the one that runs
+  if (!Wt && !forced) return beam_run(what, c, d.lex);
+  return beam_run(what, c, d);
 }
 
 // The ASG search with a lexicon and an optional word LM: wfl_asg_beam_search's call and checks,

@@ -1137,6 +1137,48 @@ Hypotheses transducer_beam_source(const at::Tensor& x, const c10::optional<at::T
           }};
 }
 
+// The options of the Transducer search with a lexicon as both of its ops take them
+// (engine.TransducerLexiconBeamPlan.on_device binds the values it has checked): transducer_beam_source's, and the
+// lexicon, word LM (or none) and constants of the CTC lexicon search.
+struct TransducerLexiconPlan {
+  int blank;
+  bool forced;
+  int beam, K, nbest;
+  std::shared_ptr<DeviceLexicon> lexicon;
+  std::shared_ptr<DeviceLm> lm;
+  double lm_weight, word_bonus, length_bonus;
+  bool score_eos;
+  TransducerLexiconPlan(int blank_, bool forced_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLexicon>& lexicon_,
+                        const std::shared_ptr<DeviceLm>& lm_, double lm_weight_, double word_bonus_, double length_bonus_,
+                        bool score_eos_)
+      : blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
+        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_) {
+    TORCH_CHECK(lexicon, "transducer_beam_search_lexicon: a lexicon is needed");
+    TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
+                "transducer_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
+  }
+};
+
+// The Transducer search with a lexicon (wfl_transducer_beam_search_lexicon): transducer_beam_source
+// with the plan above.
+Hypotheses transducer_lexicon_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
+                                          const c10::optional<at::Tensor>& logz, const TransducerLexiconPlan& p, int nbest,
+                                          bool normalize) {
+  const char* what = "transducer_beam_search_lexicon";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  TORCH_CHECK(p.lexicon->ints.device() == x.device(), what, ": the lexicon's arrays must be on x's device");
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            check(wfl_transducer_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0,
+                                                     p.beam, p.K, nbest, normalize ? 1 : 0, &p.lexicon->lex,
+                                                     p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus, p.length_bonus,
+                                                     p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                  what);
+          }};
+}
+
 // The same search with hypotheses merged by spelling (wfl_transducer_beam_search_merged).
 // spelling: int32 [spell_ptr: C + 1 | spell_sym: num_symbols] on x's device, one contiguous tensor, a table that
 // wfl_spelling_check passed on the host (engine.Spelling.on_device).
@@ -1401,6 +1443,20 @@ at::Tensor transducer_beam_search_errors(const at::Tensor& x, const c10::optiona
 }
 
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple transducer_beam_search_lexicon(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
+                                         const c10::optional<at::Tensor>& logz, const TransducerLexiconPlan& plan, bool normalize) {
+  const Collected r = hypotheses_collect(transducer_lexicon_beam_source(x, Wt, logz, plan, plan.nbest, normalize), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+}
+
+// (the plan's first rank, unnormalised: nothing reads the scores)
+at::Tensor transducer_beam_search_lexicon_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
+                                                 const TransducerLexiconPlan& plan, const std::shared_ptr<StagedTargets>& ref,
+                                                 const ErrorTables& tables) {
+  return hypotheses_errors(transducer_lexicon_beam_source(x, Wt, c10::nullopt, plan, 1, false), ref, tables);
+}
+
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search_merged(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
                                         const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
                                         int blank, bool forced, int beam, int K, int nbest, bool normalize) {
@@ -1479,6 +1535,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transducer_beam_search_errors", &transducer_beam_search_errors, py::arg("x"), py::arg("transitions"), py::arg("blank"),
         py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("ref"), py::arg("tables"),
         "transducer_beam_search's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  py::class_<TransducerLexiconPlan>(
+      m, "TransducerLexiconPlan",
+      "the options of one Transducer beam search with a lexicon, bound (engine.TransducerLexiconBeamPlan.on_device)")
+      .def(py::init<int, bool, int, int, int, const std::shared_ptr<DeviceLexicon>&, const std::shared_ptr<DeviceLm>&, double,
+                    double, double, bool>(),
+           py::arg("blank"), py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"),
+           py::arg("lexicon"), py::arg("lm"), py::arg("lm_weight"), py::arg("word_bonus"), py::arg("length_bonus"),
+           py::arg("score_eos"),
+           "the blank and topology, a lexicon over token sequences (DeviceLexicon), its word LM (DeviceLm) or None, and the "
+           "constants of the CTC lexicon search");
+  m.def("transducer_beam_search_lexicon", &transducer_beam_search_lexicon, py::arg("x"), py::arg("transitions"), py::arg("logz"),
+        py::arg("plan"), py::arg("normalize"),
+        "Transducer prefix beam search with a lexicon on the device by a TransducerLexiconPlan: (labels int64 CPU, offsets "
+        "int64 CPU [B nbest + 1], scores float64 CPU [B, nbest]); transitions float32 [C + 1, C] or None; logz float32 [B] "
+        "(with transitions and normalize) or None");
+  m.def("transducer_beam_search_lexicon_errors", &transducer_beam_search_lexicon_errors, py::arg("x"), py::arg("transitions"),
+        py::arg("plan"), py::arg("ref"), py::arg("tables"),
+        "transducer_beam_search_lexicon's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("transducer_beam_search_merged", &transducer_beam_search_merged, py::arg("x"), py::arg("transitions"), py::arg("logz"),
         py::arg("spelling"), py::arg("num_symbols"), py::arg("blank"), py::arg("forced"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),

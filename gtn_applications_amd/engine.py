@@ -1156,6 +1156,56 @@ def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normal
     return plan.search(x, Wt, normalize, drop, num_replabels)
 
 
+def beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bonus, lm_eos, what):
+    """What the lexicon searches of ASG and the Transducer check alike, or ValueError (`what`: the call the arguments
+    were given to): lexicon a lexicon.Lexicon built for the (num_classes, blank) pair `want` (`need`: the message's words
+    for what it must be); lm None or a word LM of it; the three numbers finite; lm_eos a bool; lm_weight and lm_eos at
+    their defaults without an lm.  Returns (lm_weight, word_bonus, length_bonus, lm_eos) as floats and a bool."""
+    from .lexicon import Lexicon, check_word_lm
+    from .lm import NGramLM
+
+    def finite(v, name):
+        f = math.nan
+        if not isinstance(v, (bool, np.bool_, str, bytes)):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                pass
+        if not math.isfinite(f):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+        return f
+
+    if not isinstance(lexicon, Lexicon):
+        raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
+    if (lexicon.num_classes, lexicon.blank) != want:
+        raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}; {need}")
+    weight, omega, bonus = finite(lm_weight, "lm_weight"), finite(word_bonus, "word_bonus"), finite(length_bonus, "length_bonus")
+    if not isinstance(lm_eos, (bool, np.bool_)):
+        raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+    lm_eos = bool(lm_eos)
+    if lm is None:
+        if weight != 1.0 or lm_eos is not True:
+            raise ValueError(f"{what}: lm_weight and lm_eos need an lm")
+    elif not isinstance(lm, NGramLM):
+        raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
+    else:
+        check_word_lm(lexicon, lm, what)
+    return weight, omega, bonus, lm_eos
+
+
+def beam_lexicon_no_frames(B, nbest, lm, lm_weight, lm_eos, dtype=torch.int64):
+    """(hyps, scores) of a lexicon search for B utterances without a frame, on the host: every rank the empty sequence,
+    the first scored by the LM's </s> alone, the others -inf"""
+    hyps, scores = beam_no_frames(B, nbest, dtype)
+    end = 0.0
+    if lm is not None and lm_eos:
+        step = lm.score([], eos=True)
+        end = -math.inf if step == -math.inf else lm_weight * step
+    scores[:, 1:] = -math.inf
+    scores[:, 0] = end
+    return hyps, scores
+
+
 class AsgLexiconBeamPlan(namedtuple(
         "AsgLexiconBeamPlan", "C beam classes_per_frame nbest garbage lexicon lm lm_weight word_bonus length_bonus lm_eos")):
     """The options of one ASG beam search with a lexicon (wfl_asg_beam_search_lexicon) over C raw
@@ -1173,58 +1223,23 @@ class AsgLexiconBeamPlan(namedtuple(
         built for (C, garbage) -- with a garbage class -- or (C + 1, C) -- without one: a phantom blank that is never a
         label --; an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an lm; a
         number that is not finite."""
-        from .lexicon import Lexicon, check_word_lm
-        from .lm import NGramLM
-
-        def finite(v, name):
-            f = math.nan
-            if not isinstance(v, (bool, np.bool_, str, bytes)):
-                try:
-                    f = float(v)
-                except (TypeError, ValueError):
-                    pass
-            if not math.isfinite(f):
-                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-            return f
-
         C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
         if garbage is not None:
             g = beam_integer(garbage)
             if g is None or not 0 <= g < C:
                 raise ValueError(f"{what}: the garbage class {garbage!r} is outside [0, {C})")
             garbage = g
-        if not isinstance(lexicon, Lexicon):
-            raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
         want = (C, garbage) if garbage is not None else (C + 1, C)
-        if (lexicon.num_classes, lexicon.blank) != want:
-            raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}; "
-                             f"for {C} raw classes " + (f"with the garbage class {garbage}" if garbage is not None else
-                                                        "without a garbage class") +
-                             f" it must have {want[0]} with blank {want[1]} (ASG.lexicon builds it)")
-        weight, omega, bonus = finite(lm_weight, "lm_weight"), finite(word_bonus, "word_bonus"), finite(length_bonus, "length_bonus")
-        if not isinstance(lm_eos, (bool, np.bool_)):
-            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
-        lm_eos = bool(lm_eos)
-        if lm is None:
-            if weight != 1.0 or lm_eos is not True:
-                raise ValueError(f"{what}: lm_weight and lm_eos need an lm")
-        elif not isinstance(lm, NGramLM):
-            raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
-        else:
-            check_word_lm(lexicon, lm, what)
+        need = (f"for {C} raw classes " + (f"with the garbage class {garbage}" if garbage is not None else
+                                           "without a garbage class") +
+                f" it must have {want[0]} with blank {want[1]} (ASG.lexicon builds it)")
+        weight, omega, bonus, lm_eos = beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bonus, lm_eos, what)
         return cls(C, W, K, n, garbage, lexicon, lm, weight, omega, bonus, lm_eos)
 
     def no_frames(self, B):
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
         BeamPlan.no_frames: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
-        hyps, scores = beam_no_frames(B, self.nbest)
-        end = 0.0
-        if self.lm is not None and self.lm_eos:
-            step = self.lm.score([], eos=True)
-            end = -math.inf if step == -math.inf else self.lm_weight * step
-        scores[:, 1:] = -math.inf
-        scores[:, 0] = end
-        return hyps, scores
+        return beam_lexicon_no_frames(B, self.nbest, self.lm, self.lm_weight, self.lm_eos)
 
     def on_device(self, device):
         """The plan as the operators take it (ops.AsgLexiconPlan, csrc/torch_ops.cpp), its lexicon and lm on `device`"""
@@ -1401,6 +1416,69 @@ def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per
         return plan.no_frames(x.shape[0])
     if spelling is not None:
         return transducer_merged_search(plan, x, Wt, spelling, normalize)
+    return plan.search(x, Wt, normalize)
+
+
+class TransducerLexiconBeamPlan(namedtuple(
+        "TransducerLexiconBeamPlan", "C blank forced beam classes_per_frame nbest lexicon lm lm_weight word_bonus length_bonus lm_eos")):
+    """The options of one Transducer beam search with a lexicon (wfl_transducer_beam_search_lexicon)
+    over C classes (tokens + the blank), checked once (`checked`, the one constructor) and handed on whole:
+    TransducerBeamPlan's six fields, a lexicon.Lexicon over token sequences for (C, blank) (Transducer.word_lexicon
+    builds one), its word LM (an lm.NGramLM by the convention of lexicon.py) or None, and the constants of the CTC
+    lexicon search.  Only on_device(), search() and errors need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, word_bonus, length_bonus,
+                lm_eos, what):
+        """The plan of these arguments, within the limits of wfl_transducer_beam_search_lexicon, or ValueError (`what`:
+        the call they were given to): what TransducerBeamPlan.checked refuses; a lexicon that is none or was not built
+        for (C, blank); an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an
+        lm; a number that is not finite."""
+        p = TransducerBeamPlan.checked(C, blank, forced, beam_size, classes_per_frame, nbest, what)
+        need = f"the emissions have {p.C} with blank {p.blank} (Transducer.word_lexicon builds it)"
+        weight, omega, bonus, lm_eos = beam_lexicon_terms(lexicon, (p.C, p.blank), need, lm, lm_weight, word_bonus, length_bonus,
+                                                          lm_eos, what)
+        return cls(*p, lexicon, lm, weight, omega, bonus, lm_eos)
+
+    def no_frames(self, B, dtype=torch.int64):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
+        BeamPlan.no_frames: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
+        return beam_lexicon_no_frames(B, self.nbest, self.lm, self.lm_weight, self.lm_eos, dtype)
+
+    def on_device(self, device):
+        """The plan as the operators take it (ops.TransducerLexiconPlan, csrc/torch_ops.cpp), its lexicon and lm on `device`"""
+        return N.ops.TransducerLexiconPlan(blank=self.blank, forced=self.forced, beam=self.beam,
+                                           classes_per_frame=self.classes_per_frame, nbest=self.nbest,
+                                           lexicon=self.lexicon.on_device(device),
+                                           lm=None if self.lm is None else self.lm.on_device(device), lm_weight=self.lm_weight,
+                                           word_bonus=self.word_bonus, length_bonus=self.length_bonus, score_eos=self.lm_eos)
+
+    def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
+        """transducer_beam_search_lexicon's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt:
+        float32 [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
+        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+            logz = dense_forward(x, Wt, need_beta=False).logz if Wt is not None and normalize else None
+            flat, offsets, scores = N.ops.transducer_beam_search_lexicon(x, Wt, logz, self.on_device(x.device), bool(normalize))
+        return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
+
+
+def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_size=16, classes_per_frame=None, nbest=1,
+                                   normalize=True, lm=None, lm_weight=1.0, word_bonus=0.0, length_bonus=0.0, lm_eos=True):
+    """transducer_beam_search with a lexicon and an optional word LM (wfl_transducer_beam_search_lexicon through
+    csrc/torch_ops.cpp; the rules: include/wfl.h).  x, Wt, blank, forced and the result:
+    transducer_beam_search's.  lexicon: a lexicon.Lexicon over token sequences for (C, blank).  Only sequences of the
+    lexicon's words are returned; lm (if given) is the word LM over its word ids; every token adds length_bonus and a
+    completed word lm_weight * step(s, word) + word_bonus on top; lm_eos adds lm_weight * step(s, </s>) after the last
+    frame.  The scores include these terms.  With Wt None and forced False this is ctc_beam_search(lexicon=) without
+    lengths, bit for bit.  The options are one TransducerLexiconBeamPlan."""
+    what = "transducer_beam_search_lexicon"
+    plan = TransducerLexiconBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm,
+                                             lm_weight, word_bonus, length_bonus, lm_eos, what)
+    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return plan.no_frames(x.shape[0])
     return plan.search(x, Wt, normalize)
 
 

@@ -915,6 +915,53 @@ int wfl_transducer_beam_search_merged(const float* x, const float* Wt /* [(C+1),
                                       int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The Transducer search with a lexicon and an optional word-level n-gram LM (csrc/beam_kernels.hip).
+ *   Every rule of wfl_transducer_beam_search stands: candidates, the two masses pb / pnb, the blank-side state, prefix
+ *   identity, merging, selection and tie order.  a = lm_weight, o = word_bonus, b = length_bonus, all finite float64 (the
+ *   names of wfl_ctc_beam_search_lexicon).  The lexicon is a wfl_lexicon over TOKEN sequences for (C, blank).
+ *     1. every hypothesis carries a trie node and, with a word LM, an LM state; the empty prefix has the root and the
+ *        LM's `start`.  Both are functions of the token prefix, so merging by prefix identity stays exact, and a merged
+ *        extension carries the same term as a new one;
+ *     2. the extension of hypothesis i by a candidate c != blank, ac the value of rule 4 of wfl_transducer_beam_search
+ *        (forced = 0: both masses, pb alone for c == l; forced = 1: pb alone, and no extension in frame 0).  ac = -inf:
+ *        the extension does not exist and nothing is looked up.  Otherwise c is searched among the arcs of node_i (a
+ *        binary search, at most 31 steps).  Absent: the extension does not exist.  An inner arc: e = ac + b, the node
+ *        becomes the arc's target, the state stays.  An arc that completes word v: (l, nxt) = step(state_i, v), (0, -)
+ *        without an LM; l = -inf: the extension does not exist; otherwise e = ac + ((a l + o) + b), each operation
+ *        rounded on its own, the new node is the root and the new state nxt;
+ *     3. stays are rule 3 of wfl_transducer_beam_search: they add no term and keep node and state; the merged extension
+ *        inside a stay carries rule 2's term;
+ *     4. the bound is wfl_ctc_beam_search's: the blank gives every hypothesis a stay, so the W-th best stay of a full
+ *        beam bounds the W-th best entry from below.  The lookup of an extension with ac + (the largest term, that of
+ *        wfl_ctc_beam_search_lexicon) below the bound is skipped.  The bound decides what is ranked, never the result;
+ *     5. after the last frame, in this order: a rank whose node is not the root is dropped; forced = 1: the score is pb,
+ *        a rank with pb = -inf is dropped; forced = 0: the score is lae(pb, pnb); with score_eos != 0 and an LM a
+ *        remaining rank gets + a step(state, V + 1) and is dropped if that step is -inf; the remaining ranks are ranked
+ *        again by score, descending, ties to the earlier rank; nbest is taken after that; nothing left: the empty
+ *        sequence with score -inf;
+ *     6. where nothing is pruned, score(l) = mass_Transducer(l) + a LM(words(l)) + o #words + b |l|, plus the </s> term;
+ *        mass_Transducer(l) is the log-sum over l's alignments under the token graph and Wt; normalize != 0: minus the
+ *        normaliser of rule 7 of wfl_transducer_beam_search (logz[b] with Wt, the rows' log-sum-exps without);
+ *     7. Wt == NULL and forced == 0 are wfl_ctc_beam_search_lexicon's rules without lengths, and its search is what
+ *        runs: bit-identical results.
+ *   lex, word_lm: structs in HOST memory of DEVICE pointers, as for wfl_ctc_beam_search_lexicon; lex passed
+ *   wfl_lexicon_check for (C, blank), word_lm wfl_ngram_lm_check for V + 1 and V.  The kernels trust them.  The workspace
+ *   (wfl_transducer_beam_workspace), outputs, three launches and guarantees of wfl_transducer_beam_search: no allocation,
+ *   no synchronisation, no global atomics, no cross-workgroup waits, every loop bounded by T, W, K, the back-off cap or
+ *   31 search steps.
+ *   WFL_ERR_INVALID: what wfl_transducer_beam_search refuses, in its order; then lex or one of its arrays NULL,
+ *   num_nodes, num_arcs or num_words < 1 (or num_words = 2^31 - 1); for a non-NULL word_lm what wfl_ctc_beam_search_lm
+ *   refuses; a weight or bonus that is not finite.  Not here: a token-level LM, LM look-ahead inside words, several
+ *   spellings of one word, merging by spelling, input lengths, the ambiguous token graphs.
+ * ------------------------------------------------------------------------------------------------ */
+int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] or NULL */,
+                                       const float* logz /* [B] or NULL */, int B, int T, int C, int blank, int forced, int beam,
+                                       int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                       const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
+                                       double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                       int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
  *   what the training loop does with viterbi()'s result -- compute_edit_distance, train.py:74-87, called per batch at
  *   train.py:278-284 and test.py:94-109 -- per utterance b:
