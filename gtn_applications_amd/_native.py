@@ -57,6 +57,13 @@ class Lexicon(ctypes.Structure):
         (n, c_void_p) for n in ("arc_ptr", "arc_label", "arc_next")]
 
 
+class LexiconMarked(ctypes.Structure):
+    """Mirror of `wfl_lexicon_marked` (include/wfl.h): host pointers for wfl_lexicon_marked_check, device pointers for a
+    search."""
+
+    _fields_ = [("trie", Lexicon), ("node_word", c_void_p), ("start_node", c_void_p)]
+
+
 class LatticeDesc(ctypes.Structure):
     """Mirror of `wfl_lattice_desc` (include/wfl.h) -- field order and types must match."""
 
@@ -207,6 +214,10 @@ _SIGS = {
     "wfl_lexicon_check": (c_int, [POINTER(Lexicon), c_int, c_int]),
     "wfl_ctc_beam_search_lexicon": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Lexicon),
                                             POINTER(NgramLm), c_double, c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_lexicon_marked_check": (c_int, [POINTER(LexiconMarked), c_int, c_int]),
+    "wfl_ctc_beam_search_lexicon_marked": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                   POINTER(LexiconMarked), POINTER(NgramLm), c_double, c_double, c_double,
+                                                   c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: ASG prefix beam search
     "wfl_asg_beam_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_asg_beam_search": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P,
@@ -222,6 +233,9 @@ _SIGS = {
     "wfl_transducer_beam_search_lexicon": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    POINTER(Lexicon), POINTER(NgramLm), c_double, c_double, c_double, c_int, _P,
                                                    _P, c_int64, _P, _P, _P]),
+    "wfl_transducer_beam_search_lexicon_marked": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                          c_int, POINTER(LexiconMarked), POINTER(NgramLm), c_double, c_double,
+                                                          c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     "wfl_transducer_beam_search_merged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path

@@ -430,7 +430,11 @@ class CTC(torch.nn.Module):
         hypothesis that ends inside a word is dropped after the last frame; nothing left: the empty sequence, -inf),
         `lm` is then a word-level LM over the lexicon's word ids (NGramLM.from_arpa(path, words, blank=len(words))), a
         completed word adds lm_weight * log P_LM(word | history) + word_bonus and every label length_bonus; the output
-        is still the token labels, lexicon.words() gives the words.  `word_bonus` needs a lexicon.  CTC's search: ASG has
+        is still the token labels, lexicon.words() gives the words.  A start-marked lexicon (Lexicon(...,
+        boundary="start"), DESIGN.md section 26: word pieces that carry the word boundary at the start of a word, words
+        that are prefixes of one another or have several spellings) is taken as it is: a word then ends where the next
+        begins or with the utterance, and a hypothesis is ranked without the LM term of its last, unfinished word until
+        then.  `word_bonus` needs a lexicon.  CTC's search: ASG has
         its own (ASG.beam_search), the Transducer's token graphs have none."""
         plan, lens = self._beam_plan(outputs, input_lengths, "CTC.beam_search", beam_size, classes_per_frame, nbest, lm,
                                      lm_weight, length_bonus, lm_eos, lexicon, word_bonus)

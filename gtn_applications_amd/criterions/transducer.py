@@ -415,17 +415,28 @@ class Transducer(torch.nn.Module):
                                                        lexicon, lm, lm_weight, word_bonus, length_bonus, lm_eos, what)
         return plan, kind
 
-    def word_lexicon(self, words, wordsep=None, split=None):
+    def word_lexicon(self, words, wordsep=None, split=None, boundary="end", splits=None):
         """The lexicon.Lexicon of `words` for beam_search(lexicon=): a trie over sequences of the
         module's own tokens, for (n_tokens + 1, n_tokens) -- the emission classes and the blank of a token graph with a
         blank, which the module must have.  A word is split into its characters, or by split(word) into pieces; each
         piece must be one of the module's tokens, compared as tuple(piece) against tuple(token); with `wordsep` that
         token ends every spelling.  split= fixes ONE decomposition per word: the other decompositions of the same
         graphemes into word pieces are not in the trie.  ValueError names a word and its piece that is no token.
+        boundary="start" (DESIGN.md section 26): a start-marked lexicon -- word pieces that carry the word boundary at
+        the start of a word, words that are prefixes of one another; no wordsep then, and splits(word) -> a list of
+        decompositions gives a word several spellings, each a hypothesis of its own in the search.
         (`Transducer.lexicon` is the criterion's token-to-grapheme graph, hence the name.)"""
         what = "Transducer.word_lexicon"
         if not self._has_blank:
             raise ValueError(f'{what}: blank="none" has no class for the blank a Lexicon is built around, and no beam search')
+        if boundary not in ("end", "start"):
+            raise ValueError(f"{what}: boundary {boundary!r} is neither 'end' nor 'start'")
+        if boundary == "start" and wordsep is not None:
+            raise ValueError(f"{what}: with boundary='start' the word boundary is part of the pieces: no wordsep")
+        if splits is not None and boundary != "start":
+            raise ValueError(f"{what}: splits (several decompositions of a word) needs boundary='start'")
+        if splits is not None and split is not None:
+            raise ValueError(f"{what}: split gives one decomposition per word, splits several: give one of them")
         index = {}
         for i, tok in enumerate(self._token_pieces):
             index.setdefault(tok, i)
@@ -435,19 +446,23 @@ class Transducer(torch.nn.Module):
             if sep is None:
                 raise ValueError(f"{what}: the word separator {wordsep!r} is not one of the module's tokens")
         words = list(words)
-        spellings = []
-        for w in words:
-            pieces = list(w) if split is None else list(split(w))
-            ids = []
-            for piece in pieces:
-                i = index.get(tuple(piece))
-                if i is None:
-                    raise ValueError(f"{what}: {piece!r} of {w!r} is not one of the module's tokens")
-                ids.append(i)
-            spellings.append(ids + ([sep] if sep is not None else []))
+        spellings, word_of = [], []
+        for v, w in enumerate(words):
+            ways = [list(w) if split is None else list(split(w))] if splits is None else [list(d) for d in splits(w)]
+            for pieces in ways:
+                ids = []
+                for piece in pieces:
+                    i = index.get(tuple(piece))
+                    if i is None:
+                        raise ValueError(f"{what}: {piece!r} of {w!r} is not one of the module's tokens")
+                    ids.append(i)
+                spellings.append(ids + ([sep] if sep is not None else []))
+                word_of.append(v)
         from ..lexicon import Lexicon
 
         n = len(self._token_pieces)
+        if boundary == "start":
+            return Lexicon(spellings, n + 1, n, words=words, boundary="start", word_of=word_of)
         return Lexicon(spellings, n + 1, n, words=words)
 
     @staticmethod
@@ -529,8 +544,12 @@ class Transducer(torch.nn.Module):
         without a lexicon, and the criterion's other decompositions of the same graphemes are not searched.  A lexicon
         with merge_spellings=True raises NotImplementedError.  Without a lexicon the call is what it was, and lm,
         lm_weight, length_bonus, lm_eos and word_bonus must be at their defaults (ValueError).  B == 0 or T == 0 with a
-        lexicon: the empty sequence, scored by the LM's </s> alone.  No token-level LM, LM look-ahead, several spellings
-        per word or input lengths."""
+        lexicon: the empty sequence, scored by the LM's </s> alone.  A start-marked lexicon (word_lexicon(...,
+        boundary="start"), DESIGN.md section 26: word pieces that carry the word boundary at the start of a word, words
+        that are prefixes of one another, several spellings of a word through splits=) is taken as it is: a word ends
+        where the next begins or with the utterance, two spellings of the same words are separate hypotheses, and a
+        hypothesis is ranked without the LM term of its last, unfinished word until then.  No token-level LM, LM
+        look-ahead or input lengths."""
         what = "Transducer.beam_search"
         plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, length_bonus,
                                      lm_eos, word_bonus)

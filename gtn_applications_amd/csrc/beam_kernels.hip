@@ -44,7 +44,12 @@
 // wfl_transducer_beam_search_lexicon is the Transducer search with that lexicon and word LM: an
 // eighth pack, BeamTokLex, holds a BeamTok and a BeamLex -- the Transducer's two masses and transition gathers per
 // entry, the lexicon's node and state per hypothesis.
-// All eight issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_ctc_beam_search_lexicon_marked and wfl_transducer_beam_search_lexicon_marked are the two lexicon searches with a
+// start-marked lexicon (word pieces that carry the word boundary at the start of a word; a word
+// ends where the next begins or with the utterance): the packs BeamLexMarked and BeamTokLexMarked add node_word and
+// start_node to their siblings' fields, selected at compile time -- another step function, the node behind a word in
+// place(), the pending word's term in the final block; the siblings' kernels are the code they were.
+// All ten issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -299,6 +304,62 @@ __device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int
   return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
 }
 
+// A start-marked lexicon (wfl_lexicon_marked): BeamLex's trie with stored leaves and all arc targets
+// inner nodes, node_word[n] the word whose spelling ends at node n (-1: none), start_node[c] the root's child by class c
+// (-1: c starts no word).  A word ends where the next begins, or with the utterance.
+struct BeamLexMarked {
+  BeamLex lex;
+  const int32_t *node_word, *start_node;
+};
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamLexMarked& m) { return m.lex; }
+__device__ __forceinline__ const BeamLexMarked& beam_lex_marked_of(const BeamLexMarked& m) { return m; }
+
+// The term of a word that ends with the utterance (section 26 rule 5): alpha l + omega, each operation rounded on its own
+__device__ __forceinline__ double beam_lex_pending_term(double alpha, double l, double omega) {
+#pragma clang fp contract(off)
+  const double al = alpha * l;
+  return al + omega;
+}
+
+// beam_lex_step for a start-marked lexicon (section 26 rule 3).  One load of start_node[c] decides the case: c starts no
+// word -- the bounded search among the node's arcs (none at the root, whose arcs all start words), the state stays; c
+// starts a word from the root -- its child, the state stays; from a terminal node -- the LM step of the word that ends
+// there, enc = -(next LM state + 1) and place() takes the node from start_node[c]; from any other node -- nothing.
+__device__ __forceinline__ double beam_lex_step_marked(const BeamLexMarked& m, int node, int state, int c, int& enc) {
+  const BeamLex& lx = m.lex;
+  enc = 0;
+  const int sn = m.start_node[c];
+  if (sn < 0) {
+    if (node == 0) return -__builtin_inf();
+    const int end = lx.arc_ptr[node + 1];
+    int lo = lx.arc_ptr[node], hi = end;
+    for (int it = 0; it < 31 && lo < hi; ++it) {  // the first arc whose label is not below c
+      const int mid = lo + ((hi - lo) >> 1);
+      if (lx.arc_label[mid] < c)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (!(lo < end && lx.arc_label[lo] == c)) return -__builtin_inf();
+    enc = lx.arc_next[lo];
+    return lx.lm.beta;
+  }
+  if (node == 0) {
+    enc = sn;
+    return lx.lm.beta;
+  }
+  const int v = m.node_word[node];
+  if (v < 0) return -__builtin_inf();
+  double l = 0.0;
+  int ns = 0;
+  if (lx.has_lm) {
+    l = beam_lm_step(lx.lm, state, v, ns);
+    if (!(l > -__builtin_inf())) return -__builtin_inf();
+  }
+  enc = -(ns + 1);
+  return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
+}
+
 // the transitions of an ASG launch (wfl_asg_beam_search): Wt [(C+1), C] float32 in the criterion's layout (asg.py:54-69:
 // row 0 start -> c, row 1 + i: j -> i), and the denominator to subtract from the scores or NULL
 struct BeamAsg {
@@ -359,6 +420,32 @@ struct BeamTokLex {
 __device__ __forceinline__ const BeamTok& beam_tok_of(const BeamTokLex& a) { return a.tok; }
 __device__ __forceinline__ const BeamLex& beam_lex_of(const BeamTokLex& a) { return a.lex; }
 
+// the same launch with a start-marked lexicon (wfl_transducer_beam_search_lexicon_marked)
+struct BeamTokLexMarked {
+  BeamTok tok;
+  BeamLexMarked lex;
+};
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamTokLexMarked& a) { return a.tok; }
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamTokLexMarked& a) { return a.lex.lex; }
+__device__ __forceinline__ const BeamLexMarked& beam_lex_marked_of(const BeamTokLexMarked& a) { return a.lex; }
+
+// the lexicon's term of an extension by the convention of the launch's pack: beam_lex_step, or beam_lex_step_marked
+__device__ __forceinline__ double beam_lex_ext(const BeamLex& a, int node, int state, int c, int& enc) {
+  return beam_lex_step(a, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamAsgLex& a, int node, int state, int c, int& enc) {
+  return beam_lex_step(a.lex, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamTokLex& a, int node, int state, int c, int& enc) {
+  return beam_lex_step(a.lex, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamLexMarked& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_marked(a, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamTokLexMarked& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_marked(a.lex, node, state, c, enc);
+}
+
 // the Transducer launch that merges by spelling (wfl_transducer_beam_search_merged): BeamTok's
 // fields and the spelling table over the C classes -- class c spells the graphemes spell_sym[spell_ptr[c] ..
 // spell_ptr[c + 1]), none for the blank, 1 .. WFL_SPELL_MAX for every other class (wfl_spelling_check)
@@ -409,6 +496,25 @@ template <>
 struct BeamPack<BeamTokLex> {
   static constexpr bool lm = false, lex = true, asg = false, tok = true, spell = false;
 };
+// (the two lexicon packs with a start-marked lexicon: the traits of their end-marked siblings, and BeamMarked below)
+template <>
+struct BeamPack<BeamLexMarked> : BeamPack<BeamLex> {};
+template <>
+struct BeamPack<BeamTokLexMarked> : BeamPack<BeamTokLex> {};
+// whether the pack's lexicon is start-marked (section 26): the step of an extension, the node behind a word in place(),
+// and the pending word after the last frame
+template <typename... Lm>
+struct BeamMarked {
+  static constexpr bool value = false;
+};
+template <>
+struct BeamMarked<BeamLexMarked> {
+  static constexpr bool value = true;
+};
+template <>
+struct BeamMarked<BeamTokLexMarked> {
+  static constexpr bool value = true;
+};
 // (tok: what the three Transducer searches share -- the normaliser, the frame's log-sum-exp, the forced topology's result)
 template <>
 struct BeamPack<BeamSpell> {
@@ -446,6 +552,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
                                                            Lm... lm_arg) {
   constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg, TOK = BeamPack<Lm...>::tok;
   constexpr bool SPELL = BeamPack<Lm...>::spell;  // (TOK as well)
+  constexpr bool MARK = BeamMarked<Lm...>::value;  // (LEX as well)
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -624,7 +731,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
             double term = 0.0;
             int enc;
             if (c != garbage)
-              term = ac > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][src], lmst[cur][src], c, enc) : ninf;
+              term = ac > ninf ? beam_lex_ext(lm_arg..., tnode[cur][src], lmst[cur][src], c, enc) : ninf;
             if (term > ninf) e = ac + term;
           }
           if (p >= 0) m = beam_lae(m, e);
@@ -681,7 +788,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           if (i >= 0 && !(a.forced && t == 0)) {
             const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]);
             int enc;
-            const double term = ac > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][i], lmst[cur][i], l, enc) : ninf;
+            const double term = ac > ninf ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], l, enc) : ninf;
             if (term > ninf) pnb = beam_lae(pnb, ac + term);
           }
         } else if (i >= 0 && !(a.forced && t == 0))
@@ -706,7 +813,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         if (i >= 0) {  // the merged extension carries the term of the prefix it makes (node and state: functions of it)
           const double e = sc[p] + (h.last[i] == h.last[tid] ? h.pb[i] : h.tot[i]);
           int enc;
-          const double term = e > ninf ? beam_lex_step(beam_lex_of(lm_arg...), tnode[cur][i], lmst[cur][i], h.last[tid], enc) : ninf;
+          const double term = e > ninf ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], h.last[tid], enc) : ninf;
           if (term > ninf) pnb = beam_lae(pnb, e + term);
         }
       } else {
@@ -755,7 +862,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
               k = beam_key(ac), enc = tnode[cur][i];
             } else {
               const bool reach = ac > ninf && beam_key(ac + lx.bound) >= tau;
-              const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+              const double term = reach ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], c, enc) : ninf;
               k = term > ninf ? beam_key(ac + term) : kKeyDropped;
             }
           }
@@ -769,7 +876,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], t == 0 ? -1 : blank, c, sc[p]);
           int enc = 0;
           const bool reach = !(a.forced && t == 0) && ac > ninf && beam_key(ac + lx.bound) >= tau;
-          const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+          const double term = reach ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], c, enc) : ninf;
           k = term > ninf ? beam_key(ac + term) : kKeyDropped;
           enext[idx] = enc;
         } else if constexpr (LM) {
@@ -787,7 +894,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           int enc = 0;
           // (an entry below the bound even with the largest term is outside the beam: no lookup; + is monotone)
           const bool reach = ac > ninf && beam_key(ac + lx.bound) >= tau;
-          const double term = reach ? beam_lex_step(lx, tnode[cur][i], lmst[cur][i], c, enc) : ninf;
+          const double term = reach ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], c, enc) : ninf;
           k = term > ninf ? beam_key(ac + term) : kKeyDropped;
           enext[idx] = enc;
         } else if constexpr (ASG) {
@@ -872,7 +979,11 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           // as with the Transducer's transitions)
           const int enc = enext[idx];
           e = beam_key_total(k);
-          tnode[cur ^ 1][r] = enc >= 0 ? enc : 0, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
+          // (a start-marked lexicon: behind a word stands the first node of the next, the root's child by c)
+          int behind = 0;
+          if constexpr (MARK)
+            if (enc < 0) behind = beam_lex_marked_of(lm_arg...).start_node[c];
+          tnode[cur ^ 1][r] = enc >= 0 ? enc : behind, lmst[cur ^ 1][r] = enc >= 0 ? lmst[cur][i] : -(enc + 1);
         } else if constexpr (ASG || TOK)
           e = beam_key_total(k);  // (the total with its transition weight: the key holds it, no second gather)
         else
@@ -999,7 +1110,27 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         const BeamLex& lx = beam_lex_of(lm_arg...);
         if constexpr (TOK)
           if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];  // (-inf: dropped below, with or without </s>)
-        if (tnode[Tb & 1][tid] != 0)
+        if constexpr (MARK) {
+          // section 26 rule 5: the root (the empty sequence) as it is; a terminal node: the pending word's term and the
+          // state behind it, dropped where the LM cannot follow; any other node: inside a word, dropped
+          const int nd = tnode[Tb & 1][tid];
+          int st = lmst[Tb & 1][tid];
+          if (nd != 0) {
+            const int v = beam_lex_marked_of(lm_arg...).node_word[nd];
+            double l = v >= 0 ? 0.0 : ninf;
+            if (v >= 0 && lx.has_lm) {
+              int ns;
+              l = beam_lm_step(lx.lm, st, v, ns);
+              st = ns;
+            }
+            s = l > ninf ? s + beam_lex_pending_term(lx.lm.alpha, l, lx.omega) : ninf;
+          }
+          if (s > ninf && lx.has_lm && lx.lm.score_eos) {
+            int nx;
+            const double l = beam_lm_step(lx.lm, st, lx.lm.eos, nx);
+            s = l > ninf ? s + lx.lm.alpha * l : ninf;
+          }
+        } else if (tnode[Tb & 1][tid] != 0)
           s = ninf;
         else if (lx.has_lm && lx.lm.score_eos) {
           int nx;
@@ -1603,26 +1734,34 @@ int wfl_lexicon_check(const wfl_lexicon* lex, int C, int blank) {
   return WFL_OK;
 }
 
+// The lexicon of a launch, for the entries below: the shape of `lex`, the word LM's terms (beam_lm_terms) and the three
+// constants checked, in that order, and `d` filled from them -- the bound of an extension's term included.
+static int beam_lex_fill(const char* what, const wfl_lexicon* lex, const wfl_ngram_lm* word_lm, double lm_weight,
+                         double word_bonus, double length_bonus, int score_eos, BeamLex* d) {
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
+  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d->lm)) return rc;
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  d->arc_ptr = lex->arc_ptr, d->arc_label = lex->arc_label, d->arc_next = lex->arc_next;
+  d->has_lm = word_lm ? 1 : 0;
+  d->omega = word_bonus;
+  // (without a word LM every word's step is 0: the bounds of step are [0, 0])
+  d->bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
+  d->lm.bound = d->bound;
+  return WFL_OK;
+}
+
 int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
                                 int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
                                 const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
                                 int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
                                 double* scores, void* stream) {
   const char* what = "ctc_beam_search_lexicon";
-  if (const int rc = lexicon_shape(what, lex)) return rc;
   BeamLex d;
-  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
-  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lm)) return rc;
-  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
-    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
-    return WFL_ERR_INVALID;
-  }
-  d.arc_ptr = lex->arc_ptr, d.arc_label = lex->arc_label, d.arc_next = lex->arc_next;
-  d.has_lm = word_lm ? 1 : 0;
-  d.omega = word_bonus;
-  // (without a word LM every word's step is 0: the bounds of step are [0, 0])
-  d.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
-  d.lm.bound = d.bound;
+  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
 }
@@ -1647,21 +1786,168 @@ int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt, const fl
     set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
     return WFL_ERR_INVALID;
   }
-  if (const int rc = lexicon_shape(what, lex)) return rc;
   BeamTokLex d;
-  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
-  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lex.lm)) return rc;
-  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
-    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
+  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
+  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
+  // no transitions, CTC's topology: these are section 20's rules without lengths, and its search is the one that runs
+  if (!Wt && !forced) return beam_run(what, c, d.lex);
+  return beam_run(what, c, d);
+}
+
+static int lexicon_marked_shape(const char* what, const wfl_lexicon_marked* lex) {
+  if (!lex) {
+    set_error("%s: a NULL lexicon or array of it", what);
     return WFL_ERR_INVALID;
   }
+  if (const int rc = lexicon_shape(what, &lex->trie)) return rc;
+  if (!lex->node_word || !lex->start_node) {
+    set_error("%s: a NULL lexicon or array of it", what);
+    return WFL_ERR_INVALID;
+  }
+  return WFL_OK;
+}
+
+// Every clause of rule 1 of DESIGN.md section 26, on host arrays: arc_ptr is read first, then nothing outside
+// [0, num_arcs), [0, num_nodes) and [0, C).
+int wfl_lexicon_marked_check(const wfl_lexicon_marked* lex, int C, int blank) {
+  const char* what = "lexicon_marked_check";
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  if (C < 1 || blank < 0 || blank >= C) {
+    set_error("%s: %d classes, blank %d", what, C, blank);
+    return WFL_ERR_INVALID;
+  }
+  const wfl_lexicon& t = lex->trie;
+  const int N = t.num_nodes, A = t.num_arcs, V = t.num_words;
+  if (t.arc_ptr[0] != 0 || t.arc_ptr[N] != A) {
+    set_error("%s: arc_ptr runs from %d to %d, not from 0 to %d", what, t.arc_ptr[0], t.arc_ptr[N], A);
+    return WFL_ERR_INVALID;
+  }
+  for (int n = 0; n < N; ++n)
+    if (t.arc_ptr[n] > t.arc_ptr[n + 1] || t.arc_ptr[n] < 0 || t.arc_ptr[n + 1] > A) {
+      set_error("%s: arc_ptr descends or leaves [0, %d] at node %d", what, A, n);
+      return WFL_ERR_INVALID;
+    }
+  std::vector<char> entered((size_t)N, 0), spelled((size_t)V, 0), starts((size_t)C, 0);
+  for (int n = 0; n < N; ++n)
+    for (int a = t.arc_ptr[n]; a < t.arc_ptr[n + 1]; ++a) {
+      const int l = t.arc_label[a], nx = t.arc_next[a];
+      if (l < 0 || l >= C || l == blank) {
+        set_error("%s: arc %d of node %d has label %d (classes [0, %d), never the blank %d)", what, a, n, l, C, blank);
+        return WFL_ERR_INVALID;
+      }
+      if (a > t.arc_ptr[n] && t.arc_label[a - 1] >= l) {
+        set_error("%s: the labels of node %d are not strictly ascending at arc %d", what, n, a);
+        return WFL_ERR_INVALID;
+      }
+      if (nx < 1 || nx >= N) {
+        set_error("%s: arc %d of node %d leads to node %d (targets are 1 .. %d)", what, a, n, nx, N - 1);
+        return WFL_ERR_INVALID;
+      }
+      if (entered[(size_t)nx]) {
+        set_error("%s: node %d is the target of more than one arc (arc %d is the second)", what, nx, a);
+        return WFL_ERR_INVALID;
+      }
+      entered[(size_t)nx] = 1;
+      if (n == 0) starts[(size_t)l] = 1;
+    }
+  for (int n = 1; n < N; ++n)
+    if (!entered[(size_t)n]) {
+      set_error("%s: node %d is the target of no arc", what, n);
+      return WFL_ERR_INVALID;
+    }
+  {  // one arc into every other node still allows a cycle apart from the root: every node must be reached from it
+    std::vector<int> stack(1, 0);
+    int reached = 0;
+    while (!stack.empty()) {
+      const int n = stack.back();
+      stack.pop_back();
+      ++reached;
+      for (int a = t.arc_ptr[n]; a < t.arc_ptr[n + 1]; ++a) stack.push_back(t.arc_next[a]);
+    }
+    if (reached != N) {
+      set_error("%s: %d of %d nodes are reached from the root: the rest form a cycle", what, reached, N);
+      return WFL_ERR_INVALID;
+    }
+  }
+  for (int n = 0; n < N; ++n) {
+    const int v = lex->node_word[n];
+    if (v < -1 || v >= V) {
+      set_error("%s: node %d ends word %d of %d", what, n, v, V);
+      return WFL_ERR_INVALID;
+    }
+    if (n == 0 && v >= 0) {
+      set_error("%s: the root ends word %d (no word has an empty spelling)", what, v);
+      return WFL_ERR_INVALID;
+    }
+    if (v < 0 && t.arc_ptr[n] == t.arc_ptr[n + 1]) {
+      set_error("%s: node %d has no arc and ends no word (a dead end)", what, n);
+      return WFL_ERR_INVALID;
+    }
+    if (v >= 0) spelled[(size_t)v] = 1;
+  }
+  for (int v = 0; v < V; ++v)
+    if (!spelled[(size_t)v]) {
+      set_error("%s: word %d ends at no node", what, v);
+      return WFL_ERR_INVALID;
+    }
+  for (int c = 0; c < C; ++c) {  // start_node against the root's arcs (labels ascending: the one arc by c, if any)
+    int child = -1;
+    for (int a = t.arc_ptr[0]; a < t.arc_ptr[1]; ++a)
+      if (t.arc_label[a] == c) child = t.arc_next[a];
+    if (lex->start_node[c] != child) {
+      set_error("%s: start_node[%d] is %d, the root's child by class %d is %d", what, c, lex->start_node[c], c, child);
+      return WFL_ERR_INVALID;
+    }
+  }
+  for (int n = 1; n < N; ++n)
+    for (int a = t.arc_ptr[n]; a < t.arc_ptr[n + 1]; ++a)
+      if (starts[(size_t)t.arc_label[a]]) {
+        set_error("%s: class %d starts a word and is the label of arc %d of node %d inside one", what, t.arc_label[a], a, n);
+        return WFL_ERR_INVALID;
+      }
+  return WFL_OK;
+}
+
+// wfl_ctc_beam_search_lexicon with a start-marked lexicon: its checks in its order
+int wfl_ctc_beam_search_lexicon_marked(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                       int classes_per_frame, int nbest, int normalize, const wfl_lexicon_marked* lex,
+                                       const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
+                                       int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                                       double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon_marked";
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  BeamLexMarked d;
+  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
+  d.node_word = lex->node_word, d.start_node = lex->start_node;
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
+}
+
+// wfl_transducer_beam_search_lexicon with a start-marked lexicon: its checks in its order
+int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                                              int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                              const wfl_lexicon_marked* lex, const wfl_ngram_lm* word_lm, double lm_weight,
+                                              double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                              int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon_marked";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  BeamTokLexMarked d;
+  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex.lex)) return rc;
   d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  d.lex.arc_ptr = lex->arc_ptr, d.lex.arc_label = lex->arc_label, d.lex.arc_next = lex->arc_next;
-  d.lex.has_lm = word_lm ? 1 : 0;
-  d.lex.omega = word_bonus;
-  d.lex.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
-  d.lex.lm.bound = d.lex.bound;
-  // no transitions, CTC's topology: these are section 20's rules without lengths, and its search is the one that runs
+  d.lex.node_word = lex->node_word, d.lex.start_node = lex->start_node;
+  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_marked's rules without lengths, and its search runs
   if (!Wt && !forced) return beam_run(what, c, d.lex);
   return beam_run(what, c, d);
 }
@@ -1686,20 +1972,9 @@ int wfl_asg_beam_search_lexicon(const float* x, const float* Wt, const float* lo
     set_error("%s: garbage %d is outside [-1, %d)", what, garbage, C);
     return WFL_ERR_INVALID;
   }
-  if (const int rc = lexicon_shape(what, lex)) return rc;
   BeamAsgLex d;
-  // word v is LM label v, the LM's unused blank is V and </s> is V + 1
-  if (const int rc = beam_lm_terms(what, word_lm, true, lex->num_words + 1, lm_weight, length_bonus, score_eos, &d.lex.lm)) return rc;
-  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(word_bonus) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
-    set_error("%s: lm_weight %g, word_bonus %g and length_bonus %g must be finite", what, lm_weight, word_bonus, length_bonus);
-    return WFL_ERR_INVALID;
-  }
+  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
   d.asg = BeamAsg{Wt, logz, C};
-  d.lex.arc_ptr = lex->arc_ptr, d.lex.arc_label = lex->arc_label, d.lex.arc_next = lex->arc_next;
-  d.lex.has_lm = word_lm ? 1 : 0;
-  d.lex.omega = word_bonus;
-  d.lex.bound = beam_lex_bound(lm_weight, word_lm ? word_lm->step_min : 0.0, word_lm ? word_lm->step_max : 0.0, word_bonus, length_bonus);
-  d.lex.lm.bound = d.lex.bound;
   d.garbage = garbage;
   return beam_run(what, c, d);
 }

@@ -999,18 +999,30 @@ struct DeviceLm {
 
 // A lexicon on the device (wfl_lexicon; lexicon.py's Lexicon.on_device builds one per device): ints = [arc_ptr (N+1) |
 // arc_label (A) | arc_next (A)] int32, contiguous on one GPU, from a pack that passed wfl_lexicon_check on the host.
+// A start-marked lexicon (wfl_lexicon_marked; marked_classes = its C > 0) has [node_word (N) |
+// start_node (C)] behind them, from a pack that passed wfl_lexicon_marked_check; `marked` then, and its trie is `lex`.
 struct DeviceLexicon {
-  at::Tensor ints;  // (kept alive: lex points into it)
+  at::Tensor ints;  // (kept alive: lex and marked point into it)
   wfl_lexicon lex;
-  DeviceLexicon(const at::Tensor& ints_, int64_t N, int64_t A, int64_t V) : ints(ints_) {
+  wfl_lexicon_marked marked;
+  bool is_marked;
+  DeviceLexicon(const at::Tensor& ints_, int64_t N, int64_t A, int64_t V, int64_t marked_classes) : ints(ints_) {
     TORCH_CHECK(N >= 1 && A >= 1 && V >= 1 && N < (1LL << 31) && A < (1LL << 31) && V < (1LL << 31) - 1,
                 "ctc_beam_search_lexicon: a lexicon of ", N, " nodes, ", A, " arcs, ", V, " words");
+    TORCH_CHECK(marked_classes >= 0 && marked_classes < (1LL << 31), "ctc_beam_search_lexicon: a start-marked lexicon of ",
+                marked_classes, " classes");
+    is_marked = marked_classes > 0;
+    const int64_t extra = is_marked ? N + marked_classes : 0;
     TORCH_CHECK(ints.is_cuda() && ints.scalar_type() == at::kInt && ints.is_contiguous() && ints.dim() == 1 &&
-                    ints.numel() == N + 1 + 2 * A,
-                "ctc_beam_search_lexicon: the lexicon's int32 arrays must be one contiguous [N + 1 + 2 A] tensor on a GPU");
+                    ints.numel() == N + 1 + 2 * A + extra,
+                "ctc_beam_search_lexicon: the lexicon's int32 arrays must be one contiguous [N + 1 + 2 A] tensor on a GPU"
+                " ([N + 1 + 2 A + N + C] for a start-marked one)");
     const int32_t* ip = ints.data_ptr<int32_t>();
     lex.num_nodes = (int32_t)N, lex.num_arcs = (int32_t)A, lex.num_words = (int32_t)V, lex.reserved = 0;
     lex.arc_ptr = ip, lex.arc_label = ip + N + 1, lex.arc_next = ip + N + 1 + A;
+    marked.trie = lex;
+    marked.node_word = is_marked ? ip + N + 1 + 2 * A : nullptr;
+    marked.start_node = is_marked ? ip + N + 1 + 2 * A + N : nullptr;
   }
 };
 
@@ -1045,7 +1057,13 @@ Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& len
           [=](int64_t* cap, int64_t* bytes) { check(wfl_ctc_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
             const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
-            if (p.lexicon)
+            if (p.lexicon && p.lexicon->is_marked)
+              check(wfl_ctc_beam_search_lexicon_marked(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
+                                                       normalize ? 1 : 0, &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr,
+                                                       p.lm_weight, p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out,
+                                                       cap, offs, scores, s),
+                    "ctc_beam_search_lexicon_marked");
+            else if (p.lexicon)
               check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
                                                 normalize ? 1 : 0, &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
                                                 p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
@@ -1096,6 +1114,7 @@ struct AsgLexiconPlan {
       : beam(beam_), K(K_), nbest(nbest_), garbage(garbage_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
         word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_) {
     TORCH_CHECK(lexicon, "asg_beam_search_lexicon: a lexicon is needed");
+    TORCH_CHECK(!lexicon->is_marked, "asg_beam_search_lexicon: a start-marked lexicon is not for ASG");
     TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
                 "asg_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
   }
@@ -1171,11 +1190,19 @@ Hypotheses transducer_lexicon_beam_source(const at::Tensor& x, const c10::option
   return {x, e.B, (int64_t)e.B * nbest, true, what,
           [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_transducer_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0,
-                                                     p.beam, p.K, nbest, normalize ? 1 : 0, &p.lexicon->lex,
-                                                     p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus, p.length_bonus,
-                                                     p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                  what);
+            if (p.lexicon->is_marked)
+              check(wfl_transducer_beam_search_lexicon_marked(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank,
+                                                              p.forced ? 1 : 0, p.beam, p.K, nbest, normalize ? 1 : 0,
+                                                              &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
+                                                              p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap,
+                                                              offs, scores, s),
+                    "transducer_beam_search_lexicon_marked");
+            else
+              check(wfl_transducer_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank,
+                                                       p.forced ? 1 : 0, p.beam, p.K, nbest, normalize ? 1 : 0, &p.lexicon->lex,
+                                                       p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus, p.length_bonus,
+                                                       p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                    what);
           }};
 }
 
@@ -1484,8 +1511,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("weights", &DeviceLm::weights);
   py::class_<DeviceLexicon, std::shared_ptr<DeviceLexicon>>(m, "DeviceLexicon",
                                                             "a lexicon's pack on a GPU (lexicon.Lexicon.on_device)")
-      .def(py::init<const at::Tensor&, int64_t, int64_t, int64_t>(), py::arg("ints"), py::arg("num_nodes"), py::arg("num_arcs"),
-           py::arg("num_words"))
+      .def(py::init<const at::Tensor&, int64_t, int64_t, int64_t, int64_t>(), py::arg("ints"), py::arg("num_nodes"),
+           py::arg("num_arcs"), py::arg("num_words"), py::arg("marked_classes") = 0)
       .def_readonly("ints", &DeviceLexicon::ints);
   py::class_<ErrorTables, std::shared_ptr<ErrorTables>>(m, "ErrorTables",
                                                         "both tables of a metrics.ErrorCounter, uploaded, and its separator")

@@ -1098,7 +1098,10 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     step(s, </s>) after the last frame and ranks again; the scores include these terms.  lm None: the call it was.
     lexicon: a lexicon.Lexicon -- the search of wfl_ctc_beam_search_lexicon: only sequences of
     its words are returned, lm (if given) is the word LM over its word ids, a label adds length_bonus and a completed
-    word lm_weight * step(s, word) + word_bonus on top.  lexicon None: the call it was.  The options are one BeamPlan."""
+    word lm_weight * step(s, word) + word_bonus on top.  A start-marked lexicon (lexicon.boundary == "start", DESIGN.md
+    section 26) runs wfl_ctc_beam_search_lexicon_marked: the plan's DeviceLexicon carries the convention, and the word's
+    term arrives with the next word's first label or after the last frame.  lexicon None: the call it was.  The options
+    are one BeamPlan."""
     plan = BeamPlan.checked(x.shape[2], blank, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos,
                             lexicon, word_bonus, "ctc_beam_search")
     return plan.search(x, lengths, normalize)
@@ -1222,7 +1225,7 @@ class AsgLexiconBeamPlan(namedtuple(
         they were given to): what AsgBeamPlan.checked refuses; a garbage outside [0, C); a lexicon that is none or was not
         built for (C, garbage) -- with a garbage class -- or (C + 1, C) -- without one: a phantom blank that is never a
         label --; an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an lm; a
-        number that is not finite."""
+        number that is not finite.  NotImplementedError for a start-marked lexicon."""
         C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
         if garbage is not None:
             g = beam_integer(garbage)
@@ -1234,6 +1237,11 @@ class AsgLexiconBeamPlan(namedtuple(
                                            "without a garbage class") +
                 f" it must have {want[0]} with blank {want[1]} (ASG.lexicon builds it)")
         weight, omega, bonus, lm_eos = beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bonus, lm_eos, what)
+        if lexicon.boundary != "end":
+            raise NotImplementedError(
+                f"{what}: a start-marked lexicon (boundary='start', DESIGN.md section 26) is for CTC and the Transducer -- "
+                f"replabels pack a repeated pair of classes, and how they pack across a word boundary that no separator marks "
+                f"is a question of its own; ASG's grapheme lexicons end in a separator (ASG.lexicon(wordsep=))")
         return cls(C, W, K, n, garbage, lexicon, lm, weight, omega, bonus, lm_eos)
 
     def no_frames(self, B):
@@ -1471,7 +1479,8 @@ def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_siz
     lexicon's words are returned; lm (if given) is the word LM over its word ids; every token adds length_bonus and a
     completed word lm_weight * step(s, word) + word_bonus on top; lm_eos adds lm_weight * step(s, </s>) after the last
     frame.  The scores include these terms.  With Wt None and forced False this is ctc_beam_search(lexicon=) without
-    lengths, bit for bit.  The options are one TransducerLexiconBeamPlan."""
+    lengths, bit for bit.  A start-marked lexicon runs wfl_transducer_beam_search_lexicon_marked:
+    the plan's DeviceLexicon carries the convention.  The options are one TransducerLexiconBeamPlan."""
     what = "transducer_beam_search_lexicon"
     plan = TransducerLexiconBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm,
                                              lm_weight, word_bonus, length_bonus, lm_eos, what)

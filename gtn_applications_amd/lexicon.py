@@ -14,7 +14,16 @@ separator) are prefix-free by construction.
 The word LM convention.  A word-level LM needs no class of its own: word v is LM label v, so
 `NGramLM.from_arpa(path, words, blank=len(words))` is a back-off acceptor over word ids -- V + 1 "classes", index V the
 blank that is never used, and </s> the label V + 1 = lm.num_classes.  check_word_lm() verifies exactly that where the
-two objects meet."""
+two objects meet.
+
+The second boundary convention (boundary="start").  Word pieces carry the word boundary at the
+START of a word ("_the", "_the" + "re"): a word has no separator behind it, a word may be a proper prefix of another and
+may have several spellings, so such a vocabulary is not prefix-free.  A label sequence still has one segmentation if no
+class that begins a word also occurs inside one -- the one condition of a start-marked lexicon: a word has ended where
+the next begins, or where the utterance ends.  Its pack is wfl_lexicon_marked: the same CSR with the leaves stored and
+every arc_next a node, node_word[n] the word whose spelling ends at node n (-1: none) and start_node[c] the root's child
+by class c (-1: c begins no word).  During the search a hypothesis is ranked without the LM term of its last, unfinished
+word."""
 import ctypes
 
 import numpy as np
@@ -26,9 +35,22 @@ class Lexicon:
     """spellings[v]: the non-empty sequence of emission classes that spells word v (separator classes included);
     num_classes: the C of the emissions, blank among them.  ValueError for an empty list, an empty spelling, a class
     outside [0, C), the blank in a spelling, or a pair of words that breaks prefix-freeness (both are named).
-    words: optional names of the words, for messages."""
+    words: optional names of the words, for messages.
+    boundary="start": a start-marked lexicon (the module's docstring).  word_of[k]: the word of spelling k (default k),
+    which is how a word gets several spellings; words then names the word ids.  ValueError for an empty spelling, the
+    blank or a class outside [0, C) in a spelling, two words with one spelling, a word id without a spelling, or a class
+    that both begins a word and occurs inside one (the two words that show it are named)."""
 
-    def __init__(self, spellings, num_classes, blank, words=None):
+    def __init__(self, spellings, num_classes, blank, words=None, boundary="end", word_of=None):
+        if boundary not in ("end", "start"):
+            raise ValueError(f"Lexicon: boundary {boundary!r} is neither 'end' nor 'start'")
+        self.boundary = boundary
+        if boundary == "start":
+            self._init_start(spellings, num_classes, blank, words, word_of)
+            return
+        if word_of is not None:
+            raise ValueError("Lexicon: word_of needs boundary='start' (an end-marked lexicon is prefix-free: a word has "
+                             "one spelling)")
         self.num_classes, self.blank = int(num_classes), int(blank)
         spellings = [tuple(int(c) for c in s) for s in spellings]
         if not spellings:
@@ -97,12 +119,104 @@ class Lexicon:
                       for n in range(self.num_nodes)]
         self._on_device = {}
 
+    def _init_start(self, spellings, num_classes, blank, words, word_of):
+        self.num_classes, self.blank = int(num_classes), int(blank)
+        spellings = [tuple(int(c) for c in s) for s in spellings]
+        if not spellings:
+            raise ValueError("Lexicon: no words")
+        word_of = list(range(len(spellings))) if word_of is None else [int(v) for v in word_of]
+        if len(word_of) != len(spellings):
+            raise ValueError("Lexicon: word_of names one word per spelling")
+        V = max(word_of) + 1 if words is None else len(list(words))
+        self.word_names = None if words is None else list(words)
+        name = (lambda v: repr(self.word_names[v])) if self.word_names is not None else (lambda v: f"word {v}")
+        if self.num_classes < 1 or not 0 <= self.blank < self.num_classes:
+            raise ValueError(f"Lexicon: {self.num_classes} classes, blank {self.blank}")
+        for v in word_of:
+            if not 0 <= v < V:
+                raise ValueError(f"Lexicon: word_of names word {v}, outside [0, {V})")
+        for v in sorted(set(range(V)) - set(word_of)):
+            raise ValueError(f"Lexicon: {name(v)} has no spelling")
+        children, node_word = [{}], [-1]  # node -> {label: child node}; node -> the word that ends there
+        first, inner = {}, {}  # class -> the first word it begins / it occurs inside
+        for s, v in zip(spellings, word_of):
+            if not s:
+                raise ValueError(f"Lexicon: {name(v)} has an empty spelling")
+            for c in s:
+                if not 0 <= c < self.num_classes:
+                    raise ValueError(f"Lexicon: {name(v)} is spelled with class {c}, outside [0, {self.num_classes})")
+                if c == self.blank:
+                    raise ValueError(f"Lexicon: {name(v)} is spelled with the blank {c}")
+            first.setdefault(s[0], v)
+            for c in s[1:]:
+                inner.setdefault(c, v)
+            node = 0
+            for c in s:
+                nxt = children[node].get(c)
+                if nxt is None:
+                    nxt = children[node][c] = len(children)
+                    children.append({})
+                    node_word.append(-1)
+                node = nxt
+            if node_word[node] >= 0:
+                raise ValueError(f"Lexicon: {name(node_word[node])} and {name(v)} have the same spelling: a spelling is "
+                                 f"that of one word" if node_word[node] != v else
+                                 f"Lexicon: {name(v)} is given the same spelling twice")
+            node_word[node] = v
+        for c in sorted(set(first) & set(inner)):
+            raise ValueError(f"Lexicon: class {c} begins {name(first[c])} and occurs inside {name(inner[c])}: in a "
+                             f"start-marked lexicon no class that begins a word occurs inside one")
+        self.spellings, self.word_of = spellings, word_of
+        # breadth first from the root, children in label order
+        order, number = [0], {0: 0}
+        for n in order:
+            for c in sorted(children[n]):
+                number[children[n][c]] = len(order)
+                order.append(children[n][c])
+        arc_ptr, arc_label, arc_next = [0], [], []
+        for n in order:
+            for c in sorted(children[n]):
+                arc_label.append(c)
+                arc_next.append(number[children[n][c]])
+            arc_ptr.append(len(arc_label))
+        start = [-1] * self.num_classes
+        for c, k in children[0].items():
+            start[c] = number[k]
+        self.arc_ptr = np.asarray(arc_ptr, dtype=np.int32)
+        self.arc_label = np.asarray(arc_label, dtype=np.int32)
+        self.arc_next = np.asarray(arc_next, dtype=np.int32)
+        self.node_word = np.asarray([node_word[n] for n in order], dtype=np.int32)
+        self.start_node = np.asarray(start, dtype=np.int32)
+        self.num_nodes, self.num_arcs, self.num_words = len(order), len(arc_label), V
+        desc = self.marked_desc()
+        if N.lib.wfl_lexicon_marked_check(ctypes.byref(desc), self.num_classes, self.blank) != N.WFL_OK:
+            raise ValueError(f"Lexicon: {N.last_error()}")
+        self._arcs = [{int(arc_label[a]): int(arc_next[a]) for a in range(arc_ptr[n], arc_ptr[n + 1])}
+                      for n in range(self.num_nodes)]
+        self._on_device = {}
+
+    def marked_desc(self):
+        """the wfl_lexicon_marked of a start-marked lexicon's host arrays (they must outlive it)"""
+        trie = N.Lexicon(self.num_nodes, self.num_arcs, self.num_words, 0, self.arc_ptr.ctypes.data,
+                         self.arc_label.ctypes.data, self.arc_next.ctypes.data)
+        return N.LexiconMarked(trie, self.node_word.ctypes.data, self.start_node.ctypes.data)
+
     @classmethod
-    def from_words(cls, words, tokens, blank, wordsep=None, split=None):
+    def from_words(cls, words, tokens, blank, wordsep=None, split=None, boundary="end", splits=None):
         """words: strings; tokens: the model's tokens in class order without the blank, blank: its class index, so token
         i is class i below the blank and i + 1 from it on (the convention of NGramLM.from_arpa).  A word is split into
         its characters, or by split(word) -> list of tokens (word pieces); with `wordsep` that token's class ends every
-        spelling.  ValueError names a word with a piece that is no token."""
+        spelling.  ValueError names a word with a piece that is no token.
+        boundary="start": a start-marked lexicon; the marker is part of the pieces, so `wordsep` is refused;
+        splits(word) -> a list of decompositions, each a list of pieces: every one becomes a spelling of the word."""
+        if boundary not in ("end", "start"):
+            raise ValueError(f"Lexicon.from_words: boundary {boundary!r} is neither 'end' nor 'start'")
+        if boundary == "start" and wordsep is not None:
+            raise ValueError("Lexicon.from_words: with boundary='start' the word boundary is part of the pieces: no wordsep")
+        if splits is not None and boundary != "start":
+            raise ValueError("Lexicon.from_words: splits (several decompositions of a word) needs boundary='start'")
+        if splits is not None and split is not None:
+            raise ValueError("Lexicon.from_words: split gives one decomposition per word, splits several: give one of them")
         tokens, blank = list(tokens), int(blank)
         if not 0 <= blank <= len(tokens):
             raise ValueError(f"Lexicon.from_words: blank {blank} is outside [0, {len(tokens)}]")
@@ -112,20 +226,42 @@ class Lexicon:
         if wordsep is not None and wordsep not in label:
             raise ValueError(f"Lexicon.from_words: the word separator {wordsep!r} is not one of the model's tokens")
         words = list(words)
-        spellings = []
-        for w in words:
-            pieces = list(w) if split is None else list(split(w))
-            for p in pieces:
-                if p not in label:
-                    raise ValueError(f"Lexicon.from_words: {p!r} of {w!r} is not one of the model's tokens")
-            spellings.append([label[p] for p in pieces] + ([label[wordsep]] if wordsep is not None else []))
+        spellings, word_of = [], []
+        for v, w in enumerate(words):
+            ways = [list(w) if split is None else list(split(w))] if splits is None else [list(d) for d in splits(w)]
+            for pieces in ways:
+                for p in pieces:
+                    if p not in label:
+                        raise ValueError(f"Lexicon.from_words: {p!r} of {w!r} is not one of the model's tokens")
+                spellings.append([label[p] for p in pieces] + ([label[wordsep]] if wordsep is not None else []))
+                word_of.append(v)
+        if boundary == "start":
+            return cls(spellings, len(tokens) + 1, blank, words=words, boundary="start", word_of=word_of)
         return cls(spellings, len(tokens) + 1, blank, words=words)
 
     # ------------------------------------------------------------------------------------------------------------
     def walk(self, labels):
         """(word ids, node): the one segmentation of the label sequence into words and the trie node it ends in (0:
-        at a word boundary); None if the sequence leaves the trie"""
+        at a word boundary); None if the sequence leaves the trie.  A start-marked lexicon (DESIGN.md section 26 rule
+        5): a word ends where the next begins or, if the node is terminal, with the sequence -- the last word counts
+        then; node 0 is the empty sequence alone."""
         found, node = [], 0
+        if self.boundary == "start":
+            for c in labels:
+                c = int(c)
+                if 0 <= c < self.num_classes and self.start_node[c] >= 0:
+                    if node != 0:
+                        if self.node_word[node] < 0:
+                            return None
+                        found.append(int(self.node_word[node]))
+                    node = int(self.start_node[c])
+                else:
+                    node = self._arcs[node].get(c) if node != 0 else None
+                    if node is None:
+                        return None
+            if node != 0 and self.node_word[node] >= 0:
+                found.append(int(self.node_word[node]))
+            return found, node
         for c in labels:
             nxt = self._arcs[node].get(int(c))
             if nxt is None:
@@ -142,14 +278,15 @@ class Lexicon:
         at = self.walk(labels)
         if at is None:
             raise ValueError("Lexicon.words: the labels leave the lexicon")
-        if at[1] != 0:
+        if at[1] != 0 and (self.boundary == "end" or self.node_word[at[1]] < 0):
             raise ValueError("Lexicon.words: the labels end inside a word")
         return at[0]
 
     def on_device(self, device):
         """the operators' DeviceLexicon (csrc/torch_ops.cpp) of this pack on `device`: `.ints` int32 [arc_ptr |
-        arc_label | arc_next] there and the wfl_lexicon that points into it.  Uploaded once per device and kept, as
-        NGramLM.on_device keeps its pack."""
+        arc_label | arc_next] there and the wfl_lexicon that points into it; a start-marked lexicon's [node_word |
+        start_node] behind them, and the wfl_lexicon_marked.  Uploaded once per device and kept, as NGramLM.on_device
+        keeps its pack."""
         import torch
 
         device = torch.device(device)
@@ -158,9 +295,11 @@ class Lexicon:
         index = torch.cuda.current_device() if device.index is None else device.index
         held = self._on_device.get(index)
         if held is None:
-            ints = np.concatenate([self.arc_ptr, self.arc_label, self.arc_next])
+            marked = self.boundary == "start"
+            ints = np.concatenate([self.arc_ptr, self.arc_label, self.arc_next] + ([self.node_word, self.start_node] if marked else []))
             held = self._on_device[index] = N.ops.DeviceLexicon(torch.from_numpy(ints).to(torch.device("cuda", index)),
-                                                                self.num_nodes, self.num_arcs, self.num_words)
+                                                                self.num_nodes, self.num_arcs, self.num_words,
+                                                                self.num_classes if marked else 0)
         return held
 
 

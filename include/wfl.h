@@ -681,8 +681,8 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths /* or NULL */,
  *   no global atomics, no cross-workgroup waits, every loop bounded by T_b, W, K, the back-off cap or 31 search steps.
  *   WFL_ERR_INVALID: what wfl_ctc_beam_search refuses; lex or one of its arrays NULL, num_nodes, num_arcs or num_words
  *   < 1 (or num_words = 2^31 - 1: </s> is V + 1); a weight or bonus that is not finite; for a non-NULL word_lm what wfl_ctc_beam_search_lm refuses.
- *   Not here: a token-level LM together with a lexicon, LM look-ahead inside words, several spellings of one word,
- *   out-of-vocabulary arcs.
+ *   Not here: a token-level LM together with a lexicon, LM look-ahead inside words, out-of-vocabulary arcs.  Several
+ *   spellings of one word and vocabularies that are not prefix-free: wfl_ctc_beam_search_lexicon_marked below.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct wfl_lexicon {
   int32_t num_nodes, num_arcs, num_words, reserved;
@@ -701,6 +701,69 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths /* or NUL
                                 const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
                                 double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                                 int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The lexicon searches with a START-MARKED lexicon (csrc/beam_kernels.hip): word pieces as they are,
+ * the word boundary carried by the class that BEGINS a word.  Such a vocabulary is not prefix-free (a word may be a
+ * proper prefix of another, a word may have several spellings), yet a label sequence still has one segmentation: a
+ * word has ended where the next one begins, or where the utterance ends.  Every rule of wfl_ctc_beam_search_lexicon
+ * (and of wfl_transducer_beam_search_lexicon) stands unless replaced here; a = lm_weight, o = word_bonus, b = length_bonus.
+ *     1. the lexicon: a trie with root 0 in wfl_lexicon's CSR whose nodes may be terminal: node_word[n] = v >= 0 where a
+ *        spelling of word v ends, -1 otherwise.  Leaves are stored: every arc_next is a node >= 1.  A node without arcs
+ *        is terminal; the root is not.  Several terminal nodes may carry one word id (several spellings of a word); a
+ *        spelling is that of one word.  Spellings may be proper prefixes of one another.  The one structural condition:
+ *        the set R of labels on the root's arcs is disjoint from the labels of all deeper arcs.  start_node[c], c in
+ *        [0, C), is the root's child by c, -1 if c is not in R;
+ *     2. every hypothesis carries a trie node and, with a word LM, an LM state: the history of the COMPLETED words.
+ *        Only the empty prefix is at the root.  Both are functions of the prefix;
+ *     3. the extension i + c, s + base as in the end-marked search, -inf: it does not exist and is not looked up.
+ *        c not in R: c is searched among the arcs of node_i (the bounded binary search); absent, or node_i the root: the
+ *        extension does not exist; present: e = (s + base) + b, the node is the arc's target, the state stays.
+ *        c in R from the root: e = (s + base) + b, the node is start_node[c], the state stays.
+ *        c in R from a node with v = node_word[node_i] >= 0: (l, nxt) = step(state_i, v), (0, -) without an LM; l = -inf:
+ *        the extension does not exist; otherwise e = (s + base) + ((a l + o) + b), each operation rounded on its own,
+ *        the node is start_node[c] and the state nxt.  c in R from a non-terminal node: the extension does not exist;
+ *     4. stays, merging by prefix, candidates, entry order, the tie rule, the -inf drop rule and the prune bound do not
+ *        change: every term is b or (a l + o) + b, so max(0, max(a step_min, a step_max) + o) + b still bounds it;
+ *     5. after the last frame: a rank at the root (the empty sequence) keeps its score; a rank at a terminal node gets
+ *        + (a l + o) for its pending word, (l, nxt) = step(state, node_word[node]), moves to nxt, and is dropped if
+ *        l = -inf; a rank at any other node is dropped.  Then the </s> term, the re-ranking and nbest as in the
+ *        end-marked search, T_b = 0 included (the Transducer: the topology's score first, as in its rule 5);
+ *     6. unpruned, tot(l) = mass(l) + a LM(words(l)) + o #words + b |l| plus the </s> term for every l that ends at a
+ *        terminal node.  Two spellings of the same words are different label sequences and separate hypotheses;
+ *     7. during the search a hypothesis is ranked WITHOUT the LM term of its pending (last, unfinished) word: that term
+ *        arrives with the next word's first label or at the end.  A property, not a defect.
+ *   The same workspace functions, outputs, three launches, refusals and guarantees as the end-marked siblings: no
+ *   allocation, no synchronisation, no global atomics, no cross-workgroup waits, every loop bounded.  lex: a struct in HOST
+ *   memory of DEVICE pointers to a pack that wfl_lexicon_marked_check accepted with host pointers; the kernels trust it.
+ *   WFL_ERR_INVALID besides the siblings': node_word or start_node NULL.  The Transducer entry with Wt == NULL and
+ *   forced == 0 runs the CTC entry's search: bit-identical results.
+ *   Not here: ASG, a token-level LM together with a lexicon, LM look-ahead, merging by spelling together with a lexicon,
+ *   out-of-vocabulary arcs.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct wfl_lexicon_marked {
+  wfl_lexicon trie;          /* arc_next: every target a node in [1, num_nodes) */
+  const int32_t* node_word;  /* [num_nodes], the word whose spelling ends at the node, -1: none */
+  const int32_t* start_node; /* [C], the root's child by the class, -1: the class starts no word */
+} wfl_lexicon_marked;
+/* The pack check (host arrays, no device), every clause of rule 1: sizes >= 1, arc_ptr ascending from 0 to num_arcs;
+ * labels strictly ascending within a node, in [0, C), never the blank; every target in [1, num_nodes) and the target of
+ * exactly one arc, every node reached from the root (a tree rooted at node 0); node_word in [-1, num_words), -1 at the
+ * root, >= 0 at a node without arcs; every word id on at least one node; start_node[c] the root's child by c or -1; no
+ * label of a root arc on a deeper arc.  WFL_ERR_INVALID names the first offence in wfl_last_error(). */
+int wfl_lexicon_marked_check(const wfl_lexicon_marked* lex, int C, int blank);
+int wfl_ctc_beam_search_lexicon_marked(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank,
+                                       int beam, int classes_per_frame, int nbest, int normalize, const wfl_lexicon_marked* lex,
+                                       const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
+                                       double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                       int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt /* [(C+1), C] or NULL */,
+                                              const float* logz /* [B] or NULL */, int B, int T, int C, int blank, int forced,
+                                              int beam, int classes_per_frame, int nbest, int normalize,
+                                              const wfl_lexicon_marked* lex, const wfl_ngram_lm* word_lm /* or NULL */,
+                                              double lm_weight, double word_bonus, double length_bonus, int score_eos, void* ws,
+                                              int32_t* out, int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                              double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: ASG prefix beam search (csrc/beam_kernels.hip)
@@ -951,8 +1014,9 @@ int wfl_transducer_beam_search_merged(const float* x, const float* Wt /* [(C+1),
  *   31 search steps.
  *   WFL_ERR_INVALID: what wfl_transducer_beam_search refuses, in its order; then lex or one of its arrays NULL,
  *   num_nodes, num_arcs or num_words < 1 (or num_words = 2^31 - 1); for a non-NULL word_lm what wfl_ctc_beam_search_lm
- *   refuses; a weight or bonus that is not finite.  Not here: a token-level LM, LM look-ahead inside words, several
- *   spellings of one word, merging by spelling, input lengths, the ambiguous token graphs.
+ *   refuses; a weight or bonus that is not finite.  Not here: a token-level LM, LM look-ahead inside words, merging by
+ *   spelling, input lengths, the ambiguous token graphs.  Several spellings of one word and vocabularies that are not
+ *   prefix-free: wfl_transducer_beam_search_lexicon_marked.
  * ------------------------------------------------------------------------------------------------ */
 int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] or NULL */,
                                        const float* logz /* [B] or NULL */, int B, int T, int C, int blank, int forced, int beam,
