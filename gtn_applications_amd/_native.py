@@ -64,6 +64,14 @@ class LexiconMarked(ctypes.Structure):
     _fields_ = [("trie", Lexicon), ("node_word", c_void_p), ("start_node", c_void_p)]
 
 
+class LexiconLookahead(ctypes.Structure):
+    """Mirror of `wfl_lexicon_lookahead` (include/wfl.h): node_look a host pointer for the two look-ahead checks, which write
+    the six ranges, a device pointer for a search."""
+
+    _fields_ = [("node_look", c_void_p)] + [
+        (n, c_double) for n in ("arc_min", "arc_max", "end_min", "end_max", "start_min", "start_max")]
+
+
 class LatticeDesc(ctypes.Structure):
     """Mirror of `wfl_lattice_desc` (include/wfl.h) -- field order and types must match."""
 
@@ -236,6 +244,22 @@ _SIGS = {
     "wfl_transducer_beam_search_lexicon_marked": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                           c_int, POINTER(LexiconMarked), POINTER(NgramLm), c_double, c_double,
                                                           c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    # device: the lexicon searches with word-LM look-ahead
+    "wfl_lexicon_lookahead_check": (c_int, [POINTER(Lexicon), POINTER(LexiconLookahead)]),
+    "wfl_lexicon_marked_lookahead_check": (c_int, [POINTER(LexiconMarked), POINTER(LexiconLookahead)]),
+    "wfl_ctc_beam_search_lexicon_lookahead": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                      POINTER(Lexicon), POINTER(LexiconLookahead), POINTER(NgramLm), c_double,
+                                                      c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_ctc_beam_search_lexicon_marked_lookahead": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                             POINTER(LexiconMarked), POINTER(LexiconLookahead), POINTER(NgramLm),
+                                                             c_double, c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_transducer_beam_search_lexicon_lookahead": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                             c_int, POINTER(Lexicon), POINTER(LexiconLookahead), POINTER(NgramLm),
+                                                             c_double, c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_transducer_beam_search_lexicon_marked_lookahead": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                                    c_int, c_int, POINTER(LexiconMarked),
+                                                                    POINTER(LexiconLookahead), POINTER(NgramLm), c_double,
+                                                                    c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     "wfl_transducer_beam_search_merged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path

@@ -327,6 +327,14 @@ def ASGLoss(*args):
     return E.make_eager(ASGLossFunction.apply(*args))
 
 
+def _refuse_lookahead(what, lookahead):
+    if lookahead is not None:
+        raise NotImplementedError(
+            f"{what}: lookahead (word-LM look-ahead inside words, DESIGN.md section 27) is for CTC and the Transducer -- "
+            "ASG's stay entries look one extension up per hypothesis for their prune bound, and what look-ahead does to "
+            "that bound is a question of its own")
+
+
 def _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus):
     """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default"""
     if lm is not None:
@@ -459,7 +467,7 @@ class ASG(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False, lexicon=None, lm=None,
-                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
         """ASG prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame path
         under emissions + transitions; the criterion scores a label sequence by the sum over all its alignments (the
         force-align numerator, asg.py:72-115), and this returns the sequences it rates highest (DESIGN.md section 21 has
@@ -484,7 +492,9 @@ class ASG(torch.nn.Module):
         word spelled `a a` is found as raw `a, replabel 0`, never as raw `a, garbage, a`, which unpacks to the same
         tokens but does not walk the trie.  Without a lexicon the call is what it was, and lm, lm_weight, length_bonus,
         lm_eos and word_bonus must be at their defaults (ValueError).  B == 0 or T == 0 with a lexicon: the empty
-        sequence, scored by the LM's </s> alone."""
+        sequence, scored by the LM's </s> alone.  lookahead (CTC's and the Transducer's): anything
+        but None raises NotImplementedError, as a start-marked lexicon does."""
+        _refuse_lookahead("ASG.beam_search", lookahead)
         plan = self._beam_plan(outputs, "ASG.beam_search", beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight,
                                length_bonus, lm_eos, word_bonus)
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
@@ -499,14 +509,15 @@ class ASG(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, lexicon=None, lm=None,
-               lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
         beam launches on their device buffers; `classes_per_frame` needs a beam_size.  lexicon, lm, lm_weight,
         length_bonus, lm_eos, word_bonus: beam_search's, with a beam_size: the predictions are those of the search with
-        a lexicon."""
+        a lexicon.  lookahead: refused, as by beam_search."""
+        _refuse_lookahead("ASG.errors", lookahead)
         if beam_size is None:
             if classes_per_frame is not None:
                 raise ValueError("ASG.errors: classes_per_frame needs a beam_size")

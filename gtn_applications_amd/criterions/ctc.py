@@ -394,14 +394,14 @@ class CTC(torch.nn.Module):
         flat, kept = E.collapse_rows(best, drop=self.blank)  # (the whole batch at once: no loop over the rows)
         return E.split_rows(flat, kept, torch.int64)
 
-    def _beam_plan(self, outputs, input_lengths, what, *options):
+    def _beam_plan(self, outputs, input_lengths, what, *options, lookahead=None):
         """The arguments of a beam search, checked before anything needs a device: (the E.BeamPlan of `options`, which
-        are BeamPlan.checked's from beam_size to word_bonus; lengths or None)"""
+        are BeamPlan.checked's from beam_size to word_bonus, and of `lookahead`; lengths or None)"""
         E.check_beam_outputs(outputs, what)
         B, T, C = outputs.shape
         if C < 1:
             raise ValueError(f"{what}: outputs have no classes")
-        plan = E.BeamPlan.checked(C, self.blank, *options, what)
+        plan = E.BeamPlan.checked(C, self.blank, *options, what, lookahead=lookahead)
         return plan, None if input_lengths is None else check_input_lengths(input_lengths, B, T, what)
 
     @staticmethod
@@ -412,7 +412,7 @@ class CTC(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, input_lengths=None, return_scores=False,
-                    lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
+                    lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0, lookahead=None):
         """CTC prefix beam search (an addition: the reference has the greedy decode only).  viterbi() maximises over
         frame paths; this maximises over label sequences, whose probability is the sum over all their alignments
         (DESIGN.md section 17 has the rules; csrc/beam_kernels.hip runs them, in float64).  Per frame only the
@@ -434,10 +434,14 @@ class CTC(torch.nn.Module):
         boundary="start"), DESIGN.md section 26: word pieces that carry the word boundary at the start of a word, words
         that are prefixes of one another or have several spellings) is taken as it is: a word then ends where the next
         begins or with the utterance, and a hypothesis is ranked without the LM term of its last, unfinished word until
-        then.  `word_bonus` needs a lexicon.  CTC's search: ASG has
+        then.  `word_bonus` needs a lexicon.  `lookahead` (it needs a lexicon and an lm): "unigram"
+        or an array of one finite score per word -- the best score of the words below a trie node is paid provisionally,
+        times lm_weight, while a word is being spelled and settled where the word ends, so that a narrow beam ranks a
+        hypothesis by the word the LM wants; unpruned the results are those without it.  "unigram" takes
+        lm.unigram_scores(), a word without one the smallest of the others.  CTC's search: ASG has
         its own (ASG.beam_search), the Transducer's token graphs have none."""
         plan, lens = self._beam_plan(outputs, input_lengths, "CTC.beam_search", beam_size, classes_per_frame, nbest, lm,
-                                     lm_weight, length_bonus, lm_eos, lexicon, word_bonus)
+                                     lm_weight, length_bonus, lm_eos, lexicon, word_bonus, lookahead=lookahead)
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0])
         else:
@@ -451,19 +455,20 @@ class CTC(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, input_lengths=None, beam_size=None, classes_per_frame=None, lm=None,
-               lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0, lookahead=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `input_lengths`
         (an addition, see CTCLoss): the predictions are viterbi(outputs, input_lengths)'s.  `beam_size` (an addition):
         the predictions are beam_search(outputs, beam_size, classes_per_frame, input_lengths=input_lengths)'s instead,
         counted behind the beam launch on its device buffers; `lm`, `lm_weight`, `length_bonus`, `lm_eos`, `lexicon`,
-        `word_bonus` are beam_search's and need a beam_size."""
+        `word_bonus`, `lookahead` are beam_search's and need a beam_size."""
         if beam_size is None:
-            E.BeamPlan.refuse_without_beam(lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, "CTC.errors")
+            E.BeamPlan.refuse_without_beam(lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, "CTC.errors",
+                                           lookahead=lookahead)
         else:
             plan, lens = self._beam_plan(outputs, input_lengths, "CTC.errors", beam_size, classes_per_frame, 1, lm, lm_weight,
-                                         length_bonus, lm_eos, lexicon, word_bonus)
+                                         length_bonus, lm_eos, lexicon, word_bonus, lookahead=lookahead)
             C = outputs.shape[2]
             counter.check_hypothesis_labels(C - 1 if self.blank == C - 1 else C, "CTC.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:

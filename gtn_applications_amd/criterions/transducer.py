@@ -384,7 +384,7 @@ class Transducer(torch.nn.Module):
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
 
     def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest, lexicon=None, lm=None, lm_weight=1.0,
-                   length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+                   length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
         """The arguments of a beam search, checked before anything needs a device: (the E.TransducerBeamPlan of the
         options -- with a lexicon the E.TransducerLexiconBeamPlan; without one every keyword of the lexicon search must
         be at its default --, the transition model's kind: "none", "unigram" or "bigram")"""
@@ -408,11 +408,14 @@ class Transducer(torch.nn.Module):
                 raise NotImplementedError(f"{what}: the transition model is neither make_transitions_graph(1, C) nor "
                                           "(2, C): only no model, the unigram and the bigram model are searched")
         if lexicon is None:
+            if lookahead is not None:
+                raise ValueError(f"{what}: lookahead needs a lexicon and its word lm")
             _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
             plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
         else:
             plan = E.TransducerLexiconBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest,
-                                                       lexicon, lm, lm_weight, word_bonus, length_bonus, lm_eos, what)
+                                                       lexicon, lm, lm_weight, word_bonus, length_bonus, lm_eos, what,
+                                                       lookahead=lookahead)
         return plan, kind
 
     def word_lexicon(self, words, wordsep=None, split=None, boundary="end", splits=None):
@@ -512,7 +515,8 @@ class Transducer(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False,
-                    merge_spellings=False, lexicon=None, lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+                    merge_spellings=False, lexicon=None, lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0,
+                    lookahead=None):
         """Transducer prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame
         path; the criterion scores a token sequence by the sum over all its alignments, and this returns the token
         sequences it rates highest (DESIGN.md section 22 has the rules; csrc/beam_kernels.hip runs them, in float64).
@@ -548,11 +552,14 @@ class Transducer(torch.nn.Module):
         boundary="start"), DESIGN.md section 26: word pieces that carry the word boundary at the start of a word, words
         that are prefixes of one another, several spellings of a word through splits=) is taken as it is: a word ends
         where the next begins or with the utterance, two spellings of the same words are separate hypotheses, and a
-        hypothesis is ranked without the LM term of its last, unfinished word until then.  No token-level LM, LM
-        look-ahead or input lengths."""
+        hypothesis is ranked without the LM term of its last, unfinished word until then.  lookahead (DESIGN.md section
+        27; it needs a lexicon and an lm): "unigram" or an array of one finite score per word -- lm_weight times the best
+        score of the words below a trie node is paid provisionally while a word is being spelled and settled where the
+        word ends, so that a narrow beam ranks a hypothesis by the word the LM wants; unpruned the results are those
+        without it.  No token-level LM or input lengths."""
         what = "Transducer.beam_search"
         plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, length_bonus,
-                                     lm_eos, word_bonus)
+                                     lm_eos, word_bonus, lookahead)
         spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what, lexicon) else None
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
@@ -569,15 +576,17 @@ class Transducer(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, merge_spellings=False, lexicon=None,
-               lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+               lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
         beam launches on their device buffers; `classes_per_frame` and `merge_spellings` (beam_search's: the predictions
         are the representatives of the best spellings) need a beam_size.  lexicon, lm, lm_weight, length_bonus, lm_eos,
-        word_bonus: beam_search's, with a beam_size: the predictions are those of the search with a lexicon."""
+        word_bonus, lookahead: beam_search's, with a beam_size: the predictions are those of the search with a lexicon."""
         merge = self._merge_flag(merge_spellings, "Transducer.errors", lexicon)
+        if beam_size is None and lookahead is not None:
+            raise ValueError("Transducer.errors: lookahead needs a beam_size")
         if beam_size is None:
             if classes_per_frame is not None or merge:
                 raise ValueError("Transducer.errors: classes_per_frame and merge_spellings need a beam_size")
@@ -586,7 +595,7 @@ class Transducer(torch.nn.Module):
             _refuse_without_lexicon("Transducer.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
         else:
             plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
-                                         length_bonus, lm_eos, word_bonus)
+                                         length_bonus, lm_eos, word_bonus, lookahead)
             spelling = self._spelling(plan, "Transducer.errors") if merge else None
             counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:

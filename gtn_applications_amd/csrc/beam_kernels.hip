@@ -49,7 +49,11 @@
 // ends where the next begins or with the utterance): the packs BeamLexMarked and BeamTokLexMarked add node_word and
 // start_node to their siblings' fields, selected at compile time -- another step function, the node behind a word in
 // place(), the pending word's term in the final block; the siblings' kernels are the code they were.
-// All ten issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// The four *_lookahead entries are the lexicon searches of CTC and the Transducer, end- and start-marked, with unigram max
+// look-ahead of the word LM inside words: BeamLook<sibling's pack> adds node_look, the best word
+// score below every trie node; a hypothesis pays lm_weight node_look[node] provisionally on the way down a word and
+// settles it where the word ends, so the totals are the siblings' and a narrow beam ranks by the word the LM wants.
+// All fourteen issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -273,11 +277,40 @@ inline double beam_lex_bound(double alpha, double step_min, double step_max, dou
 
 constexpr int kLexAbsent = -2147483647 - 1;  // no arc_next: word ids are below 2^31 - 1
 
+// Word-LM look-ahead (wfl_lexicon_lookahead): look[n] is the best word score below trie node n, 0 at
+// the root; a hypothesis at node n has paid alpha look[n] provisionally.  The three terms that move it, every operation
+// rounded on its own, on the host (wfl_lexicon_lookahead_check, beam_look_bound) and on the device alike:
+// an inner arc n -> m costs (alpha (look[m] - look[n])) + beta (rule 1);
+__host__ __device__ inline double beam_look_arc_diff(double look_to, double look_from) {
+#pragma clang fp contract(off)
+  return look_to - look_from;  // (the check records the range of exactly this value)
+}
+__host__ __device__ inline double beam_look_inner_term(double alpha, double look_to, double look_from, double beta) {
+#pragma clang fp contract(off)
+  const double d = beam_look_arc_diff(look_to, look_from);
+  const double ad = alpha * d;
+  return ad + beta;
+}
+// the LM step of a word that completes at node n is settled against what was paid: l - look[n] (rules 2 and 4);
+__host__ __device__ inline double beam_look_settled(double l, double look_at) {
+#pragma clang fp contract(off)
+  return l - look_at;
+}
+// a start-marked word's first label behind a word pays the first node's share on top of the word's term (rule 3)
+__host__ __device__ inline double beam_look_start_term(double alpha, double term, double look_start) {
+#pragma clang fp contract(off)
+  const double al = alpha * look_start;
+  return term + al;
+}
+
 // The extension of a hypothesis at trie node `node` with LM state `state` by class c: its term, -inf if it does not
 // exist (no such arc, or a word the LM cannot follow the history with).  enc: where the new hypothesis stands -- an
 // inner node n as n >= 0 (the LM state stays), the root behind a word as -(next LM state + 1).  The search among the
-// node's arcs is bounded like the LM's: 31 halvings.
-__device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int state, int c, int& enc) {
+// node's arcs is bounded like the LM's: 31 halvings.  LOOK: the terms of section 27 (look: node_look), one 8-byte load
+// per end of the arc; without it `look` is not read and the function is the one it was.
+template <bool LOOK>
+__device__ __forceinline__ double beam_lex_step_at(const BeamLex& lx, const double* __restrict__ look, int node, int state,
+                                                   int c, int& enc) {
   const int end = lx.arc_ptr[node + 1];
   int lo = lx.arc_ptr[node], hi = end;
   for (int it = 0; it < 31 && lo < hi; ++it) {  // the first arc whose label is not below c
@@ -292,6 +325,7 @@ __device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int
   if (nx == kLexAbsent) return -__builtin_inf();
   if (nx >= 0) {
     enc = nx;
+    if constexpr (LOOK) return beam_look_inner_term(lx.lm.alpha, look[nx], look[node], lx.lm.beta);
     return lx.lm.beta;
   }
   double l = 0.0;
@@ -301,7 +335,11 @@ __device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int
     if (!(l > -__builtin_inf())) return -__builtin_inf();
   }
   enc = -(ns + 1);
+  if constexpr (LOOK) l = beam_look_settled(l, look[node]);
   return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
+}
+__device__ __forceinline__ double beam_lex_step(const BeamLex& lx, int node, int state, int c, int& enc) {
+  return beam_lex_step_at<false>(lx, nullptr, node, state, c, enc);
 }
 
 // A start-marked lexicon (wfl_lexicon_marked): BeamLex's trie with stored leaves and all arc targets
@@ -325,7 +363,10 @@ __device__ __forceinline__ double beam_lex_pending_term(double alpha, double l, 
 // word -- the bounded search among the node's arcs (none at the root, whose arcs all start words), the state stays; c
 // starts a word from the root -- its child, the state stays; from a terminal node -- the LM step of the word that ends
 // there, enc = -(next LM state + 1) and place() takes the node from start_node[c]; from any other node -- nothing.
-__device__ __forceinline__ double beam_lex_step_marked(const BeamLexMarked& m, int node, int state, int c, int& enc) {
+// LOOK: section 27's terms, as in beam_lex_step_at (the root's look is 0 by wfl_lexicon_marked_lookahead_check).
+template <bool LOOK>
+__device__ __forceinline__ double beam_lex_step_marked_at(const BeamLexMarked& m, const double* __restrict__ look, int node,
+                                                          int state, int c, int& enc) {
   const BeamLex& lx = m.lex;
   enc = 0;
   const int sn = m.start_node[c];
@@ -342,10 +383,12 @@ __device__ __forceinline__ double beam_lex_step_marked(const BeamLexMarked& m, i
     }
     if (!(lo < end && lx.arc_label[lo] == c)) return -__builtin_inf();
     enc = lx.arc_next[lo];
+    if constexpr (LOOK) return beam_look_inner_term(lx.lm.alpha, look[enc], look[node], lx.lm.beta);
     return lx.lm.beta;
   }
   if (node == 0) {
     enc = sn;
+    if constexpr (LOOK) return beam_look_inner_term(lx.lm.alpha, look[sn], 0.0, lx.lm.beta);
     return lx.lm.beta;
   }
   const int v = m.node_word[node];
@@ -357,7 +400,14 @@ __device__ __forceinline__ double beam_lex_step_marked(const BeamLexMarked& m, i
     if (!(l > -__builtin_inf())) return -__builtin_inf();
   }
   enc = -(ns + 1);
+  if constexpr (LOOK) {
+    const double term = beam_lex_word_term(lx.lm.alpha, beam_look_settled(l, look[node]), lx.omega, lx.lm.beta);
+    return beam_look_start_term(lx.lm.alpha, term, look[sn]);
+  }
   return beam_lex_word_term(lx.lm.alpha, l, lx.omega, lx.lm.beta);
+}
+__device__ __forceinline__ double beam_lex_step_marked(const BeamLexMarked& m, int node, int state, int c, int& enc) {
+  return beam_lex_step_marked_at<false>(m, nullptr, node, state, c, enc);
 }
 
 // the transitions of an ASG launch (wfl_asg_beam_search): Wt [(C+1), C] float32 in the criterion's layout (asg.py:54-69:
@@ -446,6 +496,48 @@ __device__ __forceinline__ double beam_lex_ext(const BeamTokLexMarked& a, int no
   return beam_lex_step_marked(a.lex, node, state, c, enc);
 }
 
+// The four lexicon searches of CTC and the Transducer with word-LM look-ahead (the wfl_*_beam_search_lexicon*_lookahead
+// entries): the sibling's pack and node_look [num_nodes] behind it, selected at compile time -- the
+// step functions' LOOK terms and the pending word's settled step in the final block; the siblings' kernels are the code
+// they were.  The lexicon's `bound` is beam_look_bound's there.
+template <typename P>
+struct BeamLook {
+  P pack;
+  const double* node_look;
+};
+using BeamLexLook = BeamLook<BeamLex>;
+using BeamLexMarkedLook = BeamLook<BeamLexMarked>;
+using BeamTokLexLook = BeamLook<BeamTokLex>;
+using BeamTokLexMarkedLook = BeamLook<BeamTokLexMarked>;
+template <typename P>
+__device__ __forceinline__ const BeamLex& beam_lex_of(const BeamLook<P>& a) {
+  return beam_lex_of(a.pack);
+}
+template <typename P>
+__device__ __forceinline__ const BeamLexMarked& beam_lex_marked_of(const BeamLook<P>& a) {
+  return beam_lex_marked_of(a.pack);
+}
+template <typename P>
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamLook<P>& a) {
+  return beam_tok_of(a.pack);
+}
+template <typename P>
+__device__ __forceinline__ const double* beam_look_of(const BeamLook<P>& a) {
+  return a.node_look;
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamLexLook& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_at<true>(a.pack, a.node_look, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamTokLexLook& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_at<true>(a.pack.lex, a.node_look, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamLexMarkedLook& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_marked_at<true>(a.pack, a.node_look, node, state, c, enc);
+}
+__device__ __forceinline__ double beam_lex_ext(const BeamTokLexMarkedLook& a, int node, int state, int c, int& enc) {
+  return beam_lex_step_marked_at<true>(a.pack.lex, a.node_look, node, state, c, enc);
+}
+
 // the Transducer launch that merges by spelling (wfl_transducer_beam_search_merged): BeamTok's
 // fields and the spelling table over the C classes -- class c spells the graphemes spell_sym[spell_ptr[c] ..
 // spell_ptr[c + 1]), none for the blank, 1 .. WFL_SPELL_MAX for every other class (wfl_spelling_check)
@@ -515,6 +607,21 @@ template <>
 struct BeamMarked<BeamTokLexMarked> {
   static constexpr bool value = true;
 };
+// (the four packs with look-ahead: the traits of their siblings, and BeamLooks below)
+template <typename P>
+struct BeamPack<BeamLook<P>> : BeamPack<P> {};
+template <typename P>
+struct BeamMarked<BeamLook<P>> : BeamMarked<P> {};
+// whether the pack's lexicon search has word-LM look-ahead (section 27): the step of an extension (by beam_lex_ext's
+// overload) and the pending word after the last frame
+template <typename... Lm>
+struct BeamLooks {
+  static constexpr bool value = false;
+};
+template <typename P>
+struct BeamLooks<BeamLook<P>> {
+  static constexpr bool value = true;
+};
 // (tok: what the three Transducer searches share -- the normaliser, the frame's log-sum-exp, the forced topology's result)
 template <>
 struct BeamPack<BeamSpell> {
@@ -542,7 +649,9 @@ struct BeamPack<BeamSpell> {
 // BeamAsg's arithmetic with BeamLex's node and state per hypothesis, term per extension and final drop-and-rerank; an
 // extension by the garbage class keeps node and state; or one BeamTokLex: the search of
 // wfl_transducer_beam_search_lexicon -- BeamTok's arithmetic with BeamLex's node and state per
-// hypothesis, term per extension (the merged one inside a stay included) and final drop ahead of the ranking.
+// hypothesis, term per extension (the merged one inside a stay included) and final drop ahead of the ranking; or a
+// start-marked sibling of a lexicon pack (section 26), or BeamLook<a lexicon pack of CTC or the Transducer>: that pack's
+// search with the terms of word-LM look-ahead (section 27) -- beam_lex_ext's overload and the pending word's settled step.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -553,6 +662,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   constexpr bool LM = BeamPack<Lm...>::lm, LEX = BeamPack<Lm...>::lex, ASG = BeamPack<Lm...>::asg, TOK = BeamPack<Lm...>::tok;
   constexpr bool SPELL = BeamPack<Lm...>::spell;  // (TOK as well)
   constexpr bool MARK = BeamMarked<Lm...>::value;  // (LEX as well)
+  constexpr bool LOOK = BeamLooks<Lm...>::value;  // (LEX as well)
   __shared__ BeamHyp beam[2];
   __shared__ long long ckey[kBeamEntries];
   __shared__ int cidx[kBeamEntries];
@@ -1123,6 +1233,9 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
               l = beam_lm_step(lx.lm, st, v, ns);
               st = ns;
             }
+            // (section 27 rule 4: the pending word's step settled against what its node has paid)
+            if constexpr (LOOK)
+              if (l > ninf) l = beam_look_settled(l, beam_look_of(lm_arg...)[nd]);
             s = l > ninf ? s + beam_lex_pending_term(lx.lm.alpha, l, lx.omega) : ninf;
           }
           if (s > ninf && lx.has_lm && lx.lm.score_eos) {
@@ -1949,6 +2062,215 @@ int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt, c
   d.lex.node_word = lex->node_word, d.lex.start_node = lex->start_node;
   // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_marked's rules without lengths, and its search runs
   if (!Wt && !forced) return beam_run(what, c, d.lex);
+  return beam_run(what, c, d);
+}
+
+// What both look-ahead checks share (DESIGN.md section 27 rule 6): the lexicon's CSR inside its arrays -- so that nothing
+// is read outside [0, num_arcs) and [0, num_nodes) --, node_look finite with 0 at the root, then the three ranges.
+// node_word: a start-marked lexicon's (every arc inner, a word completes at a terminal node), or NULL.
+static int lexicon_lookahead_check(const char* what, const wfl_lexicon* lex, const int32_t* node_word, wfl_lexicon_lookahead* look) {
+  if (!look || !look->node_look) {
+    set_error("%s: a NULL look-ahead or node_look", what);
+    return WFL_ERR_INVALID;
+  }
+  const int N = lex->num_nodes, A = lex->num_arcs;
+  if (lex->arc_ptr[0] != 0 || lex->arc_ptr[N] != A) {
+    set_error("%s: arc_ptr runs from %d to %d, not from 0 to %d", what, lex->arc_ptr[0], lex->arc_ptr[N], A);
+    return WFL_ERR_INVALID;
+  }
+  for (int n = 0; n < N; ++n)
+    if (lex->arc_ptr[n] > lex->arc_ptr[n + 1] || lex->arc_ptr[n] < 0 || lex->arc_ptr[n + 1] > A) {
+      set_error("%s: arc_ptr descends or leaves [0, %d] at node %d", what, A, n);
+      return WFL_ERR_INVALID;
+    }
+  for (int a = 0; a < A; ++a)
+    if (lex->arc_next[a] >= N || (node_word && lex->arc_next[a] < 1)) {
+      set_error("%s: arc %d leads to node %d of %d", what, a, lex->arc_next[a], N);
+      return WFL_ERR_INVALID;
+    }
+  const double* L = look->node_look;
+  for (int n = 0; n < N; ++n)
+    if (!(fabs(L[n]) < __builtin_inf())) {
+      set_error("%s: node_look[%d] is not finite", what, n);
+      return WFL_ERR_INVALID;
+    }
+  if (L[0] != 0.0) {
+    set_error("%s: node_look[0] is %g, the root's look-ahead is 0", what, L[0]);
+    return WFL_ERR_INVALID;
+  }
+  const double inf = __builtin_inf();
+  double arc_min = inf, arc_max = -inf, end_min = inf, end_max = -inf, start_min = inf, start_max = -inf;
+  for (int n = 0; n < N; ++n) {
+    bool ends = node_word && node_word[n] >= 0;
+    for (int a = lex->arc_ptr[n]; a < lex->arc_ptr[n + 1]; ++a) {
+      const int m = lex->arc_next[a];
+      if (m < 0) {
+        ends = true;
+        continue;
+      }
+      // (the difference as the kernel forms it: beam_look_inner_term's first operation; a marked root arc: L[m] - 0)
+      const double d = beam_look_arc_diff(L[m], (node_word && n == 0) ? 0.0 : L[n]);
+      arc_min = fmin(arc_min, d), arc_max = fmax(arc_max, d);
+      if (node_word && n == 0) start_min = fmin(start_min, L[m]), start_max = fmax(start_max, L[m]);
+    }
+    if (ends) end_min = fmin(end_min, L[n]), end_max = fmax(end_max, L[n]);
+  }
+  // (a range nothing fell into -- a lexicon of one-label words has no inner arc --: [0, 0], which bounds nothing away)
+  if (arc_min > arc_max) arc_min = arc_max = 0.0;
+  if (end_min > end_max) end_min = end_max = 0.0;
+  if (start_min > start_max) start_min = start_max = 0.0;
+  look->arc_min = arc_min, look->arc_max = arc_max, look->end_min = end_min, look->end_max = end_max;
+  look->start_min = start_min, look->start_max = start_max;
+  return WFL_OK;
+}
+
+int wfl_lexicon_lookahead_check(const wfl_lexicon* lex, wfl_lexicon_lookahead* look) {
+  const char* what = "lexicon_lookahead_check";
+  if (const int rc = lexicon_shape(what, lex)) return rc;
+  return lexicon_lookahead_check(what, lex, nullptr, look);
+}
+
+int wfl_lexicon_marked_lookahead_check(const wfl_lexicon_marked* lex, wfl_lexicon_lookahead* look) {
+  const char* what = "lexicon_marked_lookahead_check";
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  return lexicon_lookahead_check(what, &lex->trie, lex->node_word, look);
+}
+
+// The largest term of an extension with look-ahead (section 27 rule 6), by the operations the kernel forms a term with:
+// an inner arc's (alpha d) + beta with d in [arc_min, arc_max]; a completed word's ((alpha (l - L) + omega) + beta) + alpha S
+// with l in [step_min, step_max], L in [end_min, end_max], S in [start_min, start_max] (0, 0 end-marked: + 0 changes
+// nothing).  Every rounded operation is monotone in each argument, a product with a constant in one direction or the
+// other: its largest value is at an end of the range.  A NaN on the way (0 inf, inf - inf): no bound.
+static double beam_look_bound(double alpha, double step_min, double step_max, double omega, double beta,
+                              const wfl_lexicon_lookahead& k) {
+#pragma clang fp contract(off)
+  const double i0 = alpha * k.arc_min, i1 = alpha * k.arc_max;
+  const double lo = step_min - k.end_max, hi = step_max - k.end_min;
+  const double w0 = alpha * lo, w1 = alpha * hi;
+  const double s0 = alpha * k.start_min, s1 = alpha * k.start_max;
+  const double inner = fmax(i0, i1) + beta;
+  const double mo = fmax(w0, w1) + omega;
+  const double mb = mo + beta;
+  const double word = mb + fmax(s0, s1);
+  // (fmax drops a NaN operand: every product and difference is tested itself)
+  if (i0 != i0 || i1 != i1 || lo != lo || hi != hi || w0 != w0 || w1 != w1 || s0 != s0 || s1 != s1 || inner != inner ||
+      word != word)
+    return __builtin_inf();
+  return fmax(inner, word);
+}
+
+// What the four look-ahead entries check behind their sibling's checks and beam_lex_fill, and the bound they replace
+static int beam_look_fill(const char* what, const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm, BeamLex* d) {
+  if (!look || !look->node_look) {
+    set_error("%s: a NULL look-ahead or node_look", what);
+    return WFL_ERR_INVALID;
+  }
+  if (!(look->arc_min <= look->arc_max) || !(look->end_min <= look->end_max) || !(look->start_min <= look->start_max)) {
+    set_error("%s: a range of the look-ahead is NaN or has min > max (wfl_lexicon_lookahead_check writes them)", what);
+    return WFL_ERR_INVALID;
+  }
+  if (!word_lm) {
+    set_error("%s: look-ahead needs a word LM", what);
+    return WFL_ERR_INVALID;
+  }
+  d->bound = beam_look_bound(d->lm.alpha, word_lm->step_min, word_lm->step_max, d->omega, d->lm.beta, *look);
+  d->lm.bound = d->bound;
+  return WFL_OK;
+}
+
+// wfl_ctc_beam_search_lexicon with look-ahead: its checks in its order, then the look-ahead's
+int wfl_ctc_beam_search_lexicon_lookahead(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                          int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                          const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm, double lm_weight,
+                                          double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                          int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon_lookahead";
+  BeamLexLook d;
+  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack)) return rc;
+  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack)) return rc;
+  d.node_look = look->node_look;
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
+}
+
+// wfl_ctc_beam_search_lexicon_marked with look-ahead: its checks in its order, then the look-ahead's
+int wfl_ctc_beam_search_lexicon_marked_lookahead(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                                 int classes_per_frame, int nbest, int normalize, const wfl_lexicon_marked* lex,
+                                                 const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm, double lm_weight,
+                                                 double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                                 int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon_marked_lookahead";
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  BeamLexMarkedLook d;
+  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex)) return rc;
+  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex)) return rc;
+  d.pack.node_word = lex->node_word, d.pack.start_node = lex->start_node;
+  d.node_look = look->node_look;
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
+}
+
+// wfl_transducer_beam_search_lexicon with look-ahead: its checks in its order, then the look-ahead's
+int wfl_transducer_beam_search_lexicon_lookahead(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                                                 int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                                 const wfl_lexicon* lex, const wfl_lexicon_lookahead* look,
+                                                 const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                                 double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                                 int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon_lookahead";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  BeamTokLexLook d;
+  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex)) return rc;
+  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex)) return rc;
+  d.pack.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
+  d.node_look = look->node_look;
+  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_lookahead's rules without lengths, and its search runs
+  if (!Wt && !forced) return beam_run(what, c, BeamLexLook{d.pack.lex, d.node_look});
+  return beam_run(what, c, d);
+}
+
+// wfl_transducer_beam_search_lexicon_marked with look-ahead: its checks in its order, then the
+// look-ahead's
+int wfl_transducer_beam_search_lexicon_marked_lookahead(const float* x, const float* Wt, const float* logz, int B, int T, int C,
+                                                        int blank, int forced, int beam, int classes_per_frame, int nbest,
+                                                        int normalize, const wfl_lexicon_marked* lex,
+                                                        const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm,
+                                                        double lm_weight, double word_bonus, double length_bonus, int score_eos,
+                                                        void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                                                        double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon_marked_lookahead";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+  BeamTokLexMarkedLook d;
+  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex.lex)) return rc;
+  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex.lex)) return rc;
+  d.pack.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
+  d.pack.lex.node_word = lex->node_word, d.pack.lex.start_node = lex->start_node;
+  d.node_look = look->node_look;
+  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_marked_lookahead's rules without lengths, and its search runs
+  if (!Wt && !forced) return beam_run(what, c, BeamLexMarkedLook{d.pack.lex, d.node_look});
   return beam_run(what, c, d);
 }
 

@@ -1026,6 +1026,31 @@ struct DeviceLexicon {
   }
 };
 
+// A lexicon's word-LM look-ahead on the device (wfl_lexicon_lookahead; lexicon.py's
+// LexiconLookahead.on_device builds one per device): node_look float64 [N], contiguous on one GPU, from an array that
+// wfl_lexicon_lookahead_check (or its start-marked sibling) accepted on the host, and the six ranges that check wrote.
+struct DeviceLookahead {
+  at::Tensor node_look;  // (kept alive: look points into it)
+  wfl_lexicon_lookahead look;
+  DeviceLookahead(const at::Tensor& node_look_, double arc_min, double arc_max, double end_min, double end_max, double start_min,
+                  double start_max)
+      : node_look(node_look_) {
+    TORCH_CHECK(node_look.is_cuda() && node_look.scalar_type() == at::kDouble && node_look.is_contiguous() &&
+                    node_look.dim() == 1 && node_look.numel() >= 1,
+                "beam_search_lookahead: node_look must be one contiguous float64 [num_nodes] tensor on a GPU");
+    look.node_look = node_look.data_ptr<double>();
+    look.arc_min = arc_min, look.arc_max = arc_max, look.end_min = end_min, look.end_max = end_max;
+    look.start_min = start_min, look.start_max = start_max;
+  }
+  // (what a plan checks where the look-ahead meets its lexicon and word LM)
+  void check_for(const std::shared_ptr<DeviceLexicon>& lexicon, const std::shared_ptr<DeviceLm>& lm, const char* what) const {
+    TORCH_CHECK(lexicon && lm, what, ": lookahead needs a lexicon and its word LM");
+    TORCH_CHECK(node_look.numel() == lexicon->lex.num_nodes, what, ": the look-ahead has ", node_look.numel(),
+                " nodes, the lexicon ", lexicon->lex.num_nodes);
+    TORCH_CHECK(node_look.device() == lexicon->ints.device(), what, ": the look-ahead must be on the lexicon's device");
+  }
+};
+
 // The options of one beam search as both beam ops take them (engine.py's BeamPlan.on_device binds the values it has
 // checked).  lm none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not read; lexicon: lm is its word LM.
 struct BeamPlan {
@@ -1035,12 +1060,15 @@ struct BeamPlan {
   bool score_eos;
   std::shared_ptr<DeviceLexicon> lexicon;
   double word_bonus;
+  std::shared_ptr<DeviceLookahead> lookahead;  // or none: the lexicon search as it was
   BeamPlan(int blank_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
-           double length_bonus_, bool score_eos_, const std::shared_ptr<DeviceLexicon>& lexicon_, double word_bonus_)
+           double length_bonus_, bool score_eos_, const std::shared_ptr<DeviceLexicon>& lexicon_, double word_bonus_,
+           const std::shared_ptr<DeviceLookahead>& lookahead_)
       : blank(blank_), beam(beam_), K(K_), nbest(nbest_), lm(lm_), lm_weight(lm_weight_), length_bonus(length_bonus_),
-        score_eos(score_eos_), lexicon(lexicon_), word_bonus(word_bonus_) {
+        score_eos(score_eos_), lexicon(lexicon_), word_bonus(word_bonus_), lookahead(lookahead_) {
     TORCH_CHECK(!lm || !lexicon || lm->ints.device() == lexicon->ints.device(),
                 "ctc_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
+    if (lookahead) lookahead->check_for(lexicon, lm, "ctc_beam_search_lexicon_lookahead");
   }
 };
 
@@ -1057,7 +1085,20 @@ Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& len
           [=](int64_t* cap, int64_t* bytes) { check(wfl_ctc_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
             const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
-            if (p.lexicon && p.lexicon->is_marked)
+            if (p.lookahead && p.lexicon->is_marked)
+              check(wfl_ctc_beam_search_lexicon_marked_lookahead(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K,
+                                                                 nbest, normalize ? 1 : 0, &p.lexicon->marked,
+                                                                 &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
+                                                                 p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores,
+                                                                 s),
+                    "ctc_beam_search_lexicon_marked_lookahead");
+            else if (p.lookahead)
+              check(wfl_ctc_beam_search_lexicon_lookahead(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
+                                                          normalize ? 1 : 0, &p.lexicon->lex, &p.lookahead->look, &p.lm->lm,
+                                                          p.lm_weight, p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out,
+                                                          cap, offs, scores, s),
+                    "ctc_beam_search_lexicon_lookahead");
+            else if (p.lexicon && p.lexicon->is_marked)
               check(wfl_ctc_beam_search_lexicon_marked(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
                                                        normalize ? 1 : 0, &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr,
                                                        p.lm_weight, p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out,
@@ -1167,14 +1208,16 @@ struct TransducerLexiconPlan {
   std::shared_ptr<DeviceLm> lm;
   double lm_weight, word_bonus, length_bonus;
   bool score_eos;
+  std::shared_ptr<DeviceLookahead> lookahead;  // or none: the lexicon search as it was
   TransducerLexiconPlan(int blank_, bool forced_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLexicon>& lexicon_,
                         const std::shared_ptr<DeviceLm>& lm_, double lm_weight_, double word_bonus_, double length_bonus_,
-                        bool score_eos_)
+                        bool score_eos_, const std::shared_ptr<DeviceLookahead>& lookahead_)
       : blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
-        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_) {
+        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_), lookahead(lookahead_) {
     TORCH_CHECK(lexicon, "transducer_beam_search_lexicon: a lexicon is needed");
     TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
                 "transducer_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
+    if (lookahead) lookahead->check_for(lexicon, lm, "transducer_beam_search_lexicon_lookahead");
   }
 };
 
@@ -1190,7 +1233,19 @@ Hypotheses transducer_lexicon_beam_source(const at::Tensor& x, const c10::option
   return {x, e.B, (int64_t)e.B * nbest, true, what,
           [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
           [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            if (p.lexicon->is_marked)
+            if (p.lookahead && p.lexicon->is_marked)
+              check(wfl_transducer_beam_search_lexicon_marked_lookahead(
+                        x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0, p.beam, p.K, nbest,
+                        normalize ? 1 : 0, &p.lexicon->marked, &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
+                        p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                    "transducer_beam_search_lexicon_marked_lookahead");
+            else if (p.lookahead)
+              check(wfl_transducer_beam_search_lexicon_lookahead(
+                        x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0, p.beam, p.K, nbest,
+                        normalize ? 1 : 0, &p.lexicon->lex, &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
+                        p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                    "transducer_beam_search_lexicon_lookahead");
+            else if (p.lexicon->is_marked)
               check(wfl_transducer_beam_search_lexicon_marked(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank,
                                                               p.forced ? 1 : 0, p.beam, p.K, nbest, normalize ? 1 : 0,
                                                               &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
@@ -1514,6 +1569,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def(py::init<const at::Tensor&, int64_t, int64_t, int64_t, int64_t>(), py::arg("ints"), py::arg("num_nodes"),
            py::arg("num_arcs"), py::arg("num_words"), py::arg("marked_classes") = 0)
       .def_readonly("ints", &DeviceLexicon::ints);
+  py::class_<DeviceLookahead, std::shared_ptr<DeviceLookahead>>(
+      m, "DeviceLookahead", "a lexicon's word-LM look-ahead on a GPU (lexicon.LexiconLookahead.on_device)")
+      .def(py::init<const at::Tensor&, double, double, double, double, double, double>(), py::arg("node_look"),
+           py::arg("arc_min"), py::arg("arc_max"), py::arg("end_min"), py::arg("end_max"), py::arg("start_min"),
+           py::arg("start_max"))
+      .def_readonly("node_look", &DeviceLookahead::node_look);
   py::class_<ErrorTables, std::shared_ptr<ErrorTables>>(m, "ErrorTables",
                                                         "both tables of a metrics.ErrorCounter, uploaded, and its separator")
       .def(py::init<const ErrorSideSpec&, const ErrorSideSpec&, int64_t>(), py::arg("hyp"), py::arg("ref"), py::arg("sep"),
@@ -1522,11 +1583,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "ValueError for a staged label (StagedTargets or None) outside its table; needs no device");
   py::class_<BeamPlan>(m, "BeamPlan", "the options of one CTC beam search, bound (engine.BeamPlan.on_device)")
       .def(py::init<int, int, int, int, const std::shared_ptr<DeviceLm>&, double, double, bool,
-                    const std::shared_ptr<DeviceLexicon>&, double>(),
+                    const std::shared_ptr<DeviceLexicon>&, double, const std::shared_ptr<DeviceLookahead>&>(),
            py::arg("blank"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("lm"), py::arg("lm_weight"),
            py::arg("length_bonus"), py::arg("score_eos"), py::arg("lexicon"), py::arg("word_bonus"),
-           "an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is scored) or None, and a lexicon "
-           "(DeviceLexicon; lm is then its word LM; a word bonus) or None");
+           py::arg("lookahead") = std::shared_ptr<DeviceLookahead>(),
+           "an n-gram LM (DeviceLm; its weight, a length bonus, whether </s> is scored) or None, a lexicon "
+           "(DeviceLexicon; lm is then its word LM; a word bonus) or None, and the lexicon's look-ahead (DeviceLookahead) or None");
   m.def("ctc_beam_search", &ctc_beam_search, py::arg("x"), py::arg("lengths"), py::arg("plan"), py::arg("normalize"),
         "CTC prefix beam search on the device by a BeamPlan: (labels int64 CPU, offsets int64 CPU [B nbest + 1], scores "
         "float64 CPU [B, nbest])");
@@ -1566,12 +1628,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       m, "TransducerLexiconPlan",
       "the options of one Transducer beam search with a lexicon, bound (engine.TransducerLexiconBeamPlan.on_device)")
       .def(py::init<int, bool, int, int, int, const std::shared_ptr<DeviceLexicon>&, const std::shared_ptr<DeviceLm>&, double,
-                    double, double, bool>(),
+                    double, double, bool, const std::shared_ptr<DeviceLookahead>&>(),
            py::arg("blank"), py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"),
            py::arg("lexicon"), py::arg("lm"), py::arg("lm_weight"), py::arg("word_bonus"), py::arg("length_bonus"),
-           py::arg("score_eos"),
-           "the blank and topology, a lexicon over token sequences (DeviceLexicon), its word LM (DeviceLm) or None, and the "
-           "constants of the CTC lexicon search");
+           py::arg("score_eos"), py::arg("lookahead") = std::shared_ptr<DeviceLookahead>(),
+           "the blank and topology, a lexicon over token sequences (DeviceLexicon), its word LM (DeviceLm) or None, the "
+           "constants of the CTC lexicon search, and the lexicon's look-ahead (DeviceLookahead) or None");
   m.def("transducer_beam_search_lexicon", &transducer_beam_search_lexicon, py::arg("x"), py::arg("transitions"), py::arg("logz"),
         py::arg("plan"), py::arg("normalize"),
         "Transducer prefix beam search with a lexicon on the device by a TransducerLexiconPlan: (labels int64 CPU, offsets "

@@ -994,18 +994,22 @@ class BeamPlan(namedtuple(
     """The options of one CTC beam search over C classes, checked once (`checked`, the one constructor) and handed on whole:
     CTC.beam_search, CTC.errors(beam_size=) and ctc_beam_search build one plan per call, nothing behind them checks or
     lists the options again.  ints, floats, lm_eos a bool, lm an lm.NGramLM or None, lexicon a lexicon.Lexicon or None
-    (lm is then its word LM).  Only on_device() and search() need a device."""
+    (lm is then its word LM).  Only on_device() and search() need a device.  lookahead: None, or the prepared
+    lexicon.LexiconLookahead of a plan made with lookahead= -- not one of the tuple's fields, which
+    are the options as they were: such a plan is a BeamPlanLookahead."""
     __slots__ = ()
+    lookahead = None
 
     @classmethod
     def checked(cls, C, blank, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus,
-                what):
+                what, lookahead=None):
         """The plan of these arguments, within the limits of wfl_ctc_beam_search, or ValueError (`what`: the call they were
         given to).  classes_per_frame None: min(C, 32) -- a default, not a tuned value.  lm None: lm_weight and lm_eos at
         their defaults, and length_bonus unless there is a lexicon, whose search applies it to every label; an lm is built
         for these classes and this blank, or is the lexicon's word LM (the convention of lexicon.py).  lexicon None: no
-        word_bonus.  Numbers: Python or numpy numbers, one-element tensors (a sweep over weights), never bools or strings."""
-        from .lexicon import Lexicon, check_word_lm
+        word_bonus.  Numbers: Python or numpy numbers, one-element tensors (a sweep over weights), never bools or strings.
+        lookahead: None, "unigram" or the word scores u[v] (lexicon.check_lookahead); it needs a lexicon and an lm."""
+        from .lexicon import Lexicon, check_lookahead, check_word_lm
         from .lm import NGramLM
 
         def finite(v, name):
@@ -1047,13 +1051,15 @@ class BeamPlan(namedtuple(
         elif lm.num_classes != C or lm.blank != blank:
             raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
                              f"the emissions have {C} with blank {blank}")
-        return cls(C, blank, W, K, n, lm, weight, bonus, lm_eos, lexicon, omega)
+        plan = cls(C, blank, W, K, n, lm, weight, bonus, lm_eos, lexicon, omega)
+        look = check_lookahead(lookahead, lexicon, lm, False, what)
+        return plan if look is None else BeamPlanLookahead(plan, look)
 
     @classmethod
-    def refuse_without_beam(cls, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, what):
+    def refuse_without_beam(cls, lm, lm_weight, length_bonus, lm_eos, lexicon, word_bonus, what, lookahead=None):
         """ValueError for any of a beam search's keywords in a call that runs none: each must be at its default"""
-        if lm is not None or lexicon is not None:
-            raise ValueError(f"{what}: lm and lexicon need a beam_size")
+        if lm is not None or lexicon is not None or lookahead is not None:
+            raise ValueError(f"{what}: lm, lexicon and lookahead need a beam_size")
         cls.checked(1, 0, 1, None, 1, None, lm_weight, length_bonus, lm_eos, None, word_bonus, what)  # (only they can fail)
 
     def no_frames(self, B):
@@ -1078,7 +1084,8 @@ class BeamPlan(namedtuple(
                               lm=None if self.lm is None else self.lm.on_device(device), lm_weight=self.lm_weight,
                               length_bonus=self.length_bonus, score_eos=self.lm_eos,
                               lexicon=None if self.lexicon is None else self.lexicon.on_device(device),
-                              word_bonus=self.word_bonus)
+                              word_bonus=self.word_bonus,
+                              lookahead=None if self.lookahead is None else self.lookahead.on_device(device))
 
     def search(self, x, lengths=None, normalize=True):
         """ctc_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's"""
@@ -1086,8 +1093,18 @@ class BeamPlan(namedtuple(
         return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
+class BeamPlanLookahead(BeamPlan):
+    """A BeamPlan whose lexicon search has word-LM look-ahead: the tuple is the plan's, .lookahead
+    the prepared lexicon.LexiconLookahead that on_device() hands to the operators with it.  BeamPlan.checked makes one."""
+
+    def __new__(cls, plan, lookahead):
+        self = super().__new__(cls, *plan)
+        self.lookahead = lookahead
+        return self
+
+
 def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
-                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0):
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, lexicon=None, word_bonus=0.0, lookahead=None):
     """CTC prefix beam search on the device (wfl_ctc_beam_search through csrc/torch_ops.cpp; the rules: include/wfl.h,
     DESIGN.md section 17).  x: float32 [B,T,C] on a GPU, contiguous; lengths: int32 [B] on x's device
     (input_lengths_on_device) or None.  Returns (hyps, scores): hyps[b][r] the int64 CPU label tensor of rank r of
@@ -1100,10 +1117,12 @@ def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, len
     its words are returned, lm (if given) is the word LM over its word ids, a label adds length_bonus and a completed
     word lm_weight * step(s, word) + word_bonus on top.  A start-marked lexicon (lexicon.boundary == "start", DESIGN.md
     section 26) runs wfl_ctc_beam_search_lexicon_marked: the plan's DeviceLexicon carries the convention, and the word's
-    term arrives with the next word's first label or after the last frame.  lexicon None: the call it was.  The options
-    are one BeamPlan."""
+    term arrives with the next word's first label or after the last frame.  lexicon None: the call it was.  lookahead:
+    "unigram" or word scores u[v] [num_words] -- the lexicon search with word-LM look-ahead inside words (DESIGN.md section
+    27: wfl_ctc_beam_search_lexicon_lookahead and its start-marked sibling); it needs a lexicon and an lm; None: the call
+    it was.  The options are one BeamPlan."""
     plan = BeamPlan.checked(x.shape[2], blank, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos,
-                            lexicon, word_bonus, "ctc_beam_search")
+                            lexicon, word_bonus, "ctc_beam_search", lookahead=lookahead)
     return plan.search(x, lengths, normalize)
 
 
@@ -1433,21 +1452,27 @@ class TransducerLexiconBeamPlan(namedtuple(
     over C classes (tokens + the blank), checked once (`checked`, the one constructor) and handed on whole:
     TransducerBeamPlan's six fields, a lexicon.Lexicon over token sequences for (C, blank) (Transducer.word_lexicon
     builds one), its word LM (an lm.NGramLM by the convention of lexicon.py) or None, and the constants of the CTC
-    lexicon search.  Only on_device(), search() and errors need a device."""
+    lexicon search.  Only on_device(), search() and errors need a device.  lookahead: as BeamPlan's -- None, or the
+    prepared lexicon.LexiconLookahead of a TransducerLexiconBeamPlanLookahead."""
     __slots__ = ()
+    lookahead = None
 
     @classmethod
     def checked(cls, C, blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, word_bonus, length_bonus,
-                lm_eos, what):
+                lm_eos, what, lookahead=None):
         """The plan of these arguments, within the limits of wfl_transducer_beam_search_lexicon, or ValueError (`what`:
         the call they were given to): what TransducerBeamPlan.checked refuses; a lexicon that is none or was not built
         for (C, blank); an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an
-        lm; a number that is not finite."""
+        lm; a number that is not finite; a lookahead (None, "unigram" or word scores: lexicon.check_lookahead) without an lm."""
+        from .lexicon import check_lookahead
+
         p = TransducerBeamPlan.checked(C, blank, forced, beam_size, classes_per_frame, nbest, what)
         need = f"the emissions have {p.C} with blank {p.blank} (Transducer.word_lexicon builds it)"
         weight, omega, bonus, lm_eos = beam_lexicon_terms(lexicon, (p.C, p.blank), need, lm, lm_weight, word_bonus, length_bonus,
                                                           lm_eos, what)
-        return cls(*p, lexicon, lm, weight, omega, bonus, lm_eos)
+        plan = cls(*p, lexicon, lm, weight, omega, bonus, lm_eos)
+        look = check_lookahead(lookahead, lexicon, lm, False, what)
+        return plan if look is None else TransducerLexiconBeamPlanLookahead(plan, look)
 
     def no_frames(self, B, dtype=torch.int64):
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
@@ -1460,7 +1485,8 @@ class TransducerLexiconBeamPlan(namedtuple(
                                            classes_per_frame=self.classes_per_frame, nbest=self.nbest,
                                            lexicon=self.lexicon.on_device(device),
                                            lm=None if self.lm is None else self.lm.on_device(device), lm_weight=self.lm_weight,
-                                           word_bonus=self.word_bonus, length_bonus=self.length_bonus, score_eos=self.lm_eos)
+                                           word_bonus=self.word_bonus, length_bonus=self.length_bonus, score_eos=self.lm_eos,
+                                           lookahead=None if self.lookahead is None else self.lookahead.on_device(device))
 
     def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
         """transducer_beam_search_lexicon's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt:
@@ -1469,6 +1495,16 @@ class TransducerLexiconBeamPlan(namedtuple(
             logz = dense_forward(x, Wt, need_beta=False).logz if Wt is not None and normalize else None
             flat, offsets, scores = N.ops.transducer_beam_search_lexicon(x, Wt, logz, self.on_device(x.device), bool(normalize))
         return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
+
+
+class TransducerLexiconBeamPlanLookahead(TransducerLexiconBeamPlan):
+    """A TransducerLexiconBeamPlan whose search has word-LM look-ahead, as BeamPlanLookahead is for
+    CTC: the tuple is the plan's, .lookahead the prepared lexicon.LexiconLookahead."""
+
+    def __new__(cls, plan, lookahead):
+        self = super().__new__(cls, *plan)
+        self.lookahead = lookahead
+        return self
 
 
 def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_size=16, classes_per_frame=None, nbest=1,
@@ -1480,10 +1516,18 @@ def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_siz
     completed word lm_weight * step(s, word) + word_bonus on top; lm_eos adds lm_weight * step(s, </s>) after the last
     frame.  The scores include these terms.  With Wt None and forced False this is ctc_beam_search(lexicon=) without
     lengths, bit for bit.  A start-marked lexicon runs wfl_transducer_beam_search_lexicon_marked:
-    the plan's DeviceLexicon carries the convention.  The options are one TransducerLexiconBeamPlan."""
+    the plan's DeviceLexicon carries the convention.  Look-ahead: `lexicon` may be the prepared
+    lexicon.LexiconLookahead of one (Lexicon.lookahead(word scores), Lexicon.unigram_lookahead(lm)) -- the search is then
+    wfl_transducer_beam_search_lexicon_lookahead or its start-marked sibling, and an lm is needed.  The options are one
+    TransducerLexiconBeamPlan."""
+    from .lexicon import LexiconLookahead
+
     what = "transducer_beam_search_lexicon"
+    lookahead = None
+    if isinstance(lexicon, LexiconLookahead):
+        lookahead, lexicon = lexicon, lexicon.lexicon
     plan = TransducerLexiconBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm,
-                                             lm_weight, word_bonus, length_bonus, lm_eos, what)
+                                             lm_weight, word_bonus, length_bonus, lm_eos, what, lookahead=lookahead)
     if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
         raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
     if x.shape[0] == 0 or x.shape[1] == 0:

@@ -23,8 +23,15 @@ class that begins a word also occurs inside one -- the one condition of a start-
 the next begins, or where the utterance ends.  Its pack is wfl_lexicon_marked: the same CSR with the leaves stored and
 every arc_next a node, node_word[n] the word whose spelling ends at node n (-1: none) and start_node[c] the root's child
 by class c (-1: c begins no word).  During the search a hypothesis is ranked without the LM term of its last, unfinished
-word."""
+word.
+
+Word-LM look-ahead.  Lexicon.lookahead(word_scores) pushes the best score of the words below a
+trie node up to that node (node_look; 0 at the root) and returns the prepared LexiconLookahead -- wfl_lexicon_lookahead:
+the array and the ranges the search's prune bound is formed from, checked once by libwfl, uploaded once per device;
+Lexicon.unigram_lookahead(lm) is that of the word LM's unigram scores, built once per (lexicon, lm) pair.  The searches
+pay lm_weight * node_look provisionally on the way down a word and settle it where the word ends."""
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -118,6 +125,7 @@ class Lexicon:
         self._arcs = [{int(arc_label[a]): int(arc_next[a]) for a in range(arc_ptr[n], arc_ptr[n + 1])}
                       for n in range(self.num_nodes)]
         self._on_device = {}
+        self._unigram_lookahead = weakref.WeakKeyDictionary()  # lm -> its LexiconLookahead
 
     def _init_start(self, spellings, num_classes, blank, words, word_of):
         self.num_classes, self.blank = int(num_classes), int(blank)
@@ -194,6 +202,7 @@ class Lexicon:
         self._arcs = [{int(arc_label[a]): int(arc_next[a]) for a in range(arc_ptr[n], arc_ptr[n + 1])}
                       for n in range(self.num_nodes)]
         self._on_device = {}
+        self._unigram_lookahead = weakref.WeakKeyDictionary()  # lm -> its LexiconLookahead
 
     def marked_desc(self):
         """the wfl_lexicon_marked of a start-marked lexicon's host arrays (they must outlive it)"""
@@ -301,6 +310,124 @@ class Lexicon:
                                                                 self.num_nodes, self.num_arcs, self.num_words,
                                                                 self.num_classes if marked else 0)
         return held
+
+
+    def lookahead(self, word_scores):
+        """The LexiconLookahead of the word scores u[v] (float64 [num_words], finite, natural logs): node_look[0] = 0,
+        otherwise node_look[n] = max u[v] over the words that can still be completed from node n -- the completing arcs
+        in the subtree of n, or for a start-marked lexicon the terminal nodes in it, n included.
+        One pass from the leaves up: the breadth-first numbering puts children behind their parents.  ValueError for a
+        wrong length or an entry that is not finite."""
+        try:
+            u = np.ascontiguousarray(word_scores, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"Lexicon.lookahead: the word scores must be numbers, got {type(word_scores).__name__}") from None
+        if u.ndim != 1 or u.shape[0] != self.num_words:
+            raise ValueError(f"Lexicon.lookahead: one score per word is needed -- [{self.num_words}] --, got {list(u.shape)}")
+        if not np.isfinite(u).all():
+            v = int(np.flatnonzero(~np.isfinite(u))[0])
+            raise ValueError(f"Lexicon.lookahead: the score of word {v} is {u[v]}, not finite")
+        look = np.full(self.num_nodes, -np.inf)
+        marked = self.boundary == "start"
+        for n in range(self.num_nodes - 1, -1, -1):
+            best = u[self.node_word[n]] if marked and self.node_word[n] >= 0 else -np.inf
+            for a in range(int(self.arc_ptr[n]), int(self.arc_ptr[n + 1])):
+                m = int(self.arc_next[a])
+                best = max(best, look[m] if m >= 0 else u[-(m + 1)])
+            look[n] = best
+        look[0] = 0.0
+        return LexiconLookahead(self, look)
+
+    def unigram_lookahead(self, lm):
+        """lookahead() of the word LM's unigram scores (lm.unigram_scores(): lookahead="unigram"), built once per
+        (lexicon, lm) pair and kept.  A word whose entry is -inf takes the smallest finite entry among the words;
+        ValueError if no word has a finite entry, or if lm is no word LM of this lexicon."""
+        held = self._unigram_lookahead.get(lm)
+        if held is None:
+            check_word_lm(self, lm, "Lexicon.unigram_lookahead")
+            u = lm.unigram_scores()[:self.num_words].copy()
+            finite = np.isfinite(u)
+            if not finite.any():
+                raise ValueError("Lexicon.unigram_lookahead: the lm has a finite unigram score for none of the words")
+            u[~finite] = u[finite].min()
+            held = self._unigram_lookahead[lm] = self.lookahead(u)
+        return held
+
+
+class LexiconLookahead:
+    """The prepared word-LM look-ahead of a lexicon (wfl_lexicon_lookahead): `lexicon`, node_look
+    float64 [num_nodes] and the ranges the search's prune bound is formed from -- (arc_min, arc_max) of node_look[m] -
+    node_look[n] over the inner arcs, (end_min, end_max) of node_look over the nodes where a word can complete,
+    (start_min, start_max) of node_look over the root's children (start-marked; 0, 0 otherwise).  Checked once, here, by
+    libwfl's wfl_lexicon_lookahead_check (wfl_lexicon_marked_lookahead_check), which writes the ranges: ValueError for a
+    wrong length, an entry that is not finite, a root that is not 0.  Lexicon.lookahead() builds one from word scores."""
+
+    RANGES = ("arc_min", "arc_max", "end_min", "end_max", "start_min", "start_max")
+
+    def __init__(self, lexicon, node_look):
+        if not isinstance(lexicon, Lexicon):
+            raise ValueError(f"LexiconLookahead: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
+        self.lexicon = lexicon
+        try:
+            self.node_look = np.ascontiguousarray(node_look, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("LexiconLookahead: node_look must be numbers") from None
+        if self.node_look.ndim != 1 or self.node_look.shape[0] != lexicon.num_nodes:
+            raise ValueError(f"LexiconLookahead: node_look must be [{lexicon.num_nodes}], one entry per node of the lexicon, "
+                             f"got {list(self.node_look.shape)}")
+        desc = N.LexiconLookahead(self.node_look.ctypes.data, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        if lexicon.boundary == "start":
+            lex = lexicon.marked_desc()
+            rc = N.lib.wfl_lexicon_marked_lookahead_check(ctypes.byref(lex), ctypes.byref(desc))
+        else:
+            lex = N.Lexicon(lexicon.num_nodes, lexicon.num_arcs, lexicon.num_words, 0, lexicon.arc_ptr.ctypes.data,
+                            lexicon.arc_label.ctypes.data, lexicon.arc_next.ctypes.data)
+            rc = N.lib.wfl_lexicon_lookahead_check(ctypes.byref(lex), ctypes.byref(desc))
+        if rc != N.WFL_OK:
+            raise ValueError(f"LexiconLookahead: {N.last_error()}")
+        for name in self.RANGES:
+            setattr(self, name, float(getattr(desc, name)))
+        self._on_device = {}
+
+    def on_device(self, device):
+        """the operators' DeviceLookahead (csrc/torch_ops.cpp) on `device`: node_look there and the ranges.  Uploaded once
+        per device and kept, as Lexicon.on_device keeps its pack."""
+        import torch
+
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"LexiconLookahead.on_device: {device} is not a GPU")
+        index = torch.cuda.current_device() if device.index is None else device.index
+        held = self._on_device.get(index)
+        if held is None:
+            held = self._on_device[index] = N.ops.DeviceLookahead(
+                torch.from_numpy(self.node_look).to(torch.device("cuda", index)), *(getattr(self, name) for name in self.RANGES))
+        return held
+
+
+def check_lookahead(lookahead, lexicon, lm, merge_spellings, what):
+    """The LexiconLookahead of a search's `lookahead` keyword, or None for None; ValueError otherwise (`what`: the call it
+    was given to).  "unigram": lexicon.unigram_lookahead(lm); a LexiconLookahead of this lexicon: itself; anything else:
+    the explicit word scores u[v], lexicon.lookahead's.  It needs both a lexicon and its word LM."""
+    if lookahead is None:
+        return None
+    if merge_spellings:
+        raise ValueError(f"{what}: lookahead is the lexicon search's, merge_spellings has no lexicon")
+    if not isinstance(lexicon, Lexicon) or lm is None:
+        raise ValueError(f"{what}: lookahead needs a lexicon and its word lm")
+    check_word_lm(lexicon, lm, what)
+    try:
+        if isinstance(lookahead, str):
+            if lookahead != "unigram":
+                raise ValueError(f"lookahead {lookahead!r} is neither None, 'unigram' nor an array of word scores")
+            return lexicon.unigram_lookahead(lm)
+        if isinstance(lookahead, LexiconLookahead):
+            if lookahead.lexicon is not lexicon:
+                raise ValueError("the LexiconLookahead was prepared for another lexicon")
+            return lookahead
+        return lexicon.lookahead(lookahead)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
 
 
 def check_word_lm(lexicon, lm, what):

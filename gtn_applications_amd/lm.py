@@ -103,6 +103,21 @@ class NGramLM:
             total += w
         return total
 
+    def unigram_scores(self):
+        """float64 [num_classes]: entry v is step(base, v)[0], base the state reached from `start` by following bo_next
+        until there is no back-off (the empty history of from_arpa) -- the back-off weights on the way are not counted;
+        the blank's entry, and that of a label without an arc there, is -inf.  What lookahead="unigram" smears over a
+        lexicon's trie."""
+        base = self.start
+        while self.bo_next[base] >= 0:  # (the check bounded the chain)
+            base = int(self.bo_next[base])
+        scores = np.full(self.num_classes, -math.inf)
+        lo, hi = int(self.arc_ptr[base]), int(self.arc_ptr[base + 1])
+        labels = self.arc_label[lo:hi]
+        keep = labels < self.num_classes  # (not </s>; the blank has no arc)
+        scores[labels[keep]] = self.arc_w[lo:hi][keep]
+        return scores
+
     def on_device(self, device):
         """the operators' DeviceLm (csrc/torch_ops.cpp) of this pack on `device`: `.ints` int32 [arc_ptr | arc_label |
         arc_next | bo_next] and `.weights` float64 [arc_w | bo_w] there, and the wfl_ngram_lm that points into them.

@@ -681,7 +681,8 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths /* or NULL */,
  *   no global atomics, no cross-workgroup waits, every loop bounded by T_b, W, K, the back-off cap or 31 search steps.
  *   WFL_ERR_INVALID: what wfl_ctc_beam_search refuses; lex or one of its arrays NULL, num_nodes, num_arcs or num_words
  *   < 1 (or num_words = 2^31 - 1: </s> is V + 1); a weight or bonus that is not finite; for a non-NULL word_lm what wfl_ctc_beam_search_lm refuses.
- *   Not here: a token-level LM together with a lexicon, LM look-ahead inside words, out-of-vocabulary arcs.  Several
+ *   Not here: a token-level LM together with a lexicon, out-of-vocabulary arcs (LM look-ahead inside words:
+ *   wfl_ctc_beam_search_lexicon_lookahead, below the Transducer's lexicon search).  Several
  *   spellings of one word and vocabularies that are not prefix-free: wfl_ctc_beam_search_lexicon_marked below.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct wfl_lexicon {
@@ -738,8 +739,8 @@ int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths /* or NUL
  *   memory of DEVICE pointers to a pack that wfl_lexicon_marked_check accepted with host pointers; the kernels trust it.
  *   WFL_ERR_INVALID besides the siblings': node_word or start_node NULL.  The Transducer entry with Wt == NULL and
  *   forced == 0 runs the CTC entry's search: bit-identical results.
- *   Not here: ASG, a token-level LM together with a lexicon, LM look-ahead, merging by spelling together with a lexicon,
- *   out-of-vocabulary arcs.
+ *   Not here: ASG, a token-level LM together with a lexicon, merging by spelling together with a lexicon,
+ *   out-of-vocabulary arcs.  (LM look-ahead, which lifts rule 7: the *_lexicon_marked_lookahead entries below.)
  * ------------------------------------------------------------------------------------------------ */
 typedef struct wfl_lexicon_marked {
   wfl_lexicon trie;          /* arc_next: every target a node in [1, num_nodes) */
@@ -1014,9 +1015,9 @@ int wfl_transducer_beam_search_merged(const float* x, const float* Wt /* [(C+1),
  *   31 search steps.
  *   WFL_ERR_INVALID: what wfl_transducer_beam_search refuses, in its order; then lex or one of its arrays NULL,
  *   num_nodes, num_arcs or num_words < 1 (or num_words = 2^31 - 1); for a non-NULL word_lm what wfl_ctc_beam_search_lm
- *   refuses; a weight or bonus that is not finite.  Not here: a token-level LM, LM look-ahead inside words, merging by
- *   spelling, input lengths, the ambiguous token graphs.  Several spellings of one word and vocabularies that are not
- *   prefix-free: wfl_transducer_beam_search_lexicon_marked.
+ *   refuses; a weight or bonus that is not finite.  Not here: a token-level LM, merging by spelling, input lengths, the
+ *   ambiguous token graphs (LM look-ahead inside words: wfl_transducer_beam_search_lexicon_lookahead below).  Several
+ *   spellings of one word and vocabularies that are not prefix-free: wfl_transducer_beam_search_lexicon_marked.
  * ------------------------------------------------------------------------------------------------ */
 int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] or NULL */,
                                        const float* logz /* [B] or NULL */, int B, int T, int C, int blank, int forced, int beam,
@@ -1024,6 +1025,94 @@ int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1)
                                        const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
                                        double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                                        int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The four lexicon searches of CTC and the Transducer with word-LM LOOK-AHEAD inside words (csrc/beam_kernels.hip; DESIGN
+ * section 27).  Without it a hypothesis is ranked with no LM information about the word it is spelling: the word's term
+ * arrives with its last label (one label later still with a start-marked lexicon), and a narrow beam loses the word the
+ * LM wants before the LM has had a say.  Unigram max look-ahead ("smearing"): every word v has a score u[v] (finite,
+ * natural log; by default the word LM's unigram score) and every trie node n the best of them below it,
+ *     L[0] = 0 at the root; otherwise L[n] = max u[v] over the words that can still be completed from n -- end-marked: the
+ *     completing arcs in the subtree of n; start-marked: the terminal nodes in the subtree, n included.
+ * A hypothesis at node n has paid a L[n] provisionally; the payment moves down the trie with it and is settled where the
+ * word ends.  Every rule of the sibling entry stands unless replaced here; a = lm_weight, o = word_bonus, b = length_bonus,
+ * every operation rounded on its own (no fused multiply-add), by the same functions on the host and on the device:
+ *     1. an inner arc n -> m: the term is (a (L[m] - L[n])) + b, in place of b.  A start-marked word's first label from the
+ *        root is such an arc, with L[root] = 0;
+ *     2. an arc that completes a word at node n (end-marked), (l, nxt) = step(state, v): l = -inf: the extension does not
+ *        exist, as before; otherwise the term is (a (l - L[n]) + o) + b;
+ *     3. start-marked, a word-starting class c from a terminal node n: rule 2's term, + a L[start_node[c]];
+ *     4. after the last frame -- end-marked: unchanged, a rank inside a word is dropped with what it has paid;
+ *        start-marked: the pending word at a terminal node n gets (a (l - L[n]) + o), every other non-root rank is
+ *        dropped.  The </s> term, the re-ranking, nbest, T_b = 0 and the normalisation are unchanged;
+ *     5. the mass of a hypothesis at node n includes a L[n], a function of the prefix because the node is: merging by
+ *        prefix stays exact, stays add nothing.  Along a word the payments telescope, so unpruned the total of a sequence
+ *        of whole words is the sibling's up to rounding (the sums are associated differently), and the set of sequences
+ *        is the sibling's.  With every u[v] = 0, or with a = 0, every term is the sibling's bit for bit;
+ *     6. the prune bound is still a proof.  wfl_lexicon_lookahead_check records [arc_min, arc_max], the range of
+ *        L[m] - L[n] over the inner arcs (the rounded differences the kernel forms; a start-marked root arc counts
+ *        L[m] - 0), [end_min, end_max], the range of L[n] over the nodes where a word can complete (end-marked: a node
+ *        with a completing arc; start-marked: a terminal node), and [start_min, start_max], the range of L over the
+ *        root's children (start-marked; [0, 0] end-marked).  Per call the largest term of an extension is
+ *        max( max(a arc_min, a arc_max) + b,
+ *             ((max(a (step_min - end_max), a (step_max - end_min)) + o) + b) + max(a start_min, a start_max) ),
+ *        by the monotonicity of each rounded operation (DESIGN section 27 has the argument); a NaN on the way (0 inf,
+ *        inf - inf): no bound, every extension is looked up.
+ *   look: a struct in HOST memory; for the searches node_look is a DEVICE pointer to the array that
+ *   wfl_lexicon_lookahead_check (or wfl_lexicon_marked_lookahead_check) accepted with a host pointer, for the same
+ *   lexicon, and the six scalars are what that check wrote.  The kernels trust it: they check no index.  word_lm is
+ *   required (look-ahead of no LM is nothing).  One or two 8-byte loads per looked-up extension; no workspace of its own:
+ *   the sibling's workspace function, outputs, three launches and guarantees -- no allocation, no synchronisation, no
+ *   global atomics, no cross-workgroup waits, every loop bounded.  The Transducer entries with Wt == NULL and forced == 0
+ *   run the CTC entries' search: bit-identical results.
+ *   WFL_ERR_INVALID: what the sibling entry refuses, in its order; then look or look->node_look NULL, one of the six
+ *   scalars NaN or a range with min > max, word_lm NULL.
+ *   Not here: ASG, look-ahead that depends on the LM state, log-add smearing, a token-level LM together with a lexicon,
+ *   out-of-vocabulary arcs, back-off transition graphs, input lengths for the Transducer.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct wfl_lexicon_lookahead {
+  const double* node_look; /* [num_nodes] of the lexicon: finite, node_look[0] = 0 */
+  double arc_min, arc_max;     /* written by the check: node_look[m] - node_look[n] over the inner arcs n -> m lies between */
+  double end_min, end_max;     /* written by the check: node_look[n] over the nodes where a word can complete */
+  double start_min, start_max; /* written by the check: node_look over the root's children (start-marked), else 0, 0 */
+} wfl_lexicon_lookahead;
+/* The look-ahead's check (host arrays, no device) for a lexicon that wfl_lexicon_check accepted: lex and look and their
+ * arrays not NULL, the lexicon's sizes >= 1 and its arc_ptr / arc_next inside their arrays (read before node_look is
+ * indexed by them); every node_look[n] finite; node_look[0] == 0.  WFL_ERR_INVALID names the first offence in
+ * wfl_last_error().  On success it WRITES the six scalars of rule 6; whatever they held before is not read.  It does not
+ * ask that node_look is the maximum of any word scores: the totals telescope for every finite array (rule 5). */
+int wfl_lexicon_lookahead_check(const wfl_lexicon* lex, wfl_lexicon_lookahead* look);
+/* The same for a start-marked lexicon that wfl_lexicon_marked_check accepted (node_word is read, start_node is not). */
+int wfl_lexicon_marked_lookahead_check(const wfl_lexicon_marked* lex, wfl_lexicon_lookahead* look);
+int wfl_ctc_beam_search_lexicon_lookahead(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C, int blank,
+                                          int beam, int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                          const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm, double lm_weight,
+                                          double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                          int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                          double* scores /* [B*nbest] */, void* stream);
+int wfl_ctc_beam_search_lexicon_marked_lookahead(const float* x, const int32_t* lengths /* or NULL */, int B, int T, int C,
+                                                 int blank, int beam, int classes_per_frame, int nbest, int normalize,
+                                                 const wfl_lexicon_marked* lex, const wfl_lexicon_lookahead* look,
+                                                 const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                                 double length_bonus, int score_eos, void* ws, int32_t* out,
+                                                 int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                                 double* scores /* [B*nbest] */, void* stream);
+int wfl_transducer_beam_search_lexicon_lookahead(const float* x, const float* Wt /* [(C+1), C] or NULL */,
+                                                 const float* logz /* [B] or NULL */, int B, int T, int C, int blank, int forced,
+                                                 int beam, int classes_per_frame, int nbest, int normalize,
+                                                 const wfl_lexicon* lex, const wfl_lexicon_lookahead* look,
+                                                 const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                                 double length_bonus, int score_eos, void* ws, int32_t* out,
+                                                 int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                                 double* scores /* [B*nbest] */, void* stream);
+int wfl_transducer_beam_search_lexicon_marked_lookahead(const float* x, const float* Wt /* [(C+1), C] or NULL */,
+                                                        const float* logz /* [B] or NULL */, int B, int T, int C, int blank,
+                                                        int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                                        const wfl_lexicon_marked* lex, const wfl_lexicon_lookahead* look,
+                                                        const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                                        double length_bonus, int score_eos, void* ws, int32_t* out,
+                                                        int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                                        double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: token and word error counts behind a best path (csrc/error_kernels.hip)
