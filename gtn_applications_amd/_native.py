@@ -262,6 +262,8 @@ _SIGS = {
                                                                     c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     "wfl_transducer_beam_search_merged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_int, _P, _P, c_int64, _P, _P, _P]),
+    "wfl_transducer_beam_search_lm": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              POINTER(NgramLm), c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: token and word error counts behind a best path
     "wfl_errors_workspace": (c_int, [c_int, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wfl_errors_count": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int64, c_int64, _P, _P, _P]),

@@ -274,6 +274,8 @@ class Transducer(torch.nn.Module):
         self._spelling_table = None
         # the tokens as tuples of their elements: what word_lexicon() compares the pieces of a word against (plain too)
         self._token_pieces = [tuple(wp) for wp in tokens]
+        # the tokens as they were given, in class order: what token_lm() names the classes of an ARPA file by (plain too)
+        self._token_names = list(tokens)
         self._has_blank = blank != "none"
         self.ngram = ngram
         if ngram > 0 and transitions is not None:
@@ -384,10 +386,11 @@ class Transducer(torch.nn.Module):
         return list(torch.split(flat, np.diff(out_off).tolist()))  # (views of one tensor: one call instead of B slices + clones)
 
     def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest, lexicon=None, lm=None, lm_weight=1.0,
-                   length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
+                   length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None, token_lm=None):
         """The arguments of a beam search, checked before anything needs a device: (the E.TransducerBeamPlan of the
-        options -- with a lexicon the E.TransducerLexiconBeamPlan; without one every keyword of the lexicon search must
-        be at its default --, the transition model's kind: "none", "unigram" or "bigram")"""
+        options -- with a lexicon the E.TransducerLexiconBeamPlan; with a token_lm the E.TransducerLmBeamPlan, whose
+        scalars lm_weight, length_bonus and lm_eos then are; with neither every keyword of the two must be at its
+        default --, the transition model's kind: "none", "unigram" or "bigram")"""
         E.check_beam_outputs(outputs, what)
         self.tokens.arc_sort()
         n = ctypes.c_int()
@@ -407,7 +410,20 @@ class Transducer(torch.nn.Module):
             if kind == "general":
                 raise NotImplementedError(f"{what}: the transition model is neither make_transitions_graph(1, C) nor "
                                           "(2, C): only no model, the unigram and the bigram model are searched")
-        if lexicon is None:
+        if token_lm is not None:
+            if lexicon is not None:
+                raise NotImplementedError(
+                    f"{what}: token_lm together with a lexicon -- a token-level LM and a word LM over the same hypothesis "
+                    "are two LM states and two terms per extension: a search of its own; give one of them")
+            if lm is not None:
+                raise ValueError(f"{what}: lm is the word LM of a lexicon; with token_lm there is none")
+            if lookahead is not None:
+                raise ValueError(f"{what}: lookahead needs a lexicon and its word lm, not a token_lm")
+            if isinstance(word_bonus, bool) or not isinstance(word_bonus, numbers.Real) or float(word_bonus) != 0.0:
+                raise ValueError(f"{what}: word_bonus needs a lexicon, got {word_bonus!r}")
+            plan = E.TransducerLmBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest,
+                                                  token_lm, lm_weight, length_bonus, lm_eos, what)
+        elif lexicon is None:
             if lookahead is not None:
                 raise ValueError(f"{what}: lookahead needs a lexicon and its word lm")
             _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
@@ -468,6 +484,18 @@ class Transducer(torch.nn.Module):
             return Lexicon(spellings, n + 1, n, words=words, boundary="start", word_of=word_of)
         return Lexicon(spellings, n + 1, n, words=words)
 
+    def token_lm(self, path, bos="<s>", eos="</s>", unk="<unk>"):
+        """The lm.NGramLM of an ARPA file over the module's own tokens for beam_search(token_lm=):
+        NGramLM.from_arpa(path, the module's tokens in class order, blank=n_tokens) -- the emission classes and the
+        blank of a token graph with a blank, which the module must have.  The ARPA file names a token as the module was
+        given it."""
+        if not self._has_blank:
+            raise ValueError('Transducer.token_lm: blank="none" has no class for the blank an NGramLM is built around, and '
+                             "no beam search")
+        from ..lm import NGramLM
+
+        return NGramLM.from_arpa(path, self._token_names, blank=len(self._token_names), bos=bos, eos=eos, unk=unk)
+
     @staticmethod
     def words(lexicon, labels):
         """The word ids of a token sequence that beam_search(lexicon=) returned: lexicon.words(labels)"""
@@ -490,9 +518,14 @@ class Transducer(torch.nn.Module):
         return held[1]
 
     @staticmethod
-    def _merge_flag(merge_spellings, what, lexicon=None):
+    def _merge_flag(merge_spellings, what, lexicon=None, token_lm=None):
         if not isinstance(merge_spellings, (bool, np.bool_)):
             raise ValueError(f"{what}: merge_spellings must be True or False, got {merge_spellings!r}")
+        if merge_spellings and token_lm is not None:
+            raise NotImplementedError(
+                f"{what}: merge_spellings=True with a token_lm -- the merged search sums the token sequences that spell the "
+                "same graphemes into one hypothesis, while the LM's score and state depend on the token sequence: the "
+                "members of a merged hypothesis carry different LM terms")
         if merge_spellings and lexicon is not None:
             raise NotImplementedError(
                 f"{what}: merge_spellings=True with a lexicon -- the merged search identifies a hypothesis by the graphemes "
@@ -516,7 +549,7 @@ class Transducer(torch.nn.Module):
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False,
                     merge_spellings=False, lexicon=None, lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0,
-                    lookahead=None):
+                    lookahead=None, token_lm=None):
         """Transducer prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame
         path; the criterion scores a token sequence by the sum over all its alignments, and this returns the token
         sequences it rates highest (DESIGN.md section 22 has the rules; csrc/beam_kernels.hip runs them, in float64).
@@ -556,11 +589,19 @@ class Transducer(torch.nn.Module):
         27; it needs a lexicon and an lm): "unigram" or an array of one finite score per word -- lm_weight times the best
         score of the words below a trie node is paid provisionally while a word is being spelled and settled where the
         word ends, so that a narrow beam ranks a hypothesis by the word the LM wants; unpruned the results are those
-        without it.  No token-level LM or input lengths."""
+        without it.
+        token_lm: an lm.NGramLM over the module's own classes (self.token_lm(path) reads one from
+        an ARPA file; num_classes == n_tokens + 1, blank == n_tokens) -- shallow fusion with an n-gram LM over the tokens
+        themselves: no vocabulary, and words that no lexicon lists.  lm_weight, length_bonus and lm_eos are then its
+        scalars, as in CTC.beam_search(lm=) without a lexicon: a token c behind LM state s adds lm_weight * step(s, c) +
+        length_bonus, lm_eos lm_weight * step(s, </s>) after the last frame; the scores include these terms.  `lm`
+        remains the word LM of a lexicon: lm=, word_bonus or lookahead with a token_lm raise ValueError, a token_lm with a
+        lexicon or with merge_spellings=True NotImplementedError.  B == 0 or T == 0 with a token_lm: the empty sequence,
+        scored by the LM's </s> alone.  No input lengths."""
         what = "Transducer.beam_search"
         plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, length_bonus,
-                                     lm_eos, word_bonus, lookahead)
-        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what, lexicon) else None
+                                     lm_eos, word_bonus, lookahead, token_lm)
+        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what, lexicon, token_lm) else None
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
         else:
@@ -576,17 +617,20 @@ class Transducer(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, merge_spellings=False, lexicon=None,
-               lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
+               lm=None, lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None, token_lm=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
         beam launches on their device buffers; `classes_per_frame` and `merge_spellings` (beam_search's: the predictions
         are the representatives of the best spellings) need a beam_size.  lexicon, lm, lm_weight, length_bonus, lm_eos,
-        word_bonus, lookahead: beam_search's, with a beam_size: the predictions are those of the search with a lexicon."""
-        merge = self._merge_flag(merge_spellings, "Transducer.errors", lexicon)
+        word_bonus, lookahead: beam_search's, with a beam_size: the predictions are those of the search with a lexicon.
+        token_lm: beam_search's, with a beam_size: the predictions are those of the search with a token-level LM."""
+        merge = self._merge_flag(merge_spellings, "Transducer.errors", lexicon, token_lm)
         if beam_size is None and lookahead is not None:
             raise ValueError("Transducer.errors: lookahead needs a beam_size")
+        if beam_size is None and token_lm is not None:
+            raise ValueError("Transducer.errors: token_lm needs a beam_size")
         if beam_size is None:
             if classes_per_frame is not None or merge:
                 raise ValueError("Transducer.errors: classes_per_frame and merge_spellings need a beam_size")
@@ -595,7 +639,7 @@ class Transducer(torch.nn.Module):
             _refuse_without_lexicon("Transducer.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
         else:
             plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
-                                         length_bonus, lm_eos, word_bonus, lookahead)
+                                         length_bonus, lm_eos, word_bonus, lookahead, token_lm)
             spelling = self._spelling(plan, "Transducer.errors") if merge else None
             counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
@@ -606,6 +650,8 @@ class Transducer(torch.nn.Module):
                     return counter.totals(M.transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling))
                 if lexicon is not None:
                     return counter.totals(M.transducer_beam_search_lexicon_errors(counter, targets, x, Wt, plan))
+                if token_lm is not None:
+                    return counter.totals(M.transducer_beam_search_lm_errors(counter, targets, x, Wt, plan))
                 return counter.totals(M.transducer_beam_search_errors(counter, targets, x, Wt, plan))
         C = outputs.shape[2]
         dplan = self._device_decode(C)

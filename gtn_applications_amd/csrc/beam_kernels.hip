@@ -53,7 +53,11 @@
 // look-ahead of the word LM inside words: BeamLook<sibling's pack> adds node_look, the best word
 // score below every trie node; a hypothesis pays lm_weight node_look[node] provisionally on the way down a word and
 // settles it where the word ends, so the totals are the siblings' and a narrow beam ranks by the word the LM wants.
-// All fourteen issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_transducer_beam_search_lm is the Transducer search with the token-level n-gram LM and length bonus of the CTC one
+// (DESIGN.md section 28): a pack BeamTokLm holds a BeamTok and a BeamLm -- the Transducer's two masses and transition
+// gathers per entry, the LM's state per hypothesis, one back-off lookup per extension behind the same skip test, and
+// the forced topology's drop-and-rank-by-pb ahead of </s> in the final block.
+// All fifteen issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -461,6 +465,30 @@ __device__ __forceinline__ double beam_tok_ext(const BeamTok& a, double pb, doub
   return s + m;
 }
 
+// the Transducer launch with a token-level LM (wfl_transducer_beam_search_lm): BeamTok's
+// transitions and topology, BeamLm's acceptor over the tokens, the two scalars and the bound of an extension's term
+struct BeamTokLm {
+  BeamTok tok;
+  BeamLm lm;
+};
+__device__ __forceinline__ const BeamTok& beam_tok_of(const BeamTokLm& a) { return a.tok; }
+__device__ __forceinline__ const BeamLm& beam_lm_of(const BeamTokLm& a) { return a.lm; }
+// The LM term of such an extension whose step is l: alpha l + beta, each operation rounded on its own -- on the device
+// as where the entry forms the largest such term, so that the bound holds by the monotonicity of the rounded
+// operations (a fused multiply-add would round once and may land above).
+__device__ __forceinline__ double beam_tok_lm_term(double alpha, double l, double beta) {
+#pragma clang fp contract(off)
+  const double al = alpha * l;
+  return al + beta;
+}
+// the largest such term, l in [step_min, step_max], by the same operations (0 * inf: no bound)
+inline double beam_tok_lm_bound(double alpha, double step_min, double step_max, double beta) {
+#pragma clang fp contract(off)
+  const double t0 = alpha * step_min, t1 = alpha * step_max;
+  if (t0 != t0 || t1 != t1) return __builtin_inf();
+  return fmax(t0, t1) + beta;
+}
+
 // the Transducer launch with a lexicon (wfl_transducer_beam_search_lexicon): BeamTok's transitions
 // and topology, BeamLex's trie over token sequences, word LM and bonuses
 struct BeamTokLex {
@@ -588,6 +616,12 @@ template <>
 struct BeamPack<BeamTokLex> {
   static constexpr bool lm = false, lex = true, asg = false, tok = true, spell = false;
 };
+// (tok and lm: the Transducer's two masses and transition gathers, the LM's state arrays, term per extension and </s>
+// behind the topology's score in the ranking the Transducer's result shares with it)
+template <>
+struct BeamPack<BeamTokLm> {
+  static constexpr bool lm = true, lex = false, asg = false, tok = true, spell = false;
+};
 // (the two lexicon packs with a start-marked lexicon: the traits of their end-marked siblings, and BeamMarked below)
 template <>
 struct BeamPack<BeamLexMarked> : BeamPack<BeamLex> {};
@@ -651,7 +685,10 @@ struct BeamPack<BeamSpell> {
 // wfl_transducer_beam_search_lexicon -- BeamTok's arithmetic with BeamLex's node and state per
 // hypothesis, term per extension (the merged one inside a stay included) and final drop ahead of the ranking; or a
 // start-marked sibling of a lexicon pack (section 26), or BeamLook<a lexicon pack of CTC or the Transducer>: that pack's
-// search with the terms of word-LM look-ahead (section 27) -- beam_lex_ext's overload and the pending word's settled step.
+// search with the terms of word-LM look-ahead (section 27) -- beam_lex_ext's overload and the pending word's settled step;
+// or one BeamTokLm: the search of wfl_transducer_beam_search_lm -- BeamTok's arithmetic with
+// BeamLm's state per hypothesis, LM term per extension (the merged one inside a stay included) behind the skip test, and
+// </s> on top of the topology's score in the final ranking.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -901,6 +938,16 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
             const double term = ac > ninf ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], l, enc) : ninf;
             if (term > ninf) pnb = beam_lae(pnb, ac + term);
           }
+        } else if constexpr (LM) {
+          // (section 28: the merged extension carries the LM term of the prefix it makes -- the state is a function of
+          // it --, and does not exist where the LM has no step)
+          if (i >= 0 && !(a.forced && t == 0)) {
+            const BeamLm& lm = beam_lm_of(lm_arg...);
+            const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]);
+            int nx;
+            const double st = ac > ninf ? beam_lm_step(lm, lmst[cur][i], l, nx) : ninf;
+            if (st > ninf) pnb = beam_lae(pnb, ac + beam_tok_lm_term(lm.alpha, st, lm.beta));
+          }
         } else if (i >= 0 && !(a.forced && t == 0))
           pnb = beam_lae(pnb, beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], brow, l, sc[p]));  // (par: only where p >= 0)
         const double tot = beam_lae(pb, pnb);
@@ -989,6 +1036,18 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
           const double term = reach ? beam_lex_ext(lm_arg..., tnode[cur][i], lmst[cur][i], c, enc) : ninf;
           k = term > ninf ? beam_key(ac + term) : kKeyDropped;
           enext[idx] = enc;
+        } else if constexpr (TOK && LM) {
+          // the Transducer's extension (section 22 rule 4: both masses, the transitions gathered here; none in the forced
+          // topology's frame 0) with the LM's term and skip test; (ahead of the LM and TOK branches, which each take
+          // the other for unset)
+          const BeamLm& lm = beam_lm_of(lm_arg...);
+          const BeamTok& a = beam_tok_of(lm_arg...);
+          const double ac = beam_tok_ext(a, h.pb[i], h.pnb[i], h.last[i], t == 0 ? -1 : blank, c, sc[p]);
+          int nx = 0;
+          const bool reach = !(a.forced && t == 0) && ac > ninf && beam_key(ac + lm.bound) >= tau;
+          const double l = reach ? beam_lm_step(lm, lmst[cur][i], c, nx) : ninf;
+          k = l > ninf ? beam_key(ac + beam_tok_lm_term(lm.alpha, l, lm.beta)) : kKeyDropped;
+          enext[idx] = nx;
         } else if constexpr (LM) {
           const BeamLm& lm = beam_lm_of(lm_arg...);
           const double ac = sc[p] + (c == h.last[i] ? h.pb[i] : h.tot[i]);  // the extension without its LM term
@@ -1197,7 +1256,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     // Merging by spelling (section 23 rule 4): the ranks of one spelling are one result -- their scores added in rank
     // order, at the place (and with the token sequence) of the first of them whose score is finite.
     // The Transducer with a lexicon (section 25 rule 5): the lexicon's drop of a rank inside a word, the topology's
-    // score, </s> on top of it.
+    // score, </s> on top of it.  The Transducer with a token-level LM (section 28): the topology's score, </s> on top.
     if constexpr (SPELL) {
       if (tid < nbeam) spb[tid] = beam_tok_of(lm_arg...).forced ? f.pb[tid] : f.tot[tid];  // (spb: free behind the frames)
       __syncthreads();
@@ -1216,6 +1275,15 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         if (!owner) s = ninf;
       } else if constexpr (TOK && !LEX) {
         if (beam_tok_of(lm_arg...).forced) s = f.pb[tid];
+        // (section 28: </s> on top of the topology's score; a rank the forced topology drops is not looked up)
+        if constexpr (LM) {
+          const BeamLm& lm = beam_lm_of(lm_arg...);
+          if (s > ninf && lm.score_eos) {
+            int nx;
+            const double l = beam_lm_step(lm, lmst[Tb & 1][tid], lm.eos, nx);
+            s = l > ninf ? s + lm.alpha * l : ninf;
+          }
+        }
       } else if constexpr (LEX) {
         const BeamLex& lx = beam_lex_of(lm_arg...);
         if constexpr (TOK)
@@ -1748,6 +1816,38 @@ int wfl_ctc_beam_search_lm(const float* x, const int32_t* lengths, int B, int T,
   d.bound = (t0 != t0 || t1 != t1) ? __builtin_inf() : fmax(t0, t1) + length_bonus;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
+}
+
+// The Transducer search with a token-level n-gram LM: wfl_transducer_beam_search's call and checks
+// in its order, then wfl_ctc_beam_search_lm's checks of the LM and the two scalars.
+int wfl_transducer_beam_search_lm(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank, int forced,
+                                  int beam, int classes_per_frame, int nbest, int normalize, const wfl_ngram_lm* lm,
+                                  double lm_weight, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                  int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lm";
+  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                   scores, stream, !Wt};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  BeamTokLm d;
+  if (const int rc = beam_lm_terms(what, lm, false, C, lm_weight, length_bonus, score_eos, &d.lm)) return rc;
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g and length_bonus %g must be finite", what, lm_weight, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  d.lm.bound = beam_tok_lm_bound(lm_weight, lm->step_min, lm->step_max, length_bonus);
+  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
+  // no transitions, CTC's topology: these are section 18's rules without lengths, and its search is the one that runs
+  if (!Wt && !forced) return beam_run(what, c, d.lm);
+  return beam_run(what, c, d);
 }
 
 static int lexicon_shape(const char* what, const wfl_lexicon* lex) {

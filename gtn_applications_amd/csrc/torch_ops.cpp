@@ -1261,6 +1261,42 @@ Hypotheses transducer_lexicon_beam_source(const at::Tensor& x, const c10::option
           }};
 }
 
+// The options of the Transducer search with a token-level LM as both of its ops take them
+// (engine.TransducerLmBeamPlan.on_device binds the values it has checked): transducer_beam_source's, and the LM and two
+// scalars of the CTC search with an LM.
+struct TransducerLmPlan {
+  int blank;
+  bool forced;
+  int beam, K, nbest;
+  std::shared_ptr<DeviceLm> lm;
+  double lm_weight, length_bonus;
+  bool score_eos;
+  TransducerLmPlan(int blank_, bool forced_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
+                   double length_bonus_, bool score_eos_)
+      : blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), lm(lm_), lm_weight(lm_weight_),
+        length_bonus(length_bonus_), score_eos(score_eos_) {
+    TORCH_CHECK(lm, "transducer_beam_search_lm: a language model is needed");
+  }
+};
+
+// The Transducer search with a token-level LM (wfl_transducer_beam_search_lm): transducer_beam_source
+// with the plan above.
+Hypotheses transducer_lm_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
+                                     const TransducerLmPlan& p, int nbest, bool normalize) {
+  const char* what = "transducer_beam_search_lm";
+  const Emissions e = checked_emissions(x, what);
+  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
+  TORCH_CHECK(p.lm->ints.device() == x.device(), what, ": the LM's arrays must be on x's device");
+  return {x, e.B, (int64_t)e.B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            check(wfl_transducer_beam_search_lm(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0,
+                                                p.beam, p.K, nbest, normalize ? 1 : 0, &p.lm->lm, p.lm_weight, p.length_bonus,
+                                                p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
+                  what);
+          }};
+}
+
 // The same search with hypotheses merged by spelling (wfl_transducer_beam_search_merged).
 // spelling: int32 [spell_ptr: C + 1 | spell_sym: num_symbols] on x's device, one contiguous tensor, a table that
 // wfl_spelling_check passed on the host (engine.Spelling.on_device).
@@ -1539,6 +1575,19 @@ at::Tensor transducer_beam_search_lexicon_errors(const at::Tensor& x, const c10:
 }
 
 // -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple transducer_beam_search_lm(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
+                                    const TransducerLmPlan& plan, bool normalize) {
+  const Collected r = hypotheses_collect(transducer_lm_beam_source(x, Wt, logz, plan, plan.nbest, normalize), true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+}
+
+// (the plan's first rank, unnormalised: nothing reads the scores)
+at::Tensor transducer_beam_search_lm_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const TransducerLmPlan& plan,
+                                            const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return hypotheses_errors(transducer_lm_beam_source(x, Wt, c10::nullopt, plan, 1, false), ref, tables);
+}
+
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search_merged(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
                                         const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
                                         int blank, bool forced, int beam, int K, int nbest, bool normalize) {
@@ -1642,6 +1691,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transducer_beam_search_lexicon_errors", &transducer_beam_search_lexicon_errors, py::arg("x"), py::arg("transitions"),
         py::arg("plan"), py::arg("ref"), py::arg("tables"),
         "transducer_beam_search_lexicon's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  py::class_<TransducerLmPlan>(
+      m, "TransducerLmPlan",
+      "the options of one Transducer beam search with a token-level LM, bound (engine.TransducerLmBeamPlan.on_device)")
+      .def(py::init<int, bool, int, int, int, const std::shared_ptr<DeviceLm>&, double, double, bool>(), py::arg("blank"),
+           py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("lm"), py::arg("lm_weight"),
+           py::arg("length_bonus"), py::arg("score_eos"),
+           "the blank and topology, an LM over the tokens (DeviceLm) and the scalars of the CTC search with an LM");
+  m.def("transducer_beam_search_lm", &transducer_beam_search_lm, py::arg("x"), py::arg("transitions"), py::arg("logz"),
+        py::arg("plan"), py::arg("normalize"),
+        "Transducer prefix beam search with a token-level LM on the device by a TransducerLmPlan: (labels int64 CPU, offsets "
+        "int64 CPU [B nbest + 1], scores float64 CPU [B, nbest]); transitions float32 [C + 1, C] or None; logz float32 [B] "
+        "(with transitions and normalize) or None");
+  m.def("transducer_beam_search_lm_errors", &transducer_beam_search_lm_errors, py::arg("x"), py::arg("transitions"),
+        py::arg("plan"), py::arg("ref"), py::arg("tables"),
+        "transducer_beam_search_lm's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("transducer_beam_search_merged", &transducer_beam_search_merged, py::arg("x"), py::arg("transitions"), py::arg("logz"),
         py::arg("spelling"), py::arg("num_symbols"), py::arg("blank"), py::arg("forced"), py::arg("beam"),
         py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),

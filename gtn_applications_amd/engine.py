@@ -1535,6 +1535,83 @@ def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_siz
     return plan.search(x, Wt, normalize)
 
 
+class TransducerLmBeamPlan(namedtuple(
+        "TransducerLmBeamPlan", "C blank forced beam classes_per_frame nbest lm lm_weight length_bonus lm_eos")):
+    """The options of one Transducer beam search with a token-level n-gram LM (wfl_transducer_beam_search_lm, DESIGN.md
+    section 28) over C classes (tokens + the blank), checked once (`checked`, the one constructor) and handed on whole:
+    TransducerBeamPlan's six fields, an lm.NGramLM over those classes and that blank (Transducer.token_lm builds one),
+    and the scalars of the CTC search with an LM.  Only on_device(), search() and errors need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, blank, forced, beam_size, classes_per_frame, nbest, lm, lm_weight, length_bonus, lm_eos, what):
+        """The plan of these arguments, within the limits of wfl_transducer_beam_search_lm, or ValueError (`what`: the
+        call they were given to): what TransducerBeamPlan.checked refuses; an lm that is no lm.NGramLM or was not built
+        for (C, blank); a number that is not finite; an lm_eos that is no bool."""
+        from .lm import NGramLM
+
+        def finite(v, name):
+            f = math.nan
+            if not isinstance(v, (bool, np.bool_, str, bytes)):
+                try:
+                    f = float(v)
+                except (TypeError, ValueError):
+                    pass
+            if not math.isfinite(f):
+                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+            return f
+
+        p = TransducerBeamPlan.checked(C, blank, forced, beam_size, classes_per_frame, nbest, what)
+        if not isinstance(lm, NGramLM):
+            raise ValueError(f"{what}: the token LM must be an lm.NGramLM, got {type(lm).__name__}")
+        if lm.num_classes != p.C or lm.blank != p.blank:
+            raise ValueError(f"{what}: the token LM was built for {lm.num_classes} classes with blank {lm.blank}, "
+                             f"the emissions have {p.C} with blank {p.blank}")
+        weight, bonus = finite(lm_weight, "lm_weight"), finite(length_bonus, "length_bonus")
+        if not isinstance(lm_eos, (bool, np.bool_)):
+            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+        return cls(*p, lm, weight, bonus, bool(lm_eos))
+
+    def no_frames(self, B, dtype=torch.int64):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
+        BeamPlan.no_frames: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
+        return beam_lexicon_no_frames(B, self.nbest, self.lm, self.lm_weight, self.lm_eos, dtype)
+
+    def on_device(self, device):
+        """The plan as the operators take it (ops.TransducerLmPlan, csrc/torch_ops.cpp), its lm on `device` (the LM's own
+        per-device cache: nothing is uploaded twice)"""
+        return N.ops.TransducerLmPlan(blank=self.blank, forced=self.forced, beam=self.beam,
+                                      classes_per_frame=self.classes_per_frame, nbest=self.nbest,
+                                      lm=self.lm.on_device(device), lm_weight=self.lm_weight,
+                                      length_bonus=self.length_bonus, score_eos=self.lm_eos)
+
+    def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
+        """transducer_beam_search_lm's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt:
+        float32 [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
+        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+            logz = dense_forward(x, Wt, need_beta=False).logz if Wt is not None and normalize else None
+            flat, offsets, scores = N.ops.transducer_beam_search_lm(x, Wt, logz, self.on_device(x.device), bool(normalize))
+        return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
+
+
+def transducer_beam_search_lm(x, Wt, blank, lm, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True,
+                              lm_weight=1.0, length_bonus=0.0, lm_eos=True):
+    """transducer_beam_search with a token-level n-gram LM and a length bonus (wfl_transducer_beam_search_lm through
+    csrc/torch_ops.cpp; the rules: include/wfl.h).  x, Wt, blank, forced and the result:
+    transducer_beam_search's.  lm: an lm.NGramLM over the C classes with this blank.  An extension by token c from LM
+    state s adds lm_weight * step(s, c) + length_bonus; lm_eos adds lm_weight * step(s, </s>) after the last frame, behind
+    the topology's score, and ranks again.  The scores include these terms.  With Wt None and forced False this is
+    ctc_beam_search(lm=) without lengths, bit for bit.  The options are one TransducerLmBeamPlan."""
+    what = "transducer_beam_search_lm"
+    plan = TransducerLmBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lm, lm_weight,
+                                        length_bonus, lm_eos, what)
+    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return plan.no_frames(x.shape[0])
+    return plan.search(x, Wt, normalize)
+
+
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)
 
 

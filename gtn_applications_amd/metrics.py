@@ -168,6 +168,13 @@ def transducer_beam_search_lexicon_errors(counter, targets, x, Wt, plan):
     return N.ops.transducer_beam_search_lexicon_errors(x, Wt, plan.on_device(x.device), ref, tables)
 
 
+def transducer_beam_search_lm_errors(counter, targets, x, Wt, plan):
+    """transducer_beam_search_errors for the search with a token-level LM (`plan`: a checked engine.TransducerLmBeamPlan):
+    the launches of its search() and the counts behind them"""
+    ref, tables, _ = _staged(counter, targets, x)
+    return N.ops.transducer_beam_search_lm_errors(x, Wt, plan.on_device(x.device), ref, tables)
+
+
 def transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling):
     """transducer_beam_search_errors with hypotheses merged by spelling (`spelling`: the engine.Spelling of the plan's
     classes and blank): the launches of engine.transducer_merged_search and the counts behind them"""

@@ -918,7 +918,8 @@ int wfl_asg_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] */
  *   WFL_ERR_INVALID: a NULL required pointer (Wt and logz may be NULL), B, T or C < 1, blank outside [0, C), forced not
  *   0 or 1, beam outside [1, 64], classes_per_frame outside [1, min(C, 64)], nbest outside [1, beam], out_capacity too
  *   small, normalize != 0 with Wt but without logz, logz without Wt.  WFL_ERR_UNSUPPORTED: C > 16384.
- *   Not here: the ambiguous token graphs (no blank; the optional blank with repeats), an LM, a lexicon, input lengths.
+ *   Not here: the ambiguous token graphs (no blank; the optional blank with repeats), input lengths.  A token-level LM:
+ *   wfl_transducer_beam_search_lm; a lexicon: wfl_transducer_beam_search_lexicon.
  * ------------------------------------------------------------------------------------------------ */
 /* out_capacity = B nbest T (int32 elements of `out`), ws_bytes = the device scratch of a call */
 int wfl_transducer_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
@@ -1025,6 +1026,45 @@ int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1)
                                        const wfl_ngram_lm* word_lm /* or NULL */, double lm_weight, double word_bonus,
                                        double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                                        int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The Transducer search with a token-level n-gram LM and a length bonus (csrc/beam_kernels.hip):
+ * shallow fusion with an LM over the tokens themselves -- no vocabulary, and words that no lexicon lists.
+ *   Every rule of wfl_transducer_beam_search (rules 1-7) stands.  The LM form, step(s, c), wfl_ngram_lm and
+ *   wfl_ngram_lm_check are those of wfl_ctc_beam_search_lm: labels are the classes 0 .. C-1, never the blank (which is
+ *   one of the C classes), and label C stands for </s>.  a = lm_weight, b = length_bonus, both finite float64.
+ *     1. every hypothesis carries an LM state, the empty prefix has lm->start;
+ *     2. a stay entry (rule 3) adds nothing and keeps its state;
+ *     3. the extension of hypothesis i by a candidate c != blank (rule 4, both topologies), m the mass term rule 4 gives
+ *        for the topology (forced = 0: lae of both masses, pb alone for c == l; forced = 1: pb alone, and no extension
+ *        in frame 0): s_c + m = -inf: the extension does not exist and nothing is looked up.  Otherwise
+ *        (l, nxt) = step(state_i, c); l = -inf: the extension does not exist; otherwise e = (s_c + m) + (a l + b), each
+ *        operation rounded on its own, and the entry gets the state nxt.  A merged extension carries the same term as a
+ *        new one (state and LM score are functions of the prefix), so unpruned tot(l) = mass(l) + a LM(l) + b |l|;
+ *     4. the kernel may skip the lookup of an extension that cannot reach the W-th best stay entry even with the largest
+ *        possible term, max(a step_min, a step_max) + b.  The bound decides what is ranked, never the result;
+ *     5. after the last frame: q_r = tot_r for forced = 0; for forced = 1 q_r = pb_r, and the ranks with pb_r = -inf are
+ *        dropped first (rule 6).  With score_eos != 0 the score is q_r + a step(state_r, C) and a rank whose step is -inf
+ *        is dropped; without it the score is q_r.  One re-ranking by that score, descending, ties to the earlier rank;
+ *        nbest is taken after it; missing ranks are empty sequences with score -inf;
+ *     6. normalize subtracts what rule 7 subtracts and nothing else;
+ *     7. Wt == NULL and forced == 0 are wfl_ctc_beam_search_lm's rules without lengths, and its search is what runs:
+ *        bit-identical results;
+ *     8. candidates, prefix identity, entry order, the tie rule and the -inf drop rule do not change.
+ *   lm: a struct in HOST memory of DEVICE pointers to a pack that wfl_ngram_lm_check accepted for (C, blank), with the
+ *   step_min / step_max it wrote; the kernels trust it.  The workspace is wfl_transducer_beam_workspace's; outputs as in
+ *   wfl_transducer_beam_search.  Three launches, no allocation, no synchronisation, no atomics on global memory, no
+ *   cross-workgroup waits, every loop bounded by T, W, K, the back-off cap or 31 search steps; deterministic.
+ *   WFL_ERR_INVALID: what wfl_transducer_beam_search refuses, in its order; then what wfl_ctc_beam_search_lm refuses
+ *   about the LM (lm or one of its arrays NULL, num_states < 1, num_arcs < 0, start outside [0, num_states), step_min
+ *   or step_max NaN) and a weight or bonus that is not finite.  Not here: ASG with a letter LM, a token-level LM
+ *   together with a lexicon or with merging by spelling, input lengths, the ambiguous token graphs.
+ * ------------------------------------------------------------------------------------------------ */
+int wfl_transducer_beam_search_lm(const float* x, const float* Wt /* [(C+1), C] or NULL */, const float* logz /* [B] or NULL */,
+                                  int B, int T, int C, int blank, int forced, int beam, int classes_per_frame, int nbest,
+                                  int normalize, const wfl_ngram_lm* lm, double lm_weight, double length_bonus, int score_eos,
+                                  void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
+                                  double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The four lexicon searches of CTC and the Transducer with word-LM LOOK-AHEAD inside words (csrc/beam_kernels.hip; DESIGN
