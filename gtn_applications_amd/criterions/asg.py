@@ -8,7 +8,6 @@ transitions tensor is the graph.
 """
 import ctypes
 import itertools
-import numbers
 import os
 
 import torch
@@ -335,17 +334,6 @@ def _refuse_lookahead(what, lookahead):
             "that bound is a question of its own")
 
 
-def _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus):
-    """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default"""
-    if lm is not None:
-        raise ValueError(f"{what}: lm needs a lexicon (the lm of an ASG search is a word LM)")
-    for name, v, default in (("lm_weight", lm_weight, 1.0), ("length_bonus", length_bonus, 0.0), ("word_bonus", word_bonus, 0.0)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or float(v) != default:  # (numpy's numbers are Real too)
-            raise ValueError(f"{what}: {name} needs a lexicon, got {v!r}")
-    if lm_eos is not True:
-        raise ValueError(f"{what}: lm_eos needs a lexicon, got {lm_eos!r}")
-
-
 class ASG(torch.nn.Module):
     def __init__(self, num_classes, num_replabels=1, use_garbage=True):
         super(ASG, self).__init__()
@@ -401,7 +389,7 @@ class ASG(torch.nn.Module):
         if outputs.shape[2] != self.N:
             raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {self.N}")
         if lexicon is None:
-            _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            E.refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus, "an ASG")
             return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)
         return E.AsgLexiconBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, self.garbage_idx, lexicon, lm,
                                             lm_weight, word_bonus, length_bonus, lm_eos, what)
@@ -523,7 +511,7 @@ class ASG(torch.nn.Module):
                 raise ValueError("ASG.errors: classes_per_frame needs a beam_size")
             if lexicon is not None:
                 raise ValueError("ASG.errors: lexicon needs a beam_size")
-            _refuse_without_lexicon("ASG.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            E.refuse_without_lexicon("ASG.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus, "an ASG")
         else:
             plan = self._beam_plan(outputs, "ASG.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
                                    length_bonus, lm_eos, word_bonus)
@@ -531,9 +519,8 @@ class ASG(torch.nn.Module):
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
                 return counter([h[0] for h in plan.no_frames(outputs.shape[0])[0]], targets)
             x, W = self._beam_inputs(outputs)
-            count = M.asg_beam_search_errors if lexicon is None else M.asg_beam_search_lexicon_errors
             with torch.cuda.device(x.device), torch.no_grad():
-                return counter.totals(count(counter, targets, x, W, plan, self.garbage_idx, self.num_replabels))
+                return counter.totals(M.plan_errors(counter, targets, x, plan, W, self.garbage_idx, self.num_replabels))
         counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
         with torch.no_grad():
             if not (outputs.is_cuda and outputs.shape[0] > 0):

@@ -476,7 +476,7 @@ class CTC(torch.nn.Module):
             x = self._beam_emissions(outputs)
             with torch.cuda.device(x.device), torch.no_grad():
                 xlen = None if lens is None else E.input_lengths_on_device(lens, x.device)
-                return counter.totals(M.beam_search_errors(counter, targets, x, plan, lengths=xlen))
+                return counter.totals(M.plan_errors(counter, targets, x, plan, xlen))
         lens = None
         if input_lengths is not None:
             lens = check_input_lengths(input_lengths, outputs.shape[0], outputs.shape[1], "CTC.errors")

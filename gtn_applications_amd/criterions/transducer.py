@@ -239,17 +239,6 @@ def _alignment_graph(target, tokens, lexicon, transitions, direct=False):
 _DENSE_NGRAM = os.environ.get("WFL_DENSE_NGRAM", "1") != "0"
 
 
-def _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus):
-    """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default"""
-    if lm is not None:
-        raise ValueError(f"{what}: lm needs a lexicon (the lm of a Transducer search is a word LM)")
-    for name, v, default in (("lm_weight", lm_weight, 1.0), ("length_bonus", length_bonus, 0.0), ("word_bonus", word_bonus, 0.0)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or float(v) != default:  # (numpy's numbers are Real too)
-            raise ValueError(f"{what}: {name} needs a lexicon, got {v!r}")
-    if lm_eos is not True:
-        raise ValueError(f"{what}: lm_eos needs a lexicon, got {lm_eos!r}")
-
-
 class Transducer(torch.nn.Module):
     """A generic transducer loss (transducer.py:126-234).
 
@@ -426,7 +415,7 @@ class Transducer(torch.nn.Module):
         elif lexicon is None:
             if lookahead is not None:
                 raise ValueError(f"{what}: lookahead needs a lexicon and its word lm")
-            _refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            E.refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus, "a Transducer")
             plan = E.TransducerBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest, what)
         else:
             plan = E.TransducerLexiconBeamPlan.checked(C, n.value, mode == N.TOKENS_FORCED, beam_size, classes_per_frame, nbest,
@@ -601,16 +590,14 @@ class Transducer(torch.nn.Module):
         what = "Transducer.beam_search"
         plan, kind = self._beam_plan(outputs, what, beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight, length_bonus,
                                      lm_eos, word_bonus, lookahead, token_lm)
-        spelling = self._spelling(plan, what) if self._merge_flag(merge_spellings, what, lexicon, token_lm) else None
+        # (the plan knows its search; merging by spelling is the plain plan's, with the tokens' Spelling)
+        merged = {"spelling": self._spelling(plan, what)} if self._merge_flag(merge_spellings, what, lexicon, token_lm) else {}
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0], torch.int32)
         else:
             x, Wt = self._beam_inputs(outputs, kind)
             with torch.cuda.device(x.device), torch.no_grad():
-                if spelling is not None:
-                    hyps, scores = E.transducer_merged_search(plan, x, Wt, spelling, True, torch.int32)
-                else:
-                    hyps, scores = plan.search(x, Wt, True, torch.int32)
+                hyps, scores = plan.search(x, Wt, True, torch.int32, **merged)
         if plan.nbest == 1:
             hyps = [h[0] for h in hyps]
         return (hyps, scores) if return_scores else hyps
@@ -636,23 +623,17 @@ class Transducer(torch.nn.Module):
                 raise ValueError("Transducer.errors: classes_per_frame and merge_spellings need a beam_size")
             if lexicon is not None:
                 raise ValueError("Transducer.errors: lexicon needs a beam_size")
-            _refuse_without_lexicon("Transducer.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus)
+            E.refuse_without_lexicon("Transducer.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus, "a Transducer")
         else:
             plan, kind = self._beam_plan(outputs, "Transducer.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
                                          length_bonus, lm_eos, word_bonus, lookahead, token_lm)
-            spelling = self._spelling(plan, "Transducer.errors") if merge else None
+            merged = {"spelling": self._spelling(plan, "Transducer.errors")} if merge else {}
             counter.check_hypothesis_labels(plan.C - 1, "Transducer.errors")  # (the blank is never a label of a result)
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
                 return counter([h[0] for h in plan.no_frames(outputs.shape[0], torch.int32)[0]], targets)
             x, Wt = self._beam_inputs(outputs, kind)
             with torch.cuda.device(x.device), torch.no_grad():
-                if merge:
-                    return counter.totals(M.transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling))
-                if lexicon is not None:
-                    return counter.totals(M.transducer_beam_search_lexicon_errors(counter, targets, x, Wt, plan))
-                if token_lm is not None:
-                    return counter.totals(M.transducer_beam_search_lm_errors(counter, targets, x, Wt, plan))
-                return counter.totals(M.transducer_beam_search_errors(counter, targets, x, Wt, plan))
+                return counter.totals(M.plan_errors(counter, targets, x, plan, Wt, **merged))
         C = outputs.shape[2]
         dplan = self._device_decode(C)
         # (a blank in the last column is never emitted)

@@ -1576,6 +1576,52 @@ static int beam_run(const char* what, const BeamCall& c, Pack... pack) {
   return WFL_OK;
 }
 
+// What the seven Transducer entries do first, in this order: the call (no lengths; with transitions logz normalises,
+// not the rows), beam_call_check, the topology's flag -- beam_tok_call --, then the denominator's rule and the
+// transitions of the launch -- beam_tok_terms.  Two halves, since wfl_transducer_beam_search_merged refuses a NULL
+// spelling table between them.
+struct BeamTokCall {
+  BeamCall c;
+  BeamTok tok;
+};
+static int beam_tok_call(const char* what, const float* x, const float* Wt, int B, int T, int C, int blank, int forced, int beam, int K,
+                         int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets, double* scores,
+                         void* stream, BeamTokCall* p) {
+  p->c = BeamCall{x, nullptr, B, T, C, blank, beam, K, nbest, normalize, ws, out, out_capacity, out_offsets, scores, stream, !Wt};
+  // (beam_run makes this check again: an entry's own have always come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, p->c)) return rc;
+  if (forced != 0 && forced != 1) {
+    set_error("%s: forced %d is neither 0 nor 1", what, forced);
+    return WFL_ERR_INVALID;
+  }
+  return WFL_OK;
+}
+static int beam_tok_terms(const char* what, const float* Wt, const float* logz, int forced, BeamTokCall* p) {
+  if ((Wt != nullptr) != (logz != nullptr) && (p->c.normalize || logz)) {
+    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
+    return WFL_ERR_INVALID;
+  }
+  p->tok = BeamTok{Wt, p->c.normalize ? logz : nullptr, p->c.C, forced};
+  return WFL_OK;
+}
+static int beam_tok_prelude(const char* what, const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                            int forced, int beam, int K, int nbest, int normalize, void* ws, int32_t* out, int64_t out_capacity,
+                            int64_t* out_offsets, double* scores, void* stream, BeamTokCall* p) {
+  if (const int rc = beam_tok_call(what, x, Wt, B, T, C, blank, forced, beam, K, nbest, normalize, ws, out, out_capacity, out_offsets,
+                                   scores, stream, p))
+    return rc;
+  return beam_tok_terms(what, Wt, logz, forced, p);
+}
+
+// CTC's topology runs CTC's search: without transitions and with the optional blank a Transducer entry's rules are its
+// CTC sibling's without lengths, and that sibling's kernel is the one that runs -- with the sibling's pack `ctc` (none:
+// the plain search); otherwise the entry's own, with `tok`
+template <typename Tok, typename... Ctc>
+static int beam_run_tok(const char* what, const BeamTokCall& p, const Tok& tok, const Ctc&... ctc) {
+  if (!p.tok.Wt && !p.tok.forced) return beam_run(what, p.c, ctc...);
+  return beam_run(what, p.c, tok);
+}
+
 extern "C" {
 
 // The beam search of the ASG criterion (asg.py:54-69: the transitions; asg.py:72-115: the score of a label sequence, the
@@ -1611,22 +1657,11 @@ int wfl_transducer_beam_search(const float* x, const float* Wt, const float* log
                                int beam, int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out,
                                int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "transducer_beam_search";
-  // no lengths; with transitions logz normalises, not the rows
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own have always come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  // no transitions, CTC's topology: these are section 17's rules, and its search is the one that runs
-  if (!Wt && !forced) return beam_run(what, c);
-  return beam_run(what, c, BeamTok{Wt, normalize ? logz : nullptr, C, forced});
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
+  return beam_run_tok(what, p, p.tok);  // (CTC's side: section 17's rules, the plain search)
 }
 
 int wfl_spelling_check(const int32_t* spell_ptr, const int32_t* spell_sym, int C, int blank) {
@@ -1673,22 +1708,16 @@ int wfl_transducer_beam_search_merged(const float* x, const float* Wt, const flo
                                       int classes_per_frame, int nbest, int normalize, void* ws, int32_t* out,
                                       int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "transducer_beam_search_merged";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
+  BeamTokCall p;
+  if (const int rc = beam_tok_call(what, x, Wt, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                   out_capacity, out_offsets, scores, stream, &p))
+    return rc;
   if (!spell_ptr || !spell_sym) {
     set_error("%s: a NULL spelling table", what);
     return WFL_ERR_INVALID;
   }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  return beam_run(what, c, BeamSpell{BeamTok{Wt, normalize ? logz : nullptr, C, forced}, spell_ptr, spell_sym});
+  if (const int rc = beam_tok_terms(what, Wt, logz, forced, &p)) return rc;
+  return beam_run(what, p.c, BeamSpell{p.tok, spell_ptr, spell_sym});
 }
 
 int wfl_ctc_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int64_t* out_capacity,
@@ -1825,18 +1854,10 @@ int wfl_transducer_beam_search_lm(const float* x, const float* Wt, const float* 
                                   double lm_weight, double length_bonus, int score_eos, void* ws, int32_t* out,
                                   int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "transducer_beam_search_lm";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
   BeamTokLm d;
   if (const int rc = beam_lm_terms(what, lm, false, C, lm_weight, length_bonus, score_eos, &d.lm)) return rc;
   if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
@@ -1844,10 +1865,8 @@ int wfl_transducer_beam_search_lm(const float* x, const float* Wt, const float* 
     return WFL_ERR_INVALID;
   }
   d.lm.bound = beam_tok_lm_bound(lm_weight, lm->step_min, lm->step_max, length_bonus);
-  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  // no transitions, CTC's topology: these are section 18's rules without lengths, and its search is the one that runs
-  if (!Wt && !forced) return beam_run(what, c, d.lm);
-  return beam_run(what, c, d);
+  d.tok = p.tok;
+  return beam_run_tok(what, p, d, d.lm);  // (CTC's side: section 18's rules without lengths)
 }
 
 static int lexicon_shape(const char* what, const wfl_lexicon* lex) {
@@ -1967,46 +1986,6 @@ static int beam_lex_fill(const char* what, const wfl_lexicon* lex, const wfl_ngr
   return WFL_OK;
 }
 
-int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
-                                int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
-                                const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
-                                int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
-                                double* scores, void* stream) {
-  const char* what = "ctc_beam_search_lexicon";
-  BeamLex d;
-  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
-  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                         scores, stream}, d);
-}
-
-// The Transducer search with a lexicon and an optional word LM (DESIGN.md section 25): wfl_transducer_beam_search's call
-// and checks in its order, then wfl_ctc_beam_search_lexicon's checks of the lexicon, the LM and the three constants.
-int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
-                                       int forced, int beam, int classes_per_frame, int nbest, int normalize,
-                                       const wfl_lexicon* lex, const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
-                                       double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
-                                       int64_t* out_offsets, double* scores, void* stream) {
-  const char* what = "transducer_beam_search_lexicon";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  BeamTokLex d;
-  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
-  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  // no transitions, CTC's topology: these are section 20's rules without lengths, and its search is the one that runs
-  if (!Wt && !forced) return beam_run(what, c, d.lex);
-  return beam_run(what, c, d);
-}
-
 static int lexicon_marked_shape(const char* what, const wfl_lexicon_marked* lex) {
   if (!lex) {
     set_error("%s: a NULL lexicon or array of it", what);
@@ -2119,50 +2098,6 @@ int wfl_lexicon_marked_check(const wfl_lexicon_marked* lex, int C, int blank) {
         return WFL_ERR_INVALID;
       }
   return WFL_OK;
-}
-
-// wfl_ctc_beam_search_lexicon with a start-marked lexicon (DESIGN.md section 26): its checks in its order
-int wfl_ctc_beam_search_lexicon_marked(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
-                                       int classes_per_frame, int nbest, int normalize, const wfl_lexicon_marked* lex,
-                                       const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
-                                       int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
-                                       double* scores, void* stream) {
-  const char* what = "ctc_beam_search_lexicon_marked";
-  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
-  BeamLexMarked d;
-  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
-  d.node_word = lex->node_word, d.start_node = lex->start_node;
-  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                         scores, stream}, d);
-}
-
-// wfl_transducer_beam_search_lexicon with a start-marked lexicon (DESIGN.md section 26): its checks in its order
-int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
-                                              int forced, int beam, int classes_per_frame, int nbest, int normalize,
-                                              const wfl_lexicon_marked* lex, const wfl_ngram_lm* word_lm, double lm_weight,
-                                              double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
-                                              int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
-  const char* what = "transducer_beam_search_lexicon_marked";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
-  BeamTokLexMarked d;
-  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex.lex)) return rc;
-  d.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  d.lex.node_word = lex->node_word, d.lex.start_node = lex->start_node;
-  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_marked's rules without lengths, and its search runs
-  if (!Wt && !forced) return beam_run(what, c, d.lex);
-  return beam_run(what, c, d);
 }
 
 // What both look-ahead checks share (DESIGN.md section 27 rule 6): the lexicon's CSR inside its arrays -- so that nothing
@@ -2278,6 +2213,67 @@ static int beam_look_fill(const char* what, const wfl_lexicon_lookahead* look, c
   return WFL_OK;
 }
 
+
+}  // extern "C"
+
+// The lexicon's pack of a launch, for the nine entries below -- P: BeamLex, BeamLexMarked or the BeamLook of either, by
+// the lexicon's convention (`lex`: a wfl_lexicon or a wfl_lexicon_marked) and whether there is a look-ahead (`look`, not
+// read otherwise).  The checks in the order the entries have always had them: the start-marked lexicon's shape,
+// beam_lex_fill, beam_look_fill.
+template <typename P, typename Lexicon>
+static int beam_lex_pack(const char* what, const Lexicon* lex, const wfl_lexicon_lookahead* look, const wfl_ngram_lm* word_lm,
+                         double lm_weight, double word_bonus, double length_bonus, int score_eos, P* d) {
+  constexpr bool marked = BeamMarked<P>::value, looks = BeamLooks<P>::value;
+  auto* base = [d] {
+    if constexpr (looks)
+      return &d->pack;
+    else
+      return d;
+  }();
+  const wfl_lexicon* trie;
+  BeamLex* lx;
+  if constexpr (marked) {
+    if (const int rc = lexicon_marked_shape(what, lex)) return rc;
+    trie = &lex->trie, lx = &base->lex;
+    base->node_word = lex->node_word, base->start_node = lex->start_node;
+  } else {
+    trie = lex, lx = base;
+  }
+  if (const int rc = beam_lex_fill(what, trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, lx)) return rc;
+  if constexpr (looks) {
+    if (const int rc = beam_look_fill(what, look, word_lm, lx)) return rc;
+    d->node_look = look->node_look;
+  }
+  return WFL_OK;
+}
+
+extern "C" {
+
+int wfl_ctc_beam_search_lexicon(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
+                                const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
+                                int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                                double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon";
+  BeamLex d;
+  if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
+}
+
+// wfl_ctc_beam_search_lexicon with a start-marked lexicon (DESIGN.md section 26): its checks in its order
+int wfl_ctc_beam_search_lexicon_marked(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
+                                       int classes_per_frame, int nbest, int normalize, const wfl_lexicon_marked* lex,
+                                       const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus, double length_bonus,
+                                       int score_eos, void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
+                                       double* scores, void* stream) {
+  const char* what = "ctc_beam_search_lexicon_marked";
+  BeamLexMarked d;
+  if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
+                         scores, stream}, d);
+}
+
 // wfl_ctc_beam_search_lexicon with look-ahead: its checks in its order, then the look-ahead's
 int wfl_ctc_beam_search_lexicon_lookahead(const float* x, const int32_t* lengths, int B, int T, int C, int blank, int beam,
                                           int classes_per_frame, int nbest, int normalize, const wfl_lexicon* lex,
@@ -2286,9 +2282,7 @@ int wfl_ctc_beam_search_lexicon_lookahead(const float* x, const int32_t* lengths
                                           int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "ctc_beam_search_lexicon_lookahead";
   BeamLexLook d;
-  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack)) return rc;
-  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack)) return rc;
-  d.node_look = look->node_look;
+  if (const int rc = beam_lex_pack(what, lex, look, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
 }
@@ -2300,14 +2294,43 @@ int wfl_ctc_beam_search_lexicon_marked_lookahead(const float* x, const int32_t* 
                                                  double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
                                                  int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "ctc_beam_search_lexicon_marked_lookahead";
-  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
   BeamLexMarkedLook d;
-  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex)) return rc;
-  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex)) return rc;
-  d.pack.node_word = lex->node_word, d.pack.start_node = lex->start_node;
-  d.node_look = look->node_look;
+  if (const int rc = beam_lex_pack(what, lex, look, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
   return beam_run(what, {x, lengths, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
                          scores, stream}, d);
+}
+
+// The Transducer search with a lexicon and an optional word LM (DESIGN.md section 25): wfl_transducer_beam_search's call
+// and checks in its order, then wfl_ctc_beam_search_lexicon's checks of the lexicon, the LM and the three constants.
+int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                                       int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                       const wfl_lexicon* lex, const wfl_ngram_lm* word_lm, double lm_weight, double word_bonus,
+                                       double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                                       int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon";
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
+  BeamLex d;
+  if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  return beam_run_tok(what, p, BeamTokLex{p.tok, d}, d);  // (CTC's side: section 20's rules without lengths)
+}
+
+// wfl_transducer_beam_search_lexicon with a start-marked lexicon (DESIGN.md section 26): its checks in its order
+int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt, const float* logz, int B, int T, int C, int blank,
+                                              int forced, int beam, int classes_per_frame, int nbest, int normalize,
+                                              const wfl_lexicon_marked* lex, const wfl_ngram_lm* word_lm, double lm_weight,
+                                              double word_bonus, double length_bonus, int score_eos, void* ws, int32_t* out,
+                                              int64_t out_capacity, int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "transducer_beam_search_lexicon_marked";
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
+  BeamLexMarked d;
+  if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  return beam_run_tok(what, p, BeamTokLexMarked{p.tok, d}, d);  // (CTC's side: wfl_ctc_beam_search_lexicon_marked's rules)
 }
 
 // wfl_transducer_beam_search_lexicon with look-ahead: its checks in its order, then the look-ahead's
@@ -2318,26 +2341,14 @@ int wfl_transducer_beam_search_lexicon_lookahead(const float* x, const float* Wt
                                                  double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
                                                  int64_t* out_offsets, double* scores, void* stream) {
   const char* what = "transducer_beam_search_lexicon_lookahead";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  BeamTokLexLook d;
-  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex)) return rc;
-  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex)) return rc;
-  d.pack.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  d.node_look = look->node_look;
-  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_lookahead's rules without lengths, and its search runs
-  if (!Wt && !forced) return beam_run(what, c, BeamLexLook{d.pack.lex, d.node_look});
-  return beam_run(what, c, d);
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
+  BeamLexLook d;
+  if (const int rc = beam_lex_pack(what, lex, look, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  // (CTC's side: wfl_ctc_beam_search_lexicon_lookahead's rules without lengths)
+  return beam_run_tok(what, p, BeamTokLexLook{{p.tok, d.pack}, d.node_look}, d);
 }
 
 // wfl_transducer_beam_search_lexicon_marked with look-ahead: its checks in its order, then the
@@ -2350,28 +2361,14 @@ int wfl_transducer_beam_search_lexicon_marked_lookahead(const float* x, const fl
                                                         void* ws, int32_t* out, int64_t out_capacity, int64_t* out_offsets,
                                                         double* scores, void* stream) {
   const char* what = "transducer_beam_search_lexicon_marked_lookahead";
-  const BeamCall c{x, nullptr, B, T, C, blank, beam, classes_per_frame, nbest, normalize, ws, out, out_capacity, out_offsets,
-                   scores, stream, !Wt};
-  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
-  if (const int rc = beam_call_check(what, c)) return rc;
-  if (forced != 0 && forced != 1) {
-    set_error("%s: forced %d is neither 0 nor 1", what, forced);
-    return WFL_ERR_INVALID;
-  }
-  if ((Wt != nullptr) != (logz != nullptr) && (normalize || logz)) {
-    set_error("%s: normalised scores need logz with transitions, and logz belongs to transitions only", what);
-    return WFL_ERR_INVALID;
-  }
-  if (const int rc = lexicon_marked_shape(what, lex)) return rc;
-  BeamTokLexMarkedLook d;
-  if (const int rc = beam_lex_fill(what, &lex->trie, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.pack.lex.lex)) return rc;
-  if (const int rc = beam_look_fill(what, look, word_lm, &d.pack.lex.lex)) return rc;
-  d.pack.tok = BeamTok{Wt, normalize ? logz : nullptr, C, forced};
-  d.pack.lex.node_word = lex->node_word, d.pack.lex.start_node = lex->start_node;
-  d.node_look = look->node_look;
-  // no transitions, CTC's topology: wfl_ctc_beam_search_lexicon_marked_lookahead's rules without lengths, and its search runs
-  if (!Wt && !forced) return beam_run(what, c, BeamLexMarkedLook{d.pack.lex, d.node_look});
-  return beam_run(what, c, d);
+  BeamTokCall p;
+  if (const int rc = beam_tok_prelude(what, x, Wt, logz, B, T, C, blank, forced, beam, classes_per_frame, nbest, normalize, ws, out,
+                                      out_capacity, out_offsets, scores, stream, &p))
+    return rc;
+  BeamLexMarkedLook d;
+  if (const int rc = beam_lex_pack(what, lex, look, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d)) return rc;
+  // (CTC's side: wfl_ctc_beam_search_lexicon_marked_lookahead's rules without lengths)
+  return beam_run_tok(what, p, BeamTokLexMarkedLook{{p.tok, d.pack}, d.node_look}, d);
 }
 
 // The ASG search with a lexicon and an optional word LM: wfl_asg_beam_search's call and checks,
@@ -2395,7 +2392,7 @@ int wfl_asg_beam_search_lexicon(const float* x, const float* Wt, const float* lo
     return WFL_ERR_INVALID;
   }
   BeamAsgLex d;
-  if (const int rc = beam_lex_fill(what, lex, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
+  if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
   d.asg = BeamAsg{Wt, logz, C};
   d.garbage = garbage;
   return beam_run(what, c, d);

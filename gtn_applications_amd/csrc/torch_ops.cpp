@@ -1051,272 +1051,159 @@ struct DeviceLookahead {
   }
 };
 
-// The options of one beam search as both beam ops take them (engine.py's BeamPlan.on_device binds the values it has
-// checked).  lm none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not read; lexicon: lm is its word LM.
-struct BeamPlan {
-  int blank, beam, K, nbest;
+enum BeamFamily { kBeamCtc, kBeamAsg, kBeamTransducer };
+// the names errors carry, [family][kind]: the C entries' (a lexicon's kinds: + 1 start-marked, + 2 with look-ahead)
+enum BeamKind { kBeamPlain, kBeamLm, kBeamLexicon, kBeamLexiconMarked, kBeamLexiconLookahead, kBeamLexiconMarkedLookahead, kBeamMerged };
+#define WFL_BEAM_NAMES(f) {f, f "_lm", f "_lexicon", f "_lexicon_marked", f "_lexicon_lookahead", f "_lexicon_marked_lookahead", f "_merged"}
+const char* const kBeamNames[3][7] = {WFL_BEAM_NAMES("ctc_beam_search"), WFL_BEAM_NAMES("asg_beam_search"),
+                                      WFL_BEAM_NAMES("transducer_beam_search")};
+// The options of one bound beam search, whichever criterion's it is: what the module's four plan classes (below)
+// construct and every beam op takes.  blank: -1 for ASG, which has none; forced: the Transducer's topology; garbage:
+// ASG's with a lexicon (-1: none).  lm none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not
+// read; lexicon: lm is its word LM; lookahead none: the lexicon search as it was.
+struct BeamOptions {
+  BeamFamily family;
+  int blank;
+  bool forced;
+  int beam, K, nbest, garbage;
   std::shared_ptr<DeviceLm> lm;
-  double lm_weight, length_bonus;
-  bool score_eos;
   std::shared_ptr<DeviceLexicon> lexicon;
-  double word_bonus;
-  std::shared_ptr<DeviceLookahead> lookahead;  // or none: the lexicon search as it was
+  std::shared_ptr<DeviceLookahead> lookahead;
+  double lm_weight, word_bonus, length_bonus;
+  bool score_eos;
+  BeamOptions(BeamFamily family_, int blank_, bool forced_, int beam_, int K_, int nbest_, int garbage_ = -1,
+              const std::shared_ptr<DeviceLm>& lm_ = nullptr, const std::shared_ptr<DeviceLexicon>& lexicon_ = nullptr,
+              const std::shared_ptr<DeviceLookahead>& lookahead_ = nullptr, double lm_weight_ = 1.0, double word_bonus_ = 0.0,
+              double length_bonus_ = 0.0, bool score_eos_ = true)
+      : family(family_), blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), garbage(garbage_), lm(lm_),
+        lexicon(lexicon_), lookahead(lookahead_), lm_weight(lm_weight_), word_bonus(word_bonus_), length_bonus(length_bonus_),
+        score_eos(score_eos_) {
+    const char* what = kBeamNames[family][kBeamLexicon];
+    TORCH_CHECK(family != kBeamAsg || !lexicon || !lexicon->is_marked, what, ": a start-marked lexicon is not for ASG");
+    TORCH_CHECK(!lm || !lexicon || lm->ints.device() == lexicon->ints.device(), what,
+                ": the word LM's arrays must be on the lexicon's device");
+    if (lookahead) lookahead->check_for(lexicon, lm, kBeamNames[family][kBeamLexiconLookahead]);
+  }
+};
+
+// The four plan classes of the module, each the constructor of a BeamOptions by the keywords of its engine.*.on_device
+struct BeamPlan : BeamOptions {  // CTC's: an lm, a lexicon and its look-ahead are all optional
   BeamPlan(int blank_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
            double length_bonus_, bool score_eos_, const std::shared_ptr<DeviceLexicon>& lexicon_, double word_bonus_,
            const std::shared_ptr<DeviceLookahead>& lookahead_)
-      : blank(blank_), beam(beam_), K(K_), nbest(nbest_), lm(lm_), lm_weight(lm_weight_), length_bonus(length_bonus_),
-        score_eos(score_eos_), lexicon(lexicon_), word_bonus(word_bonus_), lookahead(lookahead_) {
-    TORCH_CHECK(!lm || !lexicon || lm->ints.device() == lexicon->ints.device(),
-                "ctc_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
-    if (lookahead) lookahead->check_for(lexicon, lm, "ctc_beam_search_lexicon_lookahead");
-  }
+      : BeamOptions(kBeamCtc, blank_, false, beam_, K_, nbest_, -1, lm_, lexicon_, lookahead_, lm_weight_, word_bonus_,
+                    length_bonus_, score_eos_) {}
 };
-
-// nothing fused: wfl_ctc_beam_search, the call it was; an lm: wfl_ctc_beam_search_lm; a lexicon: wfl_ctc_beam_search_lexicon
-Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& p, int nbest,
-                       bool normalize) {
-  const char* what = "ctc_beam_search";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor lt = checked_lengths(lengths, x, what);
-  TORCH_CHECK(!p.lm || p.lm->ints.device() == x.device(), "ctc_beam_search_lm: the LM's arrays must be on x's device");
-  TORCH_CHECK(!p.lexicon || p.lexicon->ints.device() == x.device(),
-              "ctc_beam_search_lexicon: the lexicon's arrays must be on x's device");
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_ctc_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            const int32_t* lp = lt.defined() ? lt.data_ptr<int32_t>() : nullptr;
-            if (p.lookahead && p.lexicon->is_marked)
-              check(wfl_ctc_beam_search_lexicon_marked_lookahead(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K,
-                                                                 nbest, normalize ? 1 : 0, &p.lexicon->marked,
-                                                                 &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
-                                                                 p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores,
-                                                                 s),
-                    "ctc_beam_search_lexicon_marked_lookahead");
-            else if (p.lookahead)
-              check(wfl_ctc_beam_search_lexicon_lookahead(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
-                                                          normalize ? 1 : 0, &p.lexicon->lex, &p.lookahead->look, &p.lm->lm,
-                                                          p.lm_weight, p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out,
-                                                          cap, offs, scores, s),
-                    "ctc_beam_search_lexicon_lookahead");
-            else if (p.lexicon && p.lexicon->is_marked)
-              check(wfl_ctc_beam_search_lexicon_marked(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
-                                                       normalize ? 1 : 0, &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr,
-                                                       p.lm_weight, p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out,
-                                                       cap, offs, scores, s),
-                    "ctc_beam_search_lexicon_marked");
-            else if (p.lexicon)
-              check(wfl_ctc_beam_search_lexicon(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest,
-                                                normalize ? 1 : 0, &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
-                                                p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                    "ctc_beam_search_lexicon");
-            else if (p.lm)
-              check(wfl_ctc_beam_search_lm(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0,
-                                           &p.lm->lm, p.lm_weight, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs,
-                                           scores, s),
-                    "ctc_beam_search_lm");
-            else
-              check(wfl_ctc_beam_search(x.data_ptr<float>(), lp, e.B, e.T, e.C, p.blank, p.beam, p.K, nbest, normalize ? 1 : 0, ws,
-                                        out, cap, offs, scores, s),
-                    what);
-          }};
-}
-
-// The ASG prefix beam search (wfl_asg_beam_search): the options are engine.AsgBeamPlan's, already
-// checked.  logz: float32 [B] on x's device (wfl_dense_forward's denominator: normalised scores) or none; drop,
-// num_replabels: the mapping of the results on their way out (-1, 0: the raw class sequences).
-Hypotheses asg_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, int beam, int K,
-                           int nbest, int64_t drop, int64_t num_replabels) {
-  const char* what = "asg_beam_search";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  TORCH_CHECK(W.defined(), what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
-  const int R = (int)num_replabels;
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_asg_beam_workspace(e.B, e.T, e.C, beam, K, nbest, R, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_asg_beam_search(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, beam, K, nbest, (int)drop, R, ws, out,
-                                      cap, offs, scores, s),
-                  what);
-          }};
-}
-
-// The options of the ASG search with a lexicon as both of its ops take them (engine.AsgLexiconBeamPlan.on_device binds
-// the values it has checked): asg_beam_source's, the garbage class (-1: none), and the lexicon, word LM (or none) and
-// constants of the CTC lexicon search.
-struct AsgLexiconPlan {
-  int beam, K, nbest, garbage;
-  std::shared_ptr<DeviceLexicon> lexicon;
-  std::shared_ptr<DeviceLm> lm;
-  double lm_weight, word_bonus, length_bonus;
-  bool score_eos;
+struct AsgLexiconPlan : BeamOptions {
   AsgLexiconPlan(int beam_, int K_, int nbest_, int garbage_, const std::shared_ptr<DeviceLexicon>& lexicon_,
                  const std::shared_ptr<DeviceLm>& lm_, double lm_weight_, double word_bonus_, double length_bonus_,
                  bool score_eos_)
-      : beam(beam_), K(K_), nbest(nbest_), garbage(garbage_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
-        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_) {
+      : BeamOptions(kBeamAsg, -1, false, beam_, K_, nbest_, garbage_, lm_, lexicon_, nullptr, lm_weight_, word_bonus_,
+                    length_bonus_, score_eos_) {
     TORCH_CHECK(lexicon, "asg_beam_search_lexicon: a lexicon is needed");
-    TORCH_CHECK(!lexicon->is_marked, "asg_beam_search_lexicon: a start-marked lexicon is not for ASG");
-    TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
-                "asg_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
   }
 };
-
-// The ASG search with a lexicon (wfl_asg_beam_search_lexicon): asg_beam_source with the plan above.
-Hypotheses asg_lexicon_beam_source(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz,
-                                   const AsgLexiconPlan& p, int nbest, int64_t drop, int64_t num_replabels) {
-  const char* what = "asg_beam_search_lexicon";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  TORCH_CHECK(W.defined(), what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
-  TORCH_CHECK(p.lexicon->ints.device() == x.device(), what, ": the lexicon's arrays must be on x's device");
-  const int R = (int)num_replabels;
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_asg_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, R, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_asg_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.beam, p.K, nbest, (int)drop,
-                                              R, p.garbage, &p.lexicon->lex, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
-                                              p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                  what);
-          }};
-}
-
-// The Transducer prefix beam search (wfl_transducer_beam_search): the options are
-// engine.TransducerBeamPlan's, already checked.  Wt: float32 [C + 1, C] on x's device or none (every weight 0); logz:
-// float32 [B] on x's device (wfl_dense_forward's denominator, with Wt and normalize) or none.
-Hypotheses transducer_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
-                                  int blank, bool forced, int beam, int K, int nbest, bool normalize) {
-  const char* what = "transducer_beam_search";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, beam, K, nbest, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_transducer_beam_search(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, blank, forced ? 1 : 0, beam, K,
-                                             nbest, normalize ? 1 : 0, ws, out, cap, offs, scores, s),
-                  what);
-          }};
-}
-
-// The options of the Transducer search with a lexicon as both of its ops take them
-// (engine.TransducerLexiconBeamPlan.on_device binds the values it has checked): transducer_beam_source's, and the
-// lexicon, word LM (or none) and constants of the CTC lexicon search.
-struct TransducerLexiconPlan {
-  int blank;
-  bool forced;
-  int beam, K, nbest;
-  std::shared_ptr<DeviceLexicon> lexicon;
-  std::shared_ptr<DeviceLm> lm;
-  double lm_weight, word_bonus, length_bonus;
-  bool score_eos;
-  std::shared_ptr<DeviceLookahead> lookahead;  // or none: the lexicon search as it was
+struct TransducerLexiconPlan : BeamOptions {
   TransducerLexiconPlan(int blank_, bool forced_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLexicon>& lexicon_,
                         const std::shared_ptr<DeviceLm>& lm_, double lm_weight_, double word_bonus_, double length_bonus_,
                         bool score_eos_, const std::shared_ptr<DeviceLookahead>& lookahead_)
-      : blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), lexicon(lexicon_), lm(lm_), lm_weight(lm_weight_),
-        word_bonus(word_bonus_), length_bonus(length_bonus_), score_eos(score_eos_), lookahead(lookahead_) {
+      : BeamOptions(kBeamTransducer, blank_, forced_, beam_, K_, nbest_, -1, lm_, lexicon_, lookahead_, lm_weight_, word_bonus_,
+                    length_bonus_, score_eos_) {
     TORCH_CHECK(lexicon, "transducer_beam_search_lexicon: a lexicon is needed");
-    TORCH_CHECK(!lm || lm->ints.device() == lexicon->ints.device(),
-                "transducer_beam_search_lexicon: the word LM's arrays must be on the lexicon's device");
-    if (lookahead) lookahead->check_for(lexicon, lm, "transducer_beam_search_lexicon_lookahead");
   }
 };
-
-// The Transducer search with a lexicon (wfl_transducer_beam_search_lexicon): transducer_beam_source
-// with the plan above.
-Hypotheses transducer_lexicon_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
-                                          const c10::optional<at::Tensor>& logz, const TransducerLexiconPlan& p, int nbest,
-                                          bool normalize) {
-  const char* what = "transducer_beam_search_lexicon";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  TORCH_CHECK(p.lexicon->ints.device() == x.device(), what, ": the lexicon's arrays must be on x's device");
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            if (p.lookahead && p.lexicon->is_marked)
-              check(wfl_transducer_beam_search_lexicon_marked_lookahead(
-                        x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0, p.beam, p.K, nbest,
-                        normalize ? 1 : 0, &p.lexicon->marked, &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
-                        p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                    "transducer_beam_search_lexicon_marked_lookahead");
-            else if (p.lookahead)
-              check(wfl_transducer_beam_search_lexicon_lookahead(
-                        x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0, p.beam, p.K, nbest,
-                        normalize ? 1 : 0, &p.lexicon->lex, &p.lookahead->look, &p.lm->lm, p.lm_weight, p.word_bonus,
-                        p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                    "transducer_beam_search_lexicon_lookahead");
-            else if (p.lexicon->is_marked)
-              check(wfl_transducer_beam_search_lexicon_marked(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank,
-                                                              p.forced ? 1 : 0, p.beam, p.K, nbest, normalize ? 1 : 0,
-                                                              &p.lexicon->marked, p.lm ? &p.lm->lm : nullptr, p.lm_weight,
-                                                              p.word_bonus, p.length_bonus, p.score_eos ? 1 : 0, ws, out, cap,
-                                                              offs, scores, s),
-                    "transducer_beam_search_lexicon_marked");
-            else
-              check(wfl_transducer_beam_search_lexicon(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank,
-                                                       p.forced ? 1 : 0, p.beam, p.K, nbest, normalize ? 1 : 0, &p.lexicon->lex,
-                                                       p.lm ? &p.lm->lm : nullptr, p.lm_weight, p.word_bonus, p.length_bonus,
-                                                       p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                    what);
-          }};
-}
-
-// The options of the Transducer search with a token-level LM as both of its ops take them
-// (engine.TransducerLmBeamPlan.on_device binds the values it has checked): transducer_beam_source's, and the LM and two
-// scalars of the CTC search with an LM.
-struct TransducerLmPlan {
-  int blank;
-  bool forced;
-  int beam, K, nbest;
-  std::shared_ptr<DeviceLm> lm;
-  double lm_weight, length_bonus;
-  bool score_eos;
+struct TransducerLmPlan : BeamOptions {
   TransducerLmPlan(int blank_, bool forced_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
                    double length_bonus_, bool score_eos_)
-      : blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), lm(lm_), lm_weight(lm_weight_),
-        length_bonus(length_bonus_), score_eos(score_eos_) {
+      : BeamOptions(kBeamTransducer, blank_, forced_, beam_, K_, nbest_, -1, lm_, nullptr, nullptr, lm_weight_, 0.0, length_bonus_,
+                    score_eos_) {
     TORCH_CHECK(lm, "transducer_beam_search_lm: a language model is needed");
   }
 };
 
-// The Transducer search with a token-level LM (wfl_transducer_beam_search_lm): transducer_beam_source
-// with the plan above.
-Hypotheses transducer_lm_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
-                                     const TransducerLmPlan& p, int nbest, bool normalize) {
-  const char* what = "transducer_beam_search_lm";
+// Every beam search as a source of hypotheses: the options `o` (already checked), rank count and normalisation of this
+// call, and what the families take besides -- lengths: CTC's padded batches; Wt: float32 [C + 1, C] on x's device, ASG's
+// (needed) and the Transducer's (or none: every weight 0); logz: float32 [B] on x's device (wfl_dense_forward's
+// denominator: normalised scores) or none; drop, num_replabels: ASG's mapping of the results on their way out (-1, 0:
+// the raw class sequences); spelling: the Transducer search that merges by spelling (wfl_transducer_beam_search_merged,
+// DESIGN.md section 23) -- int32 [spell_ptr: C + 1 | spell_sym: num_symbols] on x's device, one contiguous tensor, a
+// table that wfl_spelling_check passed on the host (engine.Spelling.on_device) --, or null.  The C entry is chosen
+// here and nowhere else: family x {plain, lm, lexicon} x start-marked x look-ahead, or merged.
+Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const c10::optional<at::Tensor>& Wt,
+                       const c10::optional<at::Tensor>& logz, const BeamOptions& o, int nbest, bool normalize, int64_t drop = -1,
+                       int64_t num_replabels = 0, const at::Tensor* spelling = nullptr, int64_t num_symbols = 0) {
+  const bool ctc = o.family == kBeamCtc, asg = o.family == kBeamAsg, merged = spelling != nullptr;
+  // the names errors carry: the search's (the CTC ops have always said ctc_beam_search) and the C entry's
+  const char* const* names = kBeamNames[o.family];
+  const int kind = merged ? kBeamMerged : o.lexicon ? kBeamLexicon : o.lm ? kBeamLm : kBeamPlain;
+  const char* what = names[ctc ? kBeamPlain : kind];
+  const char* entry = names[o.lexicon ? kind + (o.lexicon->is_marked ? 1 : 0) + (o.lookahead ? 2 : 0) : kind];
   const Emissions e = checked_emissions(x, what);
+  const at::Tensor lt = checked_lengths(lengths, x, what);
   const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  TORCH_CHECK(p.lm->ints.device() == x.device(), what, ": the LM's arrays must be on x's device");
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, p.beam, p.K, nbest, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            check(wfl_transducer_beam_search_lm(x.data_ptr<float>(), fptr(W), fptr(lz), e.B, e.T, e.C, p.blank, p.forced ? 1 : 0,
-                                                p.beam, p.K, nbest, normalize ? 1 : 0, &p.lm->lm, p.lm_weight, p.length_bonus,
-                                                p.score_eos ? 1 : 0, ws, out, cap, offs, scores, s),
-                  what);
-          }};
-}
-
-// The same search with hypotheses merged by spelling (wfl_transducer_beam_search_merged).
-// spelling: int32 [spell_ptr: C + 1 | spell_sym: num_symbols] on x's device, one contiguous tensor, a table that
-// wfl_spelling_check passed on the host (engine.Spelling.on_device).
-Hypotheses transducer_merged_beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
-                                         const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
-                                         int blank, bool forced, int beam, int K, int nbest, bool normalize) {
-  const char* what = "transducer_beam_search_merged";
-  const Emissions e = checked_emissions(x, what);
-  const at::Tensor W = checked_transitions(Wt, x, what), lz = checked_logz(logz, x, what);
-  TORCH_CHECK(spelling.device() == x.device() && spelling.scalar_type() == at::kInt && spelling.is_contiguous() &&
-                  spelling.dim() == 1 && num_symbols >= 0 && spelling.numel() == (int64_t)e.C + 1 + num_symbols,
+  TORCH_CHECK(!asg || W.defined(), what, ": transitions must be a contiguous float32 [C + 1, C] tensor on x's device");
+  // (a word LM is on its lexicon's device by the options' check; CTC alone names the LM first, as it always has)
+  TORCH_CHECK(!o.lm || (o.lexicon && !ctc) || o.lm->ints.device() == x.device(), names[kBeamLm], ": the LM's arrays must be on x's device");
+  TORCH_CHECK(!o.lexicon || o.lexicon->ints.device() == x.device(), names[kBeamLexicon], ": the lexicon's arrays must be on x's device");
+  TORCH_CHECK(!merged || (spelling->device() == x.device() && spelling->scalar_type() == at::kInt && spelling->is_contiguous() &&
+                          spelling->dim() == 1 && num_symbols >= 0 && spelling->numel() == (int64_t)e.C + 1 + num_symbols),
               what, ": the spelling table must be one contiguous int32 [C + 1 + symbols] tensor on x's device");
-  return {x, e.B, (int64_t)e.B * nbest, true, what,
-          [=](int64_t* cap, int64_t* bytes) { check(wfl_transducer_beam_workspace(e.B, e.T, e.C, beam, K, nbest, cap, bytes), what); },
-          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
-            const int32_t* sp = spelling.data_ptr<int32_t>();
-            check(wfl_transducer_beam_search_merged(x.data_ptr<float>(), fptr(W), fptr(lz), sp, sp + e.C + 1, e.B, e.T, e.C, blank,
-                                                    forced ? 1 : 0, beam, K, nbest, normalize ? 1 : 0, ws, out, cap, offs, scores,
-                                                    s),
+  const at::Tensor table = merged ? *spelling : at::Tensor();
+  const int B = e.B, T = e.T, C = e.C, R = (int)num_replabels, beam = o.beam, K = o.K;
+  return {x, B, (int64_t)B * nbest, true, what,
+          [=](int64_t* cap, int64_t* bytes) {
+            check(ctc   ? wfl_ctc_beam_workspace(B, T, C, beam, K, nbest, cap, bytes)
+                  : asg ? wfl_asg_beam_workspace(B, T, C, beam, K, nbest, R, cap, bytes)
+                        : wfl_transducer_beam_workspace(B, T, C, beam, K, nbest, cap, bytes),
                   what);
+          },
+          [=](void* ws, int32_t* out, int64_t cap, int64_t* offs, double* scores, void* s) {
+            const float* xp = x.data_ptr<float>();
+            const int norm = normalize ? 1 : 0, eos = o.score_eos ? 1 : 0;
+            const wfl_ngram_lm* lm = o.lm ? &o.lm->lm : nullptr;
+            // a family's entries: its leading arguments, an entry's own (`mid`), the results
+            auto ctc_call = [&](auto fn, auto... mid) {
+              return fn(xp, lt.defined() ? lt.data_ptr<int32_t>() : nullptr, B, T, C, o.blank, o.beam, o.K, nbest, norm, mid..., ws, out,
+                        cap, offs, scores, s);
+            };
+            auto asg_call = [&](auto fn, auto... mid) {
+              return fn(xp, fptr(W), fptr(lz), B, T, C, o.beam, o.K, nbest, (int)drop, R, mid..., ws, out, cap, offs, scores, s);
+            };
+            auto transducer_call = [&](auto fn, auto... mid) {
+              return fn(xp, fptr(W), fptr(lz), B, T, C, o.blank, o.forced ? 1 : 0, o.beam, o.K, nbest, norm, mid..., ws, out, cap, offs,
+                        scores, s);
+            };
+            // the one choice of start-marked x look-ahead, for the two families that have it
+            auto lexicon_call = [&](auto call, auto plain, auto marked, auto look, auto marked_look) {
+              const DeviceLexicon& dl = *o.lexicon;
+              if (o.lookahead && dl.is_marked)
+                return call(marked_look, &dl.marked, &o.lookahead->look, lm, o.lm_weight, o.word_bonus, o.length_bonus, eos);
+              if (o.lookahead) return call(look, &dl.lex, &o.lookahead->look, lm, o.lm_weight, o.word_bonus, o.length_bonus, eos);
+              if (dl.is_marked) return call(marked, &dl.marked, lm, o.lm_weight, o.word_bonus, o.length_bonus, eos);
+              return call(plain, &dl.lex, lm, o.lm_weight, o.word_bonus, o.length_bonus, eos);
+            };
+            int rc;
+            if (merged) {
+              const int32_t* sp = table.data_ptr<int32_t>();
+              rc = wfl_transducer_beam_search_merged(xp, fptr(W), fptr(lz), sp, sp + C + 1, B, T, C, o.blank, o.forced ? 1 : 0, o.beam,
+                                                     o.K, nbest, norm, ws, out, cap, offs, scores, s);
+            } else if (ctc) {
+              rc = o.lexicon ? lexicon_call(ctc_call, wfl_ctc_beam_search_lexicon, wfl_ctc_beam_search_lexicon_marked,
+                                            wfl_ctc_beam_search_lexicon_lookahead, wfl_ctc_beam_search_lexicon_marked_lookahead)
+                   : o.lm    ? ctc_call(wfl_ctc_beam_search_lm, lm, o.lm_weight, o.length_bonus, eos)
+                             : ctc_call(wfl_ctc_beam_search);
+            } else if (asg) {
+              rc = o.lexicon ? asg_call(wfl_asg_beam_search_lexicon, o.garbage, &o.lexicon->lex, lm, o.lm_weight, o.word_bonus,
+                                        o.length_bonus, eos)
+                             : asg_call(wfl_asg_beam_search);
+            } else {
+              rc = o.lexicon ? lexicon_call(transducer_call, wfl_transducer_beam_search_lexicon,
+                                            wfl_transducer_beam_search_lexicon_marked, wfl_transducer_beam_search_lexicon_lookahead,
+                                            wfl_transducer_beam_search_lexicon_marked_lookahead)
+                   : o.lm    ? transducer_call(wfl_transducer_beam_search_lm, lm, o.lm_weight, o.length_bonus, eos)
+                             : transducer_call(wfl_transducer_beam_search);
+            }
+            check(rc, entry);
           }};
 }
 
@@ -1381,12 +1268,6 @@ std::vector<at::Tensor> decode_emissions(const at::Tensor& x, const c10::optiona
 std::vector<at::Tensor> decode_paths(const at::Tensor& paths, int64_t T, int64_t drop, int64_t num_replabels, int64_t flags,
                                      bool as_int64) {
   return decode_rows(paths_source(paths, T, drop, num_replabels, flags), as_int64);
-}
-
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
-py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& plan, bool normalize) {
-  const Collected r = hypotheses_collect(beam_source(x, lengths, plan, plan.nbest, normalize), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1514,94 +1395,86 @@ at::Tensor decode_paths_errors(const at::Tensor& paths, int64_t T, int64_t drop,
   return hypotheses_errors(paths_source(paths, T, drop, num_replabels, flags), ref, tables);
 }
 
-// (the plan's first rank, unnormalised: nothing reads the scores)
+// The fourteen beam ops: seven searches, each as the op that collects its hypotheses on the host and the op that counts
+// errors behind the same launches.
+// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
+py::tuple beam_results(const Hypotheses& h) {
+  const Collected r = hypotheses_collect(h, true);
+  return py::make_tuple(r.labels, r.offsets, r.scores.view({(int64_t)h.B, -1}));
+}
+// the first rank, unnormalised (nothing reads the scores), and the counts behind it
+at::Tensor beam_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const c10::optional<at::Tensor>& Wt,
+                       const BeamOptions& o, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables, int64_t drop = -1,
+                       int64_t num_replabels = 0, const at::Tensor* spelling = nullptr, int64_t num_symbols = 0) {
+  return hypotheses_errors(beam_source(x, lengths, Wt, c10::nullopt, o, 1, false, drop, num_replabels, spelling, num_symbols), ref,
+                           tables);
+}
+
+py::tuple ctc_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& plan, bool normalize) {
+  return beam_results(beam_source(x, lengths, c10::nullopt, c10::nullopt, plan, plan.nbest, normalize));
+}
 at::Tensor ctc_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& lengths, const BeamPlan& plan,
                                   const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
-  return hypotheses_errors(beam_source(x, lengths, plan, 1, false), ref, tables);
+  return beam_errors(x, lengths, c10::nullopt, plan, ref, tables);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple asg_beam_search(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, int beam, int K,
                           int nbest, int64_t drop, int64_t num_replabels) {
-  const Collected r = hypotheses_collect(asg_beam_source(x, Wt, logz, beam, K, nbest, drop, num_replabels), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, {kBeamAsg, -1, false, beam, K, nbest}, nbest, false, drop, num_replabels));
 }
-
-// (the first rank, unnormalised: nothing reads the scores)
 at::Tensor asg_beam_search_errors(const at::Tensor& x, const at::Tensor& Wt, int beam, int K, int64_t drop, int64_t num_replabels,
                                   const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
-  return hypotheses_errors(asg_beam_source(x, Wt, c10::nullopt, beam, K, 1, drop, num_replabels), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, {kBeamAsg, -1, false, beam, K, 1}, ref, tables, drop, num_replabels);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple asg_beam_search_lexicon(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz,
                                   const AsgLexiconPlan& plan, int64_t drop, int64_t num_replabels) {
-  const Collected r = hypotheses_collect(asg_lexicon_beam_source(x, Wt, logz, plan, plan.nbest, drop, num_replabels), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, plan, plan.nbest, false, drop, num_replabels));
 }
-
-// (the plan's first rank, unnormalised: nothing reads the scores)
 at::Tensor asg_beam_search_lexicon_errors(const at::Tensor& x, const at::Tensor& Wt, const AsgLexiconPlan& plan, int64_t drop,
                                           int64_t num_replabels, const std::shared_ptr<StagedTargets>& ref,
                                           const ErrorTables& tables) {
-  return hypotheses_errors(asg_lexicon_beam_source(x, Wt, c10::nullopt, plan, 1, drop, num_replabels), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, plan, ref, tables, drop, num_replabels);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
                                  int blank, bool forced, int beam, int K, int nbest, bool normalize) {
-  const Collected r = hypotheses_collect(transducer_beam_source(x, Wt, logz, blank, forced, beam, K, nbest, normalize), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, {kBeamTransducer, blank, forced, beam, K, nbest}, nbest, normalize));
 }
-
-// (the first rank, unnormalised: nothing reads the scores)
 at::Tensor transducer_beam_search_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, int blank, bool forced, int beam,
                                          int K, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
-  return hypotheses_errors(transducer_beam_source(x, Wt, c10::nullopt, blank, forced, beam, K, 1, false), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, {kBeamTransducer, blank, forced, beam, K, 1}, ref, tables);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search_lexicon(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
                                          const c10::optional<at::Tensor>& logz, const TransducerLexiconPlan& plan, bool normalize) {
-  const Collected r = hypotheses_collect(transducer_lexicon_beam_source(x, Wt, logz, plan, plan.nbest, normalize), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, plan, plan.nbest, normalize));
 }
-
-// (the plan's first rank, unnormalised: nothing reads the scores)
 at::Tensor transducer_beam_search_lexicon_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
                                                  const TransducerLexiconPlan& plan, const std::shared_ptr<StagedTargets>& ref,
                                                  const ErrorTables& tables) {
-  return hypotheses_errors(transducer_lexicon_beam_source(x, Wt, c10::nullopt, plan, 1, false), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, plan, ref, tables);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search_lm(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
                                     const TransducerLmPlan& plan, bool normalize) {
-  const Collected r = hypotheses_collect(transducer_lm_beam_source(x, Wt, logz, plan, plan.nbest, normalize), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)plan.nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, plan, plan.nbest, normalize));
 }
-
-// (the plan's first rank, unnormalised: nothing reads the scores)
 at::Tensor transducer_beam_search_lm_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const TransducerLmPlan& plan,
                                             const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
-  return hypotheses_errors(transducer_lm_beam_source(x, Wt, c10::nullopt, plan, 1, false), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, plan, ref, tables);
 }
 
-// -> (labels int64 CPU [total], offsets int64 CPU [B nbest + 1], scores float64 CPU [B, nbest])
 py::tuple transducer_beam_search_merged(const at::Tensor& x, const c10::optional<at::Tensor>& Wt,
                                         const c10::optional<at::Tensor>& logz, const at::Tensor& spelling, int64_t num_symbols,
                                         int blank, bool forced, int beam, int K, int nbest, bool normalize) {
-  const Collected r = hypotheses_collect(
-      transducer_merged_beam_source(x, Wt, logz, spelling, num_symbols, blank, forced, beam, K, nbest, normalize), true);
-  return py::make_tuple(r.labels, r.offsets, r.scores.view({x.size(0), (int64_t)nbest}));
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, {kBeamTransducer, blank, forced, beam, K, nbest}, nbest, normalize, -1, 0,
+                                  &spelling, num_symbols));
 }
-
-// (the first rank, unnormalised: nothing reads the scores)
 at::Tensor transducer_beam_search_merged_errors(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const at::Tensor& spelling,
                                                 int64_t num_symbols, int blank, bool forced, int beam, int K,
                                                 const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
-  return hypotheses_errors(
-      transducer_merged_beam_source(x, Wt, c10::nullopt, spelling, num_symbols, blank, forced, beam, K, 1, false), ref, tables);
+  return beam_errors(x, c10::nullopt, Wt, {kBeamTransducer, blank, forced, beam, K, 1}, ref, tables, -1, 0, &spelling, num_symbols);
 }
 
 }  // namespace

@@ -5,6 +5,7 @@ all arithmetic happens in the HIP kernels behind the C ABI (include/wfl.h).
 import ctypes
 import itertools
 import math
+import numbers
 import operator
 import sys
 import threading
@@ -14,6 +15,8 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .lexicon import Lexicon, LexiconLookahead, check_lookahead, check_word_lm
+from .lm import NGramLM
 
 _F32 = torch.float32
 
@@ -989,6 +992,86 @@ def check_beam_outputs(outputs, what):
         raise ValueError(f"{what}: outputs must be a floating point tensor, got {outputs.dtype}")
 
 
+# What the plans below check alike, each rule once (`what`: the call the arguments were given to).
+
+def beam_finite(v, name, what):
+    """v as a float, or ValueError unless it is a finite number: a Python or numpy number or a one-element tensor (a
+    sweep over weights), never a bool or a string"""
+    f = math.nan
+    if not isinstance(v, (bool, np.bool_, str, bytes)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            pass
+    if not math.isfinite(f):
+        raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+    return f
+
+
+def beam_lm_scalars(lm_weight, length_bonus, lm_eos, what, word_bonus=0.0):
+    """(lm_weight, word_bonus, length_bonus, lm_eos) of an LM's terms as three floats and a bool, or ValueError: refused in
+    this order"""
+    weight, omega = beam_finite(lm_weight, "lm_weight", what), beam_finite(word_bonus, "word_bonus", what)
+    bonus = beam_finite(length_bonus, "length_bonus", what)
+    if not isinstance(lm_eos, (bool, np.bool_)):
+        raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
+    return weight, omega, bonus, bool(lm_eos)
+
+
+def check_built_for(built, noun, C, blank, what, need=None):
+    """ValueError unless `built` -- `noun`: "the lm", "the token LM", "the lexicon", "the spelling table" -- was built for
+    C classes with this blank (need: the message's words for what it must be; None: what the emissions have)"""
+    if built.num_classes != C or built.blank != blank:
+        raise ValueError(f"{what}: {noun} was built for {built.num_classes} classes with blank {built.blank}" +
+                         (f", the emissions have {C} with blank {blank}" if need is None else f"; {need}"))
+
+
+def refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus, search):
+    """ValueError for a keyword of the lexicon search in a call without a lexicon: each must be at its default (`search`:
+    "an ASG", "a Transducer")"""
+    if lm is not None:
+        raise ValueError(f"{what}: lm needs a lexicon (the lm of {search} search is a word LM)")
+    for name, v, default in (("lm_weight", lm_weight, 1.0), ("length_bonus", length_bonus, 0.0), ("word_bonus", word_bonus, 0.0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or float(v) != default:  # (numpy's numbers are Real too)
+            raise ValueError(f"{what}: {name} needs a lexicon, got {v!r}")
+    if lm_eos is not True:
+        raise ValueError(f"{what}: lm_eos needs a lexicon, got {lm_eos!r}")
+
+
+def beam_logz(x, Wt, normalize):
+    """The denominator of normalised scores: logz [B] of dense_forward(x, Wt) on x's device, or None without transitions
+    or without `normalize`"""
+    if Wt is None or not normalize:
+        return None
+    with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
+        return dense_forward(x, Wt, need_beta=False).logz
+
+
+def beam_preamble(plan, x, Wt, what, drop=None, num_replabels=0, spelling=None):
+    """What the module-level searches of ASG and the Transducer do behind their plan: ValueError for transitions that are
+    not [C + 1, C], a num_replabels or a drop (ASG's) out of range, a spelling (the Transducer's) that is not the plan's;
+    then plan.no_frames' result where x has no frame, or None: the search runs"""
+    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
+        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
+    if not isinstance(num_replabels, int) or isinstance(num_replabels, bool) or num_replabels < 0:
+        raise ValueError(f"{what}: num_replabels must be an integer >= 0, got {num_replabels!r}")
+    if drop is not None and not -1 <= int(drop) < plan.C:
+        raise ValueError(f"{what}: drop {drop} is outside [0, {plan.C})")
+    if spelling is not None:
+        check_spelling(spelling, plan, what)
+    return plan.no_frames(x.shape[0]) if x.shape[0] == 0 or x.shape[1] == 0 else None
+
+
+class _WithLookahead:
+    """A lexicon plan whose search has word-LM look-ahead: the tuple is the plan's, .lookahead the
+    prepared lexicon.LexiconLookahead that on_device() hands to the operators with it.  The plan's `checked` makes one."""
+
+    def __new__(cls, plan, lookahead):
+        self = super().__new__(cls, *plan)
+        self.lookahead = lookahead
+        return self
+
+
 class BeamPlan(namedtuple(
         "BeamPlan", "C blank beam classes_per_frame nbest lm lm_weight length_bonus lm_eos lexicon word_bonus")):
     """The options of one CTC beam search over C classes, checked once (`checked`, the one constructor) and handed on whole:
@@ -1009,37 +1092,19 @@ class BeamPlan(namedtuple(
         for these classes and this blank, or is the lexicon's word LM (the convention of lexicon.py).  lexicon None: no
         word_bonus.  Numbers: Python or numpy numbers, one-element tensors (a sweep over weights), never bools or strings.
         lookahead: None, "unigram" or the word scores u[v] (lexicon.check_lookahead); it needs a lexicon and an lm."""
-        from .lexicon import Lexicon, check_lookahead, check_word_lm
-        from .lm import NGramLM
-
-        def finite(v, name):
-            f = math.nan
-            if not isinstance(v, (bool, np.bool_, str, bytes)):
-                try:
-                    f = float(v)
-                except (TypeError, ValueError):
-                    pass
-            if not math.isfinite(f):
-                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-            return f
-
         W, K, n = beam_widths(C, beam_size, classes_per_frame, nbest, what)
         if not 0 <= int(blank) < C:
             raise ValueError(f"{what}: blank index {blank} is outside [0, {C})")
         blank = int(blank)
-        omega = finite(word_bonus, "word_bonus")
+        omega = beam_finite(word_bonus, "word_bonus", what)
         if lexicon is None:
             if omega != 0.0:
                 raise ValueError(f"{what}: word_bonus needs a lexicon")
         elif not isinstance(lexicon, Lexicon):
             raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
-        elif lexicon.num_classes != C or lexicon.blank != blank:
-            raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}, "
-                             f"the emissions have {C} with blank {blank}")
-        weight, bonus = finite(lm_weight, "lm_weight"), finite(length_bonus, "length_bonus")
-        if not isinstance(lm_eos, (bool, np.bool_)):
-            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
-        lm_eos = bool(lm_eos)
+        else:
+            check_built_for(lexicon, "the lexicon", C, blank, what)
+        weight, _, bonus, lm_eos = beam_lm_scalars(lm_weight, length_bonus, lm_eos, what)
         if lm is None:
             if weight != 1.0 or (bonus != 0.0 and lexicon is None) or lm_eos is not True:
                 raise ValueError(f"{what}: lm_weight, length_bonus and lm_eos need an lm" +
@@ -1048,9 +1113,8 @@ class BeamPlan(namedtuple(
             raise ValueError(f"{what}: lm must be an lm.NGramLM, got {type(lm).__name__}")
         elif lexicon is not None:
             check_word_lm(lexicon, lm, what)
-        elif lm.num_classes != C or lm.blank != blank:
-            raise ValueError(f"{what}: the lm was built for {lm.num_classes} classes with blank {lm.blank}, "
-                             f"the emissions have {C} with blank {blank}")
+        else:
+            check_built_for(lm, "the lm", C, blank, what)
         plan = cls(C, blank, W, K, n, lm, weight, bonus, lm_eos, lexicon, omega)
         look = check_lookahead(lookahead, lexicon, lm, False, what)
         return plan if look is None else BeamPlanLookahead(plan, look)
@@ -1065,17 +1129,9 @@ class BeamPlan(namedtuple(
     def no_frames(self, B):
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: every rank is the
         empty sequence -- no word either --, the first scored by the LM's </s> alone"""
-        hyps, scores = beam_no_frames(B, self.nbest)
         if self.lm is None and self.lexicon is None:
-            return hyps, scores
-        # (rule 7: a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
-        end = 0.0
-        if self.lm is not None and self.lm_eos:
-            step = self.lm.score([], eos=True)
-            end = -math.inf if step == -math.inf else self.lm_weight * step
-        scores[:, 1:] = -math.inf
-        scores[:, 0] = end
-        return hyps, scores
+            return beam_no_frames(B, self.nbest)
+        return beam_lexicon_no_frames(B, self.nbest, self.lm, self.lm_weight, self.lm_eos)
 
     def on_device(self, device):
         """The plan as the operators take it (ops.BeamPlan, csrc/torch_ops.cpp), its lm and lexicon on `device` (their
@@ -1093,14 +1149,8 @@ class BeamPlan(namedtuple(
         return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
-class BeamPlanLookahead(BeamPlan):
-    """A BeamPlan whose lexicon search has word-LM look-ahead: the tuple is the plan's, .lookahead
-    the prepared lexicon.LexiconLookahead that on_device() hands to the operators with it.  BeamPlan.checked makes one."""
-
-    def __new__(cls, plan, lookahead):
-        self = super().__new__(cls, *plan)
-        self.lookahead = lookahead
-        return self
+class BeamPlanLookahead(_WithLookahead, BeamPlan):
+    """A BeamPlan with look-ahead"""
 
 
 def ctc_beam_search(x, blank, beam_size=16, classes_per_frame=None, nbest=1, lengths=None, normalize=True, lm=None,
@@ -1149,10 +1199,8 @@ class AsgBeamPlan(namedtuple("AsgBeamPlan", "C beam classes_per_frame nbest")):
     def search(self, x, W, normalize=True, drop=None, num_replabels=0):
         """asg_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
         [C + 1, C] on x's device, contiguous"""
-        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-            logz = dense_forward(x, W, need_beta=False).logz if normalize else None
-        flat, offsets, scores = N.ops.asg_beam_search(x, W, logz, self.beam, self.classes_per_frame, self.nbest,
-                                                      -1 if drop is None else int(drop), int(num_replabels))
+        flat, offsets, scores = N.ops.asg_beam_search(x, W, beam_logz(x, W, normalize), self.beam, self.classes_per_frame,
+                                                      self.nbest, -1 if drop is None else int(drop), int(num_replabels))
         return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
@@ -1167,15 +1215,7 @@ def asg_beam_search(x, Wt, beam_size=16, classes_per_frame=None, nbest=1, normal
     `drop` is removed and replabels are unpacked on the way out (what ASG.viterbi does to a path).  Only the surviving
     labels and the scores leave the device.  The options are one AsgBeamPlan."""
     plan = AsgBeamPlan.checked(x.shape[2], beam_size, classes_per_frame, nbest, "asg_beam_search")
-    if tuple(Wt.shape) != (plan.C + 1, plan.C):
-        raise ValueError(f"asg_beam_search: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
-    if not isinstance(num_replabels, int) or isinstance(num_replabels, bool) or num_replabels < 0:
-        raise ValueError(f"asg_beam_search: num_replabels must be an integer >= 0, got {num_replabels!r}")
-    if drop is not None and not -1 <= int(drop) < plan.C:
-        raise ValueError(f"asg_beam_search: drop {drop} is outside [0, {plan.C})")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        return plan.no_frames(x.shape[0])
-    return plan.search(x, Wt, normalize, drop, num_replabels)
+    return beam_preamble(plan, x, Wt, "asg_beam_search", drop, num_replabels) or plan.search(x, Wt, normalize, drop, num_replabels)
 
 
 def beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bonus, lm_eos, what):
@@ -1183,28 +1223,10 @@ def beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bo
     were given to): lexicon a lexicon.Lexicon built for the (num_classes, blank) pair `want` (`need`: the message's words
     for what it must be); lm None or a word LM of it; the three numbers finite; lm_eos a bool; lm_weight and lm_eos at
     their defaults without an lm.  Returns (lm_weight, word_bonus, length_bonus, lm_eos) as floats and a bool."""
-    from .lexicon import Lexicon, check_word_lm
-    from .lm import NGramLM
-
-    def finite(v, name):
-        f = math.nan
-        if not isinstance(v, (bool, np.bool_, str, bytes)):
-            try:
-                f = float(v)
-            except (TypeError, ValueError):
-                pass
-        if not math.isfinite(f):
-            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-        return f
-
     if not isinstance(lexicon, Lexicon):
         raise ValueError(f"{what}: lexicon must be a lexicon.Lexicon, got {type(lexicon).__name__}")
-    if (lexicon.num_classes, lexicon.blank) != want:
-        raise ValueError(f"{what}: the lexicon was built for {lexicon.num_classes} classes with blank {lexicon.blank}; {need}")
-    weight, omega, bonus = finite(lm_weight, "lm_weight"), finite(word_bonus, "word_bonus"), finite(length_bonus, "length_bonus")
-    if not isinstance(lm_eos, (bool, np.bool_)):
-        raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
-    lm_eos = bool(lm_eos)
+    check_built_for(lexicon, "the lexicon", *want, what, need)
+    weight, omega, bonus, lm_eos = beam_lm_scalars(lm_weight, length_bonus, lm_eos, what, word_bonus)
     if lm is None:
         if weight != 1.0 or lm_eos is not True:
             raise ValueError(f"{what}: lm_weight and lm_eos need an lm")
@@ -1216,9 +1238,10 @@ def beam_lexicon_terms(lexicon, want, need, lm, lm_weight, word_bonus, length_bo
 
 
 def beam_lexicon_no_frames(B, nbest, lm, lm_weight, lm_eos, dtype=torch.int64):
-    """(hyps, scores) of a lexicon search for B utterances without a frame, on the host: every rank the empty sequence,
-    the first scored by the LM's </s> alone, the others -inf"""
+    """(hyps, scores) of a search with an LM's </s> term -- a lexicon's word LM (or none), a token LM -- for B utterances
+    without a frame, on the host: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
     hyps, scores = beam_no_frames(B, nbest, dtype)
+    # (a rank whose </s> step is -inf is dropped, whatever the weight -- never 0 * -inf or -w * -inf)
     end = 0.0
     if lm is not None and lm_eos:
         step = lm.score([], eos=True)
@@ -1279,10 +1302,8 @@ class AsgLexiconBeamPlan(namedtuple(
     def search(self, x, W, normalize=True, drop=None, num_replabels=0):
         """asg_beam_search_lexicon's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
         [C + 1, C] on x's device, contiguous"""
-        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-            logz = dense_forward(x, W, need_beta=False).logz if normalize else None
-            flat, offsets, scores = N.ops.asg_beam_search_lexicon(x, W, logz, self.on_device(x.device),
-                                                                  -1 if drop is None else int(drop), int(num_replabels))
+        flat, offsets, scores = N.ops.asg_beam_search_lexicon(x, W, beam_logz(x, W, normalize), self.on_device(x.device),
+                                                              -1 if drop is None else int(drop), int(num_replabels))
         return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
 
 
@@ -1299,15 +1320,7 @@ def asg_beam_search_lexicon(x, Wt, lexicon, garbage=None, beam_size=16, classes_
     what = "asg_beam_search_lexicon"
     plan = AsgLexiconBeamPlan.checked(x.shape[2], beam_size, classes_per_frame, nbest, garbage, lexicon, lm, lm_weight,
                                       word_bonus, length_bonus, lm_eos, what)
-    if tuple(Wt.shape) != (plan.C + 1, plan.C):
-        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
-    if not isinstance(num_replabels, int) or isinstance(num_replabels, bool) or num_replabels < 0:
-        raise ValueError(f"{what}: num_replabels must be an integer >= 0, got {num_replabels!r}")
-    if drop is not None and not -1 <= int(drop) < plan.C:
-        raise ValueError(f"{what}: drop {drop} is outside [0, {plan.C})")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        return plan.no_frames(x.shape[0])
-    return plan.search(x, Wt, normalize, drop, num_replabels)
+    return beam_preamble(plan, x, Wt, what, drop, num_replabels) or plan.search(x, Wt, normalize, drop, num_replabels)
 
 
 class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam classes_per_frame nbest")):
@@ -1334,14 +1347,15 @@ class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam c
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host: beam_no_frames's"""
         return beam_no_frames(B, self.nbest, dtype)
 
-    def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
+    def search(self, x, Wt=None, normalize=True, dtype=torch.int64, spelling=None):
         """transducer_beam_search's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt: float32
-        [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
-        logz = None
-        if Wt is not None and normalize:
-            with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-                logz = dense_forward(x, Wt, need_beta=False).logz
-        flat, offsets, scores = N.ops.transducer_beam_search(x, Wt, logz, self.blank, self.forced, self.beam,
+        [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`; spelling: None, or the Spelling of the
+        plan's classes and blank (check_spelling) -- transducer_merged_search's result.  The merged search is the one
+        whose kind the plan does not carry: a Spelling belongs to the criterion's tokens, not to the options of a call,
+        and `type(plan) is TransducerBeamPlan` holds for both."""
+        if spelling is not None:
+            return transducer_merged_search(self, x, Wt, spelling, normalize, dtype)
+        flat, offsets, scores = N.ops.transducer_beam_search(x, Wt, beam_logz(x, Wt, normalize), self.blank, self.forced, self.beam,
                                                              self.classes_per_frame, self.nbest, bool(normalize))
         return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
 
@@ -1400,13 +1414,9 @@ def transducer_merged_search(plan, x, Wt, spelling, normalize=True, dtype=torch.
     """TransducerBeamPlan.search for the search that merges by spelling (wfl_transducer_beam_search_merged): `plan` a
     checked TransducerBeamPlan, `spelling` the Spelling of its classes and blank; x, Wt, the result: as search()'s, a
     hypothesis a representative token sequence of its spelling"""
-    logz = None
-    if Wt is not None and normalize:
-        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-            logz = dense_forward(x, Wt, need_beta=False).logz
-    flat, offsets, scores = N.ops.transducer_beam_search_merged(x, Wt, logz, spelling.on_device(x.device), spelling.num_symbols,
-                                                                plan.blank, plan.forced, plan.beam, plan.classes_per_frame,
-                                                                plan.nbest, bool(normalize))
+    flat, offsets, scores = N.ops.transducer_beam_search_merged(x, Wt, beam_logz(x, Wt, normalize), spelling.on_device(x.device),
+                                                                spelling.num_symbols, plan.blank, plan.forced, plan.beam,
+                                                                plan.classes_per_frame, plan.nbest, bool(normalize))
     return beam_rows(flat, offsets, x.shape[0], plan.nbest, dtype), scores
 
 
@@ -1414,9 +1424,7 @@ def check_spelling(spelling, plan, what):
     """ValueError unless `spelling` is a Spelling of the plan's classes and blank"""
     if not isinstance(spelling, Spelling):
         raise ValueError(f"{what}: spelling must be an engine.Spelling, got {type(spelling).__name__}")
-    if spelling.num_classes != plan.C or spelling.blank != plan.blank:
-        raise ValueError(f"{what}: the spelling table was built for {spelling.num_classes} classes with blank {spelling.blank}, "
-                         f"the emissions have {plan.C} with blank {plan.blank}")
+    check_built_for(spelling, "the spelling table", plan.C, plan.blank, what)
 
 
 def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per_frame=None, nbest=1, normalize=True,
@@ -1435,15 +1443,8 @@ def transducer_beam_search(x, Wt, blank, forced=False, beam_size=16, classes_per
     graphemes they spell, a result is a representative token sequence of its spelling and its score the kept mass of
     every decomposition of that spelling; no two ranks spell the same.  spelling None: the call it was."""
     plan = TransducerBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, "transducer_beam_search")
-    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
-        raise ValueError(f"transducer_beam_search: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
-    if spelling is not None:
-        check_spelling(spelling, plan, "transducer_beam_search")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        return plan.no_frames(x.shape[0])
-    if spelling is not None:
-        return transducer_merged_search(plan, x, Wt, spelling, normalize)
-    return plan.search(x, Wt, normalize)
+    return (beam_preamble(plan, x, Wt, "transducer_beam_search", spelling=spelling) or
+            plan.search(x, Wt, normalize, spelling=spelling))
 
 
 class TransducerLexiconBeamPlan(namedtuple(
@@ -1464,8 +1465,6 @@ class TransducerLexiconBeamPlan(namedtuple(
         the call they were given to): what TransducerBeamPlan.checked refuses; a lexicon that is none or was not built
         for (C, blank); an lm that is no word LM of the lexicon; lm_weight or lm_eos away from their defaults without an
         lm; a number that is not finite; a lookahead (None, "unigram" or word scores: lexicon.check_lookahead) without an lm."""
-        from .lexicon import check_lookahead
-
         p = TransducerBeamPlan.checked(C, blank, forced, beam_size, classes_per_frame, nbest, what)
         need = f"the emissions have {p.C} with blank {p.blank} (Transducer.word_lexicon builds it)"
         weight, omega, bonus, lm_eos = beam_lexicon_terms(lexicon, (p.C, p.blank), need, lm, lm_weight, word_bonus, length_bonus,
@@ -1491,20 +1490,13 @@ class TransducerLexiconBeamPlan(namedtuple(
     def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
         """transducer_beam_search_lexicon's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt:
         float32 [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
-        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-            logz = dense_forward(x, Wt, need_beta=False).logz if Wt is not None and normalize else None
-            flat, offsets, scores = N.ops.transducer_beam_search_lexicon(x, Wt, logz, self.on_device(x.device), bool(normalize))
+        flat, offsets, scores = N.ops.transducer_beam_search_lexicon(x, Wt, beam_logz(x, Wt, normalize), self.on_device(x.device),
+                                                                     bool(normalize))
         return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
 
 
-class TransducerLexiconBeamPlanLookahead(TransducerLexiconBeamPlan):
-    """A TransducerLexiconBeamPlan whose search has word-LM look-ahead, as BeamPlanLookahead is for
-    CTC: the tuple is the plan's, .lookahead the prepared lexicon.LexiconLookahead."""
-
-    def __new__(cls, plan, lookahead):
-        self = super().__new__(cls, *plan)
-        self.lookahead = lookahead
-        return self
+class TransducerLexiconBeamPlanLookahead(_WithLookahead, TransducerLexiconBeamPlan):
+    """A TransducerLexiconBeamPlan with look-ahead"""
 
 
 def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_size=16, classes_per_frame=None, nbest=1,
@@ -1520,19 +1512,13 @@ def transducer_beam_search_lexicon(x, Wt, blank, lexicon, forced=False, beam_siz
     lexicon.LexiconLookahead of one (Lexicon.lookahead(word scores), Lexicon.unigram_lookahead(lm)) -- the search is then
     wfl_transducer_beam_search_lexicon_lookahead or its start-marked sibling, and an lm is needed.  The options are one
     TransducerLexiconBeamPlan."""
-    from .lexicon import LexiconLookahead
-
     what = "transducer_beam_search_lexicon"
     lookahead = None
     if isinstance(lexicon, LexiconLookahead):
         lookahead, lexicon = lexicon, lexicon.lexicon
     plan = TransducerLexiconBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lexicon, lm,
                                              lm_weight, word_bonus, length_bonus, lm_eos, what, lookahead=lookahead)
-    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
-        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        return plan.no_frames(x.shape[0])
-    return plan.search(x, Wt, normalize)
+    return beam_preamble(plan, x, Wt, what) or plan.search(x, Wt, normalize)
 
 
 class TransducerLmBeamPlan(namedtuple(
@@ -1548,29 +1534,12 @@ class TransducerLmBeamPlan(namedtuple(
         """The plan of these arguments, within the limits of wfl_transducer_beam_search_lm, or ValueError (`what`: the
         call they were given to): what TransducerBeamPlan.checked refuses; an lm that is no lm.NGramLM or was not built
         for (C, blank); a number that is not finite; an lm_eos that is no bool."""
-        from .lm import NGramLM
-
-        def finite(v, name):
-            f = math.nan
-            if not isinstance(v, (bool, np.bool_, str, bytes)):
-                try:
-                    f = float(v)
-                except (TypeError, ValueError):
-                    pass
-            if not math.isfinite(f):
-                raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
-            return f
-
         p = TransducerBeamPlan.checked(C, blank, forced, beam_size, classes_per_frame, nbest, what)
         if not isinstance(lm, NGramLM):
             raise ValueError(f"{what}: the token LM must be an lm.NGramLM, got {type(lm).__name__}")
-        if lm.num_classes != p.C or lm.blank != p.blank:
-            raise ValueError(f"{what}: the token LM was built for {lm.num_classes} classes with blank {lm.blank}, "
-                             f"the emissions have {p.C} with blank {p.blank}")
-        weight, bonus = finite(lm_weight, "lm_weight"), finite(length_bonus, "length_bonus")
-        if not isinstance(lm_eos, (bool, np.bool_)):
-            raise ValueError(f"{what}: lm_eos must be True or False, got {lm_eos!r}")
-        return cls(*p, lm, weight, bonus, bool(lm_eos))
+        check_built_for(lm, "the token LM", p.C, p.blank, what)
+        weight, _, bonus, lm_eos = beam_lm_scalars(lm_weight, length_bonus, lm_eos, what)
+        return cls(*p, lm, weight, bonus, lm_eos)
 
     def no_frames(self, B, dtype=torch.int64):
         """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
@@ -1588,9 +1557,8 @@ class TransducerLmBeamPlan(namedtuple(
     def search(self, x, Wt=None, normalize=True, dtype=torch.int64):
         """transducer_beam_search_lm's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; Wt:
         float32 [C + 1, C] on x's device, contiguous, or None; the label tensors in `dtype`"""
-        with torch.cuda.device(x.device):  # (the denominator's launches go to the current device's stream)
-            logz = dense_forward(x, Wt, need_beta=False).logz if Wt is not None and normalize else None
-            flat, offsets, scores = N.ops.transducer_beam_search_lm(x, Wt, logz, self.on_device(x.device), bool(normalize))
+        flat, offsets, scores = N.ops.transducer_beam_search_lm(x, Wt, beam_logz(x, Wt, normalize), self.on_device(x.device),
+                                                                bool(normalize))
         return beam_rows(flat, offsets, x.shape[0], self.nbest, dtype), scores
 
 
@@ -1605,11 +1573,7 @@ def transducer_beam_search_lm(x, Wt, blank, lm, forced=False, beam_size=16, clas
     what = "transducer_beam_search_lm"
     plan = TransducerLmBeamPlan.checked(x.shape[2], blank, forced, beam_size, classes_per_frame, nbest, lm, lm_weight,
                                         length_bonus, lm_eos, what)
-    if Wt is not None and tuple(Wt.shape) != (plan.C + 1, plan.C):
-        raise ValueError(f"{what}: transitions must be [{plan.C + 1}, {plan.C}], got {tuple(Wt.shape)}")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        return plan.no_frames(x.shape[0])
-    return plan.search(x, Wt, normalize)
+    return beam_preamble(plan, x, Wt, what) or plan.search(x, Wt, normalize)
 
 
 _LENGTH_RINGS = threading.local()  # per host thread, like the lattice packers' rings (_lattice_ring)

@@ -183,6 +183,22 @@ def transducer_merged_beam_search_errors(counter, targets, x, Wt, plan, spelling
                                                       plan.forced, plan.beam, plan.classes_per_frame, ref, tables)
 
 
+def plan_errors(counter, targets, x, plan, *args, spelling=None):
+    """The counts behind the best hypotheses of `plan`'s search: the plan knows which -- a checked plan of any of engine's
+    classes; args: what its search() takes behind x, without normalize and dtype (CTC: lengths; ASG: W, drop,
+    num_replabels; the Transducer: Wt).  spelling: as TransducerBeamPlan.search's, the merged search"""
+    if spelling is not None:
+        return transducer_merged_beam_search_errors(counter, targets, x, args[0], plan, spelling)
+    if isinstance(plan, E.BeamPlan):
+        return beam_search_errors(counter, targets, x, plan, *args)
+    count = next(count for cls, count in ((E.AsgBeamPlan, asg_beam_search_errors),
+                                          (E.AsgLexiconBeamPlan, asg_beam_search_lexicon_errors),
+                                          (E.TransducerBeamPlan, transducer_beam_search_errors),
+                                          (E.TransducerLexiconBeamPlan, transducer_beam_search_lexicon_errors),
+                                          (E.TransducerLmBeamPlan, transducer_beam_search_lm_errors)) if isinstance(plan, cls))
+    return count(counter, targets, x, args[0], plan, *args[1:])
+
+
 def decode_paths_errors(counter, targets, paths, drop, num_replabels=0, flags=0, T=None):
     """engine.decode_paths' launch and the counts behind it"""
     ref, tables, drop = _staged(counter, targets, paths, drop)
