@@ -9,12 +9,10 @@ beam_lm_reference.ArpaLM over word ids (word v is label v, the blank is V) or No
 beam_search() reports what a comparison needs to know, as the other references do: the smallest selection margin --
 kept against first dropped entry in every frame, and between consecutive ranks after the final drop and </s> up to the
 first one not returned -- and the number of merged extensions."""
-import math
-
-from asg_beam_reference import candidates, transition
+from asg_beam_reference import search
 from beam_lexicon_reference import is_prefix_free, proper_prefixes
 from beam_lm_reference import EOS
-from beam_reference import NEG, clean, lae
+from beam_reference import NEG
 
 
 def segment(lexicon, garbage, labels):
@@ -41,83 +39,29 @@ def beam_search(x, Wt, W, K, nbest, lexicon, garbage, lm, alpha, omega, beta, sc
     with the ranked beam [(prefix, p, part, history)], the candidates, the extension function, the merged flags and
     the sorted entries -- for a test that has to know a situation occurred."""
     inside = proper_prefixes(lexicon)
-    beam = [((), 0.0, (), lm.start if lm else None)]  # (prefix, p, labels since the last word, LM history), ranked
-    margin, merges = math.inf, 0
-    for t, raw in enumerate(x):
-        row = clean(raw)
-        cand = candidates(row, K)
-        pos = {c: p for p, (c, _) in enumerate(cand)}
-        n = len(beam)
-        # rule 4: the stays add nothing and keep node and state, for the garbage as for any other class
-        stay = [NEG] * n
-        last_pos = [None] * n
-        for i, (pre, p, _, _) in enumerate(beam):
-            if pre and pre[-1] in pos:
-                last_pos[i] = pos[pre[-1]]
-                stay[i] = (row[pre[-1]] + transition(Wt, pre[-1], pre[-1])) + p
 
-        def extension(i, c):
-            """rule 3: (e, labels since the last word, next history) of i + c; e = -inf: it does not exist"""
-            pre, p, part, hist = beam[i]
-            ac = (row[c] + transition(Wt, pre[-1] if pre else None, c)) + p
-            if ac == NEG:
-                return NEG, None, None
-            if garbage is not None and c == garbage:
-                return ac, part, hist
-            part = part + (c,)
-            if part in lexicon:  # the class completes a word
-                l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-                if l == NEG:
-                    return NEG, None, None
-                return ac + ((alpha * l + omega) + beta), (), nxt
-            if part in inside:
-                return ac + beta, part, hist
-            return NEG, None, None
+    def extend(state, pre, c):  # rule 3
+        part, hist = state
+        if garbage is not None and c == garbage:
+            return 0.0, state
+        part = part + (c,)
+        if part in lexicon:  # the class completes a word
+            l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
+            return None if l == NEG else ((alpha * l + omega) + beta, ((), nxt))
+        return (beta, (part, hist)) if part in inside else None
 
-        merged = [[False] * len(cand) for _ in range(n)]
-        for j, pj in enumerate(h[0] for h in beam):
-            if last_pos[j] is None:
-                continue
-            for i, pi in enumerate(h[0] for h in beam):
-                if len(pi) + 1 == len(pj) and pi == pj[:-1]:
-                    stay[j] = lae(stay[j], extension(i, pj[-1])[0])
-                    merged[i][last_pos[j]] = True
-                    merges += 1
-                    break
-        entries = [(stay[i], i, beam[i][0], beam[i][2], beam[i][3]) for i in range(n)]
-        for i in range(n):
-            pre = beam[i][0]
-            for p, (c, _) in enumerate(cand):
-                if not (pre and pre[-1] == c) and not merged[i][p]:
-                    e, part, nxt = extension(i, c)
-                    entries.append((e, n + i * len(cand) + p, pre + (c,), part, nxt))
-        entries = [e for e in entries if e[0] > NEG]
-        entries.sort(key=lambda e: (-e[0], e[1]))
-        if on_frame is not None:
-            on_frame(t, beam, cand, extension, merged, entries)
-        if len(entries) > W:
-            margin = min(margin, entries[W - 1][0] - entries[W][0])
-        beam = [(pre, p, part, hist) for p, _, pre, part, hist in entries[:W]]
-        if not beam:
-            break
-    # rule 5: a rank inside a word is dropped, </s>, the ranks again
-    final = []
-    for r, (pre, p, part, hist) in enumerate(beam):
+    def finish(state, s):  # rule 5: a rank inside a word is dropped, </s>
+        part, hist = state
         if part:
-            continue
-        s = p
+            return None
         if score_eos and lm:
             l, _ = lm.step(hist, EOS)
             if l == NEG:
-                continue
+                return None
             s += alpha * l
-        final.append((s, r, pre))
-    final.sort(key=lambda e: (-e[0], e[1]))
-    for r in range(min(nbest, len(final) - 1)):
-        margin = min(margin, final[r][0] - final[r + 1][0])
-    hyps = [(pre, s - logz if logz is not None else s) for s, _, pre in final[:nbest]]
-    hyps += [((), NEG)] * (nbest - len(hyps))
-    return hyps, margin, merges
+        return s
+
+    return search(x, Wt, W, K, nbest, ((), lm.start if lm else None), extend, finish, logz=logz, on_frame=on_frame)
 
 
 def brute_force(x, Wt, lexicon, garbage, lm, alpha, omega, beta, score_eos):

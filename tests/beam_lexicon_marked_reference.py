@@ -12,11 +12,8 @@ an extension unless it repeats the last label), which is rule 7 of section 25.
 beam_search() reports what a comparison needs to know, as the other references do: the smallest selection margin --
 kept against first dropped entry in every frame, and between consecutive ranks after the last frame's terms up to the
 first one not returned -- and the number of merged extensions."""
-import math
-
 from beam_lm_reference import EOS
-from beam_reference import NEG, candidates, clean, lae, row_lse
-from transducer_beam_reference import weight
+from beam_reference import NEG, search
 
 
 def starts(lexicon):
@@ -62,107 +59,51 @@ def words_of(lexicon, labels):
     return seg[0] + ([lexicon[seg[1]]] if seg[1] else [])
 
 
+def marked_lexicon_rules(lexicon, lm, alpha, omega, beta, score_eos):
+    """(start, extend, finish) of a search with a start-marked lexicon: the state is (labels of the current word, LM
+    history).  Rule 3: a label that begins no word continues the current one along the spellings and adds beta; one that
+    begins a word adds beta behind the empty prefix, behind a complete spelling that word's (alpha l + omega) + beta,
+    and does not exist behind an unfinished one.  Rule 5: after the last frame the empty sequence as it is, a complete
+    pending word's alpha l + omega, anything else dropped; then </s>'s alpha l"""
+    R, at = starts(lexicon), positions(lexicon)
+
+    def extend(state, pre, c):
+        part, hist = state
+        if c not in R:  # inside a word: the arc of the current node
+            return (beta, (part + (c,), hist)) if part and part + (c,) in at else None
+        if not part:  # the first word of the empty prefix
+            return beta, ((c,), hist)
+        if part not in lexicon:  # a new word behind an unfinished one
+            return None
+        l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
+        return None if l == NEG else ((alpha * l + omega) + beta, ((c,), nxt))
+
+    def finish(state, s):
+        part, hist = state
+        if part:
+            if part not in lexicon:
+                return None
+            l, hist = lm.step(hist, lexicon[part]) if lm else (0.0, None)
+            if l == NEG:
+                return None
+            s += alpha * l + omega
+        if score_eos and lm:
+            l, _ = lm.step(hist, EOS)
+            if l == NEG:
+                return None
+            s += alpha * l
+        return s
+
+    return ((), lm.start if lm else None), extend, finish
+
+
 def beam_search(x, blank, W, K, nbest, lexicon, lm, alpha, omega, beta, score_eos, normalize=False, Wt=None, forced=False,
                 logz=None):
     """x: the [T, C] scores of one utterance.  lexicon: {spelling tuple: word id}, start-marked; lm: an ArpaLM over word
     ids or None.  Returns (hyps, margin, merges): hyps = nbest pairs (label tuple, score) -- the score minus the rows'
     log-sum-exps if `normalize`, minus logz if given --; ranks beyond what is left after the last frame are ((), -inf)."""
-    R, at = starts(lexicon), positions(lexicon)
-    beam = [((), 0.0, NEG, (), lm.start if lm else None)]  # (prefix, pb, pnb, labels of the current word, LM history)
-    margin, merges, norm = math.inf, 0, 0.0
-    for t, raw in enumerate(x):
-        row = clean(raw)
-        norm += row_lse(row)
-        cand = candidates(row, blank, K)  # (by acoustic score alone)
-        pos = {c: p for p, (c, _) in enumerate(cand)}
-        brow = None if t == 0 else blank  # the state behind pb: the start in frame 0, the blank from frame 1 on
-        n = len(beam)
-        no_extension = forced and t == 0
-
-        def extension(i, c):
-            """rule 3: (e, labels of the current word, next history) of i + c; e = -inf: it does not exist"""
-            pre, pb, pnb, part, hist = beam[i]
-            if no_extension:
-                return NEG, None, None
-            m = pb + weight(Wt, brow, c)
-            if not forced and pre and pre[-1] != c:
-                m = lae(m, pnb + weight(Wt, pre[-1], c))
-            ac = row[c] + m
-            if ac == NEG:
-                return NEG, None, None
-            if c not in R:  # inside a word: the arc of the current node
-                if not part or part + (c,) not in at:
-                    return NEG, None, None
-                return ac + beta, part + (c,), hist
-            if not part:  # the first word of the empty prefix
-                return ac + beta, (c,), hist
-            if part not in lexicon:  # a new word behind an unfinished one
-                return NEG, None, None
-            l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-            if l == NEG:
-                return NEG, None, None
-            return ac + ((alpha * l + omega) + beta), (c,), nxt
-
-        # the stays add no term and keep position and history
-        spb, spnb = [NEG] * n, [NEG] * n
-        for i, (pre, pb, pnb, _, _) in enumerate(beam):
-            m = pb + weight(Wt, brow, blank)
-            if pre:
-                m = lae(m, pnb + weight(Wt, pre[-1], blank))
-            spb[i] = row[blank] + m
-            if pre and pre[-1] in pos:
-                spnb[i] = (row[pre[-1]] + pnb) + weight(Wt, pre[-1], pre[-1])
-        merged = [[False] * len(cand) for _ in range(n)]
-        if not no_extension:
-            for j, pj in enumerate(h[0] for h in beam):
-                if not pj or pj[-1] not in pos:
-                    continue
-                for i, pi in enumerate(h[0] for h in beam):
-                    if len(pi) + 1 == len(pj) and pi == pj[:-1]:
-                        spnb[j] = lae(spnb[j], extension(i, pj[-1])[0])
-                        merged[i][pos[pj[-1]]] = True
-                        merges += 1
-                        break
-        entries = [(lae(spb[i], spnb[i]), i, beam[i][0], spb[i], spnb[i], beam[i][3], beam[i][4]) for i in range(n)]
-        if not no_extension:
-            for i in range(n):
-                for p, (c, _) in enumerate(cand):
-                    if c != blank and not merged[i][p]:
-                        e, part, nxt = extension(i, c)
-                        entries.append((e, n + i * len(cand) + p, beam[i][0] + (c,), NEG, e, part, nxt))
-        entries = [e for e in entries if e[0] > NEG]
-        entries.sort(key=lambda e: (-e[0], e[1]))
-        if len(entries) > W:
-            margin = min(margin, entries[W - 1][0] - entries[W][0])
-        beam = [e[2:] for e in entries[:W]]
-        if not beam:
-            break
-    # rule 5: the empty sequence as it is, a complete pending word's term, anything else dropped; </s>; the ranks again
-    final = []
-    for r, (pre, pb, pnb, part, hist) in enumerate(beam):
-        s = pb if forced else lae(pb, pnb)
-        if s == NEG:
-            continue
-        if part:
-            if part not in lexicon:
-                continue
-            l, hist = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-            if l == NEG:
-                continue
-            s += alpha * l + omega
-        if score_eos and lm:
-            l, _ = lm.step(hist, EOS)
-            if l == NEG:
-                continue
-            s += alpha * l
-        final.append((s, r, pre))
-    final.sort(key=lambda e: (-e[0], e[1]))
-    for r in range(min(nbest, len(final) - 1)):
-        margin = min(margin, final[r][0] - final[r + 1][0])
-    sub = (norm if normalize else 0.0) if logz is None else logz
-    hyps = [(pre, s - sub) for s, _, pre in final[:nbest]]
-    hyps += [((), NEG)] * (nbest - len(hyps))
-    return hyps, margin, merges
+    rules = marked_lexicon_rules(lexicon, lm, alpha, omega, beta, score_eos)
+    return search(x, blank, W, K, nbest, *rules, Wt=Wt, forced=forced, normalize=normalize, logz=logz)
 
 
 def brute_force(x, blank, lexicon, lm, alpha, omega, beta, score_eos, Wt=None, forced=False, ctc=False):

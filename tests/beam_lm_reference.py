@@ -8,7 +8,7 @@ ArpaLM.step(history, label) works on class labels: history is the tuple of the l
 the sentence start is still in reach), label a class index or EOS."""
 import math
 
-from beam_reference import NEG, candidates, clean, lae, row_lse
+from beam_reference import NEG, search
 
 EOS, BOS = "</s>", "<s>"
 LN10 = math.log(10.0)
@@ -62,74 +62,29 @@ class ArpaLM:
         return total
 
 
+def token_lm_rules(lm, alpha, beta, score_eos):
+    """(start, extend, finish) of a search with an LM over the labels: the state is (LM history,); a label adds
+    alpha l + beta, a label the LM cannot follow does not exist; </s> adds alpha l after the last frame"""
+
+    def extend(state, pre, c):
+        l, nxt = lm.step(state[0], c)
+        return None if l == NEG else (alpha * l + beta, (nxt,))
+
+    def finish(state, s):
+        if score_eos:
+            l, _ = lm.step(state[0], EOS)
+            if l == NEG:
+                return None
+            s += alpha * l
+        return s
+
+    return (lm.start,), extend, finish
+
+
 def beam_search(x, blank, W, K, nbest, lm, alpha, beta, score_eos, normalize=False):
     """beam_reference.beam_search with the additions of section 18.  Returns (hyps, margin, merges) alike; the margin
     also covers the ranks after </s>."""
-    beam = [((), 0.0, NEG, lm.start)]  # (prefix, pb, pnb, LM history), ranked
-    margin, merges, norm = math.inf, 0, 0.0
-    for raw in x:
-        row = clean(raw)
-        norm += row_lse(row)
-        cand = candidates(row, blank, K)  # (by acoustic score alone)
-        pos = lambda c: next((p for p, (cc, _) in enumerate(cand) if cc == c), None)
-        n = len(beam)
-        tot = [lae(pb, pnb) for _, pb, pnb, _ in beam]
-        stay_pb = [row[blank] + tot[i] for i in range(n)]
-        stay_pnb = [NEG] * n
-        last_pos = [None] * n
-        for i, (pre, pb, pnb, _) in enumerate(beam):
-            if pre:
-                last_pos[i] = pos(pre[-1])
-                if last_pos[i] is not None:
-                    stay_pnb[i] = row[pre[-1]] + pnb
-
-        def extension(i, c):
-            """(e, next history) of i + c; e = -inf: it does not exist"""
-            pre, pb, _, hist = beam[i]
-            e = row[c] + (pb if pre and pre[-1] == c else tot[i])
-            if e == NEG:
-                return NEG, None
-            l, nxt = lm.step(hist, c)
-            return (NEG, None) if l == NEG else (e + (alpha * l + beta), nxt)
-
-        merged = [[False] * len(cand) for _ in range(n)]
-        for j, (pj, _, _, _) in enumerate(beam):
-            if last_pos[j] is None:
-                continue
-            for i, (pi, _, _, _) in enumerate(beam):
-                if len(pi) + 1 == len(pj) and pi == pj[:-1]:
-                    stay_pnb[j] = lae(stay_pnb[j], extension(i, pj[-1])[0])
-                    merged[i][last_pos[j]] = True
-                    merges += 1
-                    break
-        entries = [(lae(stay_pb[i], stay_pnb[i]), i, beam[i][0], stay_pb[i], stay_pnb[i], beam[i][3]) for i in range(n)]
-        for i in range(n):
-            for p, (c, _) in enumerate(cand):
-                if c != blank and not merged[i][p]:
-                    e, nxt = extension(i, c)
-                    entries.append((e, n + i * len(cand) + p, beam[i][0] + (c,), NEG, e, nxt))
-        entries = [e for e in entries if e[0] != NEG]
-        entries.sort(key=lambda e: (-e[0], e[1]))
-        if len(entries) > W:
-            margin = min(margin, entries[W - 1][0] - entries[W][0])
-        beam = [(pre, pb, pnb, hist) for _, _, pre, pb, pnb, hist in entries[:W]]
-        if not beam:
-            break
-    final = []
-    for r, (pre, pb, pnb, hist) in enumerate(beam):
-        s = lae(pb, pnb)
-        if score_eos:
-            l, _ = lm.step(hist, EOS)
-            if l == NEG:
-                continue
-            s += alpha * l
-        final.append((s, r, pre))
-    final.sort(key=lambda e: (-e[0], e[1]))
-    for r in range(min(nbest, len(final) - 1)):
-        margin = min(margin, final[r][0] - final[r + 1][0])
-    hyps = [(pre, s - norm if normalize else s) for s, _, pre in final[:nbest]]
-    hyps += [((), NEG)] * (nbest - len(hyps))
-    return hyps, margin, merges
+    return search(x, blank, W, K, nbest, *token_lm_rules(lm, alpha, beta, score_eos), normalize=normalize)
 
 
 def random_arpa(rs, tokens, order, keep, eos=True):

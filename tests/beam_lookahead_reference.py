@@ -8,13 +8,10 @@ look-ahead is a dict from that tuple to a score.  The LM is beam_lm_reference.Ar
 One function serves CTC and both Transducer topologies, as beam_lexicon_marked_reference's does: Wt None and forced
 False are CTC's rules.  It never skips a lookup: every extension's term is formed, so the device's prune bound is
 compared against a search without one."""
-import math
-
 from beam_lexicon_marked_reference import positions, starts
 from beam_lexicon_reference import proper_prefixes
 from beam_lm_reference import EOS
-from beam_reference import NEG, candidates, clean, lae, row_lse
-from transducer_beam_reference import weight
+from beam_reference import NEG, search
 
 
 def node_look(lexicon, scores, marked):
@@ -36,115 +33,60 @@ def unigram_scores(lm, V):
     return [low if s == NEG else s for s in u]
 
 
+def lookahead_rules(lexicon, lm, look, alpha, omega, beta, score_eos, marked):
+    """(start, extend, finish) of a lexicon search with look-ahead: the state is (labels of the current word, LM
+    history).  Rule 1: a label inside a word adds alpha (look[to] - look[from]) + beta, from the root look is 0; rule 2
+    (end-marked) and rule 3 (start-marked): the word's step is settled against what its node has paid, and a
+    start-marked word's first label pays its own node's look-ahead on top; rule 4: after the last frame a rank inside
+    a word is dropped -- start-marked: unless its spelling is complete, then settled alike --, then </s>"""
+    R = starts(lexicon) if marked else set()
+    at = positions(lexicon) if marked else proper_prefixes(lexicon)
+
+    def extend(state, pre, c):
+        part, hist = state
+        if not marked:
+            to = part + (c,)
+            if to in lexicon:  # rule 2: the word's step settled against what its node has paid
+                l, nxt = lm.step(hist, lexicon[to]) if lm else (0.0, None)
+                return None if l == NEG else ((alpha * (l - look[part]) + omega) + beta, ((), nxt))
+            return (alpha * (look[to] - look[part]) + beta, (to, hist)) if to in at else None  # rule 1
+        if c not in R:  # rule 1, inside a start-marked word
+            if not part or part + (c,) not in at:
+                return None
+            return alpha * (look[part + (c,)] - look[part]) + beta, (part + (c,), hist)
+        if not part:  # rule 1 from the root, whose look-ahead is 0
+            return alpha * (look[(c,)] - 0.0) + beta, ((c,), hist)
+        if part not in lexicon:
+            return None
+        l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
+        if l == NEG:
+            return None
+        return ((alpha * (l - look[part]) + omega) + beta) + alpha * look[(c,)], ((c,), nxt)  # rule 3
+
+    def finish(state, s):  # rule 4
+        part, hist = state
+        if part:
+            if not marked or part not in lexicon:
+                return None
+            l, hist = lm.step(hist, lexicon[part]) if lm else (0.0, None)
+            if l == NEG:
+                return None
+            s += alpha * (l - look[part]) + omega
+        if score_eos and lm:
+            l, _ = lm.step(hist, EOS)
+            if l == NEG:
+                return None
+            s += alpha * l
+        return s
+
+    return ((), lm.start if lm else None), extend, finish
+
+
 def beam_search(x, blank, W, K, nbest, lexicon, lm, look, alpha, omega, beta, score_eos, marked=False, normalize=False,
                 Wt=None, forced=False, logz=None):
     """x: the [T, C] scores of one utterance.  lexicon: {spelling tuple: word id}; lm: an ArpaLM over word ids; look:
     node_look()'s dict.  Returns (hyps, margin, merges) as the other restatements do: hyps = nbest pairs (label tuple,
     score) -- minus the rows' log-sum-exps if `normalize`, minus logz if given --, ((), -inf) beyond what is left; the
     smallest selection margin; the number of merged extensions."""
-    R = starts(lexicon) if marked else set()
-    at = positions(lexicon) if marked else proper_prefixes(lexicon)
-    beam = [((), 0.0, NEG, (), lm.start if lm else None)]  # (prefix, pb, pnb, labels of the current word, LM history)
-    margin, merges, norm = math.inf, 0, 0.0
-    for t, raw in enumerate(x):
-        row = clean(raw)
-        norm += row_lse(row)
-        cand = candidates(row, blank, K)  # (by acoustic score alone)
-        pos = {c: p for p, (c, _) in enumerate(cand)}
-        brow = None if t == 0 else blank
-        n = len(beam)
-        no_extension = forced and t == 0
-
-        def extension(i, c):
-            """(e, labels of the current word, next history) of i + c; e = -inf: it does not exist"""
-            pre, pb, pnb, part, hist = beam[i]
-            if no_extension:
-                return NEG, None, None
-            m = pb + weight(Wt, brow, c)
-            if not forced and pre and pre[-1] != c:
-                m = lae(m, pnb + weight(Wt, pre[-1], c))
-            ac = row[c] + m
-            if ac == NEG:
-                return NEG, None, None
-            if not marked:
-                to = part + (c,)
-                if to in lexicon:  # rule 2: the word's step settled against what its node has paid
-                    l, nxt = lm.step(hist, lexicon[to]) if lm else (0.0, None)
-                    if l == NEG:
-                        return NEG, None, None
-                    return ac + ((alpha * (l - look[part]) + omega) + beta), (), nxt
-                if to in at:  # rule 1
-                    return ac + (alpha * (look[to] - look[part]) + beta), to, hist
-                return NEG, None, None
-            if c not in R:  # rule 1, inside a start-marked word
-                if not part or part + (c,) not in at:
-                    return NEG, None, None
-                return ac + (alpha * (look[part + (c,)] - look[part]) + beta), part + (c,), hist
-            if not part:  # rule 1 from the root, whose look-ahead is 0
-                return ac + (alpha * (look[(c,)] - 0.0) + beta), (c,), hist
-            if part not in lexicon:
-                return NEG, None, None
-            l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-            if l == NEG:
-                return NEG, None, None
-            return ac + (((alpha * (l - look[part]) + omega) + beta) + alpha * look[(c,)]), (c,), nxt  # rule 3
-
-        spb, spnb = [NEG] * n, [NEG] * n
-        for i, (pre, pb, pnb, _, _) in enumerate(beam):
-            m = pb + weight(Wt, brow, blank)
-            if pre:
-                m = lae(m, pnb + weight(Wt, pre[-1], blank))
-            spb[i] = row[blank] + m
-            if pre and pre[-1] in pos:
-                spnb[i] = (row[pre[-1]] + pnb) + weight(Wt, pre[-1], pre[-1])
-        merged = [[False] * len(cand) for _ in range(n)]
-        if not no_extension:
-            for j, pj in enumerate(h[0] for h in beam):
-                if not pj or pj[-1] not in pos:
-                    continue
-                for i, pi in enumerate(h[0] for h in beam):
-                    if len(pi) + 1 == len(pj) and pi == pj[:-1]:
-                        spnb[j] = lae(spnb[j], extension(i, pj[-1])[0])
-                        merged[i][pos[pj[-1]]] = True
-                        merges += 1
-                        break
-        entries = [(lae(spb[i], spnb[i]), i, beam[i][0], spb[i], spnb[i], beam[i][3], beam[i][4]) for i in range(n)]
-        if not no_extension:
-            for i in range(n):
-                for p, (c, _) in enumerate(cand):
-                    if c != blank and not merged[i][p]:
-                        e, part, nxt = extension(i, c)
-                        entries.append((e, n + i * len(cand) + p, beam[i][0] + (c,), NEG, e, part, nxt))
-        entries = [e for e in entries if e[0] > NEG]
-        entries.sort(key=lambda e: (-e[0], e[1]))
-        if len(entries) > W:
-            margin = min(margin, entries[W - 1][0] - entries[W][0])
-        beam = [e[2:] for e in entries[:W]]
-        if not beam:
-            break
-    # rule 4
-    final = []
-    for r, (pre, pb, pnb, part, hist) in enumerate(beam):
-        s = pb if forced else lae(pb, pnb)
-        if s == NEG:
-            continue
-        if part:
-            if not marked or part not in lexicon:
-                continue
-            l, hist = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-            if l == NEG:
-                continue
-            s += alpha * (l - look[part]) + omega
-        if score_eos and lm:
-            l, _ = lm.step(hist, EOS)
-            if l == NEG:
-                continue
-            s += alpha * l
-        final.append((s, r, pre))
-    final.sort(key=lambda e: (-e[0], e[1]))
-    for r in range(min(nbest, len(final) - 1)):
-        margin = min(margin, final[r][0] - final[r + 1][0])
-    sub = (norm if normalize else 0.0) if logz is None else logz
-    hyps = [(pre, s - sub) for s, _, pre in final[:nbest]]
-    hyps += [((), NEG)] * (nbest - len(hyps))
-    return hyps, margin, merges
+    rules = lookahead_rules(lexicon, lm, look, alpha, omega, beta, score_eos, marked)
+    return search(x, blank, W, K, nbest, *rules, Wt=Wt, forced=forced, normalize=normalize, logz=logz)

@@ -12,42 +12,22 @@ import pytest
 import torch
 
 import asg_beam_reference as R
+import beam_support as S
+from beam_support import emissions, transitions
+from beam_support import log_normaliser as log_denominator  # (with transitions: the criterion's denominator, asg.py:114)
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
 NEG = R.NEG
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import asg
-
-    return E, M, asg
-
-
-def log_denominator(x, Wt):
-    """[B] float64: the criterion's denominator (asg.py:114) by the forward recursion in float64 -- torch on the device,
-    independent of the library; a NaN counts as -inf"""
-    xd = torch.from_numpy(x).cuda().double()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    Wd = torch.where(torch.isnan(Wd), torch.full_like(Wd, NEG), Wd)
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
+    return S.package("engine", "metrics", "criterions.asg")
 
 
 def reference(x, Wt, W, K, nbest):
     """per utterance (hyps, merges); asserts the margins, so that no utterance is left out of a comparison"""
-    out = []
-    for b in range(x.shape[0]):
-        hyps, margin, merges = R.beam_search(x[b], Wt, W, K, nbest)
-        assert margin >= MARGIN, (b, margin)
-        out.append((hyps, merges))
-    return out
+    return [(hyps, merges) for hyps, _, merges in S.margins_ok(lambda b: R.beam_search(x[b], Wt, W, K, nbest), x.shape[0])]
 
 
 def device(x, Wt, W, K, nbest, normalize=False, drop=None, num_replabels=0):
@@ -64,26 +44,8 @@ def compare(x, Wt, W, K, nbest):
     seqs, raw = device(x, Wt, W, K, nbest)
     nseqs, normed = device(x, Wt, W, K, nbest, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_denominator(x, Wt)
-    for b, (hyps, _) in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    S.assert_ranks([hyps for hyps, _ in want], seqs, raw, normed, log_denominator(x, Wt), nbest)
     return want
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
 
 
 _WIDE = {}

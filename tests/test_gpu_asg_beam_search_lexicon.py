@@ -23,26 +23,20 @@ import torch
 import asg_beam_lexicon_reference as AX
 import asg_beam_reference as AR
 import beam_lm_reference as LR
+import beam_support as S
+from beam_support import emissions, names_of, transitions
+from beam_support import log_normaliser as log_denominator  # (with transitions: the criterion's denominator, asg.py:114)
+from beam_support import spelled_asg as spelled
+from beam_support import word_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
 NEG = AR.NEG
 ALPHA, OMEGA, BETA = 0.8, 0.5, -0.3
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import asg
-    from gtn_applications_amd.lexicon import Lexicon
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, asg, Lexicon, NGramLM
-
-
-def names_of(V):
-    return [f"w{v}" for v in range(V)]
+    return S.package("engine", "metrics", "criterions.asg", "lexicon:Lexicon", "lm:NGramLM")
 
 
 def pack(spellings, C, garbage):
@@ -53,37 +47,10 @@ def pack(spellings, C, garbage):
     return Lexicon(by_id, C, garbage) if garbage is not None else Lexicon(by_id, C + 1, C)
 
 
-def make_lms(tmp_path, text, V):
-    """(the device's word LM through the loader, the reference's reading of the same text); (None, None) without text"""
-    if text is None:
-        return None, None
-    NGramLM = _mods()[4]
-    p = tmp_path / "words.arpa"
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), names_of(V), V), LR.ArpaLM(text, names_of(V), V)
-
-
-def log_denominator(x, Wt):
-    """[B] float64: the criterion's denominator (asg.py:114) by the forward recursion in float64 -- torch on the device,
-    independent of the library; a NaN counts as -inf"""
-    xd = torch.from_numpy(x).cuda().double()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    Wd = torch.where(torch.isnan(Wd), torch.full_like(Wd, NEG), Wd)
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
-
-
 def reference(x, Wt, W, K, nbest, spellings, garbage, ref_lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True):
     """per utterance the reference's hyps; asserts the margins, so that no utterance is left out of a comparison"""
-    out = []
-    for b in range(x.shape[0]):
-        hyps, margin, _ = AX.beam_search(x[b], Wt, W, K, nbest, spellings, garbage, ref_lm, alpha, omega, beta, eos)
-        assert margin >= MARGIN, (b, margin)
-        out.append(hyps)
-    return out
+    search = lambda b: AX.beam_search(x[b], Wt, W, K, nbest, spellings, garbage, ref_lm, alpha, omega, beta, eos)
+    return [res[0] for res in S.margins_ok(search, x.shape[0])]
 
 
 def device(x, Wt, W, K, nbest, lex, garbage, lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True, normalize=False, drop=None,
@@ -104,28 +71,13 @@ def compare(x, Wt, W, K, nbest, spellings, garbage, lm, ref_lm, alpha=ALPHA, ome
     seqs, raw = device(x, Wt, W, K, nbest, lex, garbage, lm, alpha, omega, beta, eos)
     nseqs, normed = device(x, Wt, W, K, nbest, lex, garbage, lm, alpha, omega, beta, eos, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_denominator(x, Wt)
-    for b, hyps in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            at = AX.segment(spellings, garbage, seqs[b][r])
-            assert at is not None and at[1] == (), (b, r, seqs[b][r])  # (every returned sequence is whole words)
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+
+    def whole_words(b, r, seq):
+        at = AX.segment(spellings, garbage, seq)
+        assert at is not None and at[1] == (), (b, r, seq)
+
+    S.assert_ranks(want, seqs, raw, normed, log_denominator(x, Wt), nbest, check=whole_words)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
 
 
 def universe(N, R, use_garbage):
@@ -142,31 +94,6 @@ def random_words(rs, N, V, longest):
         if len(found) == V:
             return [list(w) for w in sorted(found)]
     raise AssertionError("not enough different words at this size")
-
-
-def spelled(seed, B, T, C, spellings, garbage, hi=8.0):
-    """emissions that spell a sentence of lexicon words in raw classes, every class for one or two frames, the garbage
-    (where there is one) between some of them; what is left of the T frames repeats the last class; +hi on
-    N(0, 0.5^2) noise -- complete-word hypotheses survive the beam"""
-    rs = np.random.RandomState(seed)
-    x = (rs.randn(B, T, C) * 0.5).astype(np.float32)
-    words = sorted(spellings, key=spellings.get)
-    for b in range(B):
-        frames = []
-        while True:
-            more = []
-            for c in words[rs.randint(len(words))]:
-                if garbage is not None and rs.rand() < 0.4:
-                    more += [garbage] * int(rs.randint(1, 3))
-                more += [c] * int(rs.randint(1, 3))
-            if len(frames) + len(more) > T:
-                break
-            frames += more
-        if not frames:
-            frames = [garbage if garbage is not None else 0]
-        for t in range(T):
-            x[b, t, frames[min(t, len(frames) - 1)]] += hi
-    return x
 
 
 def favour(frames, C, seed, hi=8.0):

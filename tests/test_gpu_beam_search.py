@@ -2,40 +2,30 @@
 CTC.beam_search and CTC.errors(beam_size=)) against its restatement in plain Python (tests/beam_reference.py, itself
 pinned to a brute-force enumeration in tests/test_beam_abi.py).
 
-Acceptance of every comparison: the label sequences of all returned ranks are equal; unnormalised scores agree to
-1e-9 max(1, |s|) -- both sides are float64 and differ in libm rounding only; normalised scores agree at the project's
-loss bar (tests/test_gpu_configs.py: 1e-4 |want| + 2e-5), the device's row log-sum-exps being float32.  An utterance
-whose smallest selection margin in the reference is below 1e-9 could legitimately come out differently; the seeds are
-fixed so that there is none, and every test asserts that."""
+Acceptance of every comparison: tests/beam_support.py (assert_ranks, margins_ok), the normalised scores against the
+rows' log-sum-exps summed in Python."""
 import numpy as np
 import pytest
 import torch
 
 import beam_reference as R
+import beam_support as S
+from beam_support import emissions
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
-
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions.ctc import CTC
-
-    return E, M, CTC
+    return S.package("engine", "metrics", "criterions.ctc:CTC")
 
 
 def reference(x, blank, W, K, nbest, lengths=None):
     """per utterance (hyps, normalised hyps); asserts the margins and returns the merges too"""
+    rows = S.utterances(x, lengths)
     out = []
-    for b in range(x.shape[0]):
-        rows = x[b] if lengths is None else x[b, :lengths[b]]
-        hyps, margin, merges = R.beam_search(rows, blank, W, K, nbest)
-        shift = sum(R.row_lse(R.clean(row)) for row in rows)  # (the same for every hypothesis)
-        norm = [(h, s - shift if s != R.NEG else s) for h, s in hyps]
-        assert margin >= MARGIN, (b, margin)  # (no utterance is left out of a comparison)
-        out.append((hyps, norm, merges))
+    for b, (hyps, _, merges) in enumerate(S.margins_ok(lambda b: R.beam_search(rows[b], blank, W, K, nbest), len(rows))):
+        shift = S.row_shift(rows[b])  # (the same for every hypothesis)
+        out.append((hyps, [(h, s - shift if s != R.NEG else s) for h, s in hyps], merges))
     return out
 
 
@@ -54,20 +44,9 @@ def compare(x, blank, W, K, nbest, lengths=None):
     seqs, raw = device(x, blank, W, K, nbest, lengths)
     nseqs, normed = device(x, blank, W, K, nbest, lengths, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    for b, (hyps, norm, _) in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s, n = hyps[r][1], norm[r][1]
-            if s == R.NEG:
-                assert raw[b, r] == R.NEG and normed[b, r] == R.NEG, (b, r)
-                continue
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    shifts = [S.row_shift(rows) for rows in S.utterances(x, lengths)]
+    S.assert_ranks([hyps for hyps, _, _ in want], seqs, raw, normed, shifts, nbest, blank)
     return want
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
 
 
 def merging_emissions(seed, B, T, C, scale, blank, W, K, merges=20):
@@ -218,7 +197,7 @@ def test_module_returns_what_viterbi_returns_and_the_scores():
         assert [tuple(s.tolist()) for s in hyps[b]] == [h for h, _ in want[b][1]]
         for r in range(3):
             n = want[b][1][r][1]
-            assert abs(scores[b, r].item() - n) <= 1e-4 * abs(n) + 2e-5
+            assert S.normalised_close(scores[b, r].item(), n)
     one, s1 = crit.beam_search(xd, beam_size=8, classes_per_frame=6, return_scores=True)
     assert tuple(s1.shape) == (B, 1) and [p.tolist() for p in one] == [h[0].tolist() for h in hyps]
     # other floating dtypes are converted, tensors that are not on a GPU are uploaded: the same search

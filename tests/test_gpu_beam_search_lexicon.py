@@ -6,9 +6,7 @@ a separator class, packed by lexicon.Lexicon on the device side and kept as a di
 LMs are seeded random ARPA texts over the word names, loaded through NGramLM.from_arpa(path, words, blank=len(words)) on
 the device side and read by the reference's own few lines.
 
-Acceptance, as in tests/test_gpu_beam_search_lm.py: the label sequences of all returned ranks are equal; unnormalised
-scores agree to 1e-9 max(1, |s|); normalised scores at the loss bar 1e-4 |want| + 2e-5.  Every utterance must have a
-reference margin of at least 1e-9 (asserted: none is left out); the seeds are fixed so that all do."""
+Acceptance of every comparison: tests/beam_support.py (assert_ranks, margins_ok), as in tests/test_gpu_beam_search_lm.py."""
 import math
 
 import numpy as np
@@ -18,25 +16,17 @@ import torch
 import beam_lexicon_reference as XR
 import beam_lm_reference as LR
 import beam_reference as R
+import beam_support as S
+from beam_support import emissions, names_of
+from beam_support import word_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
 ALPHA, OMEGA, BETA = 0.8, 0.6, 0.3
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions.ctc import CTC
-    from gtn_applications_amd.lexicon import Lexicon
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, CTC, Lexicon, NGramLM
-
-
-def names_of(V):
-    return [f"w{v}" for v in range(V)]
+    return S.package("engine", "metrics", "criterions.ctc:CTC", "lexicon:Lexicon", "lm:NGramLM")
 
 
 def pack(spellings, C, blank):
@@ -47,23 +37,12 @@ def pack(spellings, C, blank):
     return Lexicon(by_id, C, blank)
 
 
-def make_lms(tmp_path, text, V):
-    """(the device's word LM through the loader, the reference's reading of the same text); (None, None) without text"""
-    if text is None:
-        return None, None
-    NGramLM = _mods()[4]
-    p = tmp_path / "words.arpa"
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), names_of(V), V), LR.ArpaLM(text, names_of(V), V)
-
-
 def reference(x, blank, W, K, nbest, spellings, ref_lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True, lengths=None):
+    rows = S.utterances(x, lengths)
+    search = lambda b: XR.beam_search(rows[b], blank, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos)
     out = []
-    for b in range(x.shape[0]):
-        rows = x[b] if lengths is None else x[b, :lengths[b]]
-        hyps, margin, _ = XR.beam_search(rows, blank, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos)
-        shift = sum(R.row_lse(R.clean(row)) for row in rows)
-        assert margin >= MARGIN, (b, margin)  # (no utterance is left out of a comparison)
+    for b, (hyps, _, _) in enumerate(S.margins_ok(search, len(rows))):
+        shift = S.row_shift(rows[b])
         out.append((hyps, [(h, s - shift if s != R.NEG else s) for h, s in hyps]))
     return out
 
@@ -85,21 +64,10 @@ def compare(x, blank, W, K, nbest, spellings, lm, ref_lm, alpha=ALPHA, omega=OME
     seqs, raw = device(x, blank, W, K, nbest, lex, lm, alpha, omega, beta, eos, lengths)
     nseqs, normed = device(x, blank, W, K, nbest, lex, lm, alpha, omega, beta, eos, lengths, normalize=True)
     assert nseqs == seqs
-    for b, (hyps, norm) in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s, n = hyps[r][1], norm[r][1]
-            lex.words(seqs[b][r])  # (every returned sequence is a sequence of whole words: raises otherwise)
-            if s == R.NEG:
-                assert raw[b, r] == R.NEG and normed[b, r] == R.NEG, (b, r)
-                continue
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    shifts = [S.row_shift(rows) for rows in S.utterances(x, lengths)]
+    # (every returned sequence is a sequence of whole words: lex.words raises otherwise)
+    S.assert_ranks([hyps for hyps, _ in want], seqs, raw, normed, shifts, nbest, blank, check=lambda b, r, seq: lex.words(seq))
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
 
 
 def peaked(seed, B, T, C, blank, spellings):
@@ -350,7 +318,7 @@ def test_module_beam_search_with_a_lexicon(tmp_path):
         assert [tuple(s.tolist()) for s in hyps[b]] == [h for h, _ in want[b][1]]
         for r in range(3):
             n = want[b][1][r][1]
-            assert scores[b, r].item() == n if n == R.NEG else abs(scores[b, r].item() - n) <= 1e-4 * abs(n) + 2e-5
+            assert scores[b, r].item() == n if n == R.NEG else S.normalised_close(scores[b, r].item(), n)
     best = crit.beam_search(xd, beam_size=8, classes_per_frame=6, **kw)
     assert [p.tolist() for p in best] == [h[0].tolist() for h in hyps]
     assert all(lex.words(p) is not None for p in best) and any(len(p) for p in best)

@@ -24,28 +24,22 @@ import torch
 import beam_lexicon_marked_reference as MR
 import beam_lexicon_reference as XR
 import beam_lm_reference as LR
+import beam_support as S
+from beam_support import emissions, log_normaliser, names_of, random_sentences, transitions
+from beam_support import spelled_sentences as spelled
+from beam_support import word_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN = 1e-9
 NEG = MR.NEG
 ALPHA, OMEGA, BETA = 0.8, 0.5, -0.3
 TOPOLOGIES = pytest.mark.parametrize("topology", ["ctc", "optional", "forced"])
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import asg, ctc, transducer
-    from gtn_applications_amd.lexicon import Lexicon
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, ctc, transducer, asg, Lexicon, NGramLM
-
-
-def names_of(V):
-    return [f"w{v}" for v in range(V)]
+    return S.package("engine", "metrics", "criterions.ctc", "criterions.transducer", "criterions.asg", "lexicon:Lexicon",
+                     "lm:NGramLM")
 
 
 def pack(spellings, C, blank):
@@ -55,45 +49,13 @@ def pack(spellings, C, blank):
     return Lexicon(order, C, blank, boundary="start", word_of=[spellings[s] for s in order])
 
 
-def make_lms(tmp_path, text, V, name="words.arpa"):
-    """(the device's word LM through the loader, the reference's reading of the same text); (None, None) without text"""
-    if text is None:
-        return None, None
-    NGramLM = _mods()[6]
-    p = tmp_path / name
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), names_of(V), V), LR.ArpaLM(text, names_of(V), V)
-
-
-def log_normaliser(x, Wt, lengths=None):
-    """[B] float64: the normaliser in float64 by torch on the device, independent of the library; a NaN counts as -inf.
-    With transitions the forward recursion over all frame paths, without them the rows' log-sum-exps over t < T_b."""
-    xd = torch.from_numpy(x).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    if Wt is None:
-        lse = torch.logsumexp(xd, dim=2)
-        if lengths is not None:
-            keep = torch.arange(x.shape[1], device="cuda")[None, :] < torch.tensor(lengths, device="cuda")[:, None]
-            lse = torch.where(keep, lse, torch.zeros_like(lse))
-        return lse.sum(dim=1).cpu().numpy()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
-
-
 def reference(topology, x, Wt, blank, W, K, nbest, spellings, ref_lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True,
               lengths=None):
     """per utterance the reference's hyps; asserts the margins, so that no utterance is left out of a comparison"""
-    out = []
-    for b in range(x.shape[0]):
-        rows = x[b] if lengths is None else x[b][:lengths[b]]
-        hyps, margin, _ = MR.beam_search(rows, blank, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos, Wt=Wt,
-                                         forced=topology == "forced")
-        assert margin >= MARGIN, (b, margin)
-        out.append(hyps)
-    return out
+    rows = S.utterances(x, lengths)
+    search = lambda b: MR.beam_search(rows[b], blank, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos, Wt=Wt,
+                                      forced=topology == "forced")
+    return [res[0] for res in S.margins_ok(search, len(rows))]
 
 
 def device(topology, x, Wt, blank, W, K, nbest, lex, lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True, normalize=False,
@@ -123,53 +85,13 @@ def compare(topology, x, Wt, blank, W, K, nbest, spellings, lm, ref_lm, alpha=AL
     seqs, raw = device(topology, x, Wt, blank, W, K, nbest, lex, lm, alpha, omega, beta, eos, lengths=lengths)
     nseqs, normed = device(topology, x, Wt, blank, W, K, nbest, lex, lm, alpha, omega, beta, eos, normalize=True, lengths=lengths)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_normaliser(x, Wt, lengths)
-    for b, hyps in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            assert blank not in seqs[b][r] and MR.words_of(spellings, seqs[b][r]) is not None, (b, r, seqs[b][r])
-            assert lex.words(seqs[b][r]) == MR.words_of(spellings, seqs[b][r])
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+
+    def whole_words(b, r, seq):  # (rule 5, and the device's own segmentation agrees)
+        assert MR.words_of(spellings, seq) is not None, (b, r, seq)
+        assert lex.words(seq) == MR.words_of(spellings, seq)
+
+    S.assert_ranks(want, seqs, raw, normed, log_normaliser(x, Wt, lengths), nbest, blank, whole_words)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
-
-
-def spelled(seed, B, T, C, blank, sentences, hi=8.0, noise=0.5, run=2):
-    """emissions that spell sentences[b] (a list of spellings) in a way every topology accepts: a blank frame first, every
-    label for one to `run` frames with one blank frame behind it, blanks for what is left of the T frames; +hi on
-    N(0, noise^2).  A sentence that does not fit is cut at a word."""
-    rs = np.random.RandomState(seed)
-    x = (rs.randn(B, T, C) * noise).astype(np.float32)
-    for b in range(B):
-        frames = [blank]
-        for word in sentences[b % len(sentences)]:
-            more = []
-            for c in word:
-                more += [c] * int(rs.randint(1, run + 1)) + [blank]
-            if len(frames) + len(more) > T:
-                break
-            frames += more
-        for t in range(T):
-            x[b, t, frames[t] if t < len(frames) else blank] += hi
-    return x
-
-
-def random_sentences(rs, spellings, count, words):
-    order = sorted(spellings)
-    return [[order[rs.randint(len(order))] for _ in range(words)] for _ in range(count)]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -272,7 +194,7 @@ def test_the_word_piece_file(tmp_path, topology):
     for b, hyps in enumerate(want):
         assert seqs[b] == [h for h, _ in hyps] and len(MR.words_of(spellings, hyps[0][0])) >= 3
         for r, (_, s) in enumerate(hyps):
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s))
+            assert S.raw_close(raw[b, r], s)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -455,7 +377,7 @@ def test_ctc_module_and_errors(tmp_path):
         for r, (seq, s) in enumerate(want[b]):
             if s > NEG:
                 n = s - logz[b]
-                assert abs(float(scores[b, r]) - n) <= 1e-4 * abs(n) + 2e-5
+                assert S.normalised_close(float(scores[b, r]), n)
                 assert lex.words(hyps[b][r].tolist()) == MR.words_of(NEST, seq)
     assert sum(len(h[0]) > 0 for h in hyps) >= 3
     counter = M.ErrorCounter()
@@ -500,7 +422,7 @@ def test_transducer_module_and_errors(tmp_path, ngram, kw):
         for r, (seq, s) in enumerate(want[b]):
             if s > NEG:
                 n = s - logz[b]
-                assert abs(float(scores[b, r]) - n) <= 1e-4 * abs(n) + 2e-5, (b, r)
+                assert S.normalised_close(float(scores[b, r]), n), (b, r)
                 assert crit.words(lex, hyps[b][r]) == MR.words_of(NEST, seq)
     assert sum(len(h[0]) > 0 for h in hyps) >= 3
     counter = M.ErrorCounter()

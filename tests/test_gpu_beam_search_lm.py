@@ -4,9 +4,7 @@ its restatement in plain Python (tests/beam_lm_reference.py, itself pinned to a 
 tests/test_beam_lm_abi.py).  The LMs are seeded random ARPA texts: the device side loads them through
 NGramLM.from_arpa, the reference reads the same text with its own few lines.
 
-Acceptance, as in tests/test_gpu_beam_search.py: the label sequences of all returned ranks are equal; unnormalised
-scores agree to 1e-9 max(1, |s|); normalised scores at the loss bar 1e-4 |want| + 2e-5.  Every utterance must have a
-reference margin of at least 1e-9 (asserted: none is left out); the seeds are fixed so that all do."""
+Acceptance of every comparison: tests/beam_support.py (assert_ranks, margins_ok), as in tests/test_gpu_beam_search.py."""
 import math
 
 import numpy as np
@@ -15,41 +13,25 @@ import torch
 
 import beam_lm_reference as LR
 import beam_reference as R
+import beam_support as S
+from beam_support import emissions, tokens_of
+from beam_support import token_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
 ALPHA, BETA = 0.8, 0.5
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions.ctc import CTC
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, CTC, NGramLM
-
-
-def tokens_of(C):
-    return [f"t{i}" for i in range(C - 1)]
-
-
-def make_lms(tmp_path, text, C, blank):
-    """(the device's LM through the loader, the reference's reading of the same text)"""
-    NGramLM = _mods()[3]
-    p = tmp_path / "lm.arpa"
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), tokens_of(C), blank), LR.ArpaLM(text, tokens_of(C), blank)
+    return S.package("engine", "metrics", "criterions.ctc:CTC", "lm:NGramLM")
 
 
 def reference(x, blank, W, K, nbest, ref_lm, alpha=ALPHA, beta=BETA, eos=True, lengths=None):
+    rows = S.utterances(x, lengths)
     out = []
-    for b in range(x.shape[0]):
-        rows = x[b] if lengths is None else x[b, :lengths[b]]
-        hyps, margin, _ = LR.beam_search(rows, blank, W, K, nbest, ref_lm, alpha, beta, eos)
-        shift = sum(R.row_lse(R.clean(row)) for row in rows)
-        assert margin >= MARGIN, (b, margin)  # (no utterance is left out of a comparison)
+    for b, (hyps, _, _) in enumerate(S.margins_ok(lambda b: LR.beam_search(rows[b], blank, W, K, nbest, ref_lm, alpha, beta, eos),
+                                                  len(rows))):
+        shift = S.row_shift(rows[b])
         out.append((hyps, [(h, s - shift if s != R.NEG else s) for h, s in hyps]))
     return out
 
@@ -69,20 +51,9 @@ def compare(x, blank, W, K, nbest, lm, ref_lm, alpha=ALPHA, beta=BETA, eos=True,
     seqs, raw = device(x, blank, W, K, nbest, lm, alpha, beta, eos, lengths)
     nseqs, normed = device(x, blank, W, K, nbest, lm, alpha, beta, eos, lengths, normalize=True)
     assert nseqs == seqs
-    for b, (hyps, norm) in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s, n = hyps[r][1], norm[r][1]
-            if s == R.NEG:
-                assert raw[b, r] == R.NEG and normed[b, r] == R.NEG, (b, r)
-                continue
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    shifts = [S.row_shift(rows) for rows in S.utterances(x, lengths)]
+    S.assert_ranks([hyps for hyps, _ in want], seqs, raw, normed, shifts, nbest, blank)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
 
 
 # (T, C, W, K, B)
@@ -278,7 +249,7 @@ def test_module_beam_search_with_an_lm(tmp_path):
         assert [tuple(s.tolist()) for s in hyps[b]] == [h for h, _ in want[b][1]]
         for r in range(3):
             n = want[b][1][r][1]
-            assert abs(scores[b, r].item() - n) <= 1e-4 * abs(n) + 2e-5
+            assert S.normalised_close(scores[b, r].item(), n)
     best = crit.beam_search(xd, beam_size=8, classes_per_frame=6, lm=lm, lm_weight=ALPHA, length_bonus=BETA)
     assert [p.tolist() for p in best] == [h[0].tolist() for h in hyps]
     plain = crit.beam_search(xd, beam_size=8, classes_per_frame=6)

@@ -24,10 +24,13 @@ import beam_lexicon_marked_reference as MR
 import beam_lexicon_reference as XR
 import beam_lm_reference as LR
 import beam_lookahead_reference as LA
+import beam_support as S
+from beam_support import emissions, log_normaliser, names_of, random_sentences, transitions
+from beam_support import spelled_sentences as spelled
+from beam_support import word_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
 NEG = LA.NEG
 ALPHA, OMEGA, BETA = 0.8, 0.5, -0.3
 BOUNDARIES = pytest.mark.parametrize("boundary", ["end", "start"])
@@ -35,17 +38,8 @@ TOPOLOGIES = pytest.mark.parametrize("topology", ["ctc", "optional", "forced"])
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import asg, ctc, transducer
-    from gtn_applications_amd.lexicon import Lexicon
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, ctc, transducer, asg, Lexicon, NGramLM
-
-
-def names_of(V):
-    return [f"w{v}" for v in range(V)]
+    return S.package("engine", "metrics", "criterions.ctc", "criterions.transducer", "criterions.asg", "lexicon:Lexicon",
+                     "lm:NGramLM")
 
 
 def pack(spellings, C, blank, boundary):
@@ -55,32 +49,6 @@ def pack(spellings, C, blank, boundary):
         order = sorted(spellings)
         return Lexicon(order, C, blank, boundary="start", word_of=[spellings[s] for s in order])
     return Lexicon([s for s, _ in sorted(spellings.items(), key=lambda kv: kv[1])], C, blank)
-
-
-def make_lms(tmp_path, text, V, name="words.arpa"):
-    """(the device's word LM through the loader, the restatement's reading of the same text)"""
-    NGramLM = _mods()[6]
-    p = tmp_path / name
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), names_of(V), V), LR.ArpaLM(text, names_of(V), V)
-
-
-def log_normaliser(x, Wt, lengths=None):
-    """[B] float64: the normaliser in float64 by torch on the device, independent of the library; a NaN counts as -inf.
-    With transitions the forward recursion over all frame paths, without them the rows' log-sum-exps over t < T_b."""
-    xd = torch.from_numpy(x).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    if Wt is None:
-        lse = torch.logsumexp(xd, dim=2)
-        if lengths is not None:
-            keep = torch.arange(x.shape[1], device="cuda")[None, :] < torch.tensor(lengths, device="cuda")[:, None]
-            lse = torch.where(keep, lse, torch.zeros_like(lse))
-        return lse.sum(dim=1).cpu().numpy()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
 
 
 def word_scores(ref_lm, V, scores):
@@ -94,14 +62,10 @@ def reference(topology, boundary, x, Wt, blank, W, K, nbest, spellings, ref_lm, 
     V = max(spellings.values()) + 1
     marked = boundary == "start"
     look = LA.node_look(spellings, [0.0] * V if scores is None else word_scores(ref_lm, V, scores), marked)
-    out = []
-    for b in range(x.shape[0]):
-        rows = x[b] if lengths is None else x[b][:lengths[b]]
-        hyps, margin, _ = LA.beam_search(rows, blank, W, K, nbest, spellings, ref_lm, look, alpha, omega, beta, eos, marked=marked,
-                                         Wt=Wt, forced=topology == "forced")
-        assert margin >= MARGIN, (b, margin)
-        out.append(hyps)
-    return out
+    rows = S.utterances(x, lengths)
+    search = lambda b: LA.beam_search(rows[b], blank, W, K, nbest, spellings, ref_lm, look, alpha, omega, beta, eos, marked=marked,
+                                      Wt=Wt, forced=topology == "forced")
+    return [res[0] for res in S.margins_ok(search, len(rows))]
 
 
 def device(topology, x, Wt, blank, W, K, nbest, lex, lm, scores="unigram", alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True,
@@ -142,53 +106,13 @@ def compare(topology, boundary, x, Wt, blank, W, K, nbest, spellings, lm, ref_lm
     nseqs, normed = device(topology, x, Wt, blank, W, K, nbest, lex, lm, scores, alpha, omega, beta, eos, normalize=True,
                            lengths=lengths)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_normaliser(x, Wt, lengths)
-    for b, hyps in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            assert blank not in seqs[b][r] and words_of(spellings, boundary, seqs[b][r]) is not None, (b, r, seqs[b][r])
-            assert lex.words(seqs[b][r]) == words_of(spellings, boundary, seqs[b][r])
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+
+    def whole_words(b, r, seq):  # (and the device's own segmentation agrees)
+        assert words_of(spellings, boundary, seq) is not None, (b, r, seq)
+        assert lex.words(seq) == words_of(spellings, boundary, seq)
+
+    S.assert_ranks(want, seqs, raw, normed, log_normaliser(x, Wt, lengths), nbest, blank, whole_words)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
-
-
-def spelled(seed, B, T, C, blank, sentences, hi=8.0, noise=0.5, run=2):
-    """emissions that spell sentences[b] (a list of spellings) in a way every topology accepts: a blank frame first, every
-    label for one to `run` frames with one blank frame behind it, blanks for what is left of the T frames; +hi on
-    N(0, noise^2).  A sentence that does not fit is cut at a word."""
-    rs = np.random.RandomState(seed)
-    x = (rs.randn(B, T, C) * noise).astype(np.float32)
-    for b in range(B):
-        frames = [blank]
-        for word in sentences[b % len(sentences)]:
-            more = []
-            for c in word:
-                more += [c] * int(rs.randint(1, run + 1)) + [blank]
-            if len(frames) + len(more) > T:
-                break
-            frames += more
-        for t in range(T):
-            x[b, t, frames[t] if t < len(frames) else blank] += hi
-    return x
-
-
-def random_sentences(rs, spellings, count, words):
-    order = sorted(spellings)
-    return [[order[rs.randint(len(order))] for _ in range(words)] for _ in range(count)]
 
 
 def random_lexicon(rs, boundary, C, blank, V, max_len, n_starts):
@@ -477,7 +401,7 @@ def test_ctc_module_and_errors(tmp_path, boundary):
         for r, (seq, s) in enumerate(want[b]):
             if s > NEG:
                 n = s - logz[b]
-                assert abs(float(scores[b, r]) - n) <= 1e-4 * abs(n) + 2e-5
+                assert S.normalised_close(float(scores[b, r]), n)
     assert sum(len(h[0]) > 0 for h in hyps) >= 3
     counter = M.ErrorCounter()
     targets = [rs.randint(0, 5, size=n).tolist() for n in (7, 1, 12, 3)]
@@ -523,7 +447,7 @@ def test_transducer_module_and_errors(tmp_path, boundary, ngram, kw):
         for r, (seq, s) in enumerate(want[b]):
             if s > NEG:
                 n = s - logz[b]
-                assert abs(float(scores[b, r]) - n) <= 1e-4 * abs(n) + 2e-5, (b, r)
+                assert S.normalised_close(float(scores[b, r]), n), (b, r)
                 assert crit.words(lex, hyps[b][r]) == words_of(spellings, boundary, seq)
     assert sum(len(h[0]) > 0 for h in hyps) >= 3
     counter = M.ErrorCounter()

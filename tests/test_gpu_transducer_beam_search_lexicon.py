@@ -24,30 +24,22 @@ import torch
 
 import beam_lexicon_reference as XR
 import beam_lm_reference as LR
+import beam_support as S
 import transducer_beam_lexicon_reference as TX
 import transducer_beam_reference as TR
+from beam_support import emissions, log_normaliser, names_of, transitions
+from beam_support import word_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN = 1e-9
 NEG = TR.NEG
 ALPHA, OMEGA, BETA = 0.8, 0.5, -0.3
 TOPOLOGIES = pytest.mark.parametrize("forced", [False, True], ids=["optional", "forced"])
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import transducer as T
-    from gtn_applications_amd.lexicon import Lexicon
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, T, Lexicon, NGramLM
-
-
-def names_of(V):
-    return [f"w{v}" for v in range(V)]
+    return S.package("engine", "metrics", "criterions.transducer", "lexicon:Lexicon", "lm:NGramLM")
 
 
 def pack(spellings, C, blank):
@@ -56,31 +48,6 @@ def pack(spellings, C, blank):
     by_id = sorted(spellings, key=spellings.get)
     assert [spellings[s] for s in by_id] == list(range(len(by_id)))
     return Lexicon(by_id, C, blank)
-
-
-def make_lms(tmp_path, text, V):
-    """(the device's word LM through the loader, the reference's reading of the same text); (None, None) without text"""
-    if text is None:
-        return None, None
-    NGramLM = _mods()[4]
-    p = tmp_path / "words.arpa"
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), names_of(V), V), LR.ArpaLM(text, names_of(V), V)
-
-
-def log_normaliser(x, Wt):
-    """[B] float64: the normaliser (rule 6) in float64 by torch on the device, independent of the library; a NaN counts
-    as -inf.  With transitions the forward recursion over all frame paths, without them the rows' log-sum-exps."""
-    xd = torch.from_numpy(x).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    if Wt is None:
-        return torch.logsumexp(xd, dim=2).sum(dim=1).cpu().numpy()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    Wd = torch.where(torch.isnan(Wd), torch.full_like(Wd, NEG), Wd)
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
 
 
 def count_words(spellings, seq):
@@ -92,17 +59,13 @@ def reference(x, Wt, blank, forced, W, K, nbest, spellings, ref_lm, alpha=ALPHA,
               on_frame=None):
     """per utterance the reference's hyps; asserts the margins, so that no utterance is left out of a comparison, and --
     `spells`: the emissions spell words -- that a word is found at rank 0 for three quarters of the utterances"""
-    out = []
-    for b in range(x.shape[0]):
-        hook = None if on_frame is None else (lambda *a, b=b: on_frame(b, *a))
-        hyps, margin, _ = TX.beam_search(x[b], Wt, blank, forced, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos,
-                                         on_frame=hook)
-        assert margin >= MARGIN, (b, margin)
-        out.append(hyps)
-    if spells:
-        found = sum(1 for hyps in out if hyps[0][1] > NEG and (count_words(spellings, hyps[0][0]) or 0) >= 1)
-        assert 4 * found >= 3 * len(out), (found, len(out))
-    return out
+
+    def search(b):
+        hook = None if on_frame is None else (lambda *a: on_frame(b, *a))
+        return TX.beam_search(x[b], Wt, blank, forced, W, K, nbest, spellings, ref_lm, alpha, omega, beta, eos, on_frame=hook)
+
+    found = (lambda hyps: (count_words(spellings, hyps[0][0]) or 0) >= 1) if spells else None
+    return [res[0] for res in S.margins_ok(search, x.shape[0], found)]
 
 
 def device(x, Wt, blank, forced, W, K, nbest, lex, lm, alpha=ALPHA, omega=OMEGA, beta=BETA, eos=True, normalize=False):
@@ -124,27 +87,12 @@ def compare(x, Wt, blank, forced, W, K, nbest, spellings, lm, ref_lm, alpha=ALPH
     seqs, raw = device(x, Wt, blank, forced, W, K, nbest, lex, lm, alpha, omega, beta, eos)
     nseqs, normed = device(x, Wt, blank, forced, W, K, nbest, lex, lm, alpha, omega, beta, eos, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_normaliser(x, Wt)
-    for b, hyps in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            assert blank not in seqs[b][r] and count_words(spellings, seqs[b][r]) is not None, (b, r, seqs[b][r])  # (whole words)
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+
+    def whole_words(b, r, seq):
+        assert count_words(spellings, seq) is not None, (b, r, seq)
+
+    S.assert_ranks(want, seqs, raw, normed, log_normaliser(x, Wt), nbest, blank, whole_words)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
 
 
 def tokens_of(C, blank):
@@ -489,7 +437,7 @@ def test_module_against_the_reference_and_the_loss(tmp_path, ngram, kw):
                 assert got == NEG
                 continue
             n = s - logz[b]
-            assert abs(got - n) <= 1e-4 * abs(n) + 2e-5, (b, r, got, n)
+            assert S.normalised_close(got, n), (b, r, got, n)
             assert crit.words(lex, hyps[b][r]) == XR.segment(spellings, seq)[0]
             if seq:
                 loss = _minus_loss(crit, xd, b, seq)

@@ -24,68 +24,35 @@ import pytest
 import torch
 
 import beam_lm_reference as LR
+import beam_support as S
 import transducer_beam_lm_reference as TL
 import transducer_beam_reference as TR
+from beam_support import emissions, log_normaliser, tokens_of, transitions
+from beam_support import spelled_tokens as spelled
+from beam_support import token_lms as make_lms
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN = 1e-9
 NEG = TR.NEG
 ALPHA, BETA = 0.8, 0.5
 TOPOLOGIES = pytest.mark.parametrize("forced", [False, True], ids=["optional", "forced"])
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import transducer as T
-    from gtn_applications_amd.lm import NGramLM
-
-    return E, M, T, NGramLM
-
-
-def tokens_of(C):
-    return [f"t{i}" for i in range(C - 1)]
-
-
-def make_lms(tmp_path, text, C, blank, tokens=None):
-    """(the device's LM through the loader, the reference's reading of the same text)"""
-    NGramLM = _mods()[3]
-    tokens = tokens_of(C) if tokens is None else tokens
-    p = tmp_path / "tokens.arpa"
-    p.write_text(text)
-    return NGramLM.from_arpa(str(p), tokens, blank), LR.ArpaLM(text, tokens, blank)
-
-
-def log_normaliser(x, Wt):
-    """[B] float64: the normaliser (rule 7) in float64 by torch on the device, independent of the library; a NaN counts
-    as -inf.  With transitions the forward recursion over all frame paths, without them the rows' log-sum-exps."""
-    xd = torch.from_numpy(x).cuda().double()
-    xd = torch.where(torch.isnan(xd), torch.full_like(xd, NEG), xd)
-    if Wt is None:
-        return torch.logsumexp(xd, dim=2).sum(dim=1).cpu().numpy()
-    Wd = torch.from_numpy(Wt).cuda().double()
-    Wd = torch.where(torch.isnan(Wd), torch.full_like(Wd, NEG), Wd)
-    alpha = xd[:, 0] + Wd[0]
-    for t in range(1, x.shape[1]):
-        alpha = torch.logsumexp(alpha[:, None, :] + Wd[1:][None], dim=2) + xd[:, t]
-    return torch.logsumexp(alpha, dim=1).cpu().numpy()
+    return S.package("engine", "metrics", "criterions.transducer", "lm:NGramLM")
 
 
 def reference(x, Wt, blank, forced, W, K, nbest, ref_lm, alpha=ALPHA, beta=BETA, eos=True, spells=False, on_frame=None):
     """per utterance the reference's hyps; asserts the margins, so that no utterance is left out of a comparison, and --
     `spells`: the emissions spell token sequences -- that rank 0 is non-empty for three quarters of the utterances"""
-    out = []
-    for b in range(x.shape[0]):
-        hook = None if on_frame is None else (lambda *a, b=b: on_frame(b, *a))
-        hyps, margin, _ = TL.beam_search(x[b], Wt, blank, forced, W, K, nbest, ref_lm, alpha, beta, eos, on_frame=hook)
-        assert margin >= MARGIN, (b, margin)
-        out.append(hyps)
-    if spells:
-        found = sum(1 for hyps in out if hyps[0][1] > NEG and len(hyps[0][0]) >= 1)
-        assert 4 * found >= 3 * len(out), (found, len(out))
-    return out
+
+    def search(b):
+        hook = None if on_frame is None else (lambda *a: on_frame(b, *a))
+        return TL.beam_search(x[b], Wt, blank, forced, W, K, nbest, ref_lm, alpha, beta, eos, on_frame=hook)
+
+    found = (lambda hyps: len(hyps[0][0]) >= 1) if spells else None
+    return [res[0] for res in S.margins_ok(search, x.shape[0], found)]
 
 
 def device(x, Wt, blank, forced, W, K, nbest, lm, alpha=ALPHA, beta=BETA, eos=True, normalize=False):
@@ -104,46 +71,8 @@ def compare(x, Wt, blank, forced, W, K, nbest, lm, ref_lm, alpha=ALPHA, beta=BET
     seqs, raw = device(x, Wt, blank, forced, W, K, nbest, lm, alpha, beta, eos)
     nseqs, normed = device(x, Wt, blank, forced, W, K, nbest, lm, alpha, beta, eos, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_normaliser(x, Wt)
-    for b, hyps in enumerate(want):
-        assert seqs[b] == [h for h, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][1]
-            assert blank not in seqs[b][r], (b, r, seqs[b][r])
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    S.assert_ranks(want, seqs, raw, normed, log_normaliser(x, Wt), nbest, blank)
     return want, seqs, raw
-
-
-def emissions(seed, B, T, C, scale):
-    return (np.random.RandomState(seed).randn(B, T, C) * scale).astype(np.float32)
-
-
-def transitions(seed, C):
-    return (0.5 * np.random.RandomState(seed).randn(C + 1, C)).astype(np.float32)
-
-
-def spelled(seed, B, T, C, blank, hi=8.0, noise=0.5, run=2, letters=None):
-    """emissions that spell a token sequence in a way both topologies accept: a blank frame first, every token (one of
-    the first `letters` classes that are not the blank) for one to `run` frames with one blank frame behind it, blanks
-    for what is left of the T frames; +hi on N(0, noise^2)"""
-    rs = np.random.RandomState(seed)
-    x = (rs.randn(B, T, C) * noise).astype(np.float32)
-    toks = [c for c in range(C) if c != blank][:letters]
-    for b in range(B):
-        frames = [blank]
-        while True:
-            more = [toks[rs.randint(len(toks))]] * int(rs.randint(1, run + 1)) + [blank]
-            if len(frames) + len(more) > T:
-                break
-            frames += more
-        for t in range(T):
-            x[b, t, frames[t] if t < len(frames) else blank] += hi
-    return x
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -311,7 +240,7 @@ def test_the_class_count_of_the_word_piece_recipes(tmp_path, forced):
     for r, (_, s) in enumerate(want[0]):
         if s > NEG:
             n = s - logz[0]
-            assert abs(float(scores[0, r]) - n) <= 1e-4 * abs(n) + 2e-5, (r, float(scores[0, r]), n)
+            assert S.normalised_close(float(scores[0, r]), n), (r, float(scores[0, r]), n)
 
 
 def two_hundred_case(forced):
@@ -656,7 +585,7 @@ def test_module_against_the_reference_and_the_loss(tmp_path, ngram, kw):
                 assert got == NEG
                 continue
             n = s - logz[b]
-            assert abs(got - n) <= 1e-4 * abs(n) + 2e-5, (b, r, got, n)
+            assert S.normalised_close(got, n), (b, r, got, n)
             if seq:
                 loss = _minus_loss(crit, xd, b, seq)
                 bare = got - _lm_terms(ref_lm, seq, ALPHA, BETA, True)
@@ -681,7 +610,7 @@ def test_module_against_the_reference_and_the_loss(tmp_path, ngram, kw):
                     assert got == NEG
                     continue
                 n = s - logz[b]
-                assert abs(got - n) <= 1e-4 * abs(n) + 2e-5, (b, r, got, n)
+                assert S.normalised_close(got, n), (b, r, got, n)
                 if seq:
                     loss = _minus_loss(crit, xd, b, seq)
                     assert got - _lm_terms(ref_lm, seq, ALPHA, BETA, eos) <= loss + 1e-4 * abs(loss) + 2e-5, (b, r, seq, got, loss)

@@ -16,13 +16,14 @@ import numpy as np
 import pytest
 import torch
 
+import beam_support as BS
 import transducer_beam_reference as R
 import transducer_merged_beam_reference as MR
 from test_gpu_transducer_beam_search import _criterion, _minus_loss, _operands, emissions, log_normaliser, transitions
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 1e-9
+MARGIN = BS.MARGIN
 NEG = R.NEG
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AB = [[0], [1], [0, 1]]
@@ -32,11 +33,7 @@ ABC = [[0], [1], [2], [0, 1], [1, 2], [0, 1, 2]]
 
 
 def _mods():
-    from gtn_applications_amd import engine as E
-    from gtn_applications_amd import metrics as M
-    from gtn_applications_amd.criterions import transducer as TR
-
-    return E, M, TR
+    return BS.package("engine", "metrics", "criterions.transducer")
 
 
 def with_blank(spell, blank):
@@ -88,24 +85,12 @@ def compare(x, Wt, blank, forced, spell, W, K, nbest):
     seqs, raw = device(x, Wt, blank, forced, spell, W, K, nbest)
     nseqs, normed = device(x, Wt, blank, forced, spell, W, K, nbest, normalize=True)
     assert nseqs == seqs  # (the shift never changes the search)
-    logz = log_normaliser(x, Wt)
     table = [tuple(s) if s is not None else () for s in spell]
-    for b, w in enumerate(want):
+    for b in range(x.shape[0]):
         live = [MR.spelt(table, s) for s, v in zip(seqs[b], raw[b]) if v > NEG]
         assert len(set(live)) == len(live), (b, seqs[b])  # no two ranks spell the same graphemes
-        assert all(blank not in s for s in seqs[b])
-        if w is None:
-            continue
-        hyps = w[0]
-        assert seqs[b] == [rho for rho, _, _ in hyps], (b, seqs[b], hyps)
-        for r in range(nbest):
-            s = hyps[r][2]
-            if s == NEG:
-                assert raw[b, r] == NEG and normed[b, r] == NEG, (b, r)
-                continue
-            n = s - logz[b]
-            assert abs(raw[b, r] - s) <= 1e-9 * max(1.0, abs(s)), (b, r, raw[b, r], s)
-            assert abs(normed[b, r] - n) <= 1e-4 * abs(n) + 2e-5, (b, r, normed[b, r], n)
+    pairs = [None if w is None else [(rho, s) for rho, _, s in w[0]] for w in want]  # (None: left out, but for the blank)
+    BS.assert_ranks(pairs, seqs, raw, normed, log_normaliser(x, Wt), nbest, blank)
     return want
 
 
@@ -309,7 +294,7 @@ def test_module_score_is_minus_the_loss_of_the_spelling_where_nothing_is_pruned(
                 assert got == NEG
                 continue
             n = s - logz[b]
-            assert abs(got - n) <= 1e-4 * abs(n) + 2e-5, (T, b, r, got, n)
+            assert BS.normalised_close(got, n), (T, b, r, got, n)
             if S:
                 loss = _minus_loss(crit, xd, b, S)
                 assert abs(got - loss) <= 1e-4 * abs(loss) + 2e-5, (T, b, r, S, got, loss)

@@ -9,12 +9,9 @@ v, the blank is V) or None.
 beam_search() reports what a comparison needs to know, as the other references do: the smallest selection margin --
 kept against first dropped entry in every frame, and between consecutive ranks after the final drop and </s> up to the
 first one not returned -- and the number of merged extensions."""
-import math
-
-from beam_lexicon_reference import proper_prefixes, segment
+from beam_lexicon_reference import lexicon_rules, segment
 from beam_lm_reference import EOS
-from beam_reference import NEG, candidates, clean, lae
-from transducer_beam_reference import weight
+from beam_reference import NEG, search
 
 
 def beam_search(x, Wt, blank, forced, W, K, nbest, lexicon, lm, alpha, omega, beta, score_eos, logz=None, on_frame=None):
@@ -24,94 +21,8 @@ def beam_search(x, Wt, blank, forced, W, K, nbest, lexicon, lm, alpha, omega, be
     on_frame(t, beam, cand, extension, merged, entries): called in every frame with the ranked beam [(prefix, pb, pnb,
     part, history)], the candidates, the extension function, the merged flags and the sorted live entries -- for a test
     that has to know a situation occurred."""
-    inside = proper_prefixes(lexicon)
-    beam = [((), 0.0, NEG, (), lm.start if lm else None)]  # (prefix, pb, pnb, tokens since the last word, LM history)
-    margin, merges = math.inf, 0
-    for t, raw in enumerate(x):
-        row = clean(raw)
-        cand = candidates(row, blank, K)
-        pos = {c: p for p, (c, _) in enumerate(cand)}
-        brow = None if t == 0 else blank  # the state behind pb: the start in frame 0, the blank from frame 1 on
-        n = len(beam)
-        no_extension = forced and t == 0
-
-        def extension(i, c):
-            """rule 2: (e, tokens since the last word, next history) of i + c; e = -inf: it does not exist"""
-            pre, pb, pnb, part, hist = beam[i]
-            if no_extension:
-                return NEG, None, None
-            m = pb + weight(Wt, brow, c)
-            if not forced and pre and pre[-1] != c:
-                m = lae(m, pnb + weight(Wt, pre[-1], c))
-            ac = row[c] + m
-            if ac == NEG:
-                return NEG, None, None
-            part = part + (c,)
-            if part in lexicon:  # the token completes a word
-                l, nxt = lm.step(hist, lexicon[part]) if lm else (0.0, None)
-                if l == NEG:
-                    return NEG, None, None
-                return ac + ((alpha * l + omega) + beta), (), nxt
-            if part in inside:
-                return ac + beta, part, hist
-            return NEG, None, None
-
-        # rule 3: the stays add no term and keep node and state
-        spb, spnb = [NEG] * n, [NEG] * n
-        for i, (pre, pb, pnb, _, _) in enumerate(beam):
-            m = pb + weight(Wt, brow, blank)
-            if pre:
-                m = lae(m, pnb + weight(Wt, pre[-1], blank))
-            spb[i] = row[blank] + m
-            if pre and pre[-1] in pos:
-                spnb[i] = (row[pre[-1]] + pnb) + weight(Wt, pre[-1], pre[-1])
-        merged = [[False] * len(cand) for _ in range(n)]
-        if not no_extension:
-            for j, pj in enumerate(h[0] for h in beam):
-                if not pj or pj[-1] not in pos:
-                    continue
-                for i, pi in enumerate(h[0] for h in beam):
-                    if len(pi) + 1 == len(pj) and pi == pj[:-1]:
-                        spnb[j] = lae(spnb[j], extension(i, pj[-1])[0])
-                        merged[i][pos[pj[-1]]] = True
-                        merges += 1
-                        break
-        entries = [(lae(spb[i], spnb[i]), i, beam[i][0], spb[i], spnb[i], beam[i][3], beam[i][4]) for i in range(n)]
-        if not no_extension:
-            for i in range(n):
-                for p, (c, _) in enumerate(cand):
-                    if c != blank and not merged[i][p]:
-                        e, part, nxt = extension(i, c)
-                        entries.append((e, n + i * len(cand) + p, beam[i][0] + (c,), NEG, e, part, nxt))
-        entries = [e for e in entries if e[0] > NEG]
-        entries.sort(key=lambda e: (-e[0], e[1]))
-        if on_frame is not None:
-            on_frame(t, beam, cand, extension, merged, entries)
-        if len(entries) > W:
-            margin = min(margin, entries[W - 1][0] - entries[W][0])
-        beam = [e[2:] for e in entries[:W]]
-        if not beam:
-            break
-    # rule 5: a rank inside a word is dropped, the topology's score, </s>, the ranks again
-    final = []
-    for r, (pre, pb, pnb, part, hist) in enumerate(beam):
-        if part:
-            continue
-        s = pb if forced else lae(pb, pnb)
-        if s == NEG:
-            continue
-        if score_eos and lm:
-            l, _ = lm.step(hist, EOS)
-            if l == NEG:
-                continue
-            s += alpha * l
-        final.append((s, r, pre))
-    final.sort(key=lambda e: (-e[0], e[1]))
-    for r in range(min(nbest, len(final) - 1)):
-        margin = min(margin, final[r][0] - final[r + 1][0])
-    hyps = [(pre, s - logz if logz is not None else s) for s, _, pre in final[:nbest]]
-    hyps += [((), NEG)] * (nbest - len(hyps))
-    return hyps, margin, merges
+    rules = lexicon_rules(lexicon, lm, alpha, omega, beta, score_eos)
+    return search(x, blank, W, K, nbest, *rules, Wt=Wt, forced=forced, logz=logz, on_frame=on_frame)
 
 
 def brute_force(x, Wt, blank, forced, lexicon, lm, alpha, omega, beta, score_eos):
