@@ -150,31 +150,6 @@ def max_classes():
 _EARLY_GRAD = os.environ.get("WFL_ASG_EARLY_GRAD", "1") != "0"  # (0: the gradient kernels in backward -- A/B, tests)
 
 
-class _EarlyGrads:
-    """The gradients the forward launches wrote for grad_output = 1, until backward claims them."""
-
-    __slots__ = ("dx", "dW", "inputs", "transitions", "taken")
-
-    def __init__(self, dx, dW, inputs, transitions):
-        self.dx, self.dW, self.inputs, self.transitions, self.taken = dx, dW, inputs, transitions, False
-
-    def fresh(self):
-        return not self.taken
-
-    def claim(self):
-        self.taken = True
-        dx, dW, self.dx, self.dW = self.dx, self.dW, None, None
-        return dx, dW
-
-    def take(self):
-        """E.EagerLoss.backward: the buffers become the leaves' .grad"""
-        if self.taken or not all(E.takes_grad(t, g) for t, g in ((self.inputs, self.dx), (self.transitions, self.dW))
-                                 if g is not None):
-            return None
-        dx, dW = self.claim()
-        return [(t, g) for t, g in ((self.inputs, dx), (self.transitions, dW)) if g is not None]
-
-
 class PackedNumerator:
     """A numerator lattice packed elsewhere, in the place of ASGLoss's `targets`: acceptors whose learnable arc weights
     index `transitions` row-major, with the loss factors (scale, +scale/B, -scale/B) that travel with them.  What the
@@ -242,6 +217,27 @@ class ASGLossFunction(torch.autograd.Function):
     @staticmethod
     @E.on_input_device
     def forward(ctx, inputs, transitions, targets, reduction="none"):
+        loss, step = Step.forward(inputs, transitions, targets, reduction)
+        ctx.aux = step
+        E.hold_early(ctx, step.early, step.early is not None)
+        return loss
+
+    @staticmethod
+    @E.on_input_device
+    def backward(ctx, grad_output):
+        E.check_not_released(ctx)
+        return (*ctx.aux.backward(grad_output, ctx.needs_input_grad[0], ctx.needs_input_grad[1]), None, None)
+
+
+class Step:
+    """One ASG step without an autograd node of its own -- what ASGLossFunction wraps, and what the Transducer's bigram
+    route runs inside its node (criterions/transducer.py::_BigramAsAsg): forward() launches and returns the loss with
+    the state backward() needs."""
+
+    __slots__ = ("x", "W", "fcc", "cpos", "dx_num", "dw_num", "fork", "devices", "early")
+
+    @classmethod
+    def forward(cls, inputs, transitions, targets, reduction):
         B, T, C = inputs.shape
         if reduction not in ("none", "mean"):  # asg.py:120-121
             raise ValueError("invalid value for reduction '" + str(reduction) + "'")
@@ -250,8 +246,9 @@ class ASGLossFunction(torch.autograd.Function):
         if T == 0:
             raise ValueError("ASGLoss: empty emissions (T == 0)")
         dev = E.require_gpu()
-        x = E.as_device_f32(inputs.detach(), dev)
-        W = E.as_device_f32(transitions.detach(), dev)
+        self = cls()
+        x = self.x = E.as_device_f32(inputs.detach(), dev)
+        W = self.W = E.as_device_f32(transitions.detach(), dev)
         if isinstance(targets, PackedNumerator):
             if targets.B != B:
                 raise ValueError(f"got {targets.B} targets for a batch of {B}")
@@ -274,51 +271,39 @@ class ASGLossFunction(torch.autograd.Function):
         # `early`: the denominator's gradient right behind its sweeps as well, for grad_output = 1 (with the numerator's
         # as its addend): between the forward and the backward kernels of a step the GPU otherwise waits ~30 us for the
         # host to come back through the autograd engine.  `loss.backward()` takes the two buffers as they are
-        # (E.EagerLoss); should the engine run this node after all, backward scales them by grad_output.  Plain leaf
-        # tensors (the reference's asg_benchmark.py:19-31 protocol on device tensors) get them as .grad; a model's
-        # output, an nn.Parameter (the ASG module, anything under DistributedDataParallel) get them as the root
-        # gradients of an engine pass that starts at those tensors (E.EagerLoss.backward).
+        # (E.EagerLoss.backward has who gets them how); should the engine run the node after all, backward scales
+        # them by grad_output.
         early = need_grad and _EARLY_GRAD and all(E.may_hand_over(t) and t.device == x.device
                                                   for t in (inputs, transitions) if t.requires_grad)
         fork = E.side_stream(dev)
         pack.order_behind_upload(fork.side)  # (a cached pack uploaded on a third stream)
         phases = E.phase_events("asg", _PHASES)  # (None: no launch group of this step is timed)
-        loss, da, db, dz, ws, dx_num, dw_num, dx, dW = N.ops.asg_forward(
+        loss, da, db, dz, ws, self.dx_num, self.dw_num, dx, dW = N.ops.asg_forward(
             x, W, ctypes.addressof(pack.desc), pack.ints, pack.floats, scale, cpos, cneg, need_dx, need_dw, early,
             fork.side.cuda_stream, phases or [])
-        fcc = E.DenseState()
+        fcc = self.fcc = E.DenseState()
         fcc.B, fcc.T, fcc.C, fcc.alpha, fcc.beta, fcc.logz, fcc.ws = B, T, C, da, db, dz, ws
-        ctx.aux = (x, W, fcc, cpos, dx_num, dw_num, fork if need_grad else None)
-        ctx.devices = (inputs.device, transitions.device)
-        ctx.early = None
-        if early:
-            ctx.early = _EarlyGrads(dx, dW, inputs, transitions)
-            ctx.eager_take = ctx.early.take
-            E.watch_node_hooks(ctx)
-        return loss if inputs.is_cuda else loss.cpu()
+        self.cpos, self.fork = cpos, fork if need_grad else None
+        self.devices = (inputs.device, transitions.device)
+        self.early = E.EarlyGrads((inputs, transitions), (dx, dW)) if early else None
+        return (loss if inputs.is_cuda else loss.cpu()), self
 
-    @staticmethod
-    @E.on_input_device
-    def backward(ctx, grad_output):
-        E.check_not_released(ctx)
-        if ctx.early is not None and ctx.early.fresh():
-            # the buffers of the forward launches, scaled in place (wfl_scale returns at once when grad_output is 1); a
-            # second pass over a retained graph finds them used and recomputes below
-            dx, dW = ctx.early.claim()
-            gout = E.as_device_f32(grad_output.detach().reshape(1), (dx if dx is not None else dW).device)
-            dx = E.scale_inplace(dx, gout) if dx is not None and ctx.needs_input_grad[0] else None
-            dW = E.scale_inplace(dW, gout) if dW is not None and ctx.needs_input_grad[1] else None
-            return E.on_device_of(dx, ctx.devices[0]), E.on_device_of(dW, ctx.devices[1]), None, None
-        x, W, fcc, cpos, dx_num, dw_num, fork = ctx.aux
-        gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] and dx_num is not None else None
-        dW = torch.empty_like(W) if ctx.needs_input_grad[1] and dw_num is not None else None
-        if dx is not None or dW is not None:
-            fork.join(dx_num, dw_num)
-            # + posteriors of the fully connected graph, - posteriors of the force-aligned one (asg.py:158-168)
-            E.dense_grad(x, W, fcc, cpos, coef_w=cpos, gout=gout, dx=dx, accumulate=False, dW=dW,
-                         addend=dx_num if dx is not None else None, dW_addend=dw_num if dW is not None else None)
-        return E.on_device_of(dx, ctx.devices[0]), E.on_device_of(dW, ctx.devices[1]), None, None
+    def backward(self, grad_output, need_dx, need_dw):
+        """-> (dx, dW) on the operands' devices, None for one not needed: the buffers of the forward launches, scaled
+        in place; a second pass over a retained graph finds them used and recomputes"""
+        grads = self.early.claim(grad_output, (need_dx, need_dw)) if self.early is not None else None
+        if grads is None:
+            x, W, cpos, dx_num, dw_num = self.x, self.W, self.cpos, self.dx_num, self.dw_num
+            gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
+            dx = torch.empty_like(x) if need_dx and dx_num is not None else None
+            dW = torch.empty_like(W) if need_dw and dw_num is not None else None
+            if dx is not None or dW is not None:
+                self.fork.join(dx_num, dw_num)
+                # + posteriors of the fully connected graph, - posteriors of the force-aligned one (asg.py:158-168)
+                E.dense_grad(x, W, self.fcc, cpos, coef_w=cpos, gout=gout, dx=dx, accumulate=False, dW=dW,
+                             addend=dx_num if dx is not None else None, dW_addend=dw_num if dW is not None else None)
+            grads = dx, dW
+        return E.on_device_of(grads[0], self.devices[0]), E.on_device_of(grads[1], self.devices[1])
 
 
 def ASGLoss(*args):

@@ -6,6 +6,7 @@ on host threads (ctc.py:38-65), this sends the whole batch through the CTC fast-
 (csrc/ctc_kernels.hip; up to four target positions per lane) -- or, for targets longer than 255
 labels, through the generic lattice engine (csrc/lattice_kernels.hip).  Both are HIP paths; there is no CPU path.
 """
+import collections
 import operator
 import os
 
@@ -66,6 +67,11 @@ class BlankLabelUnderLengths(ValueError):
         self.targets = targets
 
 
+# ctx.aux of CTCLossFunction, per route.  "pipelined": one launch for loss and gradient (ctx.early holds that); "fast": the
+# chains alone, no gradient asked; "lattice": the lattice engine, st its LatticeState.  coef: the gradient's factors
+_Saved = collections.namedtuple("_Saved", "kind x coef tg blank lse st", defaults=(None,) * 4)
+
+
 class CTCLossFunction(torch.autograd.Function):
     """`input_lengths` (padded batches; an addition to the reference's call): utterance b has the frames [0, T_b), the
     frames behind them are read as certain-blank frames -- 0 for the blank, -inf for every other class -- which are the
@@ -123,7 +129,7 @@ class CTCLossFunction(torch.autograd.Function):
             # section 16): CTCLoss and the CTC module catch this and give such labels a column of their own -- with
             # the staged targets at hand, whose labels were checked against the caller's C just above
             raise BlankLabelUnderLengths(tg)
-        need_grad = log_probs.requires_grad
+        need_grad, early = log_probs.requires_grad, None
         xlen = ctx.xlen = ctx.launch_xlen = None
         if lens is not None:
             xlen = ctx.xlen = E.input_lengths_on_device(lens, dev)
@@ -148,14 +154,15 @@ class CTCLossFunction(torch.autograd.Function):
                                                 lse=lse, shared_ws=True, xlen=ctx.launch_xlen)
             if xlen is not None:  # (the eager gradient: zeroed here, on the launch's stream, before anything can hand it out)
                 E.zero_pad_rows(dx, xlen)
-            ctx.aux = ("pipelined", x, tg, int(blank_idx), dx, coef, lse)
+            ctx.aux = _Saved("pipelined", x, coef, tg, int(blank_idx), lse)
+            early = E.EarlyGrads((log_probs,), (dx,))  # (for backward; not offered: the loss stays a plain tensor)
         elif ctx_log_softmax(ctx):
             raise RuntimeError("fused log_softmax CTC is only used on the pipelined path")
         elif E.ctc_fast_path_ok(tg.max_len, C):
             scale, _, coef = E.loss_factors(tg, reduction)
             ws, nll = E.ctc_forward(x, tg, int(blank_idx))
             loss = E.reduce_loss(nll, scale, 1.0)
-            ctx.aux = ("fast", x, tg, int(blank_idx), None, nll, coef)
+            ctx.aux = _Saved("fast", x, coef, tg, int(blank_idx))
         else:
             pack = tg.cache.get(("ctc_lattice", int(blank_idx), C))
             if pack is None:
@@ -164,34 +171,31 @@ class CTCLossFunction(torch.autograd.Function):
             scale, _, coef = E.loss_factors(tg, reduction)
             st = E.lattice_forward(x, pack, need_beta=need_grad)
             loss = E.reduce_loss(st.logz, scale, -1.0)
-            ctx.aux = ("lattice", x, st, coef)
+            ctx.aux = _Saved("lattice", x, coef, st=st)
+        E.hold_early(ctx, early, False)
         ctx.in_device, ctx.in_dtype = log_probs.device, log_probs.dtype
         return loss if log_probs.is_cuda else loss.cpu()
 
     @staticmethod
     @E.on_input_device
     def backward(ctx, grad_output):
-        kind, x, *_ = ctx.aux
-        gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
-        if kind == "pipelined":
-            _, _, tg, blank, dx, coef, lse = ctx.aux
-            if dx is None:
-                # a second backward through a retained graph: the eager gradient was handed out (and scaled in
-                # place) by the first one, so run the same launch again -- with the same row log-sum-exps when
-                # the log_softmax is fused -- into a fresh buffer, the upstream scalar applied by the kernel
-                dx = torch.empty_like(x)
-                E.ctc_forward_backward(x, tg, blank, coef, gout, dx, lse=lse, shared_ws=True, xlen=ctx.launch_xlen)
-                if ctx.xlen is not None:
-                    E.zero_pad_rows(dx, ctx.xlen)
-            else:
-                E.scale_inplace(dx, gout)
-                ctx.aux = ("pipelined", x, tg, blank, None, coef, lse)
-        elif kind == "fast":
+        sv = ctx.aux
+        if sv.kind == "fast":
             raise RuntimeError("CTCLoss: backward through an input that did not require grad in forward")
+        early = ctx.early.claim(grad_output) if ctx.early is not None else None  # (the eager gradient, scaled in place)
+        if early is not None:
+            dx = early[0]
         else:
-            dx = torch.empty_like(x)
-            _, _, st, coef = ctx.aux
-            E.lattice_grad(st, coef, gout=gout, dx=dx)
+            dx = torch.empty_like(sv.x)
+            gout = E.as_device_f32(grad_output.detach().reshape(1), sv.x.device)
+            if sv.kind == "pipelined":
+                # a second backward through a retained graph: the eager gradient was handed out by the first one, so
+                # run the same launch again -- with the same row log-sum-exps when the log_softmax is fused -- into a
+                # fresh buffer, the upstream scalar applied by the kernel
+                E.ctc_forward_backward(sv.x, sv.tg, sv.blank, sv.coef, gout, dx, lse=sv.lse, shared_ws=True,
+                                       xlen=ctx.launch_xlen)
+            else:
+                E.lattice_grad(sv.st, sv.coef, gout=gout, dx=dx)
             if ctx.xlen is not None:
                 E.zero_pad_rows(dx, ctx.xlen)
         if ctx.in_device.type != "cuda":

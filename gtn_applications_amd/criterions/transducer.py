@@ -799,22 +799,9 @@ def _bigram_route(inputs, targets, tokens, lexicon, transition_params, numerator
     return _BigramAsAsg.apply(inputs, transition_params, _asg.PackedNumerator(pack, scale, cpos, cneg, B))
 
 
-class _InnerCtx:
-    """What ASGLossFunction's forward / backward keep on their autograd context, for a caller that runs them inside a
-    node of its own (_BigramAsAsg): plain attributes, and the two hook registrars E.watch_node_hooks looks for."""
-
-    needs_input_grad = (True, True, False, False)
-
-    def register_hook(self, fn):
-        return None
-
-    def register_prehook(self, fn):
-        return None
-
-
 class _BigramAsAsg(torch.autograd.Function):
     """_bigram_route's step as ONE autograd node: the operands of the ASG step from (emissions, transition_params) --
-    three small torch ops -- ASGLossFunction's forward on them (csrc/torch_ops.cpp::asg_forward), and in backward its
+    three small torch ops -- the ASG step on them (asg.Step: csrc/torch_ops.cpp::asg_forward), and in backward its
     two gradients mapped back to the caller's tensors.  (Spelled with differentiable torch ops around ASGLoss the step
     carried eight more autograd nodes: ~0.1 ms of host time where the step is host-bound.)"""
 
@@ -827,24 +814,20 @@ class _BigramAsAsg(torch.autograd.Function):
         dev = E.require_gpu()
         xd, Wd = _bigram_dense_operands(E.as_device_f32(inputs.detach(), dev),
                                         E.as_device_f32(transition_params.detach(), dev).reshape(-1), C)
-        # (what ASGLossFunction.forward asks its operands: which gradients the step will be asked for -- the end arcs'
-        # gradient is the last frame's rows of the emission gradient, so the parameters alone ask for that one too)
+        # (requires_grad tells the step which gradients it will be asked for -- the end arcs' gradient is the last frame's
+        # rows of the emission gradient, so the parameters alone ask for that too; its early gradients are not offered)
         xd.requires_grad_(inputs.requires_grad or transition_params.requires_grad)
         Wd.requires_grad_(transition_params.requires_grad)
         ctx.bigram = (C, inputs.device, transition_params.device, transition_params.shape)
-        ctx.inner = _InnerCtx()
-        loss = _asg.ASGLossFunction.forward(ctx.inner, xd, Wd, packed, "none")
+        loss, ctx.step = _asg.Step.forward(xd, Wd, packed, "none")
         return loss if inputs.is_cuda else loss.cpu()
 
     @staticmethod
     @E.on_input_device
     def backward(ctx, grad_output):
-        from . import asg as _asg
-
         C, in_dev, par_dev, par_shape = ctx.bigram
         need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        ctx.inner.needs_input_grad = (need_x or need_p, need_p, False, False)
-        dxd, dWd, _, _ = _asg.ASGLossFunction.backward(ctx.inner, grad_output)
+        dxd, dWd = ctx.step.backward(grad_output, need_x or need_p, need_p)
         dp = None
         if need_p:
             # the end arcs' scores rode on the last frame's emissions: their gradient is that frame's rows, summed
@@ -911,13 +894,10 @@ class TransducerLossFunction(torch.autograd.Function):
             num.xg, num.alpha, num.beta, num.logz = xg, al, be, lz
             num.x, num.row_lse = (x if log_softmax else None), lse
             ctx.aux = _Saved(x, None, num, None, cpos, cneg)
-            ctx.early = None
             ctx.devices = (inputs.device, None)
-            if in_launch:
-                ctx.early = _EarlyGrad(dx_early, num, cneg, inputs)
-                ctx.eager_take = ctx.early.take if E.may_hand_over(inputs) else None
-                if ctx.eager_take is not None:
-                    E.watch_node_hooks(ctx)
+            early = E.EarlyGrads((inputs,), (dx_early,), lambda gout, bufs: E.lattice_grad_rest(
+                num, cneg, gout, bufs[0])) if in_launch else None
+            E.hold_early(ctx, early, in_launch and E.may_hand_over(inputs))
             return loss if inputs.is_cuda else loss.cpu()
         # normaliser: forward_score(emissions o transitions), transducer.py:286-288, independent of the numerator sweep:
         # forked onto a second stream so that the two overlap
@@ -927,7 +907,7 @@ class TransducerLossFunction(torch.autograd.Function):
         fork.join(den.xg, den.alpha, den.beta, den.logz)
         loss = E.reduce_loss(den.logz, scale, 1.0, minus=num.logz)
         ctx.aux = _Saved(x, params, num, den, cpos, cneg)
-        ctx.early = None
+        E.hold_early(ctx, None, False)
         ctx.devices = (inputs.device, transition_params.device)
         return loss if inputs.is_cuda else loss.cpu()
 
@@ -935,15 +915,11 @@ class TransducerLossFunction(torch.autograd.Function):
     @E.on_input_device
     def backward(ctx, grad_output):
         E.check_not_released(ctx)
-        if ctx.early is not None and ctx.early.dx is not None:
-            # the launch of the sweeps wrote the gradient for grad_output = 1: scaled in place (wfl_scale returns at once
-            # when grad_output is 1), then the rows of the utterances that launch did not serve.  A second pass over a
-            # retained graph finds the buffer gone and recomputes below.
-            dx, ctx.early.dx = ctx.early.dx, None
-            gout = E.as_device_f32(grad_output.detach().reshape(1), dx.device)
-            E.scale_inplace(dx, gout)
-            E.lattice_grad_rest(ctx.early.num, ctx.early.cneg, gout, dx)
-            return E.on_device_of(dx, ctx.devices[0]), None, None, None, None, None, None
+        # the launch of the sweeps wrote the gradient for grad_output = 1: scaled in place, then the rows of the utterances
+        # that launch did not serve.  A second pass over a retained graph finds the buffer gone and recomputes below.
+        early = ctx.early.claim(grad_output) if ctx.early is not None else None
+        if early is not None:
+            return E.on_device_of(early[0], ctx.devices[0]), None, None, None, None, None, None
         x, params, num, den, cpos, cneg = ctx.aux
         gout = E.as_device_f32(grad_output.detach().reshape(1), x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -965,24 +941,6 @@ class _FusedLogSoftmaxTransducerLoss(TransducerLossFunction):
                 reduction="none"):
         return TransducerLossFunction._forward(ctx, True, inputs, targets, tokens, lexicon, transition_params,
                                                transitions, reduction)
-
-
-class _EarlyGrad:
-    """The emission gradient the sweeps' launch wrote for grad_output = 1, until backward claims it."""
-
-    __slots__ = ("dx", "num", "cneg", "inputs")
-
-    def __init__(self, dx, num, cneg, inputs):
-        self.dx, self.num, self.cneg, self.inputs = dx, num, cneg, inputs
-
-    def take(self):
-        """E.EagerLoss.backward: the buffer only lacks the rows of the utterances the launch did not serve."""
-        if self.dx is None or not E.takes_grad(self.inputs, self.dx):
-            return None
-        dx, self.dx = self.dx, None
-        with torch.cuda.device(dx.device):
-            E.lattice_grad_rest(self.num, self.cneg, None, dx)
-        return [(self.inputs, dx)]
 
 
 _IN_LAUNCH_GRAD = os.environ.get("WFL_TRANSDUCER_IN_LAUNCH_GRAD", "1") != "0"  # (0: gradient in backward -- A/B, tests)

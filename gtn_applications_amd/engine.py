@@ -9,6 +9,7 @@ import numbers
 import operator
 import sys
 import threading
+import weakref
 from collections import OrderedDict, namedtuple
 
 import numpy as np
@@ -563,12 +564,63 @@ class EagerLoss(torch.Tensor):
         return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs=inputs)
 
 
-def watch_node_hooks(ctx):
-    """forward() of a criterion that offers `eager_take`: remember (ctx._wfl_hooked) whether somebody registers a hook on
-    the autograd node -- the engine runs those, EagerLoss.backward does not, so it must stand back.  The node offers no
-    way to ask afterwards; the wrappers hold the node weakly (no cycle that would keep the forward's buffers alive)."""
-    import weakref
+class EarlyGrads:
+    """The gradients the forward launches of a step wrote for grad_output = 1, until ONE backward claims them: the
+    criterion's node under the autograd engine (claim) or EagerLoss.backward (take).  tensors: whose gradients; buffers:
+    theirs, None where there is none; rest(gout, buffers): completes them behind the scaling (lattice_grad_rest)."""
 
+    __slots__ = ("tensors", "buffers", "rest")
+
+    def __init__(self, tensors, buffers, rest=None):
+        self.tensors, self.buffers, self.rest = tensors, buffers, rest
+
+    @property
+    def dx(self):  # (the emission gradient's buffer, None once taken)
+        return None if self.buffers is None else self.buffers[0]
+
+    def claim(self, gout, want=None):
+        """-> the buffers, scaled in place by grad_output `gout` (None: it is 1, no launch; wfl_scale returns at once when
+        it is) and completed by `rest`.  want: a flag per buffer, None comes back for one not wanted, unscaled.  The
+        first call takes them; every later one returns None: recompute."""
+        bufs, self.buffers = self.buffers, None
+        if bufs is None:
+            return None
+        if want is not None:
+            bufs = tuple(b if w else None for b, w in zip(bufs, want))
+        if gout is not None:
+            live = [b for b in bufs if b is not None]
+            gout = as_device_f32(gout.detach().reshape(1), live[0].device)
+            for b in live:
+                scale_inplace(b, gout)
+        if self.rest is not None:
+            self.rest(gout, bufs)
+        return bufs
+
+    def take(self):
+        """EagerLoss.backward: -> [(tensor, grad), ...] with the buffers as they are; None if they are taken, or if a
+        tensor cannot be handed its buffer (takes_grad) -- they stay claimable then."""
+        if self.buffers is None:
+            return None
+        pairs = [(t, g) for t, g in zip(self.tensors, self.buffers) if g is not None]
+        if not all(takes_grad(t, g) for t, g in pairs):
+            return None
+        if self.rest is None:
+            self.claim(None)
+        else:  # (it launches: on the buffers' device)
+            with torch.cuda.device(pairs[0][1].device):
+                self.claim(None)
+        return pairs
+
+
+def hold_early(ctx, early, offer):
+    """forward() of a criterion: `early` (an EarlyGrads or None) on the autograd node, for backward to claim.  offer:
+    EagerLoss.backward may take it too (ctx.eager_take) -- unless somebody registers a hook on the node, remembered as
+    ctx._wfl_hooked: the engine runs those, EagerLoss.backward does not, so it must stand back.  The node offers no
+    way to ask afterwards; the wrappers hold the node weakly (no cycle that would keep the forward's buffers alive)."""
+    ctx.early = early
+    if not offer:
+        return
+    ctx.eager_take = early.take
     ref = weakref.ref(ctx)
     ctx._wfl_hooked = False
     for name in ("register_hook", "register_prehook"):

@@ -295,6 +295,92 @@ def test_dense_ngram_routes_equal_the_general_path(ngram, kind):
         crit.transition_params.requires_grad_(True)
 
 
+_BIGRAM_FORMS = {}
+
+
+def _bigram_forms_case(kind):
+    """(criterion, emissions, targets, (dx, dparams) of the general path) at the shape of
+    test_dense_ngram_routes_equal_the_general_path with the bigram model; computed once per kind, never written to"""
+    from gtn_applications_amd.criterions import transducer as TR
+
+    if kind not in _BIGRAM_FORMS:
+        torch.manual_seed(3)
+        N, T, L, B = 23, 60, 9, 5
+        kw = dict(blank="optional", allow_repeats=False) if kind == "ctc" else {}
+        crit = TR.Transducer([(i,) for i in range(N)], {i: i for i in range(N)}, ngram=2, reduction="mean", **kw).cuda()
+        with torch.no_grad():
+            crit.transition_params.normal_(0, 0.5)
+        x0 = torch.randn(B, T, N + (1 if kind == "ctc" else 0)).cuda()
+        targets = [torch.randint(N, (L,)) for _ in range(B)]
+        x = x0.clone().requires_grad_(True)
+        crit.tokens.arc_sort(True)
+        TR.TransducerLossFunction.apply(x, targets, crit.tokens, crit.lexicon, crit.transition_params, crit.transitions,
+                                        crit.reduction).backward()
+        want = x.grad.cpu(), crit.transition_params.grad.cpu().clone()
+        crit.transition_params.grad = None
+        _BIGRAM_FORMS[kind] = crit, x0, targets, want
+    return _BIGRAM_FORMS[kind]
+
+
+@pytest.mark.parametrize("early", [True, False])
+@pytest.mark.parametrize("kind", ["ctc", "asg"])
+def test_bigram_route_call_forms(kind, early, monkeypatch):
+    """criterions/transducer.py::_BigramAsAsg beyond one backward() with grad_output = 1: the ASG step inside its node
+    (criterions/asg.py::Step) scales the gradients its forward launches wrote (early) or computes them in backward (not
+    early) -- under a grad_output of 0.75, over a retained graph twice (the second pass recomputes, and equals the
+    first), and with only the emissions or only the parameters requiring grad.  Against the general lattice path at the
+    tolerances of test_dense_ngram_routes_equal_the_general_path, atol times the factor of the expected gradient."""
+    from gtn_applications_amd.criterions import asg
+
+    crit, x0, targets, (dx0, dp0) = _bigram_forms_case(kind)
+    monkeypatch.setattr(asg, "_EARLY_GRAD", early)
+
+    def close_dx(got, mult, msg):
+        torch.testing.assert_close(got.cpu(), mult * dx0, rtol=1e-4, atol=mult * 2e-6, msg=lambda m: f"{msg} dx: {m}")
+
+    def close_dp(got, mult, msg):
+        torch.testing.assert_close(got.cpu(), mult * dp0, rtol=1e-4, atol=mult * 2e-5, msg=lambda m: f"{msg} dparams: {m}")
+
+    try:
+        # grad_output = 0.75, for both gradients and for either alone (the bigram's end arcs take theirs from the
+        # emission gradient's last frame, so the parameters alone ask the step for that one too)
+        for need_x, need_p in ((True, True), (False, True), (True, False)):
+            msg = f"scaled x={need_x} p={need_p}"
+            x = x0.clone().requires_grad_(need_x)
+            crit.transition_params.requires_grad_(need_p)
+            crit.transition_params.grad = None
+            loss = crit(x, targets)
+            assert type(loss) is torch.Tensor  # (the route offers nothing to an eager backward)
+            (loss * 0.75).backward()
+            if need_x:
+                close_dx(x.grad, 0.75, msg)
+            else:
+                assert x.grad is None
+            if need_p:
+                close_dp(crit.transition_params.grad, 0.75, msg)
+            else:
+                assert crit.transition_params.grad is None
+        # twice over a retained graph: .grad holds the sum, the second pass equals the first
+        x = x0.clone().requires_grad_(True)
+        crit.transition_params.requires_grad_(True)
+        crit.transition_params.grad = None
+        loss = crit(x, targets)
+        loss.backward(retain_graph=True)
+        dx1, dp1 = x.grad.clone(), crit.transition_params.grad.clone()
+        close_dx(dx1, 1.0, "first pass")
+        close_dp(dp1, 1.0, "first pass")
+        loss.backward()
+        close_dx(x.grad, 2.0, "both passes")
+        close_dp(crit.transition_params.grad, 2.0, "both passes")
+        close_dx(x.grad - dx1, 1.0, "second pass")
+        close_dp(crit.transition_params.grad - dp1, 1.0, "second pass")
+        torch.testing.assert_close(x.grad - dx1, dx1, rtol=1e-4, atol=2e-6)
+        torch.testing.assert_close(crit.transition_params.grad - dp1, dp1, rtol=1e-4, atol=2e-5)
+    finally:
+        crit.transition_params.requires_grad_(True)
+        crit.transition_params.grad = None
+
+
 @pytest.mark.parametrize("ngram", [1, 2])
 def test_dense_ngram_routes_on_degenerate_batches(ngram):
     """The short cuts of TransducerLoss (unigram / bigram) on the shapes the general path also has to get right: one
