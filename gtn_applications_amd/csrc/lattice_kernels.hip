@@ -3749,6 +3749,7 @@ static int stream_mode(const wfl_lattice_desc& d) {
 // where the streamed area starts in the alpha buffer (float units, behind the tuned layout; 16-byte aligned)
 static int64_t stream_area_off(const wfl_lattice_desc& d, int T) { return (ab_tail(d, T).total_floats() + 3) & ~(int64_t)3; }
 static std::atomic<uint64_t> g_streamed_launches{0};  // wfl_lattice_diagnostics out[8]
+static std::atomic<uint64_t> g_streamed_global{0};    // out[9]: sweep launches with the state vectors in global memory
 
 int wfl_lattice_workspace(const wfl_lattice_desc* d, int T, int64_t* xg_elems, int64_t* ab_elems) {
   if (!d || T < 0) {
@@ -3799,6 +3800,7 @@ static int lattice_forward_streamed(const wfl_lattice_desc* d, const int32_t* in
   if (rc) return rc;
   WFL_LAUNCH_CHECK();
   g_streamed_launches.fetch_add(1);
+  if (mode == 2) g_streamed_global.fetch_add(1);
   return WFL_OK;
 }
 
@@ -4403,7 +4405,7 @@ int wfl_lattice_diagnostics(uint64_t* out, int n) {
   }
   LiveState& ls = live_state();
   std::lock_guard<std::mutex> lock(ls.mu);
-  const uint64_t v[9] = {ls.attempts,
+  const uint64_t v[10] = {ls.attempts,
                          ls.host ? (uint64_t) * (volatile uint32_t*)&ls.host[0] : 0,
                          ls.host ? (uint64_t) * (volatile uint32_t*)&ls.host[1] : 0,
                          ls.skipped,
@@ -4411,8 +4413,9 @@ int wfl_lattice_diagnostics(uint64_t* out, int n) {
                          ls.env_serial ? 1u : 0u,
                          (uint64_t)ls.max_spins,
                          ls.fork ? 1u : 0u,
-                         g_streamed_launches.load()};
-  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
+                          g_streamed_launches.load(),
+                          g_streamed_global.load()};
+  for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
   return WFL_OK;
 }
 

@@ -290,7 +290,11 @@ int wfl_lattice_forward_grad(const wfl_lattice_desc* d, const int32_t* ints, con
  *          of arcs, states and emission rows) are swept with their arcs streamed from L2 -- decided from the
  *          descriptor's maxima, the same way by every call (and by wfl_lattice_workspace, which then asks for room
  *          for the streamed arc copies behind the alpha layout); WFL_LATTICE_STREAMED=1 / 2 forces that path (tests).
- * The device counters behind out[1..2] are read without synchronisation: they lag the stream. n <= 9 words. */
+ *   out[9] of the sweep launches in out[8], those whose state vectors lived in global memory (the alpha / beta arrays
+ *          themselves: 2 * max_states doubles did not fit LDS beside the emission rows, or WFL_LATTICE_STREAMED=2);
+ *          the others kept them in LDS.  The gradient of either is the same launch and is not counted here.
+ * The device counters behind out[1..2] are read without synchronisation: they lag the stream. n <= 10 words; a caller
+ * that asks for fewer gets the first n. */
 int wfl_lattice_diagnostics(uint64_t* out, int n);
 int wfl_lattice_grad_rest(const wfl_lattice_desc* d, const int32_t* ints, const float* floats,
                           const float* xg, int T, int C, const float* weights, const float* alpha,
