@@ -233,6 +233,8 @@ _SIGS = {
     "wfl_asg_beam_search_lexicon": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                             POINTER(Lexicon), POINTER(NgramLm), c_double, c_double, c_double, c_int, _P, _P,
                                             c_int64, _P, _P, _P]),
+    "wfl_asg_beam_search_lm": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       POINTER(NgramLm), c_double, c_double, c_int, _P, _P, c_int64, _P, _P, _P]),
     # device: Transducer prefix beam search
     "wfl_transducer_beam_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_transducer_beam_search": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,

@@ -8,6 +8,7 @@ transitions tensor is the graph.
 """
 import ctypes
 import itertools
+import numbers
 import os
 
 import torch
@@ -367,12 +368,26 @@ class ASG(torch.nn.Module):
         return collapse_and_unpack(paths, self.garbage_idx, self.num_replabels)
 
     def _beam_plan(self, outputs, what, beam_size, classes_per_frame, nbest, lexicon=None, lm=None, lm_weight=1.0,
-                   length_bonus=0.0, lm_eos=True, word_bonus=0.0):
+                   length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None, token_lm=None):
         """The arguments of a beam search, checked before anything needs a device: the E.AsgBeamPlan of the options, with
-        a lexicon the E.AsgLexiconBeamPlan; without one every keyword of the lexicon search must be at its default"""
+        a lexicon the E.AsgLexiconBeamPlan; with a token_lm the E.AsgLmBeamPlan, whose scalars lm_weight, length_bonus
+        and lm_eos then are; with neither every keyword of the two must be at its default"""
         E.check_beam_outputs(outputs, what)
         if outputs.shape[2] != self.N:
             raise ValueError(f"{what}: outputs have {outputs.shape[2]} classes, the criterion has {self.N}")
+        if token_lm is not None:
+            if lexicon is not None:
+                raise NotImplementedError(
+                    f"{what}: token_lm together with a lexicon -- a token-level LM and a word LM over the same hypothesis "
+                    "are two LM states and two terms per extension: a search of its own; give one of them")
+            if lm is not None:
+                raise ValueError(f"{what}: lm is the word LM of a lexicon; with token_lm there is none")
+            if lookahead is not None:
+                raise ValueError(f"{what}: lookahead needs a lexicon and its word lm, not a token_lm")
+            if isinstance(word_bonus, bool) or not isinstance(word_bonus, numbers.Real) or float(word_bonus) != 0.0:
+                raise ValueError(f"{what}: word_bonus needs a lexicon, got {word_bonus!r}")
+            return E.AsgLmBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, self.garbage_idx, self.num_replabels,
+                                           token_lm, lm_weight, length_bonus, lm_eos, what)
         if lexicon is None:
             E.refuse_without_lexicon(what, lm, lm_weight, length_bonus, lm_eos, word_bonus, "an ASG")
             return E.AsgBeamPlan.checked(self.N, beam_size, classes_per_frame, nbest, what)
@@ -425,6 +440,19 @@ class ASG(torch.nn.Module):
             return Lexicon(spellings, self.N, self.garbage_idx, words=words)
         return Lexicon(spellings, self.N + 1, self.N, words=words)
 
+    def token_lm(self, path, tokens, bos="<s>", eos="</s>", unk="<unk>"):
+        """The lm.NGramLM of an ARPA file over the model's tokens for beam_search(token_lm=):
+        NGramLM.from_arpa(path, tokens, blank=len(tokens)).  tokens: the model's num_classes tokens in class order, as
+        the ARPA file names them (token i is raw class i + num_replabels, and LM label i); the LM is built around a
+        phantom blank num_classes that is never a label.  The LM never sees a replabel or the garbage: it reads what
+        beam_search returns."""
+        tokens = list(tokens)
+        if len(tokens) != self.num_classes:
+            raise ValueError(f"ASG.token_lm: {len(tokens)} tokens for a criterion of {self.num_classes} classes")
+        from ..lm import NGramLM
+
+        return NGramLM.from_arpa(path, tokens, blank=len(tokens), bos=bos, eos=eos, unk=unk)
+
     def words(self, lexicon, labels):
         """The word ids of a label sequence that beam_search(lexicon=) returned (mapped: garbage dropped, replabels
         unpacked): lexicon.words of the sequence packed again.  No word ends in a token a word starts with (lexicon()
@@ -440,7 +468,7 @@ class ASG(torch.nn.Module):
 
     @E.on_input_device
     def beam_search(self, outputs, beam_size=16, classes_per_frame=None, nbest=1, return_scores=False, lexicon=None, lm=None,
-                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
+                    lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None, token_lm=None):
         """ASG prefix beam search (an addition: the reference has viterbi() only).  viterbi() gives the best frame path
         under emissions + transitions; the criterion scores a label sequence by the sum over all its alignments (the
         force-align numerator, asg.py:72-115), and this returns the sequences it rates highest (DESIGN.md section 21 has
@@ -466,10 +494,24 @@ class ASG(torch.nn.Module):
         tokens but does not walk the trie.  Without a lexicon the call is what it was, and lm, lm_weight, length_bonus,
         lm_eos and word_bonus must be at their defaults (ValueError).  B == 0 or T == 0 with a lexicon: the empty
         sequence, scored by the LM's </s> alone.  lookahead (CTC's and the Transducer's): anything
-        but None raises NotImplementedError, as a start-marked lexicon does."""
-        _refuse_lookahead("ASG.beam_search", lookahead)
+        but None raises NotImplementedError, as a start-marked lexicon does.
+
+        token_lm (an addition): an lm.NGramLM over the model's tokens (self.token_lm(path, tokens)
+        reads one from an ARPA file; num_classes == self.num_classes + 1, blank == self.num_classes) -- lexicon-free
+        decoding with a letter n-gram, shallow fusion inside the beam.  The LM reads exactly what this call returns: a
+        token steps it once, a replabel k right behind a token steps it by that token k + 1 more times, the garbage and
+        a replabel with nothing to repeat not at all.  lm_weight, length_bonus and lm_eos are then its scalars, as in
+        CTC.beam_search(lm=): every LM step adds lm_weight * step(s, token) + length_bonus, lm_eos adds lm_weight *
+        step(s, </s>) after the last frame; the scores include these terms.  The search and the n-best list are still
+        over raw sequences: raw `a, garbage, a` and raw `a, replabel 0` return the same tokens, carry the same LM term
+        and are two hypotheses, each with the mass of its own alignments, so an n-best list may name an output twice.
+        `lm` remains the word LM of a lexicon: lm=, word_bonus or lookahead beside a token_lm raise ValueError, a
+        token_lm with a lexicon NotImplementedError.  B == 0 or T == 0 with a token_lm: the empty sequence, scored by
+        the LM's </s> alone.  Without token_lm the call is what it was."""
+        if token_lm is None:
+            _refuse_lookahead("ASG.beam_search", lookahead)
         plan = self._beam_plan(outputs, "ASG.beam_search", beam_size, classes_per_frame, nbest, lexicon, lm, lm_weight,
-                               length_bonus, lm_eos, word_bonus)
+                               length_bonus, lm_eos, word_bonus, lookahead, token_lm)
         if outputs.shape[0] == 0 or outputs.shape[1] == 0:
             hyps, scores = plan.no_frames(outputs.shape[0])
         else:
@@ -482,15 +524,19 @@ class ASG(torch.nn.Module):
 
     @E.on_input_device
     def errors(self, outputs, targets, counter, *, beam_size=None, classes_per_frame=None, lexicon=None, lm=None,
-               lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None):
+               lm_weight=1.0, length_bonus=0.0, lm_eos=True, word_bonus=0.0, lookahead=None, token_lm=None):
         """compute_edit_distance(self.viterbi(outputs), targets, preprocessor) (train.py:74-87, 278-284) as
         (tokens_dist, words_dist, n_tokens, n_words), with `counter` a metrics.ErrorCounter: where viterbi() decodes on
         the device the count runs behind the same decode and the predictions never reach the host.  `beam_size` (an
         addition): the predictions are beam_search(outputs, beam_size, classes_per_frame)'s instead, counted behind the
         beam launches on their device buffers; `classes_per_frame` needs a beam_size.  lexicon, lm, lm_weight,
         length_bonus, lm_eos, word_bonus: beam_search's, with a beam_size: the predictions are those of the search with
-        a lexicon.  lookahead: refused, as by beam_search."""
-        _refuse_lookahead("ASG.errors", lookahead)
+        a lexicon.  lookahead: refused, as by beam_search.  token_lm: beam_search's, with a beam_size: the predictions
+        are those of the search with a token-level LM."""
+        if token_lm is None:
+            _refuse_lookahead("ASG.errors", lookahead)
+        elif beam_size is None:
+            raise ValueError("ASG.errors: token_lm needs a beam_size")
         if beam_size is None:
             if classes_per_frame is not None:
                 raise ValueError("ASG.errors: classes_per_frame needs a beam_size")
@@ -499,7 +545,7 @@ class ASG(torch.nn.Module):
             E.refuse_without_lexicon("ASG.errors", lm, lm_weight, length_bonus, lm_eos, word_bonus, "an ASG")
         else:
             plan = self._beam_plan(outputs, "ASG.errors", beam_size, classes_per_frame, 1, lexicon, lm, lm_weight,
-                                   length_bonus, lm_eos, word_bonus)
+                                   length_bonus, lm_eos, word_bonus, lookahead, token_lm)
             counter.check_hypothesis_labels(self.num_classes, "ASG.errors")
             if outputs.shape[0] == 0 or outputs.shape[1] == 0:
                 return counter([h[0] for h in plan.no_frames(outputs.shape[0])[0]], targets)

@@ -57,7 +57,12 @@
 // (DESIGN.md section 28): a pack BeamTokLm holds a BeamTok and a BeamLm -- the Transducer's two masses and transition
 // gathers per entry, the LM's state per hypothesis, one back-off lookup per extension behind the same skip test, and
 // the forced topology's drop-and-rank-by-pb ahead of </s> in the final block.
-// All fifteen issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
+// wfl_asg_beam_search_lm is the ASG search with that token-level LM and length bonus: a pack BeamAsgLm
+// holds a BeamAsg, a BeamLm over the criterion's tokens and the raw alphabet (replabels, garbage) the LM reads through --
+// the LM reads what the mapped write launch emits: a token steps it once, a replabel right behind a token steps it by
+// that token again (k + 1 times), the garbage and any other replabel step it not at all; a hypothesis carries the
+// token a replabel would repeat beside its LM state.
+// All sixteen issue these launches through one host path, beam_run (behind the kernels): an entry makes the checks that are
 // its own, describes the call in a BeamCall and hands over its pack, by which beam_run picks the beam kernel.
 // No atomics on global memory and no cross-workgroup waits; the one LDS counter only decides where an entry sits in the
 // compact list, never its rank: the result is deterministic.
@@ -489,6 +494,65 @@ inline double beam_tok_lm_bound(double alpha, double step_min, double step_max, 
   return fmax(t0, t1) + beta;
 }
 
+// the ASG launch with a token-level LM (wfl_asg_beam_search_lm): BeamAsg's transitions, BeamLm's
+// acceptor over the N = C - replabels - (garbage >= 0) tokens (lm.eos = N + 1), and the raw alphabet the LM reads
+// through: replabel k is raw class k < replabels, token i is raw class i + replabels, `garbage` the garbage class (-1:
+// none).  lm.bound: the largest term of an extension (beam_asg_lm_bound).
+struct BeamAsgLm {
+  BeamAsg asg;
+  BeamLm lm;
+  int replabels;
+  int garbage;
+};
+__device__ __forceinline__ const BeamAsgLm& beam_asg_lm_of(const BeamAsgLm& a) { return a; }
+__device__ __forceinline__ const BeamAsg& beam_asg_of(const BeamAsgLm& a) { return a.asg; }
+__device__ __forceinline__ const BeamLm& beam_lm_of(const BeamAsgLm& a) { return a.lm; }
+// rep': the token a replabel right behind the prefix + c would repeat (-1: none), from the prefix' own `rep` -- the
+// write launch's rule (beam_map_walk, read forwards): the garbage is not seen, a token is the next to repeat, a
+// replabel uses the token up
+__device__ __forceinline__ int beam_asg_lm_rep(const BeamAsgLm& a, int rep, int c) {
+  if (c == a.garbage) return rep;
+  return c >= a.replabels ? c - a.replabels : -1;
+}
+// The LM term of the extension by raw class c of a hypothesis with LM state `state` and `rep` (section 29 rules 1 and
+// 2): the labels c emits -- none for the garbage and for a replabel with nothing to repeat, the token c - R once, the
+// token `rep` c + 1 times for a replabel behind it -- stepped in order, term = term + (alpha l + beta) per label, each
+// operation rounded on its own (as where beam_asg_lm_bound forms the largest such sum); -inf where a step is: the
+// extension does not exist.  next: the state behind the labels (`state` where nothing is emitted).  At most max(1, R)
+// lookups; the loop is bounded by R.
+__device__ __forceinline__ double beam_asg_lm_term(const BeamAsgLm& a, int state, int rep, int c, int& next) {
+#pragma clang fp contract(off)
+  next = state;
+  if (c == a.garbage) return 0.0;
+  const bool token = c >= a.replabels;
+  if (!token && rep < 0) return 0.0;
+  const int u = token ? c - a.replabels : rep, n = token ? 1 : c + 1;
+  double term = 0.0;
+  for (int q = n; q > 0 && term > -__builtin_inf(); --q) {  // (n <= max(1, R): a replabel is a class below R)
+    int nx;
+    const double l = beam_lm_step(a.lm, next, u, nx);
+    const double al = a.lm.alpha * l;
+    const double t = al + a.lm.beta;
+    term = l > -__builtin_inf() ? term + t : -__builtin_inf();
+    next = nx;
+  }
+  return term;
+}
+// the largest such term: n = 0 .. max(1, R) accumulations of max(alpha step_min, alpha step_max) + beta, by the same
+// rounded operations -- every partial sum of a term is below the partial sum here by their monotonicity (0 * inf: no bound)
+inline double beam_asg_lm_bound(double alpha, double step_min, double step_max, double beta, int R) {
+#pragma clang fp contract(off)
+  const double t0 = alpha * step_min, t1 = alpha * step_max;
+  if (t0 != t0 || t1 != t1) return __builtin_inf();
+  const double m = fmax(t0, t1) + beta;
+  double acc = 0.0, bound = 0.0;
+  for (int n = 0; n < (R > 1 ? R : 1); ++n) {
+    acc = acc + m;
+    bound = fmax(bound, acc);
+  }
+  return bound;
+}
+
 // the Transducer launch with a lexicon (wfl_transducer_beam_search_lexicon): BeamTok's transitions
 // and topology, BeamLex's trie over token sequences, word LM and bonuses
 struct BeamTokLex {
@@ -606,6 +670,11 @@ template <>
 struct BeamPack<BeamAsgLex> {
   static constexpr bool lm = false, lex = true, asg = true, tok = false, spell = false;
 };
+// (asg and lm: ASG's single mass and transition gather, the LM's state arrays and </s> ranking, and `rep` per hypothesis)
+template <>
+struct BeamPack<BeamAsgLm> {
+  static constexpr bool lm = true, lex = false, asg = true, tok = false, spell = false;
+};
 template <>
 struct BeamPack<BeamTok> {
   static constexpr bool lm = false, lex = false, asg = false, tok = true, spell = false;
@@ -688,7 +757,10 @@ struct BeamPack<BeamSpell> {
 // search with the terms of word-LM look-ahead (section 27) -- beam_lex_ext's overload and the pending word's settled step;
 // or one BeamTokLm: the search of wfl_transducer_beam_search_lm -- BeamTok's arithmetic with
 // BeamLm's state per hypothesis, LM term per extension (the merged one inside a stay included) behind the skip test, and
-// </s> on top of the topology's score in the final ranking.
+// </s> on top of the topology's score in the final ranking; or one BeamAsgLm: the search of wfl_asg_beam_search_lm
+//  -- BeamAsg's arithmetic with BeamLm's state and `rep` per hypothesis, beam_asg_lm_term per
+// extension (the merged one inside a stay and the one that stands in for a missing stay in the bound included) behind
+// the skip test, and the LM search's </s> ranking.
 template <int NT, typename... Lm>
 __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restrict__ lengths, int T, int blank, int W, int K,
                                                            int nbest, int normalize, const int32_t* __restrict__ cand_cls,
@@ -737,6 +809,13 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
   }
   // merging by spelling only: the token count of every hypothesis (len counts graphemes there), and per frame the
   // member mask of every hypothesis' spelling class
+  // ASG with a token-level LM only: the token a replabel behind every hypothesis would repeat (double-buffered like
+  // the beam); an entry's own follows from its parent's and its class in place(): nothing is kept per entry
+  int(*hrep)[kBeamMax] = nullptr;
+  if constexpr (ASG && LM) {
+    __shared__ int s_hrep[2][kBeamMax];
+    hrep = s_hrep;
+  }
   int(*ntok)[kBeamMax] = nullptr;
   unsigned long long* cmask = nullptr;
   if constexpr (SPELL) {
@@ -759,6 +838,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     beam[0].pb[0] = 0.0, beam[0].pnb[0] = ninf, beam[0].tot[0] = 0.0;
     beam[0].hash[0] = 0ull, beam[0].hash2[0] = 0ull, beam[0].last[0] = -1, beam[0].len[0] = 0, beam[0].node[0] = -1;
     if constexpr (LM) lmst[0][0] = beam_lm_of(lm_arg...).start;
+    if constexpr (ASG && LM) hrep[0][0] = -1;
     if constexpr (LEX) lmst[0][0] = beam_lex_of(lm_arg...).has_lm ? beam_lex_of(lm_arg...).lm.start : 0, tnode[0][0] = 0;
     if constexpr (SPELL) ntok[0][0] = 0;
   }
@@ -853,7 +933,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
       if (tid < nbeam) {
         const BeamAsg& a = beam_asg_of(lm_arg...);
         const int p = lpos[tid], l = h.last[tid], i = par[tid];
-        double m = p >= 0 ? (sc[p] + beam_asg_w(a, l, l)) + h.tot[tid] : ninf;
+        double m = ninf;
+        if constexpr (LEX || !LM) m = p >= 0 ? (sc[p] + beam_asg_w(a, l, l)) + h.tot[tid] : ninf;
         long long rk;
         if constexpr (LEX) {
           // With a lexicon one extension per hypothesis is looked up here: the one merged into this stay (p >= 0, i >= 0),
@@ -882,6 +963,30 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
             if (term > ninf) e = ac + term;
           }
           if (p >= 0) m = beam_lae(m, e);
+          rk = beam_key(p >= 0 ? m : e);
+          spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = beam_key(m);
+        } else if constexpr (LM) {
+          // (ahead of the plain branch below.)  With a token-level LM one extension per hypothesis gets its term here: the
+          // one merged into this stay (p >= 0, i >= 0), which carries the term of the prefix it makes (state and rep:
+          // functions of it), or -- where there is no stay (p < 0, and then i < 0) -- the first own extension, which
+          // stands in for the bound below with its real term, lookups included: it may serve only if it EXISTS; where
+          // a step is -inf the hypothesis contributes kKeyDropped and the frame's bound prunes nothing.
+          const BeamAsgLm& al = beam_asg_lm_of(lm_arg...);
+          int src = i, c = l, q = p;
+          if (p < 0) {
+            const unsigned long long own = ~mmask[tid];
+            q = own ? __ffsll(own) - 1 : ncand;
+            if (q < ncand) src = tid, c = cls[q];
+          }
+          double e = ninf;
+          if (src >= 0) {
+            const double ac = (sc[q] + beam_asg_w(a, h.last[src], c)) + h.tot[src];
+            int nx;
+            const double term = ac > ninf ? beam_asg_lm_term(al, lmst[cur][src], hrep[cur][src], c, nx) : ninf;
+            if (term > ninf) e = ac + term;
+          }
+          // (the stay's own term behind the lookup: nothing of it is live across the LM's loops)
+          if (p >= 0) m = beam_lae((sc[p] + beam_asg_w(a, l, l)) + h.tot[tid], e);
           rk = beam_key(p >= 0 ? m : e);
           spb[tid] = ninf, spnb[tid] = m, stot[tid] = m, skey[tid] = beam_key(m);
         } else {
@@ -1024,6 +1129,23 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
             }
           }
           enext[idx] = enc;
+        } else if constexpr (ASG && LM) {
+          // ASG's extension (one mass, the transition gathered here) with the token-level LM's term (section 29): what
+          // c emits through the raw alphabet stepped from i's state; (ahead of the LM and ASG branches, which each take
+          // the other for unset.)  The skip test is the LM search's with the largest term of up to max(1, R) steps; an
+          // extension that emits nothing has term 0 <= that bound and is not looked up either way.
+          const BeamAsgLm& al = beam_asg_lm_of(lm_arg...);
+          const int l = h.last[i];
+          int nx = lmst[cur][i];
+          if (c == l)
+            k = kKeyDropped;  // (i's stay, not an extension)
+          else {
+            const double ac = (sc[p] + beam_asg_w(al.asg, l, c)) + h.tot[i];
+            const bool reach = ac > ninf && beam_key(ac + al.lm.bound) >= tau;
+            const double term = reach ? beam_asg_lm_term(al, lmst[cur][i], hrep[cur][i], c, nx) : ninf;
+            k = term > ninf ? beam_key(ac + term) : kKeyDropped;
+          }
+          enext[idx] = nx;
         } else if constexpr (TOK && LEX) {
           // the Transducer's extension (section 22 rule 4: both masses, the transitions gathered here; none in the forced
           // topology's frame 0) with the lexicon's term and skip test; (ahead of the LEX and TOK branches, which each
@@ -1105,6 +1227,7 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         g.pb[r] = spb[idx], g.pnb[r] = spnb[idx], g.tot[r] = stot[idx];
         g.hash[r] = h.hash[idx], g.hash2[r] = h.hash2[idx], g.last[r] = h.last[idx], g.len[r] = h.len[idx], g.node[r] = h.node[idx];
         if constexpr (LM) lmst[cur ^ 1][r] = lmst[cur][idx];
+        if constexpr (ASG && LM) hrep[cur ^ 1][r] = hrep[cur][idx];
         if constexpr (LEX) lmst[cur ^ 1][r] = lmst[cur][idx], tnode[cur ^ 1][r] = tnode[cur][idx];
         if constexpr (SPELL) ntok[cur ^ 1][r] = ntok[cur][idx];
       } else if constexpr (SPELL) {
@@ -1140,6 +1263,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
         const int i = (idx - kBeamMax) / kBeamCand, p = (idx - kBeamMax) - i * kBeamCand;
         const int c = cls[p];
         double e;
+        if constexpr (ASG && LM)  // (ahead of the LM branch: the parent's rep and c give the entry's)
+          hrep[cur ^ 1][r] = beam_asg_lm_rep(beam_asg_lm_of(lm_arg...), hrep[cur][i], c);
         if constexpr (LM)
           e = beam_key_total(k), lmst[cur ^ 1][r] = enext[idx];  // (the total with its LM term: the key holds it)
         else if constexpr (LEX) {
@@ -1257,6 +1382,8 @@ __global__ void __launch_bounds__(NT) beam_search_kernel(const int32_t* __restri
     // order, at the place (and with the token sequence) of the first of them whose score is finite.
     // The Transducer with a lexicon (section 25 rule 5): the lexicon's drop of a rank inside a word, the topology's
     // score, </s> on top of it.  The Transducer with a token-level LM (section 28): the topology's score, </s> on top.
+    // ASG with a token-level LM (section 29): the LM search's branch as it stands -- the one mass in tot, </s> = N + 1
+    // from the pack's BeamLm, then logz where the call normalises.
     if constexpr (SPELL) {
       if (tid < nbeam) spb[tid] = beam_tok_of(lm_arg...).forced ? f.pb[tid] : f.tot[tid];  // (spb: free behind the frames)
       __syncthreads();
@@ -2394,6 +2521,44 @@ int wfl_asg_beam_search_lexicon(const float* x, const float* Wt, const float* lo
   BeamAsgLex d;
   if (const int rc = beam_lex_pack(what, lex, nullptr, word_lm, lm_weight, word_bonus, length_bonus, score_eos, &d.lex)) return rc;
   d.asg = BeamAsg{Wt, logz, C};
+  d.garbage = garbage;
+  return beam_run(what, c, d);
+}
+
+// The ASG search with a token-level n-gram LM: wfl_asg_beam_search's call and checks, the raw
+// alphabet the LM reads through (garbage, replabels), then wfl_ctc_beam_search_lm's checks of the LM and the two scalars.
+int wfl_asg_beam_search_lm(const float* x, const float* Wt, const float* logz, int B, int T, int C, int beam, int classes_per_frame,
+                           int nbest, int drop, int num_replabels, int garbage, int replabels, const wfl_ngram_lm* lm,
+                           double lm_weight, double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                           int64_t* out_offsets, double* scores, void* stream) {
+  const char* what = "asg_beam_search_lm";
+  if (!Wt) {
+    set_error("%s: a NULL pointer", what);
+    return WFL_ERR_INVALID;
+  }
+  const BeamCall c{x, nullptr, B, T, C, -1, beam, classes_per_frame, nbest, logz ? 1 : 0, ws, out, out_capacity, out_offsets,
+                   scores, stream, false, true, drop, num_replabels};
+  // (beam_run makes this check again: this entry's own come behind it and ahead of the room in `out`)
+  if (const int rc = beam_call_check(what, c)) return rc;
+  if (garbage < -1 || garbage >= C) {
+    set_error("%s: garbage %d is outside [-1, %d)", what, garbage, C);
+    return WFL_ERR_INVALID;
+  }
+  const int64_t tokens = (int64_t)C - replabels - (garbage >= 0 ? 1 : 0);
+  if (replabels < 0 || tokens < 1) {
+    set_error("%s: replabels %d is negative or, with garbage %d, leaves no token among %d classes", what, replabels, garbage, C);
+    return WFL_ERR_INVALID;
+  }
+  BeamAsgLm d;
+  // token i is LM label i, the LM's unused blank is N and </s> is N + 1
+  if (const int rc = beam_lm_terms(what, lm, false, (int)tokens + 1, lm_weight, length_bonus, score_eos, &d.lm)) return rc;
+  if (!(fabs(lm_weight) < __builtin_inf()) || !(fabs(length_bonus) < __builtin_inf())) {
+    set_error("%s: lm_weight %g and length_bonus %g must be finite", what, lm_weight, length_bonus);
+    return WFL_ERR_INVALID;
+  }
+  d.lm.bound = beam_asg_lm_bound(lm_weight, lm->step_min, lm->step_max, length_bonus, replabels);
+  d.asg = BeamAsg{Wt, logz, C};
+  d.replabels = replabels;
   d.garbage = garbage;
   return beam_run(what, c, d);
 }

@@ -1059,8 +1059,9 @@ const char* const kBeamNames[3][7] = {WFL_BEAM_NAMES("ctc_beam_search"), WFL_BEA
                                       WFL_BEAM_NAMES("transducer_beam_search")};
 // The options of one bound beam search, whichever criterion's it is: what the module's four plan classes (below)
 // construct and every beam op takes.  blank: -1 for ASG, which has none; forced: the Transducer's topology; garbage:
-// ASG's with a lexicon (-1: none).  lm none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not
-// read; lexicon: lm is its word LM; lookahead none: the lexicon search as it was.
+// ASG's with a lexicon or a token-level LM (-1: none); replabels: the raw alphabet's, ASG's with a token-level LM.  lm
+// none: lm_weight, score_eos and -- without a lexicon -- length_bonus are not read; lexicon: lm is its word LM;
+// lookahead none: the lexicon search as it was.
 struct BeamOptions {
   BeamFamily family;
   int blank;
@@ -1071,13 +1072,14 @@ struct BeamOptions {
   std::shared_ptr<DeviceLookahead> lookahead;
   double lm_weight, word_bonus, length_bonus;
   bool score_eos;
+  int replabels;
   BeamOptions(BeamFamily family_, int blank_, bool forced_, int beam_, int K_, int nbest_, int garbage_ = -1,
               const std::shared_ptr<DeviceLm>& lm_ = nullptr, const std::shared_ptr<DeviceLexicon>& lexicon_ = nullptr,
               const std::shared_ptr<DeviceLookahead>& lookahead_ = nullptr, double lm_weight_ = 1.0, double word_bonus_ = 0.0,
-              double length_bonus_ = 0.0, bool score_eos_ = true)
+              double length_bonus_ = 0.0, bool score_eos_ = true, int replabels_ = 0)
       : family(family_), blank(blank_), forced(forced_), beam(beam_), K(K_), nbest(nbest_), garbage(garbage_), lm(lm_),
         lexicon(lexicon_), lookahead(lookahead_), lm_weight(lm_weight_), word_bonus(word_bonus_), length_bonus(length_bonus_),
-        score_eos(score_eos_) {
+        score_eos(score_eos_), replabels(replabels_) {
     const char* what = kBeamNames[family][kBeamLexicon];
     TORCH_CHECK(family != kBeamAsg || !lexicon || !lexicon->is_marked, what, ": a start-marked lexicon is not for ASG");
     TORCH_CHECK(!lm || !lexicon || lm->ints.device() == lexicon->ints.device(), what,
@@ -1086,7 +1088,7 @@ struct BeamOptions {
   }
 };
 
-// The four plan classes of the module, each the constructor of a BeamOptions by the keywords of its engine.*.on_device
+// The five plan classes of the module, each the constructor of a BeamOptions by the keywords of its engine.*.on_device
 struct BeamPlan : BeamOptions {  // CTC's: an lm, a lexicon and its look-ahead are all optional
   BeamPlan(int blank_, int beam_, int K_, int nbest_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
            double length_bonus_, bool score_eos_, const std::shared_ptr<DeviceLexicon>& lexicon_, double word_bonus_,
@@ -1101,6 +1103,14 @@ struct AsgLexiconPlan : BeamOptions {
       : BeamOptions(kBeamAsg, -1, false, beam_, K_, nbest_, garbage_, lm_, lexicon_, nullptr, lm_weight_, word_bonus_,
                     length_bonus_, score_eos_) {
     TORCH_CHECK(lexicon, "asg_beam_search_lexicon: a lexicon is needed");
+  }
+};
+struct AsgLmPlan : BeamOptions {
+  AsgLmPlan(int beam_, int K_, int nbest_, int garbage_, int replabels_, const std::shared_ptr<DeviceLm>& lm_, double lm_weight_,
+            double length_bonus_, bool score_eos_)
+      : BeamOptions(kBeamAsg, -1, false, beam_, K_, nbest_, garbage_, lm_, nullptr, nullptr, lm_weight_, 0.0, length_bonus_,
+                    score_eos_, replabels_) {
+    TORCH_CHECK(lm, "asg_beam_search_lm: a language model is needed");
   }
 };
 struct TransducerLexiconPlan : BeamOptions {
@@ -1195,6 +1205,7 @@ Hypotheses beam_source(const at::Tensor& x, const c10::optional<at::Tensor>& len
             } else if (asg) {
               rc = o.lexicon ? asg_call(wfl_asg_beam_search_lexicon, o.garbage, &o.lexicon->lex, lm, o.lm_weight, o.word_bonus,
                                         o.length_bonus, eos)
+                   : o.lm    ? asg_call(wfl_asg_beam_search_lm, o.garbage, o.replabels, lm, o.lm_weight, o.length_bonus, eos)
                              : asg_call(wfl_asg_beam_search);
             } else {
               rc = o.lexicon ? lexicon_call(transducer_call, wfl_transducer_beam_search_lexicon,
@@ -1437,6 +1448,15 @@ at::Tensor asg_beam_search_lexicon_errors(const at::Tensor& x, const at::Tensor&
   return beam_errors(x, c10::nullopt, Wt, plan, ref, tables, drop, num_replabels);
 }
 
+py::tuple asg_beam_search_lm(const at::Tensor& x, const at::Tensor& Wt, const c10::optional<at::Tensor>& logz, const AsgLmPlan& plan,
+                             int64_t drop, int64_t num_replabels) {
+  return beam_results(beam_source(x, c10::nullopt, Wt, logz, plan, plan.nbest, false, drop, num_replabels));
+}
+at::Tensor asg_beam_search_lm_errors(const at::Tensor& x, const at::Tensor& Wt, const AsgLmPlan& plan, int64_t drop,
+                                     int64_t num_replabels, const std::shared_ptr<StagedTargets>& ref, const ErrorTables& tables) {
+  return beam_errors(x, c10::nullopt, Wt, plan, ref, tables, drop, num_replabels);
+}
+
 py::tuple transducer_beam_search(const at::Tensor& x, const c10::optional<at::Tensor>& Wt, const c10::optional<at::Tensor>& logz,
                                  int blank, bool forced, int beam, int K, int nbest, bool normalize) {
   return beam_results(beam_source(x, c10::nullopt, Wt, logz, {kBeamTransducer, blank, forced, beam, K, nbest}, nbest, normalize));
@@ -1539,6 +1559,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("asg_beam_search_lexicon_errors", &asg_beam_search_lexicon_errors, py::arg("x"), py::arg("transitions"), py::arg("plan"),
         py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
         "asg_beam_search_lexicon's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
+  py::class_<AsgLmPlan>(m, "AsgLmPlan",
+                        "the options of one ASG beam search with a token-level LM, bound (engine.AsgLmBeamPlan.on_device)")
+      .def(py::init<int, int, int, int, int, const std::shared_ptr<DeviceLm>&, double, double, bool>(), py::arg("beam"),
+           py::arg("classes_per_frame"), py::arg("nbest"), py::arg("garbage"), py::arg("replabels"), py::arg("lm"),
+           py::arg("lm_weight"), py::arg("length_bonus"), py::arg("score_eos"),
+           "the raw alphabet the LM reads through (the garbage class, -1: none; the replabels), an LM over the tokens "
+           "(DeviceLm) and the scalars of the CTC search with an LM");
+  m.def("asg_beam_search_lm", &asg_beam_search_lm, py::arg("x"), py::arg("transitions"), py::arg("logz"), py::arg("plan"),
+        py::arg("drop"), py::arg("num_replabels"),
+        "ASG prefix beam search with a token-level LM on the device by an AsgLmPlan: (labels int64 CPU, offsets int64 CPU "
+        "[B nbest + 1], scores float64 CPU [B, nbest]); logz float32 [B] (normalised scores) or None");
+  m.def("asg_beam_search_lm_errors", &asg_beam_search_lm_errors, py::arg("x"), py::arg("transitions"), py::arg("plan"),
+        py::arg("drop"), py::arg("num_replabels"), py::arg("ref"), py::arg("tables"),
+        "asg_beam_search_lm's best hypotheses into device memory and the error counts behind them: int64 CPU [B, 4]");
   m.def("transducer_beam_search", &transducer_beam_search, py::arg("x"), py::arg("transitions"), py::arg("logz"),
         py::arg("blank"), py::arg("forced"), py::arg("beam"), py::arg("classes_per_frame"), py::arg("nbest"), py::arg("normalize"),
         "Transducer prefix beam search on the device (engine.TransducerBeamPlan's options): (labels int64 CPU, offsets int64 "

@@ -1375,6 +1375,83 @@ def asg_beam_search_lexicon(x, Wt, lexicon, garbage=None, beam_size=16, classes_
     return beam_preamble(plan, x, Wt, what, drop, num_replabels) or plan.search(x, Wt, normalize, drop, num_replabels)
 
 
+class AsgLmBeamPlan(namedtuple(
+        "AsgLmBeamPlan", "C beam classes_per_frame nbest garbage replabels lm lm_weight length_bonus lm_eos")):
+    """The options of one ASG beam search with a token-level n-gram LM (wfl_asg_beam_search_lm) over
+    C raw classes (replabels + tokens + garbage), checked once (`checked`, the one constructor) and handed on whole:
+    AsgBeamPlan's four ints, the raw alphabet the LM reads through -- the garbage class (None: the criterion has none)
+    and the number of replabels --, an lm.NGramLM over the N = C - replabels - (garbage is not None) tokens, built for
+    (N + 1, N) (ASG.token_lm builds one), and the scalars of the CTC search with an LM.  Only on_device(), search() and
+    errors need a device."""
+    __slots__ = ()
+
+    @classmethod
+    def checked(cls, C, beam_size, classes_per_frame, nbest, garbage, replabels, lm, lm_weight, length_bonus, lm_eos, what):
+        """The plan of these arguments, within the limits of wfl_asg_beam_search_lm, or ValueError (`what`: the call they
+        were given to): what AsgBeamPlan.checked refuses; a garbage outside [0, C); replabels that are no integer >= 0 or
+        leave no token; an lm that is no lm.NGramLM or was not built for (N + 1, N); a number that is not finite; an
+        lm_eos that is no bool."""
+        C, W, K, n = AsgBeamPlan.checked(C, beam_size, classes_per_frame, nbest, what)
+        if garbage is not None:
+            g = beam_integer(garbage)
+            if g is None or not 0 <= g < C:
+                raise ValueError(f"{what}: the garbage class {garbage!r} is outside [0, {C})")
+            garbage = g
+        R = beam_integer(replabels)
+        if R is None or R < 0:
+            raise ValueError(f"{what}: replabels must be an integer >= 0, got {replabels!r}")
+        tokens = C - R - (garbage is not None)
+        if tokens < 1:
+            raise ValueError(f"{what}: {R} replabels" + (" and the garbage class" if garbage is not None else "") +
+                             f" leave no token among {C} classes")
+        if not isinstance(lm, NGramLM):
+            raise ValueError(f"{what}: the token LM must be an lm.NGramLM, got {type(lm).__name__}")
+        check_built_for(lm, "the token LM", tokens + 1, tokens, what,
+                        f"for {C} raw classes with {R} replabels " + ("and a garbage class" if garbage is not None else
+                                                                      "and no garbage class") +
+                        f" it must have {tokens + 1} with blank {tokens} (ASG.token_lm builds it)")
+        weight, _, bonus, lm_eos = beam_lm_scalars(lm_weight, length_bonus, lm_eos, what)
+        return cls(C, W, K, n, garbage, R, lm, weight, bonus, lm_eos)
+
+    def no_frames(self, B):
+        """(hyps, scores) of search() for B utterances without a frame (B == 0 or T == 0), on the host, as
+        BeamPlan.no_frames: every rank the empty sequence, the first scored by the LM's </s> alone, the others -inf"""
+        return beam_lexicon_no_frames(B, self.nbest, self.lm, self.lm_weight, self.lm_eos)
+
+    def on_device(self, device):
+        """The plan as the operators take it (ops.AsgLmPlan, csrc/torch_ops.cpp), its lm on `device` (the LM's own
+        per-device cache: nothing is uploaded twice)"""
+        return N.ops.AsgLmPlan(beam=self.beam, classes_per_frame=self.classes_per_frame, nbest=self.nbest,
+                               garbage=-1 if self.garbage is None else self.garbage, replabels=self.replabels,
+                               lm=self.lm.on_device(device), lm_weight=self.lm_weight, length_bonus=self.length_bonus,
+                               score_eos=self.lm_eos)
+
+    def search(self, x, W, normalize=True, drop=None, num_replabels=0):
+        """asg_beam_search_lm's (hyps, scores) for x: float32 [B,T,C] on a GPU, contiguous, C the plan's; W: float32
+        [C + 1, C] on x's device, contiguous"""
+        flat, offsets, scores = N.ops.asg_beam_search_lm(x, W, beam_logz(x, W, normalize), self.on_device(x.device),
+                                                         -1 if drop is None else int(drop), int(num_replabels))
+        return beam_rows(flat, offsets, x.shape[0], self.nbest), scores
+
+
+def asg_beam_search_lm(x, Wt, lm, garbage=None, replabels=0, beam_size=16, classes_per_frame=None, nbest=1, normalize=True,
+                       drop=None, num_replabels=0, lm_weight=1.0, length_bonus=0.0, lm_eos=True):
+    """asg_beam_search with a token-level n-gram LM and a length bonus (wfl_asg_beam_search_lm through csrc/torch_ops.cpp;
+    the rules: include/wfl.h).  x, Wt, drop, num_replabels and the result: asg_beam_search's.
+    garbage, replabels: the raw alphabet the LM reads through -- replabel k is raw class k, token i is raw class
+    i + replabels, `garbage` the garbage class or None; lm: an lm.NGramLM over the N = C - replabels - (garbage is not
+    None) tokens, built for (N + 1, N).  The LM reads what the mapping (drop = garbage, num_replabels = replabels) writes:
+    a token steps it once, a replabel k right behind a token steps it by that token k + 1 more times, the garbage and any
+    other replabel not at all; every step adds lm_weight * step(s, token) + length_bonus, lm_eos adds lm_weight *
+    step(s, </s>) after the last frame and ranks again.  The scores include these terms.  The search and the n-best list
+    stay over raw sequences; drop and num_replabels map the results on the way out and are independent of the LM's view
+    (drop None, num_replabels 0: the raw sequences under the same LM).  The options are one AsgLmBeamPlan."""
+    what = "asg_beam_search_lm"
+    plan = AsgLmBeamPlan.checked(x.shape[2], beam_size, classes_per_frame, nbest, garbage, replabels, lm, lm_weight, length_bonus,
+                                 lm_eos, what)
+    return beam_preamble(plan, x, Wt, what, drop, num_replabels) or plan.search(x, Wt, normalize, drop, num_replabels)
+
+
 class TransducerBeamPlan(namedtuple("TransducerBeamPlan", "C blank forced beam classes_per_frame nbest")):
     """The options of one Transducer beam search over C classes (tokens + the blank), checked once (`checked`, the one
     constructor) and handed on whole, as BeamPlan is for CTC and AsgBeamPlan for ASG: Transducer.beam_search,

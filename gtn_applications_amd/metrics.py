@@ -154,6 +154,13 @@ def asg_beam_search_lexicon_errors(counter, targets, x, W, plan, drop, num_repla
     return N.ops.asg_beam_search_lexicon_errors(x, W, plan.on_device(x.device), drop, num_replabels, ref, tables)
 
 
+def asg_beam_search_lm_errors(counter, targets, x, W, plan, drop, num_replabels):
+    """asg_beam_search_errors for the search with a token-level LM (`plan`: a checked engine.AsgLmBeamPlan): the launches
+    of its search() and the counts behind them"""
+    ref, tables, drop = _staged(counter, targets, x, drop)
+    return N.ops.asg_beam_search_lm_errors(x, W, plan.on_device(x.device), drop, num_replabels, ref, tables)
+
+
 def transducer_beam_search_errors(counter, targets, x, Wt, plan):
     """The launches of engine.TransducerBeamPlan.search (`plan`: checked; its best hypothesis only; Wt: the transitions
     or None) and the counts behind them, on x's device: [B, 4] int64 on the host and nothing else"""
@@ -193,6 +200,7 @@ def plan_errors(counter, targets, x, plan, *args, spelling=None):
         return beam_search_errors(counter, targets, x, plan, *args)
     count = next(count for cls, count in ((E.AsgBeamPlan, asg_beam_search_errors),
                                           (E.AsgLexiconBeamPlan, asg_beam_search_lexicon_errors),
+                                          (E.AsgLmBeamPlan, asg_beam_search_lm_errors),
                                           (E.TransducerBeamPlan, transducer_beam_search_errors),
                                           (E.TransducerLexiconBeamPlan, transducer_beam_search_lexicon_errors),
                                           (E.TransducerLmBeamPlan, transducer_beam_search_lm_errors)) if isinstance(plan, cls))

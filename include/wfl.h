@@ -814,7 +814,8 @@ int wfl_transducer_beam_search_lexicon_marked(const float* x, const float* Wt /*
  *   synchronisation, no atomics on global memory, no cross-workgroup waits, every loop bounded by T, W, K.
  *   WFL_ERR_INVALID: a NULL required pointer (logz may be NULL), B, T or C < 1, beam outside [1, 64], classes_per_frame
  *   outside [1, min(C, 64)], nbest outside [1, beam], drop outside [-1, C), num_replabels < 0, out_capacity too small.
- *   WFL_ERR_UNSUPPORTED: C > 16384, T max(1, num_replabels) >= 2^31.  Not here: an LM or a lexicon, input lengths.
+ *   WFL_ERR_UNSUPPORTED: C > 16384, T max(1, num_replabels) >= 2^31.  Not here: input lengths.  A lexicon:
+ *   wfl_asg_beam_search_lexicon; a token-level LM: wfl_asg_beam_search_lm.
  * ------------------------------------------------------------------------------------------------ */
 /* out_capacity = B nbest T max(1, num_replabels) (int32 elements of `out`), ws_bytes = the device scratch of a call */
 int wfl_asg_beam_workspace(int B, int T, int C, int beam, int classes_per_frame, int nbest, int num_replabels,
@@ -869,8 +870,9 @@ int wfl_asg_beam_search(const float* x, const float* Wt /* [(C+1), C] */, const 
  *   back-off cap or 31 search steps.
  *   WFL_ERR_INVALID: what wfl_asg_beam_search refuses; garbage outside [-1, C); lex or one of its arrays NULL, num_nodes,
  *   num_arcs or num_words < 1 (or num_words = 2^31 - 1); a weight or bonus that is not finite; for a non-NULL word_lm
- *   what wfl_ctc_beam_search_lm refuses.  Not here: a token-level LM, LM look-ahead inside words, several spellings of
- *   one word, out-of-vocabulary arcs, input lengths.
+ *   what wfl_ctc_beam_search_lm refuses.  Not here: a token-level LM together with the lexicon (alone:
+ *   wfl_asg_beam_search_lm), LM look-ahead inside words, several spellings of one word, out-of-vocabulary arcs, input
+ *   lengths.
  * ------------------------------------------------------------------------------------------------ */
 int wfl_asg_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] */, const float* logz /* [B] or NULL */, int B,
                                 int T, int C, int beam, int classes_per_frame, int nbest, int drop, int num_replabels,
@@ -878,6 +880,59 @@ int wfl_asg_beam_search_lexicon(const float* x, const float* Wt /* [(C+1), C] */
                                 double lm_weight, double word_bonus, double length_bonus, int score_eos, void* ws,
                                 int32_t* out, int64_t out_capacity, int64_t* out_offsets /* [B*nbest+1] */,
                                 double* scores /* [B*nbest] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The ASG search with a token-level n-gram LM and a length bonus (csrc/beam_kernels.hip): the letter
+ * criterion decoded lexicon-free with a letter n-gram.
+ *   THE LM READS EXACTLY WHAT THE MAPPED WRITE LAUNCH EMITS: the raw class sequence with the garbage dropped and the
+ *   replabels unpacked by wfl_decode_paths' rule.  R = `replabels`, G = `garbage` (-1: none), N = C - R - (G >= 0 ? 1 : 0)
+ *   the number of tokens; replabel k is raw class k < R, token i is raw class i + R.  The LM is a wfl_ngram_lm over the N
+ *   tokens: LM label i is token i, built for (num_classes = N + 1, blank = N) -- the phantom blank N is never a label --,
+ *   LM label N + 1 is </s>.  Every rule of wfl_asg_beam_search stands; step, wfl_ngram_lm and wfl_ngram_lm_check are
+ *   wfl_ctc_beam_search_lm's; a = lm_weight, b = length_bonus, both finite float64.  A hypothesis carries, beside its
+ *   mass, an LM state (lm->start for the empty prefix) and rep: the token a replabel right behind the prefix would
+ *   repeat, or -1 (the empty prefix: -1).  Both are functions of the raw prefix, so merging by prefix identity (rule 5 of
+ *   the ASG search) stays exact, and a merged extension carries the same term as a new one.
+ *     1. extension: hypothesis i with last label l (or the start), candidate c != l, ac = (s + Wt[1+c][l]) + p_i as in
+ *        rule 4 of the ASG search.  ac = -inf: the extension does not exist and nothing is looked up.  Otherwise c emits
+ *        a list of LM labels and moves rep: c == G emits nothing, state and rep stay; c >= R (and c != G) emits [c - R],
+ *        rep' = c - R; c < R with rep >= 0 emits rep another c + 1 times, rep' = -1; c < R with rep = -1 (a replabel at
+ *        the start or behind another replabel) emits nothing, rep' = -1 -- the write launch emits nothing for it either;
+ *     2. term = 0; for each emitted label u in order: (lw, state) = step(state, u); lw = -inf: the extension does not
+ *        exist; otherwise term = term + (a lw + b), each operation rounded on its own.  Then e = ac + term.  An extension
+ *        that emits nothing has e = ac and costs no lookup; at most max(1, R) lookups per extension;
+ *     3. stays add nothing and keep the LM state and rep.  Candidates (by emission score alone), entry order, the tie
+ *        rule and the -inf drop rule are the ASG search's;
+ *     4. after the last frame: with score_eos != 0 rank r gets + a step(state_r, N + 1) and is dropped if that step is
+ *        -inf; one re-ranking by score, descending, ties to the earlier rank; nbest is taken after it; missing ranks are
+ *        empty sequences with score -inf; logz[b] is subtracted if given, and nothing else;
+ *     5. where nothing is pruned, score(l) = mass_ASG(l) + a LM(map(l)) + b |map(l)|, plus the </s> term; map is the
+ *        write launch's mapping with (drop = G, num_replabels = R);
+ *     6. the search and the n-best list stay over RAW sequences: two raw sequences with the same mapped output (a, G, a
+ *        and a, r0) are separate hypotheses with the same LM term, as in wfl_asg_beam_search;
+ *     7. the bound.  The ASG search bounds the W-th best entry by one entry per hypothesis of a full beam: its stay or,
+ *        where its last label is no candidate, its first own extension.  Such an entry may serve only if it EXISTS: the
+ *        stand-in extension is scored with its real term, lookups included, and where a step is -inf the hypothesis
+ *        contributes nothing and the frame's bound is -inf.  The lookup of any other extension may be skipped when
+ *        ac + bound is below that bound of the frame, `bound` the largest term an extension can have: the maximum over
+ *        n = 0 .. max(1, R) of n accumulations of max(a step_min, a step_max) + b, formed on the host by the kernel's
+ *        rounded operations.  The bound decides what is ranked, never the result.
+ *   drop, num_replabels: the mapping of the results on the way out, as in wfl_asg_beam_search -- kept apart from garbage,
+ *   replabels, so that raw results can be asked for under the same LM.  lm: a struct in HOST memory of DEVICE pointers to
+ *   a pack that wfl_ngram_lm_check accepted for (N + 1, N), with the step_min / step_max it wrote; the kernels trust it.
+ *   The workspace is wfl_asg_beam_workspace's; outputs, launches (three, four with a mapping) and guarantees as
+ *   wfl_asg_beam_search: no allocation, no synchronisation, no atomics on global memory, no cross-workgroup waits, every
+ *   loop bounded by T, W, K, R, the back-off cap or 31 search steps; deterministic.
+ *   WFL_ERR_INVALID, in this order: what wfl_asg_beam_search refuses; garbage outside [-1, C); replabels < 0 or
+ *   C - replabels - (garbage >= 0) < 1; what wfl_ctc_beam_search_lm refuses about the LM and the two scalars; then
+ *   out_capacity too small.  Not here: merging raw hypotheses by mapped output, a token LM together with a lexicon, input
+ *   lengths (ASG has none anywhere).
+ * ------------------------------------------------------------------------------------------------ */
+int wfl_asg_beam_search_lm(const float* x, const float* Wt /* [(C+1), C] */, const float* logz /* [B] or NULL */, int B, int T,
+                           int C, int beam, int classes_per_frame, int nbest, int drop, int num_replabels,
+                           int garbage /* -1: none */, int replabels, const wfl_ngram_lm* lm, double lm_weight,
+                           double length_bonus, int score_eos, void* ws, int32_t* out, int64_t out_capacity,
+                           int64_t* out_offsets /* [B*nbest+1] */, double* scores /* [B*nbest] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device kernels: Transducer prefix beam search (csrc/beam_kernels.hip)
@@ -1061,8 +1116,8 @@ int wfl_transducer_beam_search_lexicon(const float* x, const float* Wt /* [(C+1)
  *   cross-workgroup waits, every loop bounded by T, W, K, the back-off cap or 31 search steps; deterministic.
  *   WFL_ERR_INVALID: what wfl_transducer_beam_search refuses, in its order; then what wfl_ctc_beam_search_lm refuses
  *   about the LM (lm or one of its arrays NULL, num_states < 1, num_arcs < 0, start outside [0, num_states), step_min
- *   or step_max NaN) and a weight or bonus that is not finite.  Not here: ASG with a letter LM, a token-level LM
- *   together with a lexicon or with merging by spelling, input lengths, the ambiguous token graphs.
+ *   or step_max NaN) and a weight or bonus that is not finite.  Not here: a token-level LM together with a lexicon or
+ *   with merging by spelling, input lengths, the ambiguous token graphs.  ASG with a letter LM: wfl_asg_beam_search_lm.
  * ------------------------------------------------------------------------------------------------ */
 int wfl_transducer_beam_search_lm(const float* x, const float* Wt /* [(C+1), C] or NULL */, const float* logz /* [B] or NULL */,
                                   int B, int T, int C, int blank, int forced, int beam, int classes_per_frame, int nbest,
