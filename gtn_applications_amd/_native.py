@@ -209,6 +209,7 @@ _SIGS = {
     "wfl_row_argmax": (c_int, [_P, c_int64, c_int, _P, _P]),
     # device: the decode behind a best path
     "wfl_decode_chunk_frames": (c_int, []),
+    "wfl_errors_chunk_steps": (c_int, []),
     "wfl_decode_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "wfl_decode_emissions": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),
     "wfl_decode_emissions_lengths": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P]),

@@ -276,6 +276,8 @@ using namespace wfl;
 
 extern "C" {
 
+int wfl_errors_chunk_steps(void) { return kErrChunk; }
+
 int wfl_errors_workspace(int B, int64_t hyp_capacity, int64_t ref_labels, int hyp_max_expansion, int ref_max_expansion,
                          int64_t* ws_bytes) {
   if (B < 1 || hyp_capacity < 0 || ref_labels < 0 || hyp_max_expansion < 0 || ref_max_expansion < 0 || !ws_bytes) {

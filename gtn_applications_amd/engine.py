@@ -979,6 +979,12 @@ def decode_chunk_frames():
     return int(N.lib.wfl_decode_chunk_frames())
 
 
+def errors_chunk_steps():
+    """Wavefront steps per LDS fill of the device error counts' distance launch (wfl_errors_chunk_steps): a strip's cell
+    values and boundary column are carried across a fill."""
+    return int(N.lib.wfl_errors_chunk_steps())
+
+
 def decode_emissions(x, drop, bias=None, num_replabels=0, flags=0, dtype=torch.int32, lengths=None):
     """viterbi()'s decode from emissions, on the device (wfl_decode_emissions through csrc/torch_ops.cpp): per frame the
     first maximal class of x [B,T,C] (+ bias [C]), runs collapsed, `drop` (None: nothing) dropped, replabels unpacked.

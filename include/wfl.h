@@ -532,6 +532,10 @@ int wfl_ctc_grad_lengths(const float* x, int B, int T, int C, const int32_t* tar
 /* frames per chunk: the frames are split into chunks over the grid, and the previous label, the last kept value and
  * the output count are carried across the chunk boundaries (tests straddle them) */
 int wfl_decode_chunk_frames(void);
+/* wavefront steps per LDS fill of wfl_errors_count's distance launch (compute_edit_distance, train.py:74-87; test.py:94-109):
+ * a strip of W <= 64 reference columns against n hypothesis rows takes n + W - 1 steps, and the cell values and the
+ * boundary column are carried from one fill to the next (tests cross it) */
+int wfl_errors_chunk_steps(void);
 /* out_capacity = B T max(1, num_replabels) (int32 elements of `out`), ws_bytes = the device scratch of a call */
 int wfl_decode_workspace(int B, int T, int num_replabels, int64_t* out_capacity, int64_t* ws_bytes);
 /* lab[b][t] = the first maximal class of x[b,t,:] + bias (x [B,T,C] float32; bias [C] or NULL: the unigram transition

@@ -1,6 +1,6 @@
 """CPU tests (-m "not gpu") of the error counts' C ABI (csrc/error_kernels.hip, include/wfl.h) and of
-metrics.ErrorCounter's host side: the header declares the two entry points, libwfl.so exports them, the ctypes table
-resolves them, wfl_errors_workspace bounds the scratch from capacities and longest expansions alone, the counter builds
+metrics.ErrorCounter's host side: the header declares the entry points, libwfl.so exports them, the ctypes table
+resolves them, wfl_errors_chunk_steps gives the distance launch's steps per LDS fill, wfl_errors_workspace bounds the scratch from capacities and longest expansions alone, the counter builds
 the tables tokens_to_text / to_text spell (train.py:80), and the caller errors are ValueErrors before any launch.  No
 device compute here."""
 import ctypes
@@ -17,7 +17,7 @@ from gtn_applications_amd import _native as N
 from gtn_applications_amd import metrics as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("wfl_errors_workspace", "wfl_errors_count")
+NEW_SYMBOLS = ("wfl_errors_workspace", "wfl_errors_count", "wfl_errors_chunk_steps")
 
 
 def test_header_declares_and_library_exports_the_entry_points():
@@ -42,6 +42,11 @@ def test_ctypes_table_and_operators_resolve():
         fn = getattr(N.lib, name)
         assert fn.restype is ctypes.c_int and fn.argtypes is not None, name
     assert len(N.lib.wfl_errors_count.argtypes) == 17 and len(N.lib.wfl_errors_workspace.argtypes) == 6
+    # the distance launch's steps per LDS fill: host code, no device needed; a multiple of the wave the edge tests build on
+    from gtn_applications_amd import engine as E
+
+    K = N.lib.wfl_errors_chunk_steps()
+    assert len(N.lib.wfl_errors_chunk_steps.argtypes) == 0 and E.errors_chunk_steps() == K and K >= 128 and K % 64 == 0
     for fn in ("errors_count", "decode_emissions_errors", "decode_paths_errors"):
         assert hasattr(N.ops, fn), fn
     from gtn_applications_amd.criterions import asg, ctc, transducer

@@ -190,7 +190,7 @@ def _emission_case(rs, B, T, C, special):
     return torch.from_numpy(x).cuda()
 
 
-@pytest.mark.parametrize("C", [1, 2, 63, 64, 65, 100, 257, 1001])
+@pytest.mark.parametrize("C", [1, 2, 63, 64, 65, 100, 128, 129, 200, 256, 257, 512, 513, 1001, 1024, 1025, 2049])
 def test_emissions_decode_equals_argmax_and_the_row_by_row_collapse(C):
     N, E, _ = _mods()
     rs = np.random.RandomState(C)
